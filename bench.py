@@ -8,15 +8,20 @@ across ranks with no data-path collective; the only exchange is the RCCL all-red
 scalar free energy).  Chain c of the job draws its data from numpy default_rng(42 + c)
 (SURVEY §8d C2); the observations are resident in HBM when the timed region starts.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 without a torch.distributed environment re-executes itself under torch.distributed.run
 (one rank per GPU, 127.0.0.1 rendezvous); under a launcher it reads RANK/LOCAL_RANK/WORLD_SIZE.
 
 Prints ONE JSON line (rank 0).  `value` = reference-equivalent message-rule evaluations per
 second over all ranks (6 per (chain, time step) per sweep, SURVEY Appendix C — what the
-reference counts as after_message_rule_call events).  After the timed region rank 0 checks two
-chains (first / last) against the CPU oracle (`parity_spot`) — the checker, never the thing measured.
+reference counts as after_message_rule_call events); `ms_per_step` = milliseconds of one timed step.
+A plain run sets up, warms up, times the K steps and prints that line, nothing else.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last step computed (dump_outputs) as DIR/<name>.npy.
+--full: everything beyond the headline figure as well — the CPU baseline (before the GPU legs), a check of two chains
+(first / last) against the CPU oracle after the timed region (`parity_spot`: the checker, never the thing measured),
+the other BASELINE configurations and variants (`extra`, `roofline_per_chain_models`) and the detail file.
 """
 import argparse
 import hashlib
@@ -133,6 +138,24 @@ def _parity_check(mean, cov, fe, mdl, y_host, chains, missing):
         out["fe_rel"] = max(out["fe_rel"], float(abs(fe[c] - ofe) / abs(ofe)))
     out["ok"] = bool(out["mean_rel"] < 1e-6 and out["cov_rel"] < 1e-6 and out["fe_rel"] < 1e-8)
     return out
+
+
+def dump_outputs(eng, out_dir, fe_global, n_chains=32, n_steps=4096, seed=20240):
+    """What a caller of the timed path receives after its last step, as float64 DIR/<name>.npy (≈ 21 MB at the headline size):
+      posterior_mean [n_chains][n_steps][d], posterior_cov [n_chains][n_steps][d][d] — the posteriors of a fixed, seeded sample of this rank's
+        chains at a fixed, seeded sample of time steps (both ascending; the whole posterior of the headline batch is 16 GB);
+      free_energy_per_chain [chains of this rank]; free_energy [1]: the job's Bethe free energy (the sum over ranks).
+    The sample depends on T and the chain count only, so two builds run with the same arguments write comparable files."""
+    T, C = eng.T, eng.n_chains
+    rng = np.random.default_rng(seed)
+    chains = np.sort(rng.choice(C, size=min(n_chains, C), replace=False))
+    steps = np.sort(rng.choice(T, size=min(n_steps, T), replace=False))
+    mean, cov = eng.marginals_of_chains(chains)
+    arrays = {"posterior_mean": mean[:, steps], "posterior_cov": cov[:, steps], "free_energy_per_chain": eng.free_energy_per_chain(),
+              "free_energy": np.array([fe_global])}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def timed_sweeps(eng, steps, warmup, filter_run=False, repeats=2):
@@ -879,7 +902,7 @@ def compact_line(out):
     """The ONE line rank 0 prints, below 8 KB (the driver keeps the parsed fixed keys and an 8 KB tail: a 15 KB line lost most extras): the
     contract's fields, the dominant kernel's roofline with a scalar summary [ms, roofline fraction, parity ok] of EVERY configuration under
     roofline.per_config, the CPU baseline, and per configuration the few rates that name it.  Workload texts, kernel breakdowns, notes, counter sources:
-    the detail file (--detail, default bench_detail.json) and DESIGN.md §6."""
+    the detail file (--detail; with --full by default bench_detail.json) and DESIGN.md §6."""
     pick = lambda d, keys: {k: d[k] for k in keys if isinstance(d, dict) and k in d and d[k] is not None}
     line = pick(out, ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data"))
     line["vs_baseline"] = out.get("vs_baseline")
@@ -1152,16 +1175,25 @@ def main(argv=None, engine_cls=None, gpu_cls=_Gpu, extra_cls=None):
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak: --chains per GPU (the driver's scaling run); strong: --chains in total, split over the ranks")
     ap.add_argument("--segments", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline, the parity spot, the extra configurations and write the detail file (a plain run: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (a seeded sample of the posteriors, the free energies) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-sample-chains", type=int, default=96,
                     help="chains of the benchmarked batch the single-core CPU restatement is timed on (96: about 12 s of one host core)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the per-chain-model variant and the C3/C4/C5 lines")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"),
-                    help="file that receives the full record (the printed line is its compact form, below 8 KB); '' = none")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the per-chain-model variant and the C3/C4/C5 lines")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the parity spots")
+    ap.add_argument("--detail", default=None,
+                    help="file that receives the full record (the printed line is its compact form, below 8 KB); '' = none; "
+                         "default: bench_detail.json with --full, none without")
     ap.add_argument("--force-dist", action="store_true",
                     help="create the RCCL process group and run the free-energy exchange even with one rank (exercises the N > 1 code path on a 1-GPU box)")
     args = ap.parse_args(argv)
+    if not args.full:   # a plain run: the headline figure only
+        args.no_cpu_baseline = args.no_parity = args.no_extras = True
+    if args.detail is None:
+        args.detail = os.path.join(ROOT, "bench_detail.json") if args.full else ""
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         respawn_under_launcher(args.gpus)
@@ -1337,6 +1369,8 @@ def main(argv=None, engine_cls=None, gpu_cls=_Gpu, extra_cls=None):
         "free_energy_rank0": fe_local,
         "free_energy_global": float(fe_sum.item()) if dist is not None else fe_local,
     }
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, out["free_energy_global"])
     if rank == 0 and not args.no_parity:
         out["parity_spot"] = parity_spot(eng, mdl, y_host, [0, C - 1] if C > 1 else [0])
     if rank == 0 and cpu_base is not None:   # timed before the process group was created (above)

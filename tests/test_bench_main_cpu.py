@@ -140,7 +140,7 @@ def _worker_extras(rank, world, port, out_dir):
 
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
-        bench.main(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--T", "16", "--chains", "2", "--no-cpu-baseline", "--no-parity"],
+        bench.main(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--T", "16", "--chains", "2", "--full", "--no-cpu-baseline", "--no-parity"],
                    engine_cls=StubEngine, gpu_cls=bench._HostOnly,
                    extra_cls=dict(hgf_cls=StubHgf, gmm_cls=StubGmm, shard_cls=StubShard, c4_series=3, c4_T=20, c5_points=50, steps4=2, steps5=4))
     with open(os.path.join(out_dir, f"rank{rank}.txt"), "w") as f:
@@ -267,3 +267,49 @@ def test_timed_sweeps_takes_the_better_repeat_for_time_and_for_every_kernel():
     ms, kt = bench.timed_sweeps(e, steps=5, warmup=2, repeats=2)
     assert kt == {"k_forward": 0.27, "k_backward": 0.23} and ms >= 0.0
     assert e.n == 2 + 2 * 5 + 2 * 5 and e.prof is False
+
+
+class CountingStub(StubEngine):
+    """StubEngine with the outputs a caller of the timed path reads: posterior mean := y of the chain, covariance := its outer product,
+    free energy per chain := Σ y of the chain (checksums of the data, as above)."""
+    made = []
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.n_chains = self.C
+        CountingStub.made.append(self)
+
+    def marginals_of_chains(self, chains, want_cov=True):
+        mean = np.transpose(self._y.reshape(self.T, self.C, 4)[:, np.asarray(chains)], (1, 0, 2)).copy()
+        return mean, mean[..., :, None] * mean[..., None, :]
+
+    def free_energy_per_chain(self):
+        return self._y.reshape(self.T, self.C, 4).sum(axis=(0, 2))
+
+
+def test_plain_run_times_exactly_the_steps_and_dumps_the_outputs(tmp_path, capsys):
+    """A plain run: --warmup + --steps sweeps of the timed engine and nothing else (no CPU baseline, parity spot or extra line);
+    --dump-outputs writes float64 .npy files below 64 MB that are identical from run to run with the same arguments."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        os.environ.pop(k, None)
+    files = []
+    for run in range(2):
+        CountingStub.made.clear()
+        out_dir = tmp_path / f"run{run}"
+        bench.main(["--gpus", "1", "--steps", "7", "--warmup", "2", "--T", "5000", "--chains", "40", "--dump-outputs", str(out_dir)],
+                   engine_cls=CountingStub, gpu_cls=bench._HostOnly)
+        line = json.loads(capsys.readouterr().out.strip())
+        timed = CountingStub.made[-1]
+        assert timed.runs == 2 + 7 and all(e.runs == 0 for e in CountingStub.made[:-1])
+        assert line["steps"] == 7 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["cpu_baseline"] is None
+        assert "parity_spot" not in line and "extra" not in line and "detail" not in line
+        files.append({p.name: np.load(p) for p in sorted(out_dir.iterdir())})
+    got = files[0]
+    assert set(got) == {"posterior_mean.npy", "posterior_cov.npy", "free_energy_per_chain.npy", "free_energy.npy"}
+    assert all(a.dtype == np.float64 for a in got.values()) and sum(a.nbytes for a in got.values()) < 64 << 20
+    assert got["posterior_mean.npy"].shape == (32, 4096, 4) and got["posterior_cov.npy"].shape == (32, 4096, 4, 4)
+    assert got["free_energy_per_chain.npy"].shape == (40,) and got["free_energy.npy"][0] == line["free_energy_global"]
+    assert all(np.array_equal(got[k], files[1][k]) for k in got)

@@ -60,7 +60,7 @@ def test_c_abi_mixture_statistics_exchange():
 
 def _bench(*extra):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--T", "4000",
-                          "--chains", "192", "--no-cpu-baseline", "--no-extras", *extra], capture_output=True, text=True, timeout=600,
+                          "--chains", "192", "--full", "--no-cpu-baseline", "--no-extras", *extra], capture_output=True, text=True, timeout=600,
                          cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     return json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
