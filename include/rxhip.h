@@ -42,6 +42,8 @@ extern "C" {
  *     RXHIP_ONE_PASS=0|1        d, dy <= 4 shared-model batches: force the four-phase / the one-pass table-driven schedule (default: by size)
  *     RXHIP_ONE_SEGMENT=1       d, dy <= 4 masked / per-step engines: one segment per chain
  *     RXHIP_BACKWARD_LANES=1    one-pass schedule: the backward sweep of the four-phase schedule instead of the table-driven one
+ *     RXHIP_MEAN_RECORDS=1      one-pass schedule: a filtered-mean record per time index instead of the reverse filter from checkpoints
+ *     RXHIP_MEAN_CHECKPOINT=K   one-pass schedule: the reverse filter with checkpoint stride K (1, 2, 4, … 32) whatever its bound says
  *     RXHIP_SMALL_SWEEP=0       few short chains: the five launches of the four-phase schedule instead of k_small_sweep (one launch)
  *     RXHIP_ELEM_FULL=1         per-chain models at d, dy <= 4: every recursion of the sweep in full to the end of every segment (no frozen tails, full records)
  *     RXHIP_NOISE_MOMENTS_PASS=1  unknown-noise engines: the residual second moments by a separate pass over the posteriors instead of inside the backward sweep
@@ -796,6 +798,12 @@ rxhip_status rxhip_reset_kernel_times(rxhip_engine* e);
  * such tables.  Waits for those kernels.  The reference has no counterpart: it recomputes these messages for every chain
  * and every call (src/inference/batch.jl:391-430). */
 rxhip_status rxhip_get_model_tables_ms(rxhip_engine* e, double* ms);
+/* How the table-driven backward sweep of a shared-model batch (d, dy <= 4) gets its filtered means: *K = 0 reads a record per time
+ * index that the forward pass wrote; *K = 8, 16 or 32 rebuilds them by running the filter backward from checkpoints the forward
+ * pass wrote every K steps.  K is fixed at creation: the largest stride whose reverse steps stay inside a bound
+ * computed from the model's tables; 0 when none does, when dy > d, A is singular or the schedule has no table-driven sweep.
+ * RXHIP_MEAN_RECORDS / RXHIP_MEAN_CHECKPOINT (test hooks, "Environment") override the choice. */
+rxhip_status rxhip_get_mean_checkpoint_stride(rxhip_engine* e, int32_t* K);
 /* Where the host time of the engine's creation went, in milliseconds: ms4[0] host arithmetic on model tables (models of state
  * dimension < 32; 0 for tables that came from the cache), ms4[1] device kernels that build tables (enqueue — or completion where
  * their status is needed before the engine exists), ms4[2] uploads (tables, constants; host → device copies + their sync),

@@ -112,6 +112,11 @@ struct rxhip_engine : rxhip_engine_life {
     double *d_ftab = nullptr, *d_mtab = nullptr, *d_ntab = nullptr, *d_pos = nullptr, *d_fseg = nullptr;
     double fe_const = 0.0;
     double *d_gtab = nullptr, *d_segend = nullptr, *d_sblk = nullptr;
+    // reverse-filter schedule (k_backward_sh_rev): checkpoint stride 2^ck_log2 of the z records, 0: a record per time index
+    int ck_log2 = 0;
+    long long nck = 0;
+    double *d_amp = nullptr, *d_ainv = nullptr;
+    int* d_ckfail = nullptr;
     hipEvent_t ev_tab0 = nullptr, ev_tab1 = nullptr;  // around the once-per-engine table kernels (rxhip_get_model_tables_ms)  // table-driven backward sweep (k_backward_sh): batches of a multiple of 64 chains
     bool sequential = false;  // no per-position tables: missing observations / per-step constants (per-chain records; the segment
                               // elements are computed in the lane, k_seg_elements, or the chain is ONE segment)

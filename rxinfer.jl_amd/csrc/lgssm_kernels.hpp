@@ -212,6 +212,12 @@ struct Params {
                             // not the 160 B/U of posteriors that the next iteration overwrites unread (rxhip_get_marginals returns the LAST iteration's)
     int tinv_records;       // per-chain, time-invariant models on long segments: k_forward_tinv / k_backward_tinv (mean-only records behind the fixed point)
     int elem_full;          // test hook: k_seg_elements runs the full recursion to the end of every segment (no frozen tail)
+    // one-pass runs whose backward sweep rebuilds the filtered means by the reverse filter (k_backward_sh_rev): k_forward0<…, true>
+    // stores z only at CHECKPOINTS — every K = 2^ck_log2 steps of a segment and at its end — in slot 1 + s·nck + j of `filt`
+    // (slot 0 is the t = 0 record of the boundary scan)
+    int ck_log2;
+    long long nck;          // checkpoint slots per segment: ⌈L / K⌉
+    const double* ainv;     // [D][D]  A⁻¹ (k_smooth_tab_steps)
 };
 
 // ------------------------------------------------------------------------------------------
@@ -1194,7 +1200,10 @@ __device__ __forceinline__ bool load_elemx(const Params& p, long long s, long lo
 // every lane.  The segment's evidence comes from the same quantities:
 //     −2 log p(y_seg | y_before) = const_s + q0 + [m_s'A1 m_s − 2 η'A2 m_s − η'W η],   q0 = Σ_i e_i'(S⁰_i)⁻¹e_i
 // with e_i the known-start innovations (k_fe_seg evaluates the bracket, const_s is summed on the host).
-template <int D, int DY, bool FE>
+//
+// CK: the backward sweep rebuilds the filtered means by the reverse filter (k_backward_sh_rev), so z is stored only at the
+// checkpoints (Params::ck_log2); the m / η / q0 arithmetic is the same instruction sequence either way.
+template <int D, int DY, bool FE, bool CK = false>
 __global__ void __launch_bounds__(64) k_forward0(Params p, const CstArg<CstLayout<D, DY>::SIZE> cb) {
     using CL = CstLayout<D, DY>;
     using FL = F0Layout<D, DY>;
@@ -1308,6 +1317,7 @@ __global__ void __launch_bounds__(64) k_forward0(Params p, const CstArg<CstLayou
                 }
 #pragma unroll
                 for (int a = 0; a < D; ++a) m[a] = mn[a];
+                if (CK && ((i + 1) & ((1LL << p.ck_log2) - 1)) != 0 && i + 1 != len) continue;   // not a checkpoint
                 // z_t = b_i + M_t η_i  (values, not pointers, select between LDS and memory: a pointer that may be either
                 // becomes a generic pointer, which this compiler cannot lower here)
                 double z[2 * MP2], mrow[D * D];
@@ -1327,7 +1337,8 @@ __global__ void __launch_bounds__(64) k_forward0(Params p, const CstArg<CstLayou
                     z[a] = s;
                 }
                 if (D < 2 * MP2) z[2 * MP2 - 1] = 0.0;
-                double2* base = reinterpret_cast<double2*>(p.filt) + (((t0 + i) * p.nb64 + (chain >> 6)) * MP2) * 64 + (chain & 63);
+                const long long slot = CK ? 1 + seg * p.nck + (i >> p.ck_log2) : t0 + i;
+                double2* base = reinterpret_cast<double2*>(p.filt) + ((slot * p.nb64 + (chain >> 6)) * MP2) * 64 + (chain & 63);
 #pragma unroll
                 for (int k = 0; k < MP2; ++k) base[k * 64] = make_double2(z[2 * k], z[2 * k + 1]);
             }
@@ -2840,7 +2851,19 @@ struct SmoothTabParams {
     double* segend;      // [S][SegEndTab::SIZE]
     double* blk;         // [S][ceil(L / SMOOTH_LB)][SmoothBlk::SIZE]
     int* status;
+    // reverse-filter tables (k_backward_sh_rev), null / 0 otherwise: the F slot of row t holds V_p(t+1) instead of F_t,
+    // amp[t] bounds ‖A⁻¹(I + V_p(t+1) B'Q⁻¹B)‖₂ (the reverse step t+1 → t), ckfail collects one bit per checkpoint
+    // stride 8 / 16 / 32 whose worst window product exceeds REV_AMP_LIMIT
+    int rev;
+    double* amp;         // [T]
+    double* ainv;        // [D][D]
+    int* ckfail;
 };
+// Largest product of per-step bounds allowed inside one checkpoint window.  Measured on the C1/C2 model (numpy, T = 2·10⁴,
+// |m|/sd up to 1.2e2): the worst windows of K = 8 / 16 / 32 have products 12 / 49 / 363 and rebuild the filtered means to
+// 1.6e-13 / 3.9e-13 / 1.6e-12 posterior sd, so the limit admits K = 16 there and keeps admitted windows inside 1e-12 sd
+// (tests/test_reverse_filter.py).
+constexpr double REV_AMP_LIMIT = 1.0e2;
 __host__ __device__ inline long long smooth_blocks_per_segment(long long L) { return (L + SMOOTH_LB - 1) / SMOOTH_LB; }
 
 template <int D>
@@ -2865,6 +2888,114 @@ __device__ __forceinline__ void congruence(const double (&G)[D][D], const double
             out[a][b] = acc;
             out[b][a] = acc;
         }
+}
+
+// general inverse by Gauss–Jordan elimination with partial pivoting; false when a pivot vanishes or a result is not finite
+template <int D>
+__device__ __forceinline__ bool gen_inv(const double (&A)[D][D], double (&X)[D][D]) {
+    double M[D][2 * D];
+#pragma unroll
+    for (int a = 0; a < D; ++a)
+#pragma unroll
+        for (int b = 0; b < D; ++b) {
+            M[a][b] = A[a][b];
+            M[a][D + b] = a == b ? 1.0 : 0.0;
+        }
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        int piv = k;
+        double best = fabs(M[k][k]);
+#pragma unroll
+        for (int a = k + 1; a < D; ++a)
+            if (fabs(M[a][k]) > best) {
+                best = fabs(M[a][k]);
+                piv = a;
+            }
+#pragma unroll
+        for (int a = k + 1; a < D; ++a) {   // swap rows k and piv by selects (indices stay compile-time constants)
+            const bool sw = a == piv;
+#pragma unroll
+            for (int b = 0; b < 2 * D; ++b) {
+                const double tk = M[k][b], ta = M[a][b];
+                M[k][b] = sw ? ta : tk;
+                M[a][b] = sw ? tk : ta;
+            }
+        }
+        const double pv = M[k][k];
+        ok = ok && pv != 0.0;
+        const double r = 1.0 / pv;
+#pragma unroll
+        for (int b = 0; b < 2 * D; ++b) M[k][b] *= r;
+#pragma unroll
+        for (int a = 0; a < D; ++a)
+            if (a != k) {
+                const double f = M[a][k];
+#pragma unroll
+                for (int b = 0; b < 2 * D; ++b) M[a][b] -= f * M[k][b];
+            }
+    }
+#pragma unroll
+    for (int a = 0; a < D; ++a)
+#pragma unroll
+        for (int b = 0; b < D; ++b) {
+            X[a][b] = M[a][D + b];
+            ok = ok && isfinite(X[a][b]);
+        }
+    return ok;
+}
+
+// an upper bound on the spectral norm ‖M‖₂:  with X = M'M / s, s = ‖M'M‖∞ ≥ λmax(M'M),  λmax(M'M) ≤ s ‖X¹⁶‖∞^(1/16)
+// (within a factor D^(1/32) of the norm; +∞ when M is not finite)
+template <int D>
+__device__ __forceinline__ double spec_norm_bound(const double (&M)[D][D]) {
+    double X[D][D];
+    double s = 0.0;
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        double r = 0.0;
+#pragma unroll
+        for (int b = 0; b < D; ++b) {
+            double acc = 0.0;
+#pragma unroll
+            for (int k = 0; k < D; ++k) acc += M[k][a] * M[k][b];
+            X[a][b] = acc;
+            r += fabs(acc);
+        }
+        s = fmax(s, r);
+    }
+    if (!(s < INFINITY)) return INFINITY;
+    if (s == 0.0) return 0.0;
+#pragma unroll
+    for (int a = 0; a < D; ++a)
+#pragma unroll
+        for (int b = 0; b < D; ++b) X[a][b] /= s;
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {   // X ← X²
+        double Y[D][D];
+#pragma unroll
+        for (int a = 0; a < D; ++a)
+#pragma unroll
+            for (int b = 0; b < D; ++b) {
+                double acc = 0.0;
+#pragma unroll
+                for (int k = 0; k < D; ++k) acc += X[a][k] * X[k][b];
+                Y[a][b] = acc;
+            }
+#pragma unroll
+        for (int a = 0; a < D; ++a)
+#pragma unroll
+            for (int b = 0; b < D; ++b) X[a][b] = Y[a][b];
+    }
+    double n = 0.0;
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        double r = 0.0;
+#pragma unroll
+        for (int b = 0; b < D; ++b) r += fabs(X[a][b]);
+        n = fmax(n, r);
+    }
+    return sqrt(s * pow(n, 1.0 / 16.0));
 }
 
 template <int D, int DY>
@@ -2904,12 +3035,42 @@ __global__ void __launch_bounds__(64) k_smooth_tab_steps(SmoothTabParams q, cons
     double* row = q.gtab + t * ST::SIZE;
     const double* N = q.ntab + t * MT;
     const bool at_start = t % q.L == 0;  // at the segment's own start boundary the filtered mean is m_seg itself: no N term
+    if (q.rev) {   // reverse step t+1 → t:  m_f(t) = A⁻¹ (I + V_p(t+1) B'Q⁻¹B) m_f(t+1) − A⁻¹ V_p(t+1) B'Q⁻¹ y_{t+1}
+        double Am[D][D], Ai[D][D], Mr[D][D];
+#pragma unroll
+        for (int a = 0; a < D; ++a)
+#pragma unroll
+            for (int b = 0; b < D; ++b) Am[a][b] = c[CL::A + a * D + b];
+        const bool inv_ok = gen_inv<D>(Am, Ai);
+#pragma unroll
+        for (int a = 0; a < D; ++a)
+#pragma unroll
+            for (int b = 0; b < D; ++b) {
+                double acc = 0.0;
+#pragma unroll
+                for (int k = 0; k < D; ++k) {
+                    double phi = (k == b) ? 1.0 : 0.0;   // (I + V_p L)[k][b]
+#pragma unroll
+                    for (int j = 0; j < D; ++j) phi += Vp(k, j) * c[CL::LOBS + sidx(j, b)];
+                    acc += Ai[a][k] * phi;
+                }
+                Mr[a][b] = acc;
+            }
+        q.amp[t] = inv_ok ? spec_norm_bound<D>(Mr) : INFINITY;
+        if (t == 0) {
+#pragma unroll
+            for (int a = 0; a < D; ++a)
+#pragma unroll
+                for (int b = 0; b < D; ++b) q.ainv[a * D + b] = Ai[a][b];
+        }
+    }
 #pragma unroll
     for (int a = 0; a < D; ++a)
 #pragma unroll
         for (int b = 0; b < D; ++b) {
             double f = 0.0;
-            if (!at_start) {
+            if (q.rev) f = Vp(a, b);   // (the reverse sweep's F slot)
+            else if (!at_start) {
 #pragma unroll
                 for (int k = 0; k < D; ++k) f += E[a][k] * N[k * D + b];
             }
@@ -2944,6 +3105,26 @@ __global__ void __launch_bounds__(64) k_smooth_tab_compose(SmoothTabParams q) {
     const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     long long u0, u1;
     if (!smooth_block_range(q, id, u0, u1)) return;
+    if (q.rev) {
+        // worst window product of the per-step bounds for the strides K = 8, 16, 32.  Windows are aligned to the segment start
+        // (so none straddles a block): the reverse chain restarts at a row t with (t − t_b) % K == 0 and runs over the K − 1
+        // rows above it; factors below 1 count as 1, so the product bounds the growth from every row of the window.
+        double pk[3] = {1.0, 1.0, 1.0};
+        int fail = 0;
+        for (long long t = u0; t < u1; ++t) {
+            const double a = q.amp[t];
+            const double f = a >= 1.0 ? a : (a < 1.0 ? 1.0 : INFINITY);   // (NaN: no bound)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                if (((t - u0) & ((8LL << k) - 1)) == 0) pk[k] = 1.0;
+                else {
+                    pk[k] *= f;
+                    if (!(pk[k] <= REV_AMP_LIMIT)) fail |= 1 << k;
+                }
+            }
+        }
+        if (fail) atomicOr(q.ckfail, fail);
+    }
     double Ga[D][D], Ca[D][D];
     {
         const double* row = q.gtab + (u1 - 1) * ST::SIZE;
@@ -3218,6 +3399,207 @@ __global__ void __launch_bounds__(64) k_backward_sh(Params p, const double* __re
                 }
 #pragma unroll
                 for (int a = 0; a < D; ++a) ms[a] = mn[a];
+                write_out(t, row + ST::VS);
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (i0 + U < len) stash(b ^ 1);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+
+// Phase 4 for shared-model batches on the reverse-filter schedule: k_forward0<…, true> left z only at checkpoints (every K steps
+// of a segment and at its end), and this sweep rebuilds every other filtered mean by running the filter BACKWARD in time.
+// With V_p V_f⁻¹ = I + V_p B'Q⁻¹B the Kalman update inverts exactly:
+//     m_p(t+1) = m_f(t+1) + V_p(t+1) (B'Q⁻¹B m_f(t+1) − B'Q⁻¹ y_{t+1}),      m_f(t) = A⁻¹ m_p(t+1),
+// so the observations (8·dy B per step, the size of the z record at dy = d) replace the records, and the smoothed mean is
+//     m_s(t) = E_t m_f(t) + G_t m_s(t+1)
+// (table row t: E_t, V_p(t+1) in the F slot, G_t, V_s(t)).  The reverse chain restarts from every checkpoint (m_f = z + N_t m_seg)
+// and from m_seg at the segment start, so it never runs more than K − 1 steps; K is chosen at creation from the bound the
+// table kernels fold (REV_AMP_LIMIT).  Covariance stores and the table-row stream are those of k_backward_sh.
+template <int D, int DY>
+__global__ void __launch_bounds__(64) k_backward_sh_rev(Params p, const double* __restrict__ gtab, const double* __restrict__ segend,
+                                                        const CstArg<CstLayout<D, DY>::SIZE> cb) {
+    using ST = SmoothTab<D>;
+    using CL = CstLayout<D, DY>;
+    constexpr int MP2 = DimM<D>::MP2;
+    constexpr int MT = TimeTab<D>::MT;
+    constexpr int U = 4;                     // steps per table chunk
+    constexpr int RP = ST::SIZE / 2;         // 16-byte pieces per row
+    constexpr int NPC = U * RP;
+    constexpr int PPL = (NPC + 63) / 64;
+    constexpr int NMP = 32 * D;              // 16-byte pieces of the 64 means of a time index
+    constexpr int NCP = 32 * D * D;          // … of the 64 covariances
+    __shared__ double2 tbuf[2][NPC];
+    __shared__ double mtile[64 * D];
+    const int lane = threadIdx.x;
+    const long long g0 = (long long)blockIdx.x * 64;  // n_chains % 64 == 0: the wave holds 64 chains of ONE segment
+    const long long seg = g0 / p.n_chains;
+    const long long chain0 = g0 - seg * p.n_chains;
+    const long long chain = chain0 + lane;
+    const long long len = seg_len(p, seg);
+    const long long tb = seg * p.L, te = tb + len;
+    const CPtr c{cb.v};
+    const int lg = p.ck_log2;
+    const long long K = 1LL << lg;
+    // the checkpoint of time index t ∈ (tb, te]: slot 1 + seg·nck + (t − tb − 1)/K
+    auto load_ck = [&](long long t, double2 (&r)[MP2]) { load_filt_m_sh<D>(p, 1 + seg * p.nck + ((t - tb - 1) >> lg), chain, r); };
+    double mseg[D];
+    auto ck_mean = [&](const double2 (&r)[MP2], long long t, double (&mf)[D]) {   // m_f(t) = z_t + N_t m_seg
+        unpack_m_sh<D>(r, mf);
+        const double* N = p.ntab + t * MT;
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            double s = mf[i];
+#pragma unroll
+            for (int k = 0; k < D; ++k) s += N[i * D + k] * mseg[k];
+            mf[i] = s;
+        }
+    };
+
+    double mf[D], ms[D];
+    {
+        const double* q = p.fstart + (seg * Dim<D>::NP) * p.n_chains + chain;
+        const double* bq = p.beta + ((seg + 1) * Dim<D>::NP) * p.n_chains + chain;
+        double xb[D];
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            mseg[i] = q[i * p.n_chains];
+            xb[i] = bq[i * p.n_chains];
+        }
+        if (len > 0) {
+            double2 r[MP2];
+            load_ck(te, r);
+            ck_mean(r, te, mf);
+        } else {
+#pragma unroll
+            for (int i = 0; i < D; ++i) mf[i] = mseg[i];
+        }
+        const double* se = segend + seg * SegEndTab<D>::SIZE;
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < D; ++k) s += se[SegEndTab<D>::H1 + i * D + k] * mf[k] + se[SegEndTab<D>::H2 + i * D + k] * xb[k];
+            ms[i] = s;
+        }
+    }
+    auto write_out = [&](long long t, const double* vs) {
+#pragma unroll
+        for (int i = 0; i < D; ++i) mtile[lane * D + i] = ms[i];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        double2* om = reinterpret_cast<double2*>(p.mean + (t * p.n_chains + chain0) * D);
+        double2* oc = reinterpret_cast<double2*>(p.cov + (t * p.n_chains + chain0) * D * D);
+#pragma unroll
+        for (int k = 0; k < (NMP + 63) / 64; ++k) {
+            const int q = k * 64 + lane;
+            if (q < NMP) stream_store(om + q, mtile[2 * q], mtile[2 * q + 1]);
+        }
+#pragma unroll
+        for (int k = 0; k < (NCP + 63) / 64; ++k) {
+            const int q = k * 64 + lane;
+            if (q < NCP) stream_store(oc + q, vs[(2 * q) % (D * D)], vs[(2 * q + 1) % (D * D)]);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    };
+    if (seg == p.S - 1) write_out(te, gtab + te * ST::SIZE + ST::VS);
+
+    const double2* g2 = reinterpret_cast<const double2*>(gtab);
+    double2 tr[PPL];
+    auto fetch = [&](long long i0) {
+#pragma unroll
+        for (int k = 0; k < PPL; ++k) {
+            const int idx = k * 64 + lane;
+            const long long r = i0 + idx / RP;  // step index
+            tr[k] = (idx < NPC && r < len) ? g2[(te - 1 - r) * RP + idx % RP] : make_double2(0.0, 0.0);
+        }
+    };
+    auto stash = [&](int b) {
+#pragma unroll
+        for (int k = 0; k < PPL; ++k) {
+            const int idx = k * 64 + lane;
+            if (idx < NPC) tbuf[b][idx] = tr[k];
+        }
+    };
+    fetch(0);
+    stash(0);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    // the next checkpoint below te (a multiple of K past tb; none when it would be tb itself), prefetched a whole window ahead
+    long long tc = len > 0 ? tb + (((len - 1) >> lg) << lg) : tb;
+    double2 rc[MP2];
+    if (tc > tb) load_ck(tc, rc);
+    double yn[DY];   // y_{t+1} of the next step, one step ahead
+    if (len > 0) load_y<DY>(p.y, te, p.n_chains, chain, yn);
+    int b = 0;
+    for (long long i0 = 0; i0 < len; i0 += U, b ^= 1) {  // `len` is uniform across the wave
+        if (i0 + U < len) fetch(i0 + U);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const long long i = i0 + u;
+            if (i < len) {
+                const long long t = te - 1 - i;
+                const double* row = reinterpret_cast<const double*>(&tbuf[b][0]) + u * ST::SIZE;
+                double yb[DY];
+#pragma unroll
+                for (int k = 0; k < DY; ++k) yb[k] = yn[k];
+                if (t > tb) load_y<DY>(p.y, t, p.n_chains, chain, yn);
+                double mfn[D];
+                if (t == tb) {   // the start boundary: the scan's own filtered mean
+#pragma unroll
+                    for (int k = 0; k < D; ++k) mfn[k] = mseg[k];
+                } else if (t == tc) {   // a checkpoint: restart the reverse chain
+                    ck_mean(rc, t, mfn);
+                    tc -= K;
+                    if (tc > tb) load_ck(tc, rc);
+                } else {
+                    double w[D], mp[D];
+#pragma unroll
+                    for (int a = 0; a < D; ++a) {   // w = B'Q⁻¹B m_f − B'Q⁻¹ y
+                        double s = 0.0;
+#pragma unroll
+                        for (int k = 0; k < D; ++k) s += c[CL::LOBS + sidx(a, k)] * mf[k];
+#pragma unroll
+                        for (int k = 0; k < DY; ++k) s -= c[CL::G + a * DY + k] * yb[k];
+                        w[a] = s;
+                    }
+#pragma unroll
+                    for (int a = 0; a < D; ++a) {   // m_p(t+1) = m_f(t+1) + V_p(t+1) w
+                        double s = mf[a];
+#pragma unroll
+                        for (int k = 0; k < D; ++k) s += row[ST::F + a * D + k] * w[k];
+                        mp[a] = s;
+                    }
+#pragma unroll
+                    for (int a = 0; a < D; ++a) {   // m_f(t) = A⁻¹ m_p(t+1)  (wave-uniform loads, kept out of the VGPRs)
+                        double s = 0.0;
+#pragma unroll
+                        for (int k = 0; k < D; ++k) s += p.ainv[a * D + k] * mp[k];
+                        mfn[a] = s;
+                    }
+                }
+                double mn[D];
+#pragma unroll
+                for (int a = 0; a < D; ++a) {
+                    double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+                    for (int k = 0; k < D; ++k) {
+                        s0 += row[ST::E + a * D + k] * mfn[k];
+                        s1 += row[ST::G + a * D + k] * ms[k];
+                    }
+                    mn[a] = s0 + s1;
+                }
+#pragma unroll
+                for (int a = 0; a < D; ++a) {
+                    ms[a] = mn[a];
+                    mf[a] = mfn[a];
+                }
                 write_out(t, row + ST::VS);
             }
         }

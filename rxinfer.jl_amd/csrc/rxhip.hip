@@ -1526,7 +1526,8 @@ static bool engine_pool_key(const rxhip_lgssm_desc* ds, std::string& key) {
     put(hdr, sizeof hdr);
     const size_t d = (size_t)ds->d, dy = (size_t)ds->dy;
     put(ds->A, 8 * d * d); put(ds->B, 8 * dy * d); put(ds->P, 8 * d * d); put(ds->Q, 8 * dy * dy); put(ds->m0, 8 * d); put(ds->V0, 8 * d * d);
-    for (const char* name : {"RXHIP_ONE_PASS", "RXHIP_ONE_SEGMENT", "RXHIP_SMALL_SWEEP", "RXHIP_BACKWARD_LANES", "RXHIP_HOST_TABLES"}) {   // schedule hooks read at creation
+    for (const char* name : {"RXHIP_ONE_PASS", "RXHIP_ONE_SEGMENT", "RXHIP_SMALL_SWEEP", "RXHIP_BACKWARD_LANES", "RXHIP_HOST_TABLES", "RXHIP_MEAN_RECORDS",
+                             "RXHIP_MEAN_CHECKPOINT"}) {   // schedule hooks read at creation
         const char* v = hook_env(name);
         key.push_back('|');
         if (v) key.append(v);
@@ -2209,6 +2210,19 @@ rxhip_status rxhip_lgssm_create(const rxhip_lgssm_desc* ds, rxhip_engine** out) 
         ap.upload(&e->d_cy_raw, e->h_cy.data(), sizeof(double) * e->h_cy.size());
     }
     if (e->uniform && !scan.empty()) ap.upload(&e->d_scan, scan.data(), sizeof(double) * scan.size());
+    // Reverse-filter candidates (k_backward_sh_rev): the table-driven backward sweep, no more observation than
+    // state components (the observations it reads instead of the z records are not larger).  The stride is chosen below, once
+    // the tables exist; RXHIP_MEAN_RECORDS=1 keeps a record per time index, RXHIP_MEAN_CHECKPOINT=K forces the stride K.
+    const char* rec_env = hook_env("RXHIP_MEAN_RECORDS");
+    const char* ck_env = hook_env("RXHIP_MEAN_CHECKPOINT");
+    int ck_forced = 0;
+    if (ck_env) {
+        ck_forced = std::atoi(ck_env);
+        if (ck_forced < 1 || ck_forced > 32 || (ck_forced & (ck_forced - 1)))
+            return fail(e, RXHIP_ERR_BADARG, "RXHIP_MEAN_CHECKPOINT=%s: a power of two from 1 to 32", ck_env);
+    }
+    const bool rev_cand = e->fused && C % 64 == 0 && !hook_env("RXHIP_BACKWARD_LANES") && e->dy <= e->d && e->T > 1 &&
+                          !(rec_env && std::atoi(rec_env) != 0);
     if (e->fused) {
         ap.upload(&e->d_ftab, ft.ftab.data(), sizeof(double) * ft.ftab.size());
         ap.upload(&e->d_pos, ft.pos.data(), sizeof(double) * ft.pos.size());
@@ -2220,6 +2234,11 @@ rxhip_status rxhip_lgssm_create(const rxhip_lgssm_desc* ds, rxhip_engine** out) 
             ap.plain(&e->d_segend, sizeof(double) * Sg * vt->se_size);
             ap.plain(&e->d_sblk, sizeof(double) * Sg * (size_t)smooth_blocks_per_segment(e->L) * 3 * e->d * e->d);
         }
+        if (rev_cand) {
+            ap.plain(&e->d_amp, sizeof(double) * T);
+            ap.zeroed(&e->d_ainv, sizeof(double) * e->d * e->d);
+            ap.zeroed(&e->d_ckfail, sizeof(int));
+        }
     }
     ap.zeroed_last(&e->d_status, sizeof(int));   // status | mean | cov | fe_chain: one span (rxhip_lgssm_infer reads it back with one copy)
     ap.zeroed(&e->d_fe_part, sizeof(double) * (Sg + 2) * C);   // one slot per segment + the t = 0 update (+ the Wishart slot of a noise engine)
@@ -2228,7 +2247,7 @@ rxhip_status rxhip_lgssm_create(const rxhip_lgssm_desc* ds, rxhip_engine** out) 
     ap.plain(&e->d_fe_blocks, sizeof(double) * ((C + 63) / 64));
     if (e->uniform) {  // mean part per chain + one covariance copy per model (see lgssm_kernels.hpp store_filt_sh)
         const size_t MP2 = ((size_t)e->d + 1) / 2;
-        ap.plain(&e->d_filt, sizeof(double) * T * MP2 * 2 * (((C + 63) / 64) * 64));
+        if (!rev_cand) ap.plain(&e->d_filt, sizeof(double) * T * MP2 * 2 * (((C + 63) / 64) * 64));   // (else sized by the stride, below)
         ap.plain(&e->d_vtab, sizeof(double) * T * ((size_t)e->d * (e->d + 1) / 2));
     } else
         ap.plain(&e->d_filt, sizeof(double) * T * NP2 * 2 * (((C + 63) / 64) * 64));
@@ -2259,13 +2278,36 @@ rxhip_status rxhip_lgssm_create(const rxhip_lgssm_desc* ds, rxhip_engine** out) 
             SmoothTabParams sq{};
             sq.T = e->T; sq.L = e->L; sq.S = e->S; sq.vtab = e->d_vtab; sq.ntab = e->d_ntab; sq.scan = e->d_scan;
             sq.gtab = e->d_gtab; sq.segend = e->d_segend; sq.blk = e->d_sblk; sq.status = e->d_status;
+            sq.rev = rev_cand ? 1 : 0; sq.amp = e->d_amp; sq.ainv = e->d_ainv; sq.ckfail = e->d_ckfail;
             vt->smooth_tables(sq, e->h_cst0.data(), e->stream);
+            if (rev_cand) {   // the largest stride whose windows all pass the bound (one word: a bit per failing stride 8, 16, 32)
+                int ckfail = 0;
+                HIPCHK(e, hipMemcpyAsync(&ckfail, e->d_ckfail, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+                HIPCHK(e, hipStreamSynchronize(e->stream));
+                e->ck_log2 = 0;
+                if (ck_forced) {
+                    while ((1 << e->ck_log2) < ck_forced) ++e->ck_log2;
+                } else {
+                    for (int k = 2; k >= 0 && !e->ck_log2; --k)
+                        if (!((ckfail >> k) & 1)) e->ck_log2 = 3 + k;
+                }
+                if (!e->ck_log2) {   // no admissible stride: the records schedule, whose F slot holds F_t (rebuild the rows)
+                    sq.rev = 0;
+                    vt->smooth_tables(sq, e->h_cst0.data(), e->stream);
+                }
+            }
         }
         HIPCHK(e, hipEventRecord(e->ev_tab1, e->stream));
         // no synchronisation here: the table kernels are ordered before every sweep on the engine's stream, and a covariance
         // that is not positive definite raises the status flag the first run reports (RXHIP_ERR_NOT_POSDEF)
         HIPCHK(e, hipGetLastError());
         tr.mark("lanes: device tables (enqueued)", STAGE_TABLES_DEVICE);
+    }
+    if (rev_cand) {   // z records: one slot per checkpoint (+ the t = 0 record of the boundary scan), or one per time index
+        const size_t MP2 = ((size_t)e->d + 1) / 2;
+        if (e->ck_log2) e->nck = (e->L + (1LL << e->ck_log2) - 1) >> e->ck_log2;
+        const size_t slots = e->ck_log2 ? 1 + Sg * (size_t)e->nck : T;
+        HIPCHK(e, hipMalloc(&e->d_filt, sizeof(double) * slots * MP2 * 2 * (((C + 63) / 64) * 64)));
     }
     return RXHIP_OK;
 }
@@ -2692,6 +2734,9 @@ static rxhip_status run_impl(rxhip_engine* e, int32_t iterations, int32_t want_f
     p.y = e->d_y;
     p.filt = e->d_filt;
     p.nb64 = (e->n_chains + 63) / 64;
+    p.ck_log2 = e->ck_log2;
+    p.nck = e->nck;
+    p.ainv = e->d_ainv;
     p.vtab = e->d_vtab;
     p.scan = e->d_scan;
     p.mean = e->d_mean;
@@ -2839,7 +2884,7 @@ static rxhip_status run_impl(rxhip_engine* e, int32_t iterations, int32_t want_f
             }
         } else if (fused) {  // one pass over the observations: known-start recursion + z_t records + evidence parts
             if ((st = prof_begin(e, RXHIP_K_FORWARD))) return st;
-            e->vt->forward0(p, e->h_cst0.data(), fe, e->stream);
+            e->vt->forward0(p, e->h_cst0.data(), fe, e->ck_log2 > 0, e->stream);
             if ((st = prof_end(e))) return st;
         } else if (small_now) {   // a few chains, a short series: aggregate, boundary scan, forward, backward and the free energy in ONE launch
             e->vt->small_sweep(p, e->h_cst0.data(), fe, e->stream);
@@ -2867,7 +2912,7 @@ static rxhip_status run_impl(rxhip_engine* e, int32_t iterations, int32_t want_f
                 e->vt->fe_seg(p, e->stream);
             if (!filter) {
                 if ((st = prof_begin(e, RXHIP_K_BACKWARD))) return st;
-                if (fused && e->d_gtab) e->vt->backward_sh(p, e->d_gtab, e->d_segend, e->stream);
+                if (fused && e->d_gtab) e->vt->backward_sh(p, e->h_cst0.data(), e->d_gtab, e->d_segend, e->ck_log2 > 0, e->stream);
                 else e->vt->backward(p, e->h_cst0.data(), e->uniform, e->stream);
                 if ((st = prof_end(e))) return st;
             }
@@ -3341,6 +3386,12 @@ rxhip_status rxhip_get_create_stages(rxhip_engine* e, double* ms4) {
     TREE_GUARD(e);
     if (!e || !ms4) return RXHIP_ERR_BADARG;
     for (int q = 0; q < STAGE_COUNT; ++q) ms4[q] = e->stage_ms[q];
+    return RXHIP_OK;
+}
+rxhip_status rxhip_get_mean_checkpoint_stride(rxhip_engine* e, int32_t* K) {
+    TREE_GUARD(e);
+    if (!e || !K) return RXHIP_ERR_BADARG;
+    *K = e->ck_log2 ? (int32_t)1 << e->ck_log2 : 0;
     return RXHIP_OK;
 }
 rxhip_status rxhip_get_model_tables_ms(rxhip_engine* e, double* ms) {

@@ -80,9 +80,12 @@ struct Launch {
         else if (p.tinv_records) hipLaunchKernelGGL((k_backward_tinv<D, DY>), grid, dim3(64), 0, s, p);
         else hipLaunchKernelGGL((k_backward<D, DY, false>), grid, dim3(64), 0, s, p, CstArg<1>{});
     }
-    static void forward0(const Params& p, const double* hc, bool fe, hipStream_t s) {
+    static void forward0(const Params& p, const double* hc, bool fe, bool ck, hipStream_t s) {   // ck: z at checkpoints only
         const long long total = p.n_chains * (long long)p.S;
-        if (fe) hipLaunchKernelGGL((k_forward0<D, DY, true>), dim3(nblk(total, 64)), dim3(64), 0, s, p, carg(hc));
+        if (ck) {
+            if (fe) hipLaunchKernelGGL((k_forward0<D, DY, true, true>), dim3(nblk(total, 64)), dim3(64), 0, s, p, carg(hc));
+            else hipLaunchKernelGGL((k_forward0<D, DY, false, true>), dim3(nblk(total, 64)), dim3(64), 0, s, p, carg(hc));
+        } else if (fe) hipLaunchKernelGGL((k_forward0<D, DY, true>), dim3(nblk(total, 64)), dim3(64), 0, s, p, carg(hc));
         else hipLaunchKernelGGL((k_forward0<D, DY, false>), dim3(nblk(total, 64)), dim3(64), 0, s, p, carg(hc));
     }
     static void time_tables(const TimeTabParams& q, hipStream_t s) {
@@ -98,8 +101,9 @@ struct Launch {
         hipLaunchKernelGGL((k_smooth_tab_chain<D>), dim3(nblk(q.S, 64)), dim3(64), 0, s, q);
         hipLaunchKernelGGL((k_smooth_tab_apply<D>), dim3(nblk(nblocks, 64)), dim3(64), 0, s, q);
     }
-    static void backward_sh(const Params& p, const double* gtab, const double* segend, hipStream_t s) {
-        hipLaunchKernelGGL((k_backward_sh<D>), dim3((unsigned)(p.n_chains / 64 * p.S)), dim3(64), 0, s, p, gtab, segend);
+    static void backward_sh(const Params& p, const double* hc, const double* gtab, const double* segend, bool rev, hipStream_t s) {
+        if (rev) hipLaunchKernelGGL((k_backward_sh_rev<D, DY>), dim3((unsigned)(p.n_chains / 64 * p.S)), dim3(64), 0, s, p, gtab, segend, carg(hc));
+        else hipLaunchKernelGGL((k_backward_sh<D>), dim3((unsigned)(p.n_chains / 64 * p.S)), dim3(64), 0, s, p, gtab, segend);
     }
     static void forecast(const PredictParams& p, hipStream_t s) {
         hipLaunchKernelGGL((k_forecast<D, DY>), dim3(nblk(p.n_chains, 64)), dim3(64), 0, s, p);

@@ -282,6 +282,13 @@ class LGSSMEngine:
         self._chk(_lib.lib().rxhip_get_model_tables_ms(self._h, ctypes.byref(ms)))
         return ms.value
 
+    def mean_checkpoint_stride(self):
+        """checkpoint stride K of the reverse-filter backward sweep; 0: a filtered-mean record per time index
+        (rxhip_get_mean_checkpoint_stride)"""
+        k = ctypes.c_int32()
+        self._chk(_lib.lib().rxhip_get_mean_checkpoint_stride(self._h, ctypes.byref(k)))
+        return k.value
+
     def create_stages(self):
         """host milliseconds of the engine's creation by stage (rxhip_get_create_stages)"""
         ms = (ctypes.c_double * 4)()
