@@ -299,6 +299,11 @@ typedef struct {
      * rxhip_tree_create and rxhip_tree_plan — never silently the other variational family's posterior.  NULL = the factorisation above (joint Gaussian
      * interfaces), which is what GraphPPL's default constraints (BetheFactorization) produce for the BP families. */
     const int32_t* factor_cluster;
+    /* `@initialization μ(v) = D` (InitMsgExtraKey): NULL, or per variable RXHIP_INIT_NORMAL / RXHIP_INIT_MVNORMAL (else RXHIP_INIT_NONE) and the offset of
+     * D's parameters (mean, covariance) in const_pool (−1: none).  The node-array executor reads it as the initial value of the factor → variable messages
+     * into v whose edge lies on a cycle: its loopy schedule (below).  Every other engine ignores it. */
+    const int32_t* var_msg_init_family;
+    const int64_t* var_msg_init;
 } rxhip_graph_desc;
 
 /* result of the lowering pass for the LGSSM family; matrices are written into caller buffers of the sizes below
@@ -418,7 +423,7 @@ rxhip_status rxhip_create(const rxhip_graph_desc* g, int32_t segments, int32_t d
  *         message — q(z) is its product with all other messages into z, moment-matched by Gauss–Hermite cubature (rxhip_graph_desc.gh_points, default 31) against
  *         that product, and z's neighbours (structured Gaussian nodes only) see the message through its Gaussian moments, as the reference does;
  *     scalar Gaussian nodes whose variance / precision is a DATA variable (`x ~ Normal(mean = m_prev, var = v_prev)` of a model driven by @autoupdates)
- * whose Gaussian variables form a forest (no cycles; precision variables may touch any number of nodes — the mean-field factorisation cuts those
+ * whose Gaussian variables form a forest (no cycles, or cycles a message initialisation cuts: "Loopy graphs" below; precision variables may touch any number of nodes — the mean-field factorisation cuts those
  * loops; no Gaussian variable at all is a forest too: `P ~ Wishart; y[i] ~ MvNormal(μ = m, Λ = P)` with a known mean,
  * test/models/iid/mv_iid_precision_known_mean_tests.jl), every dimension ≤ 64.  Factorisation (rxhip_graph_desc.factor_cluster): a Gaussian node under
  * q(out, μ) — structured, the default — or under q(out) q(μ) (`constraints = MeanField()`): its rules then read MARGINALS,
@@ -445,6 +450,21 @@ rxhip_status rxhip_create(const rxhip_graph_desc* g, int32_t segments, int32_t d
  * observation map with fewer rows than columns (where `mean_cov` of the reference throws).
  * Iterations (VMP): per iteration one sum-product sweep with E[W] of the current q(W), all marginals, then every q(W) update, then the free energy —
  * the order of rxhip_lgssm_noise_create above.  A run starts from the `@initialization` marginals (default: the priors).
+ * Loopy graphs (rxhip_graph_desc.var_msg_init): a cycle among the Gaussian variables is cut by a message initialisation `μ(v) = D` on a variable of the cycle.
+ * The cut messages — LOOP messages — are the factor → variable messages into v whose edge is not a bridge of the Gaussian factor graph (a node under
+ * q(out) q(μ) counts as two leaf factors there, as above).  In every iteration each reader of a loop message takes the value of the previous iteration (the
+ * first iteration reads D), the message is computed again by its ordinary rule, and that new value is what the next iteration reads; every other message is
+ * scheduled in dependency levels as on a forest.  Marginals and Bethe terms at the end of an iteration read the latest value of every message (for a loop
+ * message: the one just computed); the free-energy terms are the node-local ones of the forest (below).
+ * This reading of InitMsgExtraKey ("the initial value of the variable's inbound messages on its cycles") is an assumption of this executor, as the VMP
+ * update order is; what the tests pin is the fixed point — converged means equal exact conditioning (Weiss & Freeman 2001) — not the reference's
+ * per-iteration trajectory.  A dependency cycle that no initialisation cuts is RXHIP_ERR_UNSUPPORTED with "cycle" and a variable of the loop in the text;
+ * an initialisation on a variable that lies on no cycle has no effect (a forest runs bit for bit as without it); initialisations on precision, discrete
+ * or GCV variables, and loop messages in a graph with NormalMixture / GCV nodes, Wishart / Gamma precision variables or Gaussian nodes under q(out) q(μ),
+ * are RXHIP_ERR_UNSUPPORTED.  Every dimension ≤ 64 and every kernel family run it; the free energy is the forest's node-local sum on the values the
+ * schedule reads — v2f messages from the previous iteration's loop values, marginals from the new ones — which equals the Bethe free energy at a fixed
+ * point (node beliefs then agree with the marginals), not before.  rxhip_tree_continue carries the loop
+ * messages from one run to the next, as it carries q(W).
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
     int64_t n_ops, n_levels, n_messages;  /* ops of one iteration, dependency levels, stored messages */
@@ -466,6 +486,7 @@ typedef struct {
                                              2: a workgroup of four wavefronts per (op, replica), matrices staged in LDS (33 … 64); −1 from rxhip_tree_plan (chosen with the batch) */
     int64_t strand_bytes_per_sweep;       /* bytes_per_sweep of the strand schedule, whichever mode runs */
     int64_t fe_bytes_per_sweep;           /* what the second phase (Bethe terms, q(W) updates, the sum) reads and writes per replica: messages, marginals, data values, terms, statistics */
+    int64_t n_loop_messages;              /* messages the loopy schedule carries from one iteration to the next (0: the Gaussian variables form a forest) */
 } rxhip_tree_info;
 rxhip_status rxhip_tree_create(const rxhip_graph_desc* g, int32_t device, void* stream, rxhip_engine** out);
 /* The graph compiler alone — host only, no device: would rxhip_tree_create take this graph, and with what schedule?  Fills the static fields of `out`
@@ -486,7 +507,7 @@ rxhip_status rxhip_tree_get_precision(rxhip_engine* e, int64_t var, double* nu, 
 rxhip_status rxhip_tree_get_discrete(rxhip_engine* e, int64_t var, double* out, int32_t* n_components);
 rxhip_status rxhip_tree_get_info(rxhip_engine* e, rxhip_tree_info* out);
 /* on != 0: every later rxhip_run CONTINUES from the q(W) the previous run ended with instead of the `@initialization` marginals (the first run still
- * starts there) — for drivers that take one VMP iteration per call, as the loop of src/inference/batch.jl:391-430 does (the plugin's `fire!`):
+ * starts there; the loop messages of a loopy schedule are carried alike) — for drivers that take one VMP iteration per call, as the loop of src/inference/batch.jl:391-430 does (the plugin's `fire!`):
  * k calls of rxhip_run(1) then equal one rxhip_run(k), bit for bit.  The twin of rxhip_lgssm_noise_continue. */
 rxhip_status rxhip_tree_continue(rxhip_engine* e, int32_t on);
 /* rxhip_run, rxhip_get_free_energy (sum over the replicas, per iteration), rxhip_get_free_energy_per_chain (per replica, last iteration),

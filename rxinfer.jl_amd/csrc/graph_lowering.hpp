@@ -256,8 +256,8 @@ inline int spd_inverse_checked(int d, const double* W, std::vector<double>& inv)
 }
 struct NormalisedGraph {
     rxhip_graph_desc g;
-    std::vector<int32_t> var_kind, var_rows, var_cols, factor_type, var_init_family;
-    std::vector<int64_t> var_const, factor_iface, var_init;
+    std::vector<int32_t> var_kind, var_rows, var_cols, factor_type, var_init_family, var_msg_init_family;
+    std::vector<int64_t> var_const, factor_iface, var_init, var_msg_init;
     std::vector<double> pool;
 };
 inline rxhip_status normalise_precision_nodes(const rxhip_graph_desc* g0, NormalisedGraph& N, bool& changed) {
@@ -280,6 +280,10 @@ inline rxhip_status normalise_precision_nodes(const rxhip_graph_desc* g0, Normal
     N.pool.assign(g0->const_pool, g0->const_pool + g0->n_const);
     if (g0->var_init_family) N.var_init_family.assign(g0->var_init_family, g0->var_init_family + NV);
     if (g0->var_init) N.var_init.assign(g0->var_init, g0->var_init + NV);
+    if (g0->var_msg_init_family && g0->var_msg_init) {
+        N.var_msg_init_family.assign(g0->var_msg_init_family, g0->var_msg_init_family + NV);
+        N.var_msg_init.assign(g0->var_msg_init, g0->var_msg_init + NV);
+    }
     for (long long f = 0; f < NF; ++f) {
         const int t = g0->factor_type[f];
         if (t != RXHIP_NODE_NORMAL_MEAN_PRECISION && t != RXHIP_NODE_MVNORMAL_MEAN_PRECISION) continue;
@@ -301,6 +305,7 @@ inline rxhip_status normalise_precision_nodes(const rxhip_graph_desc* g0, Normal
         N.var_const.push_back((long long)N.pool.size());
         if (!N.var_init_family.empty()) N.var_init_family.push_back(RXHIP_INIT_NONE);
         if (!N.var_init.empty()) N.var_init.push_back(-1);
+        if (!N.var_msg_init.empty()) { N.var_msg_init_family.push_back(RXHIP_INIT_NONE); N.var_msg_init.push_back(-1); }
         N.pool.insert(N.pool.end(), inv.begin(), inv.end());
         N.factor_iface[(size_t)3 * f + 2] = nv;
         N.factor_type[f] = t == RXHIP_NODE_NORMAL_MEAN_PRECISION ? RXHIP_NODE_NORMAL_MEAN_VARIANCE : RXHIP_NODE_MVNORMAL_MEAN_COV;
@@ -312,6 +317,8 @@ inline rxhip_status normalise_precision_nodes(const rxhip_graph_desc* g0, Normal
     N.g.const_pool = N.pool.data(); N.g.n_const = (long long)N.pool.size();
     N.g.var_init_family = N.var_init_family.empty() ? nullptr : N.var_init_family.data();
     N.g.var_init = N.var_init.empty() ? nullptr : N.var_init.data();
+    N.g.var_msg_init_family = N.var_msg_init.empty() ? nullptr : N.var_msg_init_family.data();
+    N.g.var_msg_init = N.var_msg_init.empty() ? nullptr : N.var_msg_init.data();
     return RXHIP_OK;
 }
 
@@ -747,6 +754,8 @@ inline rxhip_status lower_lgssm_noise(const rxhip_graph_desc* g, LgssmNoise& L) 
     N.g = *g;
     N.g.n_variables = (long long)N.var_kind.size();
     N.g.n_factors = NF - 1;
+    N.g.var_msg_init_family = nullptr;   // (the chain lowering reads no message initialisation; the tables above have another length)
+    N.g.var_msg_init = nullptr;
     N.g.var_kind = N.var_kind.data(); N.g.var_rows = N.var_rows.data(); N.g.var_cols = N.var_cols.data(); N.g.var_const = N.var_const.data();
     N.g.factor_type = N.factor_type.data(); N.g.factor_iface = N.factor_iface.data();
     N.g.const_pool = N.pool.data(); N.g.n_const = (long long)N.pool.size();

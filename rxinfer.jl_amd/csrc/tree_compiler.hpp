@@ -129,6 +129,12 @@ struct Program {
     bool fe_heavy = false;   // the second phase holds OP_FE_ADD2 or OP_PREC_UPDATE ops (else the light kernel instance runs it)
     int n_push = 0, lazy_level = -1;   // marginals stored as images of other marginals (OP_MARG_PUSH): a level of their own behind everything a run executes, launched on demand
     std::vector<char> is_push;         // per variable
+    // the loopy schedule (build_edges): n_loop messages whose readers take the previous iteration's value.  Their old values sit in the message slots
+    // [0, loop_doubles) — broadcast from loop_init at the start of a run — and their producers write [loop_doubles, 2·loop_doubles) in the same order:
+    // one copy per iteration (k_tree_carry) hands the new values over
+    int n_loop = 0;
+    long long loop_doubles = 0;
+    std::vector<double> loop_init;     // [loop_doubles] D of every loop message, in the form the message is stored in
 };
 
 struct Compiler {
@@ -463,6 +469,7 @@ struct Compiler {
         }
         var_edges.assign(nv, {});
         fac_edges.assign(nf, std::vector<int>(3, -1));
+        for (int64_t v = 0; v < g->n_variables && !msg_inits; ++v) msg_inits = msg_init_family(v) != RXHIP_INIT_NONE;
         std::vector<int> uf(nv + 2 * nf);   // (a node under q(out) q(μ) is two leaf factors as far as cycles go: its interfaces do not exchange messages)
         std::iota(uf.begin(), uf.end(), 0);
         auto find = [&](int x) { while (uf[x] != x) { uf[x] = uf[uf[x]]; x = uf[x]; } return x; };
@@ -475,7 +482,7 @@ struct Compiler {
                 const int v = (int)iface((int)f, k);
                 if (P.vclass[v] != VC_GAUSS) continue;
                 const int ra = find(v), rb = find((int)(nv + f + ((mf[f] && k == 1) ? nf : 0)));
-                if (ra == rb) fail(RXHIP_ERR_UNSUPPORTED, "the Gaussian variables do not form a tree (a cycle through variable %d): loopy graphs have no exact schedule", v);
+                if (ra == rb && !msg_inits) fail(RXHIP_ERR_UNSUPPORTED, "the Gaussian variables do not form a tree (a cycle through variable %d): loopy graphs have no exact schedule", v);
                 uf[ra] = rb;
                 fac_edges[f][k] = (int)edges.size();
                 var_edges[v].push_back((int)edges.size());
@@ -488,6 +495,91 @@ struct Compiler {
         // (no Gaussian variable but a precision variable: `y[i] ~ MvNormal(μ = m, Λ = P)` with a KNOWN mean, test/models/iid/mv_iid_precision_known_mean_tests.jl —
         //  no message at all, the schedule is the nodes' residual moments, the q(W) updates and the Bethe sum)
         if (E == 0 && !any_prec) fail(RXHIP_ERR_UNSUPPORTED, "no random variable of the Gaussian / Wishart / Gamma family in the graph");
+        loop_.assign((size_t)2 * E, 0);
+        if (msg_inits) mark_loop_messages();
+    }
+
+    // ---- the loopy schedule: `μ(v) = D` cuts the factor → variable messages into v whose edge lies on a cycle (is not a bridge) ----
+    bool msg_inits = false;            // the descriptor carries message initialisations
+    std::vector<char> loop_;           // per message: a loop message (f2v only)
+    std::vector<int> new_off;          // per message: where a loop message's producer writes (−1)
+    int msg_init_family(int64_t v) const {
+        return (g->var_msg_init_family && g->var_msg_init && g->var_msg_init[v] >= 0) ? g->var_msg_init_family[v] : (int)RXHIP_INIT_NONE;
+    }
+    void mark_loop_messages() {
+        // bridges of the Gaussian factor graph (variables and factors as vertices; a node under q(out) q(μ) is two leaf factors): iterative Tarjan on edge ids
+        const int NVX = (int)(nv + 2 * nf);
+        std::vector<std::vector<std::pair<int, int>>> adj((size_t)NVX);
+        auto fnode = [&](const Edge& ed) { return (int)(nv + ed.f + ((mf[ed.f] && ed.k == 1) ? nf : 0)); };
+        for (int e = 0; e < E; ++e) {
+            adj[edges[e].v].push_back({fnode(edges[e]), e});
+            adj[fnode(edges[e])].push_back({edges[e].v, e});
+        }
+        std::vector<int> tin((size_t)NVX, -1), low((size_t)NVX, 0);
+        std::vector<char> bridge((size_t)E, 0);
+        int timer = 0;
+        struct Frame { int u, pe; size_t i; };
+        std::vector<Frame> st;
+        for (int s0 = 0; s0 < NVX; ++s0) {
+            if (tin[s0] >= 0 || adj[s0].empty()) continue;
+            tin[s0] = low[s0] = timer++;
+            st.push_back({s0, -1, 0});
+            while (!st.empty()) {
+                Frame& fr = st.back();
+                if (fr.i < adj[fr.u].size()) {
+                    const auto nb = adj[fr.u][fr.i++];
+                    if (nb.second == fr.pe) continue;
+                    if (tin[nb.first] >= 0) low[fr.u] = std::min(low[fr.u], tin[nb.first]);
+                    else {
+                        tin[nb.first] = low[nb.first] = timer++;
+                        st.push_back({nb.first, nb.second, 0});
+                    }
+                } else {
+                    const Frame done_fr = fr;
+                    st.pop_back();
+                    if (!st.empty()) {
+                        const int p = st.back().u;
+                        low[p] = std::min(low[p], low[done_fr.u]);
+                        if (low[done_fr.u] > tin[p]) bridge[done_fr.pe] = 1;
+                    }
+                }
+            }
+        }
+        for (int64_t v = 0; v < nv; ++v) {
+            const int fam = msg_init_family(v);
+            if (fam == RXHIP_INIT_NONE) continue;
+            if (P.vclass[v] == VC_PREC || P.vclass[v] == VC_CAT || P.vclass[v] == VC_DIR || gcv_z[v])
+                fail(RXHIP_ERR_UNSUPPORTED, "message initialisation on variable %lld: only Gaussian variables take one here (not precision, discrete or GCV volatility variables)", (long long)v);
+            if (P.vclass[v] != VC_GAUSS) fail(RXHIP_ERR_BADARG, "message initialisation on variable %lld, which is not a random variable", (long long)v);
+            const int d = P.dim[v];
+            if (!(fam == RXHIP_INIT_MVNORMAL || (fam == RXHIP_INIT_NORMAL && d == 1))) fail(RXHIP_ERR_BADARG, "message initialisation on variable %lld: Normal (scalars) or MvNormal expected", (long long)v);
+            if (g->var_msg_init[v] + (int64_t)d + (int64_t)d * d > g->n_const) fail(RXHIP_ERR_BADARG, "message initialisation on variable %lld: parameters outside the pool", (long long)v);
+            for (int e : var_edges[v])
+                if (!bridge[e]) { loop_[e] = 1; ++P.n_loop; }
+        }
+        if (P.n_loop && (P.has_mix || P.has_gcv)) fail(RXHIP_ERR_UNSUPPORTED, "a loopy schedule through a graph with NormalMixture or GCV nodes");
+        if (P.n_loop) {   // (what the loopy schedule is tested on: Gaussian sum-product without VMP state)
+            for (int64_t v = 0; v < nv; ++v)
+                if (P.vclass[v] == VC_PREC) fail(RXHIP_ERR_UNSUPPORTED, "a loopy schedule in a graph with Wishart / Gamma precision variables (variable %lld)", (long long)v);
+            if (P.has_mf) fail(RXHIP_ERR_UNSUPPORTED, "a loopy schedule in a graph with Gaussian nodes under q(out) q(μ)");
+        }
+    }
+    // D of loop message e in the form the message is stored in: (m, V) or (V⁻¹ m, V⁻¹), lower triangles packed row-major
+    void loop_init_values(int e, double* out) {
+        const int v = edges[e].v, d = P.dim[v];
+        const double* q = g->const_pool + g->var_msg_init[v];
+        std::vector<double> V(q + d, q + d + (size_t)d * d), W((size_t)d * d);
+        for (int i = 0; i < d; ++i)
+            for (int j = 0; j < d; ++j) V[(size_t)i * d + j] = 0.5 * (q[d + i * d + j] + q[d + j * d + i]);
+        if (!host_chol_inv(d, V.data(), W.data(), nullptr)) fail(RXHIP_ERR_NOT_POSDEF, "message initialisation on variable %d is not a proper Gaussian", v);
+        const bool wp = form[e] != 0;
+        for (int i = 0; i < d; ++i) {
+            double a = q[i];
+            if (wp) { a = 0.0; for (int k = 0; k < d; ++k) a += W[(size_t)i * d + k] * q[k]; }
+            out[i] = a;
+        }
+        for (int i = 0, k = 0; i < d; ++i)
+            for (int j = 0; j <= i; ++j) out[d + k++] = wp ? W[(size_t)i * d + j] : V[(size_t)i * d + j];
     }
 
     // ---- dependencies of every message ----
@@ -582,7 +674,7 @@ struct Compiler {
         if (memo != -2) return memo;
         if (k == 0) {
             const int e = var_edges[v][idx];
-            return memo = (null_[e] ? -1 : level[e]);
+            return memo = (null_[e] ? -1 : loop_[e] ? 0 : level[e]);
         }
         int cnt = 0, mx = -1;
         const int nchild = (int)h.lvl[k - 1].size();
@@ -638,7 +730,13 @@ struct Compiler {
         alias.assign(M, -1); off.assign(M, -1); level.assign(M, 0);
         std::vector<int> indeg(M);
         std::vector<int> q;
-        for (int m = 0; m < M; ++m) { indeg[m] = (int)deps[m].size(); if (!indeg[m]) q.push_back(m); }
+        // a loop message is read as its previous iteration's value: no ordering dependency, level 0 to its readers (rl)
+        auto rl = [&](int x) { return loop_[x] ? 0 : level[x]; };
+        for (int m = 0; m < M; ++m) {
+            indeg[m] = 0;
+            for (int dpm : deps[m]) indeg[m] += !loop_[dpm];
+            if (!indeg[m]) q.push_back(m);
+        }
         size_t head = 0;
         int processed = 0;
         while (head < q.size()) {
@@ -650,7 +748,7 @@ struct Compiler {
                 for (int dpm : deps[m]) if (!null_[dpm]) live.push_back(dpm);
                 needed[m] = factor_uses_v2f(edges[e].f);
                 if (live.empty()) null_[m] = 1;
-                else if (live.size() == 1) { alias[m] = alias[live[0]] >= 0 ? alias[live[0]] : live[0]; form[m] = form[live[0]]; level[m] = level[live[0]]; }
+                else if (live.size() == 1 && !loop_[live[0]]) { alias[m] = alias[live[0]] >= 0 ? alias[live[0]] : live[0]; form[m] = form[live[0]]; level[m] = level[live[0]]; }
                 else if (is_hub(edges[e].v)) {   // the product of the siblings along this edge's path through the variable's tree (above)
                     form[m] = 1;
                     int cnt = 0, lv = 0;
@@ -659,7 +757,7 @@ struct Compiler {
                         if (l >= 0) { ++cnt; lv = std::max(lv, l); }
                     });
                     level[m] = lv + rounds(std::max(cnt, 1));
-                } else { form[m] = 1; int lv = 0; for (int x : live) lv = std::max(lv, level[x]); level[m] = lv + rounds((int)live.size()); }
+                } else { form[m] = 1; int lv = 0; for (int x : live) lv = std::max(lv, rl(x)); level[m] = lv + rounds((int)live.size()); }   // (one loop message alone: a product of one)
             } else {        // factor -> variable
                 const Edge& ed = edges[m];
                 needed[m] = 1;
@@ -690,9 +788,24 @@ struct Compiler {
                 else form[m] = form[deps[m][0]];
             }
             done[m] = 1;
-            for (int u : users[m]) if (--indeg[u] == 0) q.push_back(u);
+            if (!loop_[m])
+                for (int u : users[m]) if (--indeg[u] == 0) q.push_back(u);
         }
-        if (processed != M) fail(RXHIP_ERR_UNSUPPORTED, "internal: the message dependencies of this graph are not acyclic");
+        if (processed != M) {
+            // a dependency cycle no message initialisation cuts: walk unprocessed dependencies until a message repeats — its variable lies on the loop
+            int m = 0;
+            while (done[m]) ++m;
+            std::vector<char> seen(M, 0);
+            while (!seen[m]) {
+                seen[m] = 1;
+                for (int dpm : deps[m])
+                    if (!done[dpm] && !loop_[dpm]) { m = dpm; break; }
+            }
+            fail(RXHIP_ERR_UNSUPPORTED, "the Gaussian variables form a cycle through variable %d that no message initialisation cuts (`@initialization μ(v) = …` on a variable of the loop)",
+                 edges[m % E].v);
+        }
+        for (int m = 0; m < E; ++m)
+            if (loop_[m] && null_[m]) fail(RXHIP_ERR_UNSUPPORTED, "variable %d: a message on its loop is computed from no information at all", edges[m].v);
         for (int64_t v = 0; v < nv; ++v)
             if (P.vclass[v] == VC_GAUSS) {
                 bool any = false;
@@ -781,8 +894,18 @@ struct Compiler {
         for (size_t i = 0; i < gcvs.size(); ++i) { gcvs[i].state = (int)po; po += 5; gcvs[i].stat = (int)i; }   // (ψ: the first residual-moment slots)   // γ(z): [· | · | E γ | 1 / E γ | E log γ] — the layout of a scalar precision variable's state
         P.marg_doubles = mo; P.prec_doubles = po;
         long long so = 0;
+        new_off.assign((size_t)2 * E, -1);
+        if (P.n_loop) {
+            for (int m = 0; m < E; ++m)
+                if (loop_[m]) { off[m] = (int)so; so += msz(P.dim[edges[m].v]); ++P.n_messages; }
+            P.loop_doubles = so;
+            P.loop_init.assign((size_t)so, 0.0);
+            for (int m = 0; m < E; ++m)
+                if (loop_[m]) { new_off[m] = off[m] + (int)P.loop_doubles; loop_init_values(m, P.loop_init.data() + off[m]); }
+            so *= 2;
+        }
         for (int m = 0; m < 2 * E; ++m)
-            if (!null_[m] && needed[m] && alias[m] < 0) { off[m] = (int)so; so += msz(P.dim[edges[m % E].v]); ++P.n_messages; }
+            if (!null_[m] && needed[m] && alias[m] < 0 && !loop_[m]) { off[m] = (int)so; so += msz(P.dim[edges[m % E].v]); ++P.n_messages; }
         for (int m = 0; m < 2 * E; ++m)   // an alias of a message nobody else needed (cannot happen: every f2v is needed)
             if (alias[m] >= 0 && off[alias[m]] < 0) fail(RXHIP_ERR_BADARG, "internal: alias of an unallocated message");
         if (so > (1ll << 30) || mo > (1ll << 30) || vo > (1ll << 30)) fail(RXHIP_ERR_UNSUPPORTED, "graph too large for the executor's 32-bit slot offsets");
@@ -1076,6 +1199,7 @@ struct Compiler {
                     P.bytes_per_sweep += 8ll * msz(d);
                 }
             }
+            if (loop_[m]) recs.back().w[W_OUT] = new_off[m];
             P.bytes_per_sweep += 8ll * msz(d);
         }
         // marginals: one level behind the last message
@@ -1119,7 +1243,12 @@ struct Compiler {
             const int d = P.dim[v];
             std::vector<std::pair<int, int>> ins;
             int hub_lv = 0;
-            if (is_hub((int)v)) {   // the top nodes of the variable's tree (their products exist already wherever a neighbour needed them)
+            bool has_loop = false;
+            for (int e : var_edges[v]) has_loop = has_loop || loop_[e];
+            if (has_loop) {   // the loop messages just computed: not the hub's partial products, which hold the previous iteration's
+                for (int e : var_edges[v])
+                    if (!null_[e]) ins.push_back({loop_[e] ? new_off[e] : src_off(e), (int)form[e]});
+            } else if (is_hub((int)v)) {   // the top nodes of the variable's tree (their products exist already wherever a neighbour needed them)
                 const Hub& h = hubs[hub_of[v]];
                 const int top = h.height - 1;
                 for (int c = 0; c < (int)h.lvl[top].size(); ++c) {
@@ -1449,6 +1578,8 @@ struct Compiler {
     }
     // messages nobody reads (since the marginals of `A * x` outputs stopped being products of messages: the message toward such an output when the node behind
     // it is observed, the product that fed it): their ops go, and then whatever only they were reading
+    bool is_loop_old(int o) const { return P.n_loop && o >= 0 && o < P.loop_doubles; }
+    bool is_loop_new(int o) const { return P.n_loop && o >= P.loop_doubles && o < 2 * P.loop_doubles; }
     void eliminate_dead_messages() {
         std::unordered_map<int, int> prod;
         std::vector<int> readers(recs.size(), 0);
@@ -1462,7 +1593,7 @@ struct Compiler {
             }
         std::vector<int> work;
         for (size_t i = 0; i < recs.size(); ++i)
-            if (produces_msg(recs[i].w[W_OP]) && readers[i] == 0) work.push_back((int)i);
+            if (produces_msg(recs[i].w[W_OP]) && readers[i] == 0 && !is_loop_new(recs[i].w[W_OUT])) work.push_back((int)i);   // (a loop message is read by the next iteration)
         while (!work.empty()) {
             const int i = work.back();
             work.pop_back();
@@ -1470,7 +1601,7 @@ struct Compiler {
             dead[i] = 1;
             for (const In& in : op_inputs(recs[i].w)) {
                 auto it = prod.find(in.off);
-                if (it != prod.end() && --readers[it->second] == 0) work.push_back(it->second);
+                if (it != prod.end() && --readers[it->second] == 0 && !is_loop_new(it->first)) work.push_back(it->second);
             }
         }
         std::vector<OpRec> keep;
@@ -1491,6 +1622,7 @@ struct Compiler {
             if (produces_msg(r.w[W_OP])) { P.bytes_per_sweep += 8ll * msz(r.w[W_OP] == OP_MUL_IN ? r.w[W_D1] : r.w[W_D0]); ++P.n_messages; }
             else if (r.w[W_OP] == OP_MARGINAL) P.bytes_per_sweep += 8ll * msz(r.w[W_D0]) + 8;
         }
+        P.bytes_per_sweep += 16ll * P.loop_doubles;   // the carry: every loop message read in the new region and written to the old one
         // the second phase: a message per FE_NOISE2 / FE_ADD2 input, a marginal (mean, packed covariance, log-determinant) or a mean per marginal read, data
         // values, the statistics of the q(W) updates, one double per term written or summed
         P.fe_bytes = 0;
@@ -1597,6 +1729,7 @@ struct Compiler {
             const std::vector<In> ins = inputs(i);
             int best = -1, best_k = -1;
             for (size_t k = 0; k < ins.size(); ++k) {
+                if (is_loop_old(ins[k].off)) continue;   // (the previous iteration's value: in HBM before the sweep starts)
                 auto it = prod.find(ins[k].off);
                 if (it == prod.end()) fail(RXHIP_ERR_BADARG, "internal: op %d reads a message nobody produces", i);
                 const int j = it->second;
@@ -1606,6 +1739,7 @@ struct Compiler {
             if (best >= 0) {
                 const int sb = strand_of[best];
                 for (size_t k = 0; k < ins.size() && best >= 0; ++k) {
+                    if (is_loop_old(ins[k].off)) continue;
                     const int s2 = strand_of[prod[ins[k].off]];
                     if (s2 != sb && slevel[s2] >= slevel[sb]) best = -1;
                 }
@@ -1620,7 +1754,8 @@ struct Compiler {
                 reg_idx[i] = ins[best_k].idx;
             } else {
                 int lv = (op == OP_DERIVE_MUL || op == OP_DERIVE_ADD || op == OP_CAT_UPDATE) ? oplevel[i] : L0;
-                for (const In& in : ins) lv = std::max(lv, slevel[strand_of[prod[in.off]]] + 1);
+                for (const In& in : ins)
+                    if (!is_loop_old(in.off)) lv = std::max(lv, slevel[strand_of[prod[in.off]]] + 1);
                 strand_of[i] = (int)members.size();
                 members.push_back({i});
                 slevel.push_back(lv);
@@ -1658,13 +1793,14 @@ struct Compiler {
                 const int op = w[W_OP];
                 if (produces_msg(op)) {
                     const int dout = op == OP_MUL_IN ? w[W_D1] : w[W_D0];
-                    if (readers[i] == 1 && next_in_strand[i] >= 0) w[W_FLAGS] |= F_NO_STORE;
+                    if (readers[i] == 1 && next_in_strand[i] >= 0 && !is_loop_new(w[W_OUT])) w[W_FLAGS] |= F_NO_STORE;   // (a loop message is carried to the next iteration from HBM)
                     else P.bytes_per_sweep_strands += msz8(dout);
                 } else if (op == OP_MARGINAL) P.bytes_per_sweep_strands += msz8(w[W_D0]) + 8;
                 P.sops.insert(P.sops.end(), w, w + OP_WORDS);
             }
         }
         for (int l = 0; l < nsl; ++l) P.slvl_ptr[l + 1] += P.slvl_ptr[l];
+        P.bytes_per_sweep_strands += 16ll * P.loop_doubles;   // (the carry)
         if (P.sops.empty()) P.sops.assign(OP_WORDS, 0);
         if (P.strands.empty()) P.strands.assign(2, 0);
         // the floor of any schedule: the data in, the posteriors of the named variables (mean, packed covariance, log-determinant slot) out

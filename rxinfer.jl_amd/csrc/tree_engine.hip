@@ -42,7 +42,7 @@ struct Engine {
     int mode = 0, mode_fe = 0, rb = 16, rb_fe = 16, wg = 256;   // schedule of the sweep phase / of the Bethe phase (tree_kernels.hpp: 0 a launch per level, 1 resident levels, 2 walk)
     int *d_ops = nullptr, *d_aux = nullptr, *d_lvl = nullptr, *d_status = nullptr, *d_sops = nullptr, *d_strands = nullptr;
     double *d_cpool = nullptr, *d_msg = nullptr, *d_marg = nullptr, *d_val = nullptr, *d_prec = nullptr, *d_term = nullptr, *d_stat = nullptr, *d_prec_init = nullptr, *d_marg_init = nullptr,
-           *d_fe_rep = nullptr, *d_fe_hist = nullptr, *d_fe_part = nullptr;
+           *d_fe_rep = nullptr, *d_fe_hist = nullptr, *d_fe_part = nullptr, *d_loop_init = nullptr;
     int fe_cap = 0;
     bool have_data = false, ran = false;
     bool cont = false;   // rxhip_tree_continue: later runs go on from the q(W) the previous run ended with
@@ -116,6 +116,17 @@ __global__ void __launch_bounds__(256) k_tree_fe_total(const double* __restrict_
 __global__ void __launch_bounds__(256) k_tree_broadcast(double* __restrict__ dst, const double* __restrict__ init, long long n, long long RS, int elem_fast) {
     const long long total = n * RS;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) dst[i] = init[elem_fast ? i % n : i / RS];
+}
+
+// the loop messages of a loopy schedule (tree_compiler.hpp mark_loop_messages): slots [0, n) of every replica's messages hold the values the sweep reads, the
+// producers write [n, 2n).  init != nullptr: slot k ← init[k] (a run starts from the message initialisations); else slot k ← slot n + k (the carry between
+// iterations).  Element k of replica r at k·es + r·rs: a lane per element, consecutive lanes along the stride-1 index
+__global__ void __launch_bounds__(256) k_tree_carry(double* __restrict__ msg, const double* __restrict__ init, long long n, long long R, long long es, long long rs) {
+    const long long total = n * R;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long k = es == 1 ? i % n : i / R, r = es == 1 ? i / n : i % R;
+        msg[k * es + r * rs] = init ? init[k] : msg[(n + k) * es + r * rs];
+    }
 }
 
 // host layout <-> replica-fastest device layout, on the device (at 65 536 replicas the host loops these replace ran for seconds)
@@ -383,7 +394,7 @@ rxhip_status create(const rxhip_graph_desc* g, int device, void* stream, Engine*
     if (e->tiled && (st = wave_attributes(P.dmax, err))) return cleanup(st);
     if ((st = upload(&e->d_sops, P.sops, err)) || (st = upload(&e->d_strands, P.strands, err))) return cleanup(st);
     if ((st = upload(&e->d_ops, P.ops, err)) || (st = upload(&e->d_aux, P.aux, err)) || (st = upload(&e->d_lvl, P.lvl_ptr, err)) || (st = upload(&e->d_cpool, P.cpool, err)) ||
-        (st = upload(&e->d_prec_init, P.prec_init, err)) || (st = upload(&e->d_marg_init, P.marg_init, err)) || (st = zalloc(&e->d_msg, P.msg_doubles * e->RS, err)) || (st = zalloc(&e->d_marg, P.marg_doubles * e->RS, err)) ||
+        (st = upload(&e->d_prec_init, P.prec_init, err)) || (st = upload(&e->d_marg_init, P.marg_init, err)) || (st = upload(&e->d_loop_init, P.loop_init, err)) || (st = zalloc(&e->d_msg, P.msg_doubles * e->RS, err)) || (st = zalloc(&e->d_marg, P.marg_doubles * e->RS, err)) ||
         (st = zalloc(&e->d_val, P.val_doubles * e->RS, err)) || (st = zalloc(&e->d_prec, P.prec_doubles * e->RS, err)) || (st = zalloc(&e->d_term, P.term_slots * e->RS, err)) ||
         (st = zalloc(&e->d_stat, P.stat_doubles * e->RS, err)) || (st = zalloc(&e->d_fe_rep, e->RS, err)) || (st = zalloc(&e->d_fe_part, (e->R + FE_CHUNK - 1) / FE_CHUNK, err)))
         return cleanup(st);
@@ -420,7 +431,7 @@ void destroy(Engine* e) {
     DevScope ds(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     for (void* q : {(void*)e->d_sops, (void*)e->d_strands, (void*)e->d_ops, (void*)e->d_aux, (void*)e->d_lvl, (void*)e->d_status, (void*)e->d_cpool, (void*)e->d_msg, (void*)e->d_marg, (void*)e->d_val, (void*)e->d_prec,
-                    (void*)e->d_term, (void*)e->d_stat, (void*)e->d_prec_init, (void*)e->d_marg_init, (void*)e->d_fe_rep, (void*)e->d_fe_hist, (void*)e->d_fe_part})
+                    (void*)e->d_term, (void*)e->d_stat, (void*)e->d_prec_init, (void*)e->d_marg_init, (void*)e->d_loop_init, (void*)e->d_fe_rep, (void*)e->d_fe_hist, (void*)e->d_fe_part})
         if (q) (void)hipFree(q);
     for (hipGraphExec_t x : e->gexec) if (x) (void)hipGraphExecDestroy(x);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
@@ -508,6 +519,10 @@ rxhip_status run(Engine* e, int iterations, int want_fe, std::string& err) {
                            (long long)P.marg_doubles, e->RS, e->elem_fast ? 1 : 0);
     }
     const TreeParams p = params_of(e, want_fe);
+    const long long loop_items = P.loop_doubles * e->R;
+    const unsigned loop_blocks = (unsigned)std::min<long long>((loop_items + 255) / 256, 4096);
+    if (P.n_loop && !(e->cont && e->ran))   // the message initialisations the first iteration's readers of the loop messages take
+        hipLaunchKernelGGL(k_tree_carry, dim3(loop_blocks), dim3(256), 0, e->stream, e->d_msg, (const double*)e->d_loop_init, P.loop_doubles, e->R, p.es, p.rs_msg);
     // without the free energy on a graph without precision variables the sweep ends with the marginals
     const int l_end = (!want_fe && P.prec_doubles == 0) ? P.fe_level : (P.lazy_level >= 0 ? P.lazy_level : P.n_levels);
     if (!e->ev0) { TCHK(hipEventCreate(&e->ev0)); TCHK(hipEventCreate(&e->ev1)); }
@@ -532,6 +547,8 @@ rxhip_status run(Engine* e, int iterations, int want_fe, std::string& err) {
     for (int it = 0; it < iterations; ++it) {
         if (gx) TCHK(hipGraphLaunch(gx, e->stream));
         else launch(e, p, 0, l_end);
+        if (P.n_loop)   // the loop messages just computed become what the next iteration (or a continued run) reads
+            hipLaunchKernelGGL(k_tree_carry, dim3(loop_blocks), dim3(256), 0, e->stream, e->d_msg, (const double*)nullptr, P.loop_doubles, e->R, p.es, p.rs_msg);
         if (want_fe) {   // Σ over replicas of term[root]: chunks of FE_CHUNK into partials, the partials (≤ FE_CHUNK of them: up to 16.7 M replicas) into the iteration's slot
             const unsigned nb = (unsigned)((e->R + FE_CHUNK - 1) / FE_CHUNK);
             const double* root = e->d_term + (size_t)P.fe_root * (e->elem_fast ? 1 : e->RS);
@@ -710,6 +727,7 @@ void info(Engine* e, rxhip_tree_info* out) {
     out->kernels = e->mode < 0 ? -1 : !e->tiled ? 0 : P.dmax <= 32 ? 1 : 2;
     out->strand_bytes_per_sweep = P.bytes_per_sweep_strands;
     out->fe_bytes_per_sweep = P.fe_bytes;
+    out->n_loop_messages = P.n_loop;
     out->dmax = P.dmax; out->mode = e->mode; out->replicas_per_workgroup = e->rb;
     int np = 0;
     for (int c : P.vclass) np += c == VC_PREC;

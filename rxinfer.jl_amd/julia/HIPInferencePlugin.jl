@@ -104,6 +104,8 @@ mutable struct GraphTables
     var_const::Vector{Int64}
     var_init_family::Vector{Int32}
     var_init::Vector{Int64}
+    var_msg_init_family::Vector{Int32}    # `@initialization μ(x) = …` (InitMsgExtraKey): rxhip_graph_desc.var_msg_init_family / var_msg_init
+    var_msg_init::Vector{Int64}
     var_name::Vector{String}              # for dump_graph / error messages only
     var_index::Vector{Any}
     factor_type::Vector{Int32}
@@ -115,7 +117,7 @@ mutable struct GraphTables
     const_pool::Vector{Float64}
     gh_points::Int32
     id_of::Dict{GraphPPL.NodeLabel, Int64}
-    GraphTables() = new(Int32[], Int32[], Int32[], Int64[], Int32[], Int64[], String[], Any[], Int32[], String[], Int64[0], Int64[],
+    GraphTables() = new(Int32[], Int32[], Int32[], Int64[], Int32[], Int64[], Int32[], Int64[], String[], Any[], Int32[], String[], Int64[0], Int64[],
                         String[], Int32[], Float64[], Int32(0), Dict{GraphPPL.NodeLabel, Int64}())
 end
 
@@ -164,8 +166,17 @@ function build_tables(model::GraphPPL.Model)
             fam, ioff = ip[1], Int64(length(t.const_pool))
             append!(t.const_pool, ip[2])
         end
-        GraphPPL.hasextra(nodedata, InitMsgExtraKey) && throw(UnsupportedGraph("@initialization of a message (μ(x) = …)"))
         push!(t.var_init_family, fam); push!(t.var_init, ioff)
+        # μ(x) = D: the initial value of the messages into x on its cycles — the node-array executor's loopy schedule (include/rxhip.h)
+        mfam, moff = RXHIP_INIT_NONE, Int64(-1)
+        if GraphPPL.hasextra(nodedata, InitMsgExtraKey)
+            ip = init_params(GraphPPL.getextra(nodedata, InitMsgExtraKey))
+            (ip === nothing || !(ip[1] == RXHIP_INIT_NORMAL || ip[1] == RXHIP_INIT_MVNORMAL)) &&
+                throw(UnsupportedGraph("@initialization of a message on $(GraphPPL.getname(props)): Normal / MvNormal only"))
+            mfam, moff = ip[1], Int64(length(t.const_pool))
+            append!(t.const_pool, ip[2])
+        end
+        push!(t.var_msg_init_family, mfam); push!(t.var_msg_init, moff)
     end
     GraphPPL.factor_nodes(model) do label, nodedata
         props = GraphPPL.getproperties(nodedata)::GraphPPL.FactorNodeProperties
@@ -262,8 +273,13 @@ function dump_graph(io::IO, t::GraphTables; n_replicas::Integer = 1, n_observati
         end
         if t.var_init_family[i] != RXHIP_INIT_NONE
             fam = ("", "normal", "gamma", "dirichlet", "mvnormal", "wishart")[t.var_init_family[i] + 1]
-            stop = minimum(vcat([o for o in vcat(t.var_const, t.var_init) if o > t.var_init[i]], length(t.const_pool)))
+            stop = minimum(vcat([o for o in vcat(t.var_const, t.var_init, t.var_msg_init) if o > t.var_init[i]], length(t.const_pool)))
             print(io, ",\"init\":{\"family\":\"", fam, "\",\"params\":[", join(repr.(t.const_pool[(t.var_init[i] + 1):stop]), ","), "]}")
+        end
+        if t.var_msg_init_family[i] != RXHIP_INIT_NONE
+            fam = ("", "normal", "gamma", "dirichlet", "mvnormal", "wishart")[t.var_msg_init_family[i] + 1]
+            stop = minimum(vcat([o for o in vcat(t.var_const, t.var_init, t.var_msg_init) if o > t.var_msg_init[i]], length(t.const_pool)))
+            print(io, ",\"msg_init\":{\"family\":\"", fam, "\",\"params\":[", join(repr.(t.const_pool[(t.var_msg_init[i] + 1):stop]), ","), "]}")
         end
         print(io, "}")
     end

@@ -547,6 +547,8 @@ struct GraphDesc
     n_observations::Int64
     allow_missing::Int32
     factor_cluster::Ptr{Int32}
+    var_msg_init_family::Ptr{Int32}
+    var_msg_init::Ptr{Int64}
 end
 
 # mirrors rxhip_lgssm_lowered
@@ -616,7 +618,7 @@ with_desc(f, t, n_replicas::Integer, n_observations::Integer; allow_missing::Boo
     f(GraphDesc(length(t.var_kind), pointer(t.var_kind), pointer(t.var_rows), pointer(t.var_cols), pointer(t.var_const),
                 length(t.factor_type), pointer(t.factor_type), pointer(t.factor_iface), pointer(t.const_pool), length(t.const_pool),
                 n_replicas, pointer(t.factor_iface_ptr), pointer(t.var_init_family), pointer(t.var_init), t.gh_points, n_observations,
-                allow_missing ? 1 : 0, pointer(t.factor_cluster)))
+                allow_missing ? 1 : 0, pointer(t.factor_cluster), pointer(t.var_msg_init_family), pointer(t.var_msg_init)))
 end
 
 lowering_error() = unsafe_string(ccall((:rxhip_lowering_error, librxhip), Cstring, ()))
@@ -630,7 +632,7 @@ end
 
 "the graph compiler alone (host only): would the node-array executor take this graph, and with what schedule? (include/rxhip.h rxhip_tree_plan)"
 function tree_plan(g::Ref{GraphDesc})
-    info = Ref(TreeInfo(0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0, 0, 0, 0, 0, 0))
+    info = Ref(TreeInfo(0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0, 0, 0, 0, 0, 0, 0, 0))
     rc, pr, mg = Ref{UInt64}(0), Ref{UInt64}(0), Ref{UInt64}(0)
     st = ccall((:rxhip_tree_plan, librxhip), Int32, (Ptr{GraphDesc}, Ref{TreeInfo}, Ref{UInt64}, Ref{UInt64}, Ref{UInt64}), g, info, rc, pr, mg)
     st == 0 || error("rxhip_tree_plan: status $st: $(lowering_error())")
@@ -825,6 +827,7 @@ struct TreeInfo
     kernels::Int32
     strand_bytes_per_sweep::Int64
     fe_bytes_per_sweep::Int64
+    n_loop_messages::Int64
 end
 # mirrors rxhip_rule_call
 struct RuleCall
@@ -847,7 +850,7 @@ end
 """`rxhip_tree_get_info`, or `nothing` when the handle belongs to one of the pattern-matched families (what `rxhip_create` built
 tells the plugin which set of entry points drives the engine)."""
 function tree_info(e::Engine)
-    info = Ref(TreeInfo(0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0, 0, 0, 0, 0, 0))
+    info = Ref(TreeInfo(0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0, 0, 0, 0, 0, 0, 0, 0))
     st = ccall((:rxhip_tree_get_info, librxhip), Int32, (Ptr{Cvoid}, Ref{TreeInfo}), e.handle, info)
     return st == RXHIP_OK ? info[] : nothing
 end

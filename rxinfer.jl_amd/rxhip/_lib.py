@@ -48,7 +48,9 @@ class GraphDesc(ctypes.Structure):
                 ("factor_iface_ptr", c_int64_p), ("var_init_family", c_int32_p), ("var_init", c_int64_p),
                 ("gh_points", ctypes.c_int32), ("n_observations", ctypes.c_int64), ("allow_missing", ctypes.c_int32),
                 # the factorisation of q around every node (VariationalConstraintsFactorizationIndicesKey): NULL or one cluster id per factor_iface entry
-                ("factor_cluster", c_int32_p)]
+                ("factor_cluster", c_int32_p),
+                # `@initialization μ(v) = D` (InitMsgExtraKey): NULL, or per variable RXHIP_INIT_NORMAL / MVNORMAL and the offset of D in const_pool
+                ("var_msg_init_family", c_int32_p), ("var_msg_init", c_int64_p)]
 
 
 class LgssmLowered(ctypes.Structure):
@@ -114,7 +116,8 @@ class TreeInfo(ctypes.Structure):   # rxhip_tree_info
     _fields_ = [("n_ops", ctypes.c_int64), ("n_levels", ctypes.c_int64), ("n_messages", ctypes.c_int64), ("doubles_per_replica", ctypes.c_int64),
                 ("bytes_per_sweep", ctypes.c_int64), ("dmax", ctypes.c_int32), ("mode", ctypes.c_int32), ("replicas_per_workgroup", ctypes.c_int32),
                 ("n_precision_vars", ctypes.c_int32), ("last_iteration_ms", ctypes.c_double), ("io_bytes_per_sweep", ctypes.c_int64),
-                ("n_strands", ctypes.c_int64), ("n_strand_levels", ctypes.c_int64), ("longest_strand", ctypes.c_int32), ("kernels", ctypes.c_int32), ("strand_bytes_per_sweep", ctypes.c_int64), ("fe_bytes_per_sweep", ctypes.c_int64)]
+                ("n_strands", ctypes.c_int64), ("n_strand_levels", ctypes.c_int64), ("longest_strand", ctypes.c_int32), ("kernels", ctypes.c_int32), ("strand_bytes_per_sweep", ctypes.c_int64), ("fe_bytes_per_sweep", ctypes.c_int64),
+                ("n_loop_messages", ctypes.c_int64)]
 
 
 class RuleCall(ctypes.Structure):   # rxhip_rule_call

@@ -43,6 +43,7 @@ class GraphBuilder:
         self.pool = []
         self._n = 0
         self.init_family, self.init_off = {}, {}
+        self.msg_init_family, self.msg_init_off = {}, {}   # `@initialization μ(v) = …`
         self.gh_points = 0
         self.names = []
         self.n_replicas, self.n_observations = 1, 0
@@ -77,7 +78,7 @@ class GraphBuilder:
         pool = np.concatenate(self.pool) if self.pool else np.zeros(0)
         kinds = ("random", "data", "constant")
         fams = {v: k for k, v in INIT_FAMILIES.items()}
-        ends = sorted([o for o in self.coff if o >= 0] + list(self.init_off.values()) + [pool.size])
+        ends = sorted([o for o in self.coff if o >= 0] + list(self.init_off.values()) + list(self.msg_init_off.values()) + [pool.size])
         variables = []
         for i in range(len(self.kind)):
             v = {"name": self.names[i], "kind": kinds[self.kind[i]], "rows": int(self.rows[i]), "cols": int(self.cols[i])}
@@ -86,6 +87,9 @@ class GraphBuilder:
             if i in self.init_family:
                 o = self.init_off[i]
                 v["init"] = {"family": fams[self.init_family[i]], "params": pool[o:min(e for e in ends if e > o)].tolist()}
+            if i in self.msg_init_family:
+                o = self.msg_init_off[i]
+                v["msg_init"] = {"family": fams[self.msg_init_family[i]], "params": pool[o:min(e for e in ends if e > o)].tolist()}
             variables.append(v)
         factors = []
         for t, ifs in zip(self.ftype, self.fiface):
@@ -119,6 +123,8 @@ class GraphBuilder:
                 i = (gb.randomvar if v["kind"] == "random" else gb.datavar)(v["rows"], name=v.get("name", ""))
             if "init" in v:
                 gb.initialize(i, INIT_FAMILIES[v["init"]["family"]], v["init"]["params"])
+            if "msg_init" in v:
+                gb.initialize_message(i, INIT_FAMILIES[v["msg_init"]["family"]], v["msg_init"]["params"])
         for f in dump["factors"]:
             if f["type"] not in codes:
                 raise RxHipError(_lib.ERR_UNSUPPORTED, f"node {f['type']} has no device schedule")
@@ -203,6 +209,14 @@ class GraphBuilder:
         self.pool.append(v)
         self._n += v.size
 
+    def initialize_message(self, var, family, params):
+        """`@initialization μ(var) = …` (InitMsgExtraKey): the initial value of the messages into `var` on its cycles — what cuts a loop of the Gaussian
+        variables for the node-array executor's loopy schedule (include/rxhip.h).  family: INIT_NORMAL (mean, variance) | INIT_MVNORMAL (mean[d], cov[d][d])."""
+        v = np.atleast_1d(np.asarray(params, dtype=np.float64)).ravel()
+        self.msg_init_family[var], self.msg_init_off[var] = family, self._n
+        self.pool.append(v)
+        self._n += v.size
+
     def multiply(self, out, A, x):
         """out := A * x  ->  typeof(*) node with an anonymous output variable"""
         self.ftype.append(_lib.NODE_MULTIPLY); self.fiface.append((out, A, x))
@@ -221,9 +235,13 @@ class GraphBuilder:
         ioff = np.full(nv, -1, dtype=np.int64)
         for v, f in self.init_family.items():
             fam[v], ioff[v] = f, self.init_off[v]
+        mfam = np.zeros(nv, dtype=np.int32)
+        moff = np.full(nv, -1, dtype=np.int64)
+        for v, f in self.msg_init_family.items():
+            mfam[v], moff[v] = f, self.msg_init_off[v]
         arrs = dict(kind=np.asarray(self.kind, dtype=np.int32), rows=np.asarray(self.rows, dtype=np.int32),
                     cols=np.asarray(self.cols, dtype=np.int32), coff=np.asarray(self.coff, dtype=np.int64), ft=np.ascontiguousarray(ft),
-                    fi=np.ascontiguousarray(fi), ptr=ptr, fam=fam, ioff=ioff, pool=np.concatenate(self.pool) if self.pool else np.zeros(1))
+                    fi=np.ascontiguousarray(fi), ptr=ptr, fam=fam, ioff=ioff, mfam=mfam, moff=moff, pool=np.concatenate(self.pool) if self.pool else np.zeros(1))
         g = _lib.GraphDesc()
         g.n_variables = nv
         g.var_kind = arrs["kind"].ctypes.data_as(_lib.c_int32_p)
@@ -241,6 +259,9 @@ class GraphBuilder:
         if self.init_family:
             g.var_init_family = arrs["fam"].ctypes.data_as(_lib.c_int32_p)
             g.var_init = arrs["ioff"].ctypes.data_as(_lib.c_int64_p)
+        if self.msg_init_family:
+            g.var_msg_init_family = arrs["mfam"].ctypes.data_as(_lib.c_int32_p)
+            g.var_msg_init = arrs["moff"].ctypes.data_as(_lib.c_int64_p)
         g.gh_points = int(self.gh_points)
         g.n_observations = int(n_observations)
         g.allow_missing = int(bool(allow_missing))
