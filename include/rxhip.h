@@ -434,7 +434,8 @@ rxhip_status rxhip_create(const rxhip_graph_desc* g, int32_t segments, int32_t d
  * Dimensions ≤ 8: a LANE per item, matrices in registers (csrc/tree_kernels.hpp), replica-fastest storage; schedules — a launch per level, workgroup-resident
  * levels, a lane per replica over the whole schedule, and (dimensions ≤ 4: the default) STRANDS: the sweep cut into paths of dependent ops
  * that a lane walks with the message in registers, a message going to HBM only when somebody outside its strand reads it.  Marginals of `A * x` outputs are
- * images of x's marginal: the Bethe terms form them on the fly, they are stored when a caller asks.
+ * images of x's marginal (unless x is such an output itself: then the product of the messages): the Bethe terms form them on the fly, they are stored when a
+ * caller asks.
  * Dimensions 9 … 32 (and 5 … 8 up to 1 024 replicas): a WAVEFRONT per (op, replica), matrices in registers in the accumulator layout of v_mfma_f64_16x16x4_f64
  * (csrc/tree_tile_kernels.hpp: products straight from registers, the inverse a symmetric sweep), a replica's slots contiguous in HBM; 33 … 64: a workgroup of
  * four wavefronts per (op, replica), matrices staged in LDS (csrc/tree_wave_kernels.hpp: products on the matrix cores, the inverse a 4-pivot block sweep with
@@ -462,8 +463,9 @@ rxhip_status rxhip_create(const rxhip_graph_desc* g, int32_t segments, int32_t d
  * an initialisation on a variable that lies on no cycle has no effect (a forest runs bit for bit as without it); initialisations on precision, discrete
  * or GCV variables, and loop messages in a graph with NormalMixture / GCV nodes, Wishart / Gamma precision variables or Gaussian nodes under q(out) q(μ),
  * are RXHIP_ERR_UNSUPPORTED.  Every dimension ≤ 64 and every kernel family run it; the free energy is the forest's node-local sum on the values the
- * schedule reads — v2f messages from the previous iteration's loop values, marginals from the new ones — which equals the Bethe free energy at a fixed
- * point (node beliefs then agree with the marginals), not before.  rxhip_tree_continue carries the loop
+ * schedule reads — v2f messages from the previous iteration's loop values, marginals from the new ones: a node term that needs a node-local joint (a
+ * Gaussian node or a `+` with two random interfaces) forms it from the v2f messages the node read, so the joint's marginals are the products on the
+ * node's edges, not the variables' marginals — which equals the Bethe free energy at a fixed point (node beliefs then agree with the marginals), not before.  rxhip_tree_continue carries the loop
  * messages from one run to the next, as it carries q(W).
  * ------------------------------------------------------------------------------------------ */
 typedef struct {

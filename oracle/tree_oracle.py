@@ -1,4 +1,5 @@
-"""Generic sum-product / mean-field VMP on an arbitrary acyclic Gaussian factor graph — CPU restatement, TEST INFRASTRUCTURE ONLY.
+"""Generic sum-product / mean-field VMP on an arbitrary Gaussian factor graph — acyclic, or with its cycles cut by message initialisations — CPU
+restatement, TEST INFRASTRUCTURE ONLY.
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module; the product (rxinfer.jl_amd/) never does.
 
@@ -42,6 +43,15 @@ Pinning.  tests/test_tree_oracle.py checks this module against (i) brute-force c
 free energy = −log evidence) on random trees, (ii) oracle/rxoracle.c's lgssm_bp / lgssm_noise_vmp on the state-space graphs, which are pinned to
 the reference's golden free energies (tests/test_golden_reference.py), (iii) the RNG-free known answers 3.51551 / 2.26551
 (/root/reference/test/models/models_tests.jl:255,308).
+
+Loopy graphs (include/rxhip.h "Loopy graphs").  A variable with `msg_init` (`@initialization μ(v) = D`) cuts the cycles through it: its loop messages are
+the factor → variable messages on edges that are not bridges of the Gaussian factor graph (cycle_edges: this module's own bridge finder, a spanning forest
+and the fundamental cycles).  Every reader of a loop message takes the previous iteration's value (D in the first iteration, or the `loop_state` a call
+passes in), each loop message is computed again by its rule, and the new values are what the marginals read and what `loop_state` hands back.  The node
+terms of the free energy read the v2f messages as the sweep read them; the marginal of an `A * x` output is the image of x's.  Without `msg_init` nothing
+of this runs: the results are bit for bit those of the acyclic restatement.  Pinned by tests/test_loopy_oracle.py: equal to loopy_ref.linreg_loopy (the
+regression's hand-written restatement) at every iteration to 1e-12, unchanged by an initialisation on a forest, and, on every random loopy graph the GPU
+tests use (tests/loopy_graphs.py), converged to brute-force conditioning of the means to 1e-9 sd.
 
 Input: a graph in the exchange format "rxhip-graph-1" (what HIPInferencePlugin.jl's dump_graph writes; a dict) and the data of ONE replica,
 {variable id: vector}."""
@@ -108,6 +118,42 @@ def mvdigamma(a, d):
 
 def mvlgamma(a, d):
     return 0.25 * d * (d - 1) * math.log(math.pi) + sum(gammaln(a - 0.5 * i) for i in range(d))
+
+
+def cycle_edges(edges):
+    """edges: (vertex, variable, key) of a bipartite graph — a vertex is any hashable name, a variable vertex is ("v", variable).  Returns the keys of the
+    edges that lie on a cycle (that are not bridges): a spanning forest by breadth-first search, then every edge outside the forest closes a cycle with
+    the forest path between its ends — it and that path lie on a cycle, and every forest edge on no such path is a bridge."""
+    adj = {}
+    for i, (fv, v, _) in enumerate(edges):
+        adj.setdefault(fv, []).append((("v", v), i))
+        adj.setdefault(("v", v), []).append((fv, i))
+    parent, depth, tree = {}, {}, set()
+    for s in adj:
+        if s in parent:
+            continue
+        parent[s], depth[s] = None, 0
+        queue = [s]
+        while queue:
+            u = queue.pop(0)
+            for w, i in adj[u]:
+                if w not in parent:
+                    parent[w], depth[w] = (u, i), depth[u] + 1
+                    tree.add(i)
+                    queue.append(w)
+    on_cycle = set()
+    for i, (fv, v, _) in enumerate(edges):
+        if i in tree:
+            continue
+        on_cycle.add(i)
+        a, b = fv, ("v", v)
+        while a != b:   # walk both ends up to their common ancestor
+            if depth[a] < depth[b]:
+                a, b = b, a
+            u, j = parent[a]
+            on_cycle.add(j)
+            a = u
+    return {edges[i][2] for i in on_cycle}
 
 
 class TreeGraph:
@@ -242,6 +288,38 @@ class TreeGraph:
             else:
                 raise ValueError(f"node {t} is not part of the Gaussian tree family")
 
+    def msg_init_gauss(self, v):
+        """`@initialization μ(v) = D` as (mean, covariance), or None"""
+        ini = self.vars[v].get("msg_init")
+        if ini is None:
+            return None
+        d = self.dim[v]
+        p = np.asarray(ini["params"], float)
+        return p[:d].copy(), _sym(p[d:d + d * d].reshape(d, d))
+
+    def gauss_edges(self):
+        """The edges of the Gaussian factor graph: (factor vertex, variable, (factor, interface)) for every interface of a non-prior node that a Gaussian
+        variable sits on.  A node under q(out) q(μ) is two leaf factors (its interfaces exchange no message): the factor vertex of its μ side is ('mf', factor)."""
+        out = []
+        for fi, (t, ifs) in enumerate(self.factors):
+            if t in PRIORS or t in SKIP:
+                continue
+            for k, v in enumerate(ifs):
+                if self.gauss[v]:
+                    out.append((("mf", fi) if self.mf[fi] and k == 1 else ("f", fi), v, (fi, k)))
+        return out
+
+    def non_bridges(self):
+        """The set of (factor, interface) edges of the Gaussian factor graph that lie on a cycle"""
+        return cycle_edges(self.gauss_edges())
+
+    def loop_keys(self):
+        """The LOOP messages of include/rxhip.h "Loopy graphs": the factor → variable messages (factor, interface) into a variable with a message
+        initialisation whose edge is not a bridge of the Gaussian factor graph"""
+        cyc = self.non_bridges()
+        return [(fi, k) for v in range(len(self.vars)) if self.gauss[v] and self.vars[v].get("msg_init") is not None
+                for fi, k in self.nbrs[v] if (fi, k) in cyc]
+
     def alpha0(self, sv):
         """prior concentrations of a Dirichlet / Beta variable"""
         a = self.dir[sv]
@@ -275,11 +353,25 @@ class TreeGraph:
         return 2.0 * shape, np.array([[1.0 / (2.0 * rate)]])
 
 
-def infer(dump, data, iterations=1, free_energy=True):
-    """Returns dict(mean={var: m}, cov={var: V}, fe=[per iteration], q_prec={var: (nu, V)}, counters=dict(rule_calls, products, marginals))
-    for ONE replica.  `data`: {variable id: vector}; a vector holding NaN is a `missing` observation: its node sends nothing and its Bethe terms cancel."""
+def infer(dump, data, iterations=1, free_energy=True, loop_state=None):
+    """Returns dict(mean={var: m}, cov={var: V}, fe=[per iteration], q_prec={var: (nu, V)}, counters=dict(rule_calls, products, marginals),
+    loop_state={(factor, interface): Msg | None}) for ONE replica.  `data`: {variable id: vector}; a vector holding NaN is a `missing` observation: its node
+    sends nothing and its Bethe terms cancel.  `loop_state`: the loop messages a run starts from instead of the initialisations D (what a continued run
+    carries: the `loop_state` an earlier call returned)."""
     g = TreeGraph(dump)
     nv = len(g.vars)
+    # the loopy schedule (include/rxhip.h "Loopy graphs"): every reader of a loop message takes the previous iteration's value (the first iteration: D, or
+    # the carried state), the message is computed again by its ordinary rule, and the marginals read the new value
+    loops = g.loop_keys()
+    if loops and (g.mixtures or g.gcv or g.prec_prior or any(g.mf)):
+        raise ValueError("a loopy schedule with VMP state (precision variables, mixtures, GCV nodes, q(out) q(μ)) is not restated")
+    loop_old = {key: (loop_state[key] if loop_state is not None else Msg("mv", *g.msg_init_gauss(g.factors[key[0]][1][key[1]]))) for key in loops}
+    # with loops, the marginal of the output of `A * x` (both Gaussian) is the image of x's marginal (include/rxhip.h) — on a tree the two are the same
+    # Gaussian.  An output whose input is such an output itself (`B (A x)`) is the product of its messages instead
+    image = {}
+    if loops:
+        cand = {ifs[0]: (fi, ifs[2]) for fi, (t, ifs) in enumerate(g.factors) if t == "*" and g.gauss[ifs[0]] and g.gauss[ifs[2]]}
+        image = {v: p for v, p in cand.items() if p[1] not in cand}
 
     def value(v):   # clamped value of a data / constant variable, or of a deterministic function of such
         if g.kind[v] == "constant":
@@ -375,7 +467,7 @@ def infer(dump, data, iterations=1, free_energy=True):
         def msg_v2f(v, fi, k):
             key = (v, fi, k)
             if key not in v2f:
-                ins = [msg_f2v(gf, gk) for gf, gk in g.nbrs[v] if (gf, gk) != (fi, k)]
+                ins = [loop_old[(gf, gk)] if (gf, gk) in loop_old else msg_f2v(gf, gk) for gf, gk in g.nbrs[v] if (gf, gk) != (fi, k)]
                 ins = [m for m in ins if m is not None]
                 if not ins:
                     v2f[key] = None   # an improper (uniform) message: the variable has no other neighbour
@@ -487,7 +579,7 @@ def infer(dump, data, iterations=1, free_energy=True):
         # ---- marginals ----
         mean, cov = {}, {}
         for v in [v for v in range(nv) if v not in det_outs] + [v for v in range(nv) if v in det_outs]:
-            if not g.gauss[v]:
+            if not g.gauss[v] or v in image:
                 continue
             counters["on"] = v not in det_outs or v in qx   # (a mean-field rule reads this marginal: it is computed whoever asks)
             ins = [m for m in (msg_f2v(fi, k) for fi, k in g.nbrs[v]) if m is not None]
@@ -514,7 +606,11 @@ def infer(dump, data, iterations=1, free_energy=True):
                 qm = float(np.sum(pts * cs) / np.sum(cs))
                 mean[v], cov[v] = np.array([qm]), np.array([[float(np.sum(cs * (pts - qm) ** 2) / np.sum(cs))]])
             counters["marginals"] += counters["on"] and v not in det_outs
+        for v, (fi, x) in image.items():
+            A = np.atleast_2d(g.const(g.factors[fi][1][1])).astype(float).reshape(g.dim[v], g.dim[x])
+            mean[v], cov[v] = A @ mean[x], _sym(A @ cov[x] @ A.T)
         counters["on"] = False
+        loop_new = {key: msg_f2v(*key) for key in loops}
 
         # ---- node-local joints of the Gaussian nodes with two random interfaces; residual second moments of every Gaussian node ----
         def node_moments(fi):
@@ -637,10 +733,12 @@ def infer(dump, data, iterations=1, free_energy=True):
         gstate = gnew
         qs = qs_new
         qx = {v: (mean[v].copy(), cov[v].copy()) for v in qx}
+        loop_old = loop_new
         counters.pop("on")
         out = dict(mean=mean, cov=cov, joints={fi: m[2] for fi, m in moments.items() if m[2] is not None}, counters=counters)
     out["fe"] = fe_hist
     out["q_prec"] = qW
     out["q_dir"] = qs
     out["q_cat"] = pi
+    out["loop_state"] = loop_old
     return out

@@ -1220,10 +1220,11 @@ struct Compiler {
             for (int mk : mx.m) push_from[mk] = -1;
             push_from[mx.out] = -1;
         }
-        for (int64_t v = 0; v < nv; ++v)
-            if (push_from[v] >= 0 && push_from[push_from[v]] >= 0) push_from[v] = -2;   // the input is an image itself: this one takes the message route
-        for (int64_t v = 0; v < nv; ++v)
-            if (push_from[v] == -2) push_from[v] = -1;
+        {   // the input is the output of such a node itself: this one takes the message route (decided on the candidates, whatever the variables' order)
+            const std::vector<int> cand = push_from;
+            for (int64_t v = 0; v < nv; ++v)
+                if (cand[v] >= 0 && cand[cand[v]] >= 0) push_from[v] = -1;
+        }
         for (int64_t v = 0; v < nv; ++v) {
             if (P.vclass[v] != VC_GAUSS || push_from[v] >= 0) continue;
             if (gcv_z[v]) {   // the volatility input of a GCV node: the ELQ message times the product of all other messages, by cubature
@@ -1297,6 +1298,26 @@ struct Compiler {
             r.w[word] = src_off(m);
             if (form[m]) r.w[W_FLAGS] |= bit;
         };
+        // Loopy schedule: the node-local joint of a Gaussian node with two random interfaces is formed from the two v2f messages the sweep read (the previous
+        // iteration's loop values, include/rxhip.h "Loopy graphs").  Its marginal on side k is the product on that edge, v2f × f2v (a loop message's f2v: the
+        // value just computed from the other side's v2f), not the variable's marginal, which reads every loop message's new value — the two agree only at a
+        // fixed point.  Returns the scratch marginal slot of the product (mean, packed covariance, log-determinant), formed with the marginals.
+        auto edge_belief = [&](int f, int k) {
+            const int d = P.dim[iface(f, k)], e = fac_edges[f][k];
+            std::vector<std::pair<int, int>> ins;
+            if (!null_[E + e]) ins.push_back({src_off(E + e), (int)form[E + e]});
+            if (!null_[e]) ins.push_back({loop_[e] ? new_off[e] : src_off(e), (int)form[e]});
+            if (ins.empty()) fail(RXHIP_ERR_UNSUPPORTED, "factor %d: no message on either side of interface %d in a loopy graph", f, k);
+            const int slot = (int)P.marg_doubles;
+            P.marg_doubles += msz(d) + 1;
+            OpRec& r = emit(LM, OP_MARGINAL, d);
+            r.w[W_OUT] = slot;
+            if (g->allow_missing) r.w[W_FLAGS] |= F_MAY_MISS;
+            r.w[W_LIST] = (int)P.aux.size();
+            r.w[W_N] = (int)ins.size();
+            for (auto& in : ins) { P.aux.push_back(in.first); P.aux.push_back(in.second); }
+            return slot;
+        };
         for (int64_t v = 0; v < nv; ++v)
             if (P.vclass[v] == VC_GAUSS) ent_coef[v] = (int)var_edges[v].size() - 1;
         for (int64_t f = 0; f < nf; ++f) {
@@ -1304,6 +1325,8 @@ struct Compiler {
             if (nclass[f] == NC_NOISE) {
                 const int d = P.dim[a];
                 const bool ga = P.vclass[a] == VC_GAUSS, gb = P.vclass[b] == VC_GAUSS, rw = P.vclass[c] == VC_PREC || gcv_of[f] >= 0;
+                const bool loopy2 = P.n_loop && ga && gb && !mf[f];   // (loops exclude q(out) q(μ) and GCV nodes: mark_loop_messages)
+                const int eb0 = loopy2 ? edge_belief((int)f, 0) : -1, eb1 = loopy2 ? edge_belief((int)f, 1) : -1;   // (before `r`: emit moves the records)
                 OpRec& r = emit(LF, ga && gb ? OP_FE_NOISE2 : (ga || gb) ? OP_FE_NOISE1 : OP_FE_NOISE0, d);
                 noise_params(r, (int)f, d);
                 if (mf[f]) {   // q(out) q(μ): the average energy from the two marginals; the clusters' entropies go with the variables' terms
@@ -1312,6 +1335,12 @@ struct Compiler {
                     r.w[W_VAL2] = P.marg_off[b];
                     ent_coef[a] -= 1;
                     ent_coef[b] -= 1;
+                } else if (loopy2) {   // the same op on the joint's own marginals: side a's message and the products on the two edges (no image push, no folded entropy)
+                    r.w[W_OP] = OP_FE_NOISE2M;
+                    msg_in(r, W_IN0, F_IN0_WP, E + fac_edges[f][0]);
+                    r.w[W_VAL] = eb0;
+                    r.w[W_VAL2] = eb1;
+                    r.w[W_OUT] = 0;
                 } else if (ga && gb) {
                     // the joint from ONE inbound message and the two marginals (tree_kernels.hpp / tree_wave_kernels.hpp OP_FE_NOISE2M); side a = the interface
                     // whose message to the node is stored in precision form (no conversion), the out side when both are

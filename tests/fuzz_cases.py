@@ -121,6 +121,56 @@ def run_case(seed, detail=False):
     return None
 
 
+def run_loopy_case(seed):
+    """A random loopy graph (tests/loopy_graphs.py::random_loopy: ring, grid, cycles through `+`, regression star, closed forest), 1 … 6 iterations, a random replica
+    count, schedule and kernel family, sometimes `missing` observations: the executor against the restatement of the loopy schedule (oracle/tree_oracle.py) on the
+    first and the last replica — means 1e-8 sd, covariances 1e-8 of sd sdᵀ, free energy 1e-8 relative.  A case counts as compared when at least one replica was.  None, or the finding as a string.  Draws of its own:
+    run_case's stay as they are."""
+    import loopy_graphs as lg
+    from rxhip import _lib
+    rng = np.random.default_rng(700_000 + seed)
+    its, R, miss = int(rng.integers(1, 7)), int(rng.choice([1, 2, 3, 64, 70])), bool(rng.random() < 0.25)
+    os.environ["RXHIP_TREE_MODE"] = str(int(rng.integers(0, 4)))
+    os.environ["RXHIP_TREE_TILE"] = str(int(rng.integers(0, 2)))
+    gb, ys, named, kind = lg.random_loopy(seed)
+    data = tg.random_data(gb, ys, R, seed)
+    if miss:
+        obs, o = {ifs[0] for ifs in gb.fiface if gb.kind[ifs[0]] == _lib.VARKIND_DATA}, 0
+        for v in ys:
+            for r in range(R):
+                if v in obs and rng.random() < 0.25:
+                    data[r, o:o + gb.rows[v]] = np.nan
+            o += gb.rows[v]
+    tag = f"loopy seed {seed} {kind} R={R} its={its} miss={miss} mode={os.environ['RXHIP_TREE_MODE']} tile={os.environ['RXHIP_TREE_TILE']}"
+    try:
+        with TreeEngine(gb, n_replicas=R, allow_missing=miss) as eng:
+            if ys:
+                eng.set_data(ys, data)
+            eng.run(its, True)
+            post, fe = eng.marginals(named["x"]), eng.free_energy_per_replica()
+            n_loop = eng.info["n_loop_messages"]
+        dump = gb.to_dump()
+        if n_loop != len(tree_oracle.TreeGraph(dump).loop_keys()):
+            return f"FAIL {tag}: {n_loop} loop messages, the restatement's bridge finder {len(tree_oracle.TreeGraph(dump).loop_keys())}"
+        worst, ef, compared = 0.0, 0.0, 0
+        for r in sorted({0, R - 1}):
+            try:
+                ref = tree_oracle.infer(dump, tg.data_dict(gb, ys, data[r]), iterations=its)
+            except tree_oracle.ImproperMessage:   # (dropped observations left a message the restatement cannot invert)
+                continue
+            compared += 1
+            for v in named["x"]:
+                sd = np.sqrt(np.diag(ref["cov"][v]))
+                worst = max(worst, float(np.max(np.abs(post[v][0][r] - ref["mean"][v]) / sd)), float(np.max(np.abs(post[v][1][r] - ref["cov"][v]) / np.outer(sd, sd))))
+            ef = max(ef, abs(fe[r] - ref["fe"][-1]) / max(1.0, abs(ref["fe"][-1])))
+        if not (worst < 1e-8 and ef < 1e-8):
+            return f"FAIL {tag}: posterior err {worst:.2e} sd, fe rel {ef:.2e}"
+    except Exception as e:
+        return f"ERROR {tag}: {str(e)[:200]}"
+    STATS["compared"] += compared > 0
+    return None
+
+
 def _spd(rng, d, s=1.0):
     a = rng.standard_normal((d, d))
     return s * (a @ a.T / d + 0.5 * np.eye(d))

@@ -1,5 +1,7 @@
 """The loopy schedule in the graph compiler (rxhip_tree_plan, no device): which message initialisations cut which cycles, what stays refused, and that
 an initialisation off every cycle changes nothing."""
+import re
+
 import numpy as np
 import pytest
 
@@ -98,3 +100,73 @@ def test_message_initialisations_survive_a_dump_round_trip():
     assert plan(g2)["n_loop_messages"] == 5
     old = {**d, "variables": [{k: v for k, v in var.items() if k != "msg_init"} for var in d["variables"]]}   # a dump without the key loads as before
     assert not GraphBuilder.from_dump(old).msg_init_family
+
+
+# ---- the cut rule on random loopy graphs (tests/loopy_graphs.py), against the restatement's own bridge finder (oracle/tree_oracle.py) ----
+
+def test_the_loop_message_count_of_sixty_random_loopy_graphs():
+    import tree_oracle
+    for seed in range(60):
+        gb, _, named, kind = lg.random_loopy(seed, lg.KINDS[seed % len(lg.KINDS)]) if seed % 3 else lg.random_loopy(seed)
+        want = len(tree_oracle.TreeGraph(gb.to_dump()).loop_keys())
+        assert want >= 2 and plan(gb)["n_loop_messages"] == want, (seed, kind)
+
+
+@pytest.mark.parametrize("cut,n_loop", [([(0, 1), (1, 0), (1, 2), (2, 1)], 12), ([(0, 0), (1, 1), (2, 2)], 8)])
+def test_a_three_by_three_grid(cut, n_loop):
+    gb, _, _ = lg.grid(0, d=2, rows=3, cols=3, cut=cut)
+    assert plan(gb)["n_loop_messages"] == n_loop
+
+
+def test_a_grid_cut_at_its_centre_alone_names_a_site_on_an_uncut_cycle():
+    gb, _, named = lg.grid(0, d=2, rows=3, cols=3, cut=[(1, 1)])
+    with pytest.raises(rxhip.RxHipError) as ei:
+        plan(gb)
+    assert ei.value.status == _lib.ERR_UNSUPPORTED and "cycle" in str(ei.value)
+    assert int(re.search(r"through variable (\d+)", str(ei.value)).group(1)) in lg.uncut_cycle_variables(gb)
+
+
+@pytest.mark.parametrize("n_cuts", [1, 2])
+def test_a_ring_of_six(n_cuts):
+    gb, _, named = lg.ring(0, d=3, n=6, chord=False)
+    want = len(named["cut"])
+    assert plan(gb)["n_loop_messages"] == 2 * want
+    rng = np.random.default_rng(1)
+    extra = [v for v in lg.uncut_cycle_variables(gb, []) if v not in named["cut"]]
+    lg.initialise(gb, rng, extra[:n_cuts])
+    assert plan(gb)["n_loop_messages"] == 2 * (want + n_cuts)
+
+
+def test_dropping_one_variable_of_a_minimal_cut_names_a_variable_of_an_uncut_cycle():
+    checked = 0
+    for seed in range(40):
+        gb, _, named, kind = lg.random_loopy(seed, lg.KINDS[seed % len(lg.KINDS)])
+        if kind == "star":   # (one cut: dropping it leaves no initialisation at all)
+            continue
+        g2, v, uncut = lg.drop_one_cut(gb, named["fvs"], np.random.default_rng(seed))
+        if not uncut:   # a second initialisation on the same cycle still cuts it
+            assert plan(g2)["n_loop_messages"] > 0
+            continue
+        with pytest.raises(rxhip.RxHipError) as ei:
+            plan(g2)
+        assert ei.value.status == _lib.ERR_UNSUPPORTED and "cycle" in str(ei.value), (seed, kind)
+        assert int(re.search(r"through variable (\d+)", str(ei.value)).group(1)) in uncut, (seed, kind, v, sorted(uncut))
+        checked += 1
+    assert checked >= 20
+
+
+def test_an_initialisation_off_every_cycle_of_a_loopy_graph_changes_nothing():
+    checked = 0
+    for seed in range(40):
+        gb, _, named, kind = lg.random_loopy(seed, lg.KINDS[seed % len(lg.KINDS)])
+        off = [v for v in named["x"] if v not in lg.uncut_cycle_variables(gb, [])]
+        if not off:
+            continue
+        p0 = plan(gb)
+        lg.initialise(gb, np.random.default_rng(seed), [off[seed % len(off)]])
+        p1 = plan(gb)
+        for k in ("n_loop_messages", "n_ops", "n_levels", "n_messages", "bytes_per_sweep", "strand_bytes_per_sweep", "rule_calls", "products", "marginals",
+                  "doubles_per_replica"):
+            assert p1[k] == p0[k], (seed, kind, k)
+        checked += 1
+    assert checked >= 20
