@@ -411,7 +411,12 @@ rxhip_status rxhip_create(const rxhip_graph_desc* g, int32_t segments, int32_t d
  * (src/model/plugins/reactivemp_free_energy.jl:51-126) for graphs of
  *     MvNormalMeanCovariance / NormalMeanVariance / MvNormalMeanPrecision / NormalMeanPrecision   (out, μ: random, data or constant;
  *         third interface: a constant, or — precision nodes — a Wishart / Gamma variable under q(out, μ) q(W));
- *     typeof(*) with a constant matrix;  typeof(+) (random + random, random + data / constant);
+ *     typeof(*) with a constant or a DATA matrix;  typeof(+) (random + random, random + data / constant);
+ *         a DATA matrix (RXHIP_VARKIND_DATA on the `A` interface, var_rows × var_cols = dim(out) × dim(in) exactly, else RXHIP_ERR_BADARG) is set by every replica
+ *         for itself through rxhip_tree_set_data; the node then computes what the graph with that replica's matrix as a constant computes — forward and backward
+ *         rule, derived clamped values `A * v`, image marginals (the log-determinant of a square image by Cholesky per replica: no host-side log|det A|) — on every
+ *         kernel family and schedule.  `dot(x, b)` is `*` with a 1 × d data matrix.  Such a variable may sit on no other interface; a RANDOM matrix stays
+ *         RXHIP_ERR_UNSUPPORTED, and so do data matrices in a graph with NormalMixture / GCV nodes or data-valued variances;
  *     Wishart / GammaShapeRate / GammaShapeScale priors with constant parameters;
  *     NormalMixture (out, switch, m[1..K], p[1..K]) under mean field with  switch ~ Categorical(s),  s ~ Dirichlet(a) | a constant — or, K = 2, switch ~ Bernoulli(s),
  *         s ~ Beta(a, b)  (round 6; dimensions ≤ 8):
@@ -442,7 +447,8 @@ rxhip_status rxhip_create(const rxhip_graph_desc* g, int32_t segments, int32_t d
  * the matrix in accumulator registers); a launch per level, or an item per replica over the whole schedule (rxhip_tree_info.kernels / .mode).
  * Data variables, derived clamped values (`a + b` of two data variables), unobserved leaves (predictions) are part of the family; so is `missing` anywhere in
  * the data when the engine is created with rxhip_graph_desc.allow_missing (a NaN observation sends no message, its node's Bethe terms cancel; not under a
- * random precision: RXHIP_ERR_UNSUPPORTED) — without it rxhip_tree_set_data refuses NaN / Inf with RXHIP_ERR_BADARG.
+ * random precision: RXHIP_ERR_UNSUPPORTED) — without it rxhip_tree_set_data refuses NaN / Inf with RXHIP_ERR_BADARG.  NaN / Inf inside a data MATRIX is
+ * RXHIP_ERR_BADARG with or without allow_missing (a missing regressor has no meaning).
  * rxhip_create falls through to this executor for every graph the pattern matcher rejects; rxhip_tree_create asks for it directly (the tests
  * compare it with the specialised engines on the graphs both can run).
  * Message forms: a rule keeps the form its inbound message has wherever the algebra allows — the additive rule and the backward rule of `+` (two random
@@ -496,7 +502,8 @@ rxhip_status rxhip_tree_create(const rxhip_graph_desc* g, int32_t device, void* 
  * marginals would count: src/inference/batch.jl:495-496); failures as rxhip_tree_create (text: rxhip_lowering_error()).  The plugin can ask before it builds
  * an engine; the CPU tests hold these counts to the oracle's. */
 rxhip_status rxhip_tree_plan(const rxhip_graph_desc* g, rxhip_tree_info* out, uint64_t* rule_calls, uint64_t* products, uint64_t* marginals);
-/* data of the listed data variables, host [replica][rows of vars[0] | rows of vars[1] | …] (src/inference/batch.jl:405-407 new_observation!) */
+/* data of the listed data variables, host [replica][rows of vars[0] | rows of vars[1] | …] (src/inference/batch.jl:405-407 new_observation!); the data matrix
+ * of a `*` node takes rows·cols doubles in its place, row-major */
 rxhip_status rxhip_tree_set_data(rxhip_engine* e, const int64_t* vars, int64_t n_vars, const double* host);
 /* posteriors of the listed random (Gaussian) variables: mean [var][replica][d], cov [var][replica][d][d], concatenated in list order.  A random
  * variable of the model that the compiler found clamped (the output of `a + b` of two data variables) and a data variable are reported as point

@@ -349,7 +349,7 @@ inline rxhip_status lower_lgssm(const rxhip_graph_desc* g, Lgssm& L) {
         const long long io[3] = {iface(g, f, 0), iface(g, f, 1), iface(g, f, 2)};
         const int t = g->factor_type[f];
         if (t == RXHIP_NODE_MULTIPLY) {
-            if (g->var_kind[io[1]] != RXHIP_VARKIND_CONST) return unsupported("`*` node with a non-constant matrix (no device schedule)");
+            if (g->var_kind[io[1]] != RXHIP_VARKIND_CONST) return unsupported("`*` node with a non-constant matrix (no state-space family; the node-array executor takes a data matrix)");
             if (g->var_kind[io[2]] == RXHIP_VARKIND_DATA && g->var_kind[io[0]] == RXHIP_VARKIND_RANDOM) {
                 if (!writes(io[0], f)) return unsupported("variable produced by two nodes");
                 mul_data[io[0]] = f;  // `B_u * u[t]`: a deterministic function of data, consumed by a `+` below

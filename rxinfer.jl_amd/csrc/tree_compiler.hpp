@@ -111,6 +111,9 @@ struct Program {
     std::vector<int> dim, vclass, marg_off, val_off, prec_off;
     std::vector<int> discrete_k;   // per variable: components of a switch / probability vector (else 0)
     std::vector<int64_t> data_vars;
+    std::vector<int> val_width;    // per data variable (by id; 0 else): doubles of its value slot — rows, or rows·cols of a data MATRIX (row-major)
+    std::vector<char> is_mat;      // per variable: the data matrix of a `*` node
+    bool has_mat = false;          // any: the launches pick the kernel instances that can load one (tree_kernels.hpp MAT)
     std::vector<double> prec_init;   // [prec_doubles] initial state (replica-independent)
     uint64_t rule_calls = 0, products = 0, marginals = 0;
     long long bytes_per_sweep = 0;
@@ -209,6 +212,13 @@ struct Compiler {
     int const_matrix(int v, int rows, int cols) {
         if ((int64_t)g->var_rows[v] * g->var_cols[v] != (int64_t)rows * cols) fail(RXHIP_ERR_BADARG, "constant %d: %d x %d expected", v, rows, cols);
         return const_value(v);
+    }
+    // the matrix of a `*` node for the op `r`: the constant's pool offset — or, a DATA matrix (every replica sets its own), its value slot with `slot_bit`
+    // (F_MAT_SLOT / F_MAT_B_SLOT) in the op's flags
+    int matrix_source(OpRec& r, int v, int rows, int cols, int slot_bit) {
+        if (!P.is_mat[v]) return const_matrix(v, rows, cols);
+        r.w[W_FLAGS] |= slot_bit;
+        return P.val_off[v];
     }
     int noise_block(int v, int d, bool is_precision) {   // Σ | W | log|W|; memoised per (constant, parametrisation): a constant that one node reads as a covariance and another as a precision gets two blocks
         std::vector<int>& noise_off = is_precision ? noise_off_prec : noise_off_cov;
@@ -410,6 +420,16 @@ struct Compiler {
 
     void check_family() {
         int dmx = 1;
+        // a data variable on the matrix interface of a `*` node is a data MATRIX: a value slot of rows·cols doubles that nothing else may read as a vector
+        P.is_mat.assign((size_t)nv, 0);
+        bool any_mat = false;
+        for (int64_t f = 0; f < nf; ++f)
+            if (nclass[f] == NC_MUL && P.vclass[iface((int)f, 1)] == VC_DATA) { P.is_mat[iface((int)f, 1)] = 1; any_mat = true; }
+        if (any_mat)
+            for (int64_t f = 0; f < nf; ++f)
+                for (int k = 0; k < n_iface((int)f); ++k)
+                    if (P.is_mat[iface((int)f, k)] && !(nclass[f] == NC_MUL && k == 1))
+                        fail(RXHIP_ERR_UNSUPPORTED, "factor %lld: variable %lld is the data matrix of a `*` node and cannot be read as a value as well", (long long)f, (long long)iface((int)f, k));
         for (int64_t f = 0; f < nf; ++f) {
             const int t = ftype((int)f), a = (int)iface((int)f, 0), b = (int)iface((int)f, 1), c = (int)iface((int)f, 2);
             if (nclass[f] == NC_NOISE) {
@@ -426,9 +446,10 @@ struct Compiler {
                 } else if (P.vclass[c] != VC_CONST) fail(RXHIP_ERR_UNSUPPORTED, "factor %lld: the third interface of a Gaussian node must be a constant, a Wishart / Gamma variable or (scalar nodes) a data variable", (long long)f);
                 dmx = std::max(dmx, P.dim[a]);
             } else if (nclass[f] == NC_MUL) {
-                if (P.vclass[b] != VC_CONST) fail(RXHIP_ERR_UNSUPPORTED, "factor %lld: `*` needs a constant matrix", (long long)f);
+                if (P.vclass[b] != VC_CONST && P.vclass[b] != VC_DATA) fail(RXHIP_ERR_UNSUPPORTED, "factor %lld: `*` needs a constant or a data matrix (a random matrix has no rule here)", (long long)f);
                 if (P.vclass[a] == VC_PREC || P.vclass[c] == VC_PREC) fail(RXHIP_ERR_UNSUPPORTED, "`*` on a precision variable");
                 if ((int64_t)g->var_rows[b] * g->var_cols[b] != (int64_t)P.dim[a] * P.dim[c]) fail(RXHIP_ERR_BADARG, "factor %lld: matrix is not %d x %d", (long long)f, P.dim[a], P.dim[c]);
+                if (P.is_mat[b] && (g->var_rows[b] != P.dim[a] || g->var_cols[b] != P.dim[c])) fail(RXHIP_ERR_BADARG, "factor %lld: data matrix is %d x %d, not %d x %d", (long long)f, g->var_rows[b], g->var_cols[b], P.dim[a], P.dim[c]);
                 if (P.vclass[a] == VC_GAUSS && P.vclass[c] != VC_GAUSS) fail(RXHIP_ERR_BADARG, "factor %lld: `*` of a clamped input with a random output", (long long)f);
                 if (clamped(a) && P.vclass[a] != VC_DERIVED) fail(RXHIP_ERR_UNSUPPORTED, "factor %lld: `*` with an observed output", (long long)f);
                 dmx = std::max(dmx, std::max(P.dim[a], P.dim[c]));
@@ -454,6 +475,9 @@ struct Compiler {
                 if (P.vclass[v] != VC_GAUSS) fail(RXHIP_ERR_UNSUPPORTED, "factor %d (GCV): y, x and z must be random Gaussian variables", gc.node);
         }
         if (P.has_valnoise && dmx > 8) fail(RXHIP_ERR_UNSUPPORTED, "data-valued variances run on the lane-per-item kernels: dimensions <= 8 (this graph: %d)", dmx);
+        P.has_mat = any_mat;
+        if (any_mat && (P.has_mix || P.has_gcv || P.has_valnoise))
+            fail(RXHIP_ERR_UNSUPPORTED, "a data matrix in `*` next to NormalMixture / GCV nodes or data-valued variances has no schedule here (constant matrices only in such graphs)");
         P.has_mf = P.has_mf || P.has_mix;   // (the switch's rule reads the marginals of the means of the previous iteration: marginals are state)
         // <= 8: the register instances (lane per op and replica); above: the graph's own maximum, staged in LDS by a wavefront per op and replica
         P.dmax = dmx <= 1 ? 1 : dmx <= 2 ? 2 : dmx <= 4 ? 4 : dmx <= 8 ? 8 : dmx;
@@ -878,8 +902,9 @@ struct Compiler {
         P.marg_off.assign(nv, -1); P.val_off.assign(nv, -1); P.prec_off.assign(nv, -1);
         cval_off.assign(nv, -1); cmat_off.assign(nv, -1); noise_off_cov.assign(nv, -1); noise_off_prec.assign(nv, -1); prior_off.assign(nv, -1);
         long long vo = 0;
+        P.val_width.assign((size_t)nv, 0);
         for (int64_t v = 0; v < nv; ++v)
-            if (P.vclass[v] == VC_DATA) { P.val_off[v] = (int)vo; vo += P.dim[v]; P.data_vars.push_back(v); }
+            if (P.vclass[v] == VC_DATA) { P.val_off[v] = (int)vo; P.val_width[v] = P.is_mat[v] ? g->var_rows[v] * g->var_cols[v] : P.dim[v]; vo += P.val_width[v]; P.data_vars.push_back(v); }
         P.data_doubles = vo;
         for (int64_t v = 0; v < nv; ++v)
             if (P.vclass[v] == VC_DERIVED) { P.val_off[v] = (int)vo; vo += P.dim[v]; }
@@ -1017,6 +1042,8 @@ struct Compiler {
                 if (fm < 0)
                     fail(RXHIP_ERR_BADARG, "variable %lld sits on a Gaussian node under q(out) q(μ) and has no @initialization marginal (Normal / MvNormal): the first iteration has nothing to read",
                          (long long)v);
+                if (P.is_mat[iface((int)fm, 1)])
+                    fail(RXHIP_ERR_UNSUPPORTED, "variable %lld, the output of `*` with a data matrix, sits on a Gaussian node under q(out) q(μ): its initial marginal would depend on the data", (long long)v);
                 const int64_t u = iface((int)fm, 2);
                 const int du = P.dim[u];
                 const double *A = cptr((int)iface((int)fm, 1)), *q = g->const_pool + g->var_init[u];
@@ -1060,7 +1087,7 @@ struct Compiler {
                         if (!ready(b)) continue;
                         OpRec& r = emit(lv[b] , OP_DERIVE_MUL, P.dim[o]);
                         r.w[W_D1] = P.dim[b];
-                        r.w[W_C0] = const_matrix(a, P.dim[o], P.dim[b]);
+                        r.w[W_C0] = matrix_source(r, a, P.dim[o], P.dim[b], F_MAT_SLOT);
                         int bit; r.w[W_VAL] = value_source(b, bit); if (bit) r.w[W_FLAGS] |= F_VAL_SLOT;
                         r.w[W_OUT] = P.val_off[o];
                         lv[o] = lv[b] + 1;
@@ -1170,7 +1197,7 @@ struct Compiler {
                 const int dout = P.dim[iface(f, 0)], din = P.dim[iface(f, 2)];
                 OpRec& r = emit(lv, ed.k == 0 ? OP_MUL_OUT : OP_MUL_IN, dout);
                 r.w[W_D1] = din;
-                r.w[W_C0] = const_matrix((int)iface(f, 1), dout, din);
+                r.w[W_C0] = matrix_source(r, (int)iface(f, 1), dout, din, F_MAT_SLOT);
                 const int se = fac_edges[f][ed.k == 0 ? 2 : 0];
                 r.w[W_IN0] = src_off(E + se);
                 if (form[E + se]) r.w[W_FLAGS] |= F_IN0_WP;
@@ -1282,7 +1309,7 @@ struct Compiler {
                 const int u = push_from[v];
                 r.w[word] = P.marg_off[u];
                 r.w[W_FLAGS] |= bit;
-                r.w[word_a] = const_matrix((int)iface(push_fac[v], 1), P.dim[v], P.dim[u]);
+                r.w[word_a] = matrix_source(r, (int)iface(push_fac[v], 1), P.dim[v], P.dim[u], bit == F_PUSH_A ? F_MAT_SLOT : F_MAT_B_SLOT);
                 r.w[word_du] = P.dim[u];
                 if (word_ld >= 0) r.w[word_ld] = push_logdet(v);
             } else
@@ -1412,7 +1439,7 @@ struct Compiler {
                     const int u = push_from[v];
                     r.w[W_IN0] = P.marg_off[u];
                     r.w[W_FLAGS] |= F_PUSH_A;
-                    r.w[W_C0] = const_matrix((int)iface(push_fac[v], 1), P.dim[v], P.dim[u]);
+                    r.w[W_C0] = matrix_source(r, (int)iface(push_fac[v], 1), P.dim[v], P.dim[u], F_MAT_SLOT);
                     r.w[W_D1] = P.dim[u];
                     r.w[W_IN1] = push_logdet(v);
                 } else
@@ -1498,7 +1525,7 @@ struct Compiler {
             const int f = push_fac[v], u = push_from[v];
             OpRec& r = emit(lv, OP_MARG_PUSH, P.dim[v]);
             r.w[W_D1] = P.dim[u];
-            r.w[W_C0] = const_matrix((int)iface(f, 1), P.dim[v], P.dim[u]);
+            r.w[W_C0] = matrix_source(r, (int)iface(f, 1), P.dim[v], P.dim[u], F_MAT_SLOT);
             r.w[W_IN0] = P.marg_off[u];
             r.w[W_OUT] = P.marg_off[v];
             r.w[W_IN1] = push_logdet((int)v);
@@ -1571,7 +1598,8 @@ struct Compiler {
         if (push_ld[v] != -2) return push_ld[v];
         const int u = push_from[v], a = (int)iface(push_fac[v], 1);
         double ld;
-        if (P.dim[v] == P.dim[u] && host_logabsdet(P.dim[v], cptr(a), &ld)) {
+        // (a data matrix has no determinant the host could know: such an image takes the Cholesky route of a non-square map, per replica)
+        if (!P.is_mat[a] && P.dim[v] == P.dim[u] && host_logabsdet(P.dim[v], cptr(a), &ld)) {
             push_ld[v] = (int)P.cpool.size();
             P.cpool.push_back(2.0 * ld);
         } else
@@ -1607,6 +1635,14 @@ struct Compiler {
     }
     // messages nobody reads (since the marginals of `A * x` outputs stopped being products of messages: the message toward such an output when the node behind
     // it is observed, the product that fed it): their ops go, and then whatever only they were reading
+    // the per-replica matrices an op reads (F_MAT_SLOT / F_MAT_B_SLOT): 8·rows·cols each — a constant matrix is shared by all replicas and stays in cache
+    static long long matrix_bytes(const int* w) {
+        const int fl = w[W_FLAGS], d = w[W_D0];
+        long long b = 0;
+        if (fl & F_MAT_SLOT) b += 8ll * d * (w[W_OP] == OP_FE_NOISE2M ? w[W_LIST] : w[W_D1]);
+        if (fl & F_MAT_B_SLOT) b += 8ll * d * w[W_N];
+        return b;
+    }
     bool is_loop_old(int o) const { return P.n_loop && o >= 0 && o < P.loop_doubles; }
     bool is_loop_new(int o) const { return P.n_loop && o >= P.loop_doubles && o < 2 * P.loop_doubles; }
     void eliminate_dead_messages() {
@@ -1648,6 +1684,7 @@ struct Compiler {
         for (const OpRec& r : recs) {
             if (r.level >= P.fe_level) continue;
             for (const In& in : op_inputs(r.w)) P.bytes_per_sweep += 8ll * msz(in.d);
+            P.bytes_per_sweep += matrix_bytes(r.w);
             if (produces_msg(r.w[W_OP])) { P.bytes_per_sweep += 8ll * msz(r.w[W_OP] == OP_MUL_IN ? r.w[W_D1] : r.w[W_D0]); ++P.n_messages; }
             else if (r.w[W_OP] == OP_MARGINAL) P.bytes_per_sweep += 8ll * msz(r.w[W_D0]) + 8;
         }
@@ -1660,6 +1697,7 @@ struct Compiler {
             const int* w = r.w;
             const int d = w[W_D0];
             for (const In& in : op_inputs(w)) P.fe_bytes += 8ll * msz(in.d);
+            P.fe_bytes += matrix_bytes(w);
             switch (w[W_OP]) {
             case OP_FE_NOISE2M:
                 P.fe_bytes += 8ll * ((w[W_FLAGS] & F_PUSH_A) ? w[W_LIST] : d) + 8ll * (msz((w[W_FLAGS] & F_PUSH_B) ? w[W_N] : d) + 1) + 8;
@@ -1819,6 +1857,7 @@ struct Compiler {
                 }
                 for (size_t k = 0; k < ins.size(); ++k)
                     if (!(ins[k].kind == reg_kind[i] && ins[k].idx == reg_idx[i])) P.bytes_per_sweep_strands += msz8(ins[k].d);
+                P.bytes_per_sweep_strands += matrix_bytes(w);
                 const int op = w[W_OP];
                 if (produces_msg(op)) {
                     const int dout = op == OP_MUL_IN ? w[W_D1] : w[W_D0];

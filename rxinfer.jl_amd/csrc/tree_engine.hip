@@ -132,7 +132,7 @@ __global__ void __launch_bounds__(256) k_tree_carry(double* __restrict__ msg, co
 // host layout <-> replica-fastest device layout, on the device (at 65 536 replicas the host loops these replace ran for seconds)
 // data: dst[(k)·RS + r] = src[r·rows + col + k] for k < width — a 32×32 LDS tile so that both sides move whole lines
 __global__ void __launch_bounds__(256) k_tree_scatter(double* __restrict__ dst, const double* __restrict__ src, long long R, long long es, long long rs, long long rows, long long col,
-                                                      long long width, int* __restrict__ status) {
+                                                      long long width, int* __restrict__ status, int bad_bit) {
     __shared__ double tile[32][33];
     const long long r0 = (long long)blockIdx.x * 32, k0 = (long long)blockIdx.y * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 × 8
@@ -146,7 +146,7 @@ __global__ void __launch_bounds__(256) k_tree_scatter(double* __restrict__ dst, 
         if (k < width && r < R) {
             const double x = tile[tx][j];
             dst[k * es + r * rs] = x;
-            if (!(fabs(x) <= 1.79769313486231570815e308)) atomicOr(status, 2);   // NaN (`missing`) or ±Inf in the data: this executor has no rule for it
+            if (!(fabs(x) <= 1.79769313486231570815e308)) atomicOr(status, bad_bit);   // NaN (`missing`) or ±Inf in the data: this executor has no rule for it (bit 2: a value; bit 4: a data matrix)
         }
     }
 }
@@ -184,13 +184,14 @@ TreeParams params_of(const Engine* e, int want_fe) {
     TreeParams p{};
     p.ops = e->d_ops; p.aux = e->d_aux; p.cpool = e->d_cpool; p.msg = e->d_msg; p.marg = e->d_marg; p.val = e->d_val; p.prec = e->d_prec;
     p.term = e->d_term; p.stat = e->d_stat; p.R = e->R; p.RS = e->RS; p.want_fe = want_fe; p.status = e->d_status;
+    p.has_mat = e->prog.has_mat ? 1 : 0;
     const Program& P = e->prog;
     p.es = e->elem_fast ? 1 : e->RS;
     p.rs_msg = e->elem_fast ? P.msg_doubles : 1; p.rs_marg = e->elem_fast ? P.marg_doubles : 1; p.rs_val = e->elem_fast ? P.val_doubles : 1;
     p.rs_prec = e->elem_fast ? P.prec_doubles : 1; p.rs_term = e->elem_fast ? P.term_slots : 1; p.rs_stat = e->elem_fast ? P.stat_doubles : 1;
     return p;
 }
-template <int N, int PHASE>
+template <int N, int PHASE, bool MAT>
 void launch_phase(const Engine* e, const TreeParams& p, int l0, int l1) {
     if (l1 <= l0) return;
     const int mode = PHASE == 0 ? e->mode : e->mode_fe;
@@ -201,22 +202,22 @@ void launch_phase(const Engine* e, const TreeParams& p, int l0, int l1) {
             const int s0 = P.slvl_ptr[l], s1 = P.slvl_ptr[l + 1];
             if (s1 == s0) continue;
             const unsigned blocks = (unsigned)std::min<long long>((long long)(s1 - s0) * nrb, 1 << 22);
-            hipLaunchKernelGGL((k_tree_strands<(N <= 4 ? N : 4)>), dim3(blocks), dim3(64), 0, e->stream, p, (const int*)e->d_sops, (const int*)e->d_strands, s0, s1);
+            hipLaunchKernelGGL((k_tree_strands<(N <= 4 ? N : 4), MAT>), dim3(blocks), dim3(64), 0, e->stream, p, (const int*)e->d_sops, (const int*)e->d_strands, s0, s1);
         }
     } else if (mode == 2 || mode == 3) {
         const unsigned blocks = (unsigned)((e->R + 63) / 64);
-        hipLaunchKernelGGL((k_tree_walk<N, PHASE>), dim3(blocks), dim3(64), 0, e->stream, p, e->prog.lvl_ptr[l0], e->prog.lvl_ptr[l1]);
+        hipLaunchKernelGGL((k_tree_walk<N, PHASE, MAT>), dim3(blocks), dim3(64), 0, e->stream, p, e->prog.lvl_ptr[l0], e->prog.lvl_ptr[l1]);
     } else if (mode == 1) {
         const int rb = PHASE == 0 ? e->rb : e->rb_fe, wg = PHASE == 0 ? e->wg : 256;   // (the Bethe phase's instance is built for 256 threads: at 512 it spills)
         const unsigned blocks = (unsigned)((e->R + rb - 1) / rb);
-        hipLaunchKernelGGL((k_tree_levels<N, PHASE>), dim3(blocks), dim3(wg), 0, e->stream, p, e->d_lvl, l0, l1, rb);
+        hipLaunchKernelGGL((k_tree_levels<N, PHASE, MAT>), dim3(blocks), dim3(wg), 0, e->stream, p, e->d_lvl, l0, l1, rb);
     } else {
         for (int l = l0; l < l1; ++l) {
             const int o0 = e->prog.lvl_ptr[l], o1 = e->prog.lvl_ptr[l + 1];
             if (o1 == o0) continue;
             const long long items = (long long)(o1 - o0) * e->R;
             const unsigned blocks = (unsigned)std::min<long long>((items + 255) / 256, 1 << 20);
-            hipLaunchKernelGGL((k_tree_ops<N, PHASE>), dim3(blocks), dim3(256), 0, e->stream, p, o0, o1);
+            hipLaunchKernelGGL((k_tree_ops<N, PHASE, MAT>), dim3(blocks), dim3(256), 0, e->stream, p, o0, o1);
         }
     }
 }
@@ -254,12 +255,18 @@ rxhip_status wave_attributes(int dmax, std::string& err) {
     TCHK(wave::wave_vt(dmax)->prepare(dmax));
     return RXHIP_OK;
 }
-template <int N>
-void launch_levels(const Engine* e, const TreeParams& p, int l0, int l1) {   // the sweep, then the second phase
+template <int N, bool MAT>
+void launch_levels_m(const Engine* e, const TreeParams& p, int l0, int l1) {   // the sweep, then the second phase
     const int lf = e->prog.fe_level;
-    launch_phase<N, 0>(e, p, l0, std::min(l1, lf));
-    if (N <= 4 && !e->prog.fe_heavy) launch_phase<N, (N <= 4 ? 2 : 1)>(e, p, std::max(l0, lf), l1);   // the light instance: no `+` of two random inputs, no q(W) update in this graph
-    else launch_phase<N, 1>(e, p, std::max(l0, lf), l1);
+    launch_phase<N, 0, MAT>(e, p, l0, std::min(l1, lf));
+    if (N <= 4 && !e->prog.fe_heavy) launch_phase<N, (N <= 4 ? 2 : 1), MAT>(e, p, std::max(l0, lf), l1);   // the light instance: no `+` of two random inputs, no q(W) update in this graph
+    else launch_phase<N, 1, MAT>(e, p, std::max(l0, lf), l1);
+}
+// a program without a data matrix launches the instances that carry no code for one (tree_kernels.hpp MAT): the kernels it ran before data matrices existed
+template <int N>
+void launch_levels(const Engine* e, const TreeParams& p, int l0, int l1) {
+    if (e->prog.has_mat) launch_levels_m<N, true>(e, p, l0, l1);
+    else launch_levels_m<N, false>(e, p, l0, l1);
 }
 void launch(const Engine* e, const TreeParams& p, int l0, int l1) {
     if (e->tiled) {
@@ -448,7 +455,7 @@ rxhip_status set_data(Engine* e, const int64_t* vars, int64_t n_vars, const doub
     for (int64_t i = 0; i < n_vars; ++i) {
         const int64_t v = vars[i];
         if (v < 0 || v >= (int64_t)P.vclass.size() || P.vclass[v] != VC_DATA) { err = "set_data: variable " + std::to_string(v) + " is not a data variable"; return RXHIP_ERR_BADARG; }
-        rows += P.dim[v];
+        rows += P.val_width[v];   // (a data matrix: rows·cols doubles, row-major)
     }
     // the host rows go up as they are ([replica][Σ dims], in blocks of at most 256 MB) and are scattered into the replica-fastest slots on the device:
     // one kernel per run of adjacent slots
@@ -464,10 +471,10 @@ rxhip_status set_data(Engine* e, const int64_t* vars, int64_t n_vars, const doub
         for (int64_t i = 0; i < n_vars;) {
             int64_t j = i;
             long long width = 0;
-            while (j < n_vars && P.val_off[vars[j]] == P.val_off[vars[i]] + width) { width += P.dim[vars[j]]; ++j; }
+            while (j < n_vars && P.val_off[vars[j]] == P.val_off[vars[i]] + width && P.is_mat[vars[j]] == P.is_mat[vars[i]]) { width += P.val_width[vars[j]]; ++j; }
             const dim3 grid((unsigned)((nr + 31) / 32), (unsigned)((width + 31) / 32));
             const long long es = e->elem_fast ? 1 : e->RS, rs = e->elem_fast ? P.val_doubles : 1;
-            hipLaunchKernelGGL(k_tree_scatter, grid, dim3(256), 0, e->stream, e->d_val + (size_t)P.val_off[vars[i]] * es + (size_t)r0 * rs, (const double*)d_tmp, nr, es, rs, rows, col, width, e->d_status);
+            hipLaunchKernelGGL(k_tree_scatter, grid, dim3(256), 0, e->stream, e->d_val + (size_t)P.val_off[vars[i]] * es + (size_t)r0 * rs, (const double*)d_tmp, nr, es, rs, rows, col, width, e->d_status, P.is_mat[vars[i]] ? 4 : 2);
             col += width;
             i = j;
         }
@@ -478,6 +485,11 @@ rxhip_status set_data(Engine* e, const int64_t* vars, int64_t n_vars, const doub
     {
         int flag = 0;
         TCHK(hipMemcpy(&flag, e->d_status, sizeof(int), hipMemcpyDeviceToHost));
+        if (flag & 4) {   // a `missing` regressor has no meaning, with or without allow_missing
+            TCHK(hipMemset(e->d_status, 0, sizeof(int)));
+            err = "set_data: a data matrix holds NaN or Inf — the matrix of a `*` node cannot be `missing`";
+            return RXHIP_ERR_BADARG;
+        }
         if ((flag & 2) && e->allow_missing) TCHK(hipMemset(e->d_status, 0, sizeof(int)));   // (NaN = `missing`: the leaves and Bethe terms of this engine look for it)
         else if (flag & 2) {
             TCHK(hipMemset(e->d_status, 0, sizeof(int)));
@@ -596,6 +608,7 @@ rxhip_status get_marginals(Engine* e, const int64_t* vars, int64_t n_vars, doubl
         const int64_t v = vars[i];
         // (a derived clamped value — `a + b` of two data variables, a random variable of the MODEL — is a point mass, as the reference publishes it; so is a data variable)
         const bool cl = v >= 0 && v < (int64_t)P.vclass.size() && (P.vclass[v] == VC_DERIVED || P.vclass[v] == VC_DATA);
+        if (cl && P.is_mat[v]) { err = "get_marginals: variable " + std::to_string(v) + " is a data matrix"; return RXHIP_ERR_BADARG; }
         if (v < 0 || v >= (int64_t)P.vclass.size() || (P.vclass[v] != VC_GAUSS && !cl)) { err = "get_marginals: variable " + std::to_string(v) + " is not a random Gaussian variable"; return RXHIP_ERR_BADARG; }
         gv[i].off = cl ? P.val_off[v] : P.marg_off[v];
         gv[i].d = P.dim[v];

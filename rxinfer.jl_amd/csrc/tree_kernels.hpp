@@ -75,6 +75,9 @@ enum : int {
     F_NOISE_VAL = 131072,      // a SCALAR Gaussian node whose variance (F_NOISE_VAL_PREC: precision) is a DATA variable — `x ~ Normal(mean = m_prev, var = v_prev)` of a streaming
                                // model's @autoupdates: the value slot W_C0 instead of a constant block (lane-per-item kernels)
     F_NOISE_VAL_PREC = 262144,
+    F_MAT_SLOT = 1048576,      // `*` with a DATA matrix (every replica its own, rxhip_tree_set_data): the matrix word of the op — W_C0 of OP_DERIVE_MUL / OP_MUL_OUT / OP_MUL_IN /
+                               // OP_MARG_PUSH / OP_FE_ENT, the F_PUSH_A matrix of OP_FE_NOISE2M / OP_FE_NOISE1 — names a value slot of rows·cols doubles (row-major), not the constant pool
+    F_MAT_B_SLOT = 2097152,    // … the F_PUSH_B matrix of OP_FE_NOISE2M
     F_VAL_MARG = 8192    // OP_LEAF: the value is the MEAN of the marginal slot W_VAL — the rule of a Gaussian node under q(out) q(μ): N(E[μ], Σ) toward out, N(E[out], Σ) toward μ
 };
 // strand schedule: an input offset that names the message the previous op of the lane's strand left in registers
@@ -100,9 +103,17 @@ struct TreeParams {
     // dimension above 8): es = 1, rs = the array's doubles per replica.
     long long es, rs_msg, rs_marg, rs_val, rs_prec, rs_term, rs_stat;
     int want_fe;
+    int has_mat;          // host side only: the program reads data matrices — the launches pick the MAT instances
     int* status;          // bit 0: a matrix that must be positive definite was not
 };
 
+// MAT (template parameter of the rule bodies and kernels): the program holds `*` nodes with DATA matrices (TreeParams.has_mat).  Instances with MAT = false carry no
+// code for them: a graph without a data matrix runs the kernels it ran before data matrices existed.  (The host emulation builds the bodies with both.)
+#ifdef RXHIP_HOST_EMUL
+constexpr bool MAT_DEFAULT = true;
+#else
+constexpr bool MAT_DEFAULT = false;
+#endif
 constexpr double T_LOG2PI = 1.8378770664093454836;
 constexpr double T_ABSENT_VARIANCE = 1.0e200;   // the moment form of "no message" (load_msg)
 constexpr double T_LOG2 = 0.69314718055994530942;
@@ -161,6 +172,18 @@ __device__ __forceinline__ void ld_cmat(const double* c, int rows, int cols, dou
     for (int i = 0; i < N; ++i)
 #pragma unroll
         for (int j = 0; j < N; ++j) M[i][j] = (i < rows && j < cols) ? c[i * cols + j] : (i == j ? pad : 0.0);
+}
+// the matrix of a `*` node: the constant at cpool + off, or (slot: F_MAT_SLOT / F_MAT_B_SLOT) this replica's own rows×cols matrix in the value slot `off` —
+// element (i, j) at (off + i·cols + j)·RS + r, coalesced across replicas like every other per-replica load; zero padding
+template <int N>
+__device__ __forceinline__ void ld_amat(const double* c, const double* val, int off, bool slot, int rows, int cols, long long RS, long long r, double (&M)[N][N]) {
+    if (slot) {
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+#pragma unroll
+            for (int j = 0; j < N; ++j) M[i][j] = (i < rows && j < cols) ? val[((long long)off + i * cols + j) * RS + r] : 0.0;
+    } else
+        ld_cmat<N>(c + off, rows, cols, 0.0, M);
 }
 template <int N>
 __device__ __forceinline__ void ld_cvec(const double* c, int d, double (&v)[N]) {
@@ -430,10 +453,10 @@ __device__ __forceinline__ bool spd_logdet(const double (&A)[N][N], double& logd
 // A marginal as the Bethe terms read it: (mean, covariance, log|V|) of the slot `off` — or, `push`, of the image of that marginal under the constant d × du
 // matrix at cpool + aoff: the output of `A * x` has the marginal (A m, A V Aᵀ) of x's (exact on a tree), so the marginals of such (anonymous) variables are
 // never stored for the free energy's sake; a singular image (more rows than columns) has log|V| = −∞, as the entropy of the message route.
-// ldoff ≥ 0: cpool[ldoff] = 2·log|det A| of a square map — log|A V Aᵀ| = log|V| + that, no Cholesky
+// ldoff ≥ 0: cpool[ldoff] = 2·log|det A| of a square map — log|A V Aᵀ| = log|V| + that, no Cholesky.  aslot: the matrix is this replica's own (ld_amat; no ldoff then)
 template <int N>
 __device__ __forceinline__ void load_marginal(const TreeParams& p, int off, bool push, int aoff, int du, int d, long long r, bool want_cov, double (&m)[N], double (&V)[N][N], double& ldV,
-                                              int ldoff = -1) {
+                                              int ldoff = -1, bool aslot = false) {
     if (!push) {
         ld_vec<N>(p.marg, off, d, p.RS, r, m);
         if (want_cov) {
@@ -444,7 +467,7 @@ __device__ __forceinline__ void load_marginal(const TreeParams& p, int off, bool
     }
     double mu[N], A[N][N];
     ld_vec<N>(p.marg, off, du, p.RS, r, mu);
-    ld_cmat<N>(p.cpool + aoff, d, du, 0.0, A);
+    ld_amat<N>(p.cpool, p.val, aoff, aslot, d, du, p.RS, r, A);
     matvec<N>(A, mu, m);
     if (!want_cov) return;
     double Vu[N][N], T1[N][N], Vp[N][N], ld;
@@ -483,14 +506,15 @@ __device__ __forceinline__ double t_mvlgamma(double a, int d) {
 // ------------------------------------------------------------------------------------------
 // the sum-product sweep: rules, products, marginals (PHASE 0) — and the Bethe terms, residual moments and q(W) updates (PHASE 1), a kernel of their own:
 // the log-gamma / digamma code and the joint-marginal algebra of the second phase would otherwise set the register budget of every rule
-template <int N, bool STRAND = false>
+template <int N, bool STRAND = false, bool MAT = MAT_DEFAULT>
 __device__ __forceinline__ void eval_bp(const TreeParams& p, const int* __restrict__ w, long long r, RegMsg<N>* reg = nullptr) {
     const int op = w[W_OP], d = w[W_D0], fl = w[W_FLAGS];
+    const int flm = MAT ? fl : 0;   // (MAT = false — a program without a data matrix: the loaders' slot branch is compiled out, the instance is the constant-only one)
     bool ok = true;
     switch (op) {
     case OP_DERIVE_MUL: {   // val[out] = A (d × d1) val[in]
         double A[N][N], x[N], y[N];
-        ld_cmat<N>(p.cpool + w[W_C0], d, w[W_D1], 0.0, A);
+        ld_amat<N>(p.cpool, p.val, w[W_C0], flm & F_MAT_SLOT, d, w[W_D1], p.RS, r, A);
         load_value<N>(p, w[W_VAL], fl & F_VAL_SLOT, w[W_D1], r, x);
         matvec<N>(A, x, y);
         st_vec<N>(p.val, w[W_OUT], d, p.RS, r, y);
@@ -689,7 +713,7 @@ __device__ __forceinline__ void eval_bp(const TreeParams& p, const int* __restri
     case OP_MUL_OUT: {   // in: dimension d1 (moment form), out: dimension d
         double a[N], V[N][N], A[N][N], m[N], T1[N][N], Vo[N][N];
         ok = load_msg<N, STRAND>(p, w[W_IN0], fl & F_IN0_WP, false, w[W_D1], r, a, V, reg);
-        ld_cmat<N>(p.cpool + w[W_C0], d, w[W_D1], 0.0, A);
+        ld_amat<N>(p.cpool, p.val, w[W_C0], flm & F_MAT_SLOT, d, w[W_D1], p.RS, r, A);
         matvec<N>(A, a, m);
         matmul<N>(A, V, T1);
         matmulT<N>(T1, A, Vo);
@@ -698,7 +722,7 @@ __device__ __forceinline__ void eval_bp(const TreeParams& p, const int* __restri
     case OP_MUL_IN: {    // in: the message toward `out`, dimension d (precision form); out: dimension d1
         double xi[N], L[N][N], A[N][N], xo[N], T1[N][N], Lo[N][N];
         ok = load_msg<N, STRAND>(p, w[W_IN0], fl & F_IN0_WP, true, d, r, xi, L, reg);
-        ld_cmat<N>(p.cpool + w[W_C0], d, w[W_D1], 0.0, A);
+        ld_amat<N>(p.cpool, p.val, w[W_C0], flm & F_MAT_SLOT, d, w[W_D1], p.RS, r, A);
 #pragma unroll
         for (int i = 0; i < N; ++i)   // the padding of Λ beyond d meets zero rows of A
             if (i >= d) L[i][i] = 0.0;
@@ -831,9 +855,10 @@ __device__ __forceinline__ void eval_bp(const TreeParams& p, const int* __restri
 }
 // LIGHT: the instance for graphs without a `+` of two random inputs and without precision variables — the log-gamma / digamma code of OP_PREC_UPDATE and the
 // two-inverse algebra of OP_FE_ADD2 would otherwise set the register budget of every Bethe term (320 VGPRs against the light instance's; tree_engine.hip picks)
-template <int N, bool LIGHT = false>
+template <int N, bool LIGHT = false, bool MAT = MAT_DEFAULT>
 __device__ __forceinline__ void eval_fe(const TreeParams& p, const int* __restrict__ w, long long r) {
     const int op = w[W_OP], d = w[W_D0], fl = w[W_FLAGS];
+    const int flm = MAT ? fl : 0;   // (MAT = false — a program without a data matrix: the loaders' slot branch is compiled out, the instance is the constant-only one)
     bool ok = true;
     switch (op) {
 #ifdef RXHIP_HOST_EMUL   // (the executor emits OP_FE_NOISE2M for these kernels; the message-only form stays as the host differential test's reference of the LDS body)
@@ -904,7 +929,7 @@ __device__ __forceinline__ void eval_fe(const TreeParams& p, const int* __restri
         const int din = w[W_D1];
         ld_vec<N>(p.marg, w[W_IN0], din, p.RS, r, m);
         ld_sym<N>(p.marg, w[W_IN0] + din, din, p.RS, r, 0.0, V);
-        ld_cmat<N>(p.cpool + w[W_C0], d, din, 0.0, A);
+        ld_amat<N>(p.cpool, p.val, w[W_C0], flm & F_MAT_SLOT, d, din, p.RS, r, A);
         matvec<N>(A, m, mo);
         matmul<N>(A, V, T1);
         matmulT<N>(T1, A, Vo);
@@ -936,8 +961,8 @@ __device__ __forceinline__ void eval_fe(const TreeParams& p, const int* __restri
             for (int j = 0; j < N; ++j) P[i][j] = ((w[W_IN0] >= 0 && i < d && j < d) ? La[i][j] : 0.0) + Wm[i][j];
         ok = spd_inv<N>(P, Pi, ldP) && ok;
         double ma[N], mb[N], Vb[N][N], ldVb, unused;
-        load_marginal<N>(p, w[W_VAL], fl & F_PUSH_A, w[W_IN1], w[W_LIST], d, r, false, ma, Vb, unused);
-        load_marginal<N>(p, w[W_VAL2], fl & F_PUSH_B, w[W_IN2], w[W_N], d, r, true, mb, Vb, ldVb, (fl & F_PUSH_B) ? w[W_D1] : -1);
+        load_marginal<N>(p, w[W_VAL], fl & F_PUSH_A, w[W_IN1], w[W_LIST], d, r, false, ma, Vb, unused, -1, flm & F_MAT_SLOT);
+        load_marginal<N>(p, w[W_VAL2], fl & F_PUSH_B, w[W_IN2], w[W_N], d, r, true, mb, Vb, ldVb, (fl & F_PUSH_B) ? w[W_D1] : -1, flm & F_MAT_B_SLOT);
         if (fl & F_JOINT_B) {
             double xb[N], Lb[N][N], T1[N][N], T3[N][N], S[N][N], Si[N][N], t[N], u[N], ldS;
             ok = load_msg<N>(p, w[W_IN1], fl & F_IN1_WP, true, d, r, xb, Lb) && ok;
@@ -1015,7 +1040,7 @@ __device__ __forceinline__ void eval_fe(const TreeParams& p, const int* __restri
         load_noise<N>(p, w, d, r, false, true, Sg, Wm, el);
         if (op == OP_FE_NOISE1) {
             double m[N], V[N][N], c[N], ldV;
-            load_marginal<N>(p, w[W_IN0], fl & F_PUSH_A, w[W_IN1], w[W_D1], d, r, true, m, V, ldV, (fl & F_PUSH_A) ? w[W_IN2] : -1);
+            load_marginal<N>(p, w[W_IN0], fl & F_PUSH_A, w[W_IN1], w[W_D1], d, r, true, m, V, ldV, (fl & F_PUSH_A) ? w[W_IN2] : -1, flm & F_MAT_SLOT);
             H = 0.5 * (d * (T_LOG2PI + 1.0) + ldV);
             if (fl & F_FOLD_ENT) H *= (double)(1 - w[W_OUT]);   // (−H of the node + coef·H of the variable, folded: −(1 − coef)·H below)
             load_value<N>(p, w[W_VAL], fl & F_VAL_SLOT, d, r, c);
@@ -1057,7 +1082,7 @@ __device__ __forceinline__ void eval_fe(const TreeParams& p, const int* __restri
         double ldV;
         if (fl & F_PUSH_A) {
             double m[N], V[N][N];
-            load_marginal<N>(p, w[W_IN0], true, w[W_C0], w[W_D1], d, r, true, m, V, ldV, w[W_IN1]);
+            load_marginal<N>(p, w[W_IN0], true, w[W_C0], w[W_D1], d, r, true, m, V, ldV, w[W_IN1], flm & F_MAT_SLOT);
         } else
             ldV = p.marg[(w[W_IN0] + d + d * (d + 1) / 2) * p.RS + r];
         p.term[(long long)w[W_TERM] * p.RS + r] = (double)w[W_N] * 0.5 * (d * (T_LOG2PI + 1.0) + ldV);
@@ -1208,11 +1233,11 @@ __device__ __forceinline__ void eval_fe(const TreeParams& p, const int* __restri
 }
 
 // one launch per level: items (op, replica) over the grid
-template <int N, int PHASE>   // PHASE 0: the sweep; 1: the Bethe terms / q(W) updates; 2: the same without OP_FE_ADD2 / OP_PREC_UPDATE (the light instance)
+template <int N, int PHASE, bool MAT = false>   // PHASE 0: the sweep; 1: the Bethe terms / q(W) updates; 2: the same without OP_FE_ADD2 / OP_PREC_UPDATE (the light instance)
 __device__ __forceinline__ void eval_op(const TreeParams& p, const int* __restrict__ w, long long r) {
-    if (PHASE == 0) eval_bp<N>(p, w, r);
-    else if (PHASE == 1) eval_fe<N, false>(p, w, r);
-    else eval_fe<N, true>(p, w, r);
+    if (PHASE == 0) eval_bp<N, false, MAT>(p, w, r);
+    else if (PHASE == 1) eval_fe<N, false, MAT>(p, w, r);
+    else eval_fe<N, true, MAT>(p, w, r);
 }
 #ifndef RXHIP_FE_WAVES
 #define RXHIP_FE_WAVES 2      // wavefronts per SIMD the light Bethe-phase instance is compiled for.  Measured at 65 536 replicas (plain / two-branch chain, Bethe phase):
@@ -1222,18 +1247,18 @@ __device__ __forceinline__ void eval_op(const TreeParams& p, const int* __restri
 #ifndef RXHIP_STRAND_WAVES
 #define RXHIP_STRAND_WAVES 2  // … the strand kernel
 #endif
-template <int N, int PHASE>
+template <int N, int PHASE, bool MAT = false>
 __global__ void __launch_bounds__(256, (PHASE == 2 && N == 4) ? RXHIP_FE_WAVES : 1) k_tree_ops(TreeParams p, int op0, int op1) {
     const long long total = (long long)(op1 - op0) * p.R;
     for (long long it = (long long)blockIdx.x * blockDim.x + threadIdx.x; it < total; it += (long long)gridDim.x * blockDim.x) {
         const long long o = it / p.R, r = it - o * p.R;
-        eval_op<N, PHASE>(p, p.ops + (size_t)(op0 + o) * OP_WORDS, r);
+        eval_op<N, PHASE, MAT>(p, p.ops + (size_t)(op0 + o) * OP_WORDS, r);
     }
 }
 // (sweep phase at N ≤ 4: up to 512 threads — eight wavefronts share a CU's level barriers; the Bethe phase and the 8×8 instance need the registers of 256)
 // the whole schedule in one launch: a workgroup owns `rb` replicas (a multiple of 16: whole 128-byte lines of every slot) and walks the levels with a
 // workgroup barrier between them — for deep, narrow graphs (a chain is three levels per time step) where a launch per level would cost more than the level
-template <int N, int PHASE>
+template <int N, int PHASE, bool MAT = false>
 __global__ void __launch_bounds__((PHASE == 0 && N <= 4) ? 512 : 256) k_tree_levels(TreeParams p, const int* __restrict__ lvl_ptr, int l0, int l1, int rb) {
     const long long r0 = (long long)blockIdx.x * rb;
     const int nr = (int)((p.R - r0) < rb ? (p.R - r0) : rb);
@@ -1242,7 +1267,7 @@ __global__ void __launch_bounds__((PHASE == 0 && N <= 4) ? 512 : 256) k_tree_lev
         const int total = (o1 - o0) * nr;
         for (int it = threadIdx.x; it < total; it += blockDim.x) {
             const int o = it / nr, r = it - o * nr;
-            eval_op<N, PHASE>(p, p.ops + (size_t)(o0 + o) * OP_WORDS, r0 + r);
+            eval_op<N, PHASE, MAT>(p, p.ops + (size_t)(o0 + o) * OP_WORDS, r0 + r);
         }
         __syncthreads();   // (waits for the level's stores: every reader of the next level is in this workgroup)
     }
@@ -1252,7 +1277,7 @@ __global__ void __launch_bounds__((PHASE == 0 && N <= 4) ? 512 : 256) k_tree_lev
 // walks the strand's ops for 64 replicas and hands each message to the next op IN REGISTERS; a message goes to HBM only if somebody outside the strand
 // (a marginal, a product elsewhere, the Bethe phase) reads it.  A chain: 2T + 1 leaf strands, then the forward and the backward recursion side by side,
 // then the marginals — three launches, the wide levels at full occupancy, the two recursions without a barrier or a dependent load between their ops.
-template <int N>
+template <int N, bool MAT = false>
 __global__ void __launch_bounds__(64, N == 4 ? RXHIP_STRAND_WAVES : 1) k_tree_strands(TreeParams p, const int* __restrict__ sops, const int* __restrict__ strands, int s0, int s1) {
     const long long nrb = (p.R + 63) / 64, total = (long long)(s1 - s0) * nrb;
     for (long long b = blockIdx.x; b < total; b += gridDim.x) {
@@ -1260,16 +1285,16 @@ __global__ void __launch_bounds__(64, N == 4 ? RXHIP_STRAND_WAVES : 1) k_tree_st
         if (r >= p.R) continue;
         const int o0 = strands[2 * (s0 + s)], n = strands[2 * (s0 + s) + 1];
         RegMsg<N> reg;
-        for (int o = o0; o < o0 + n; ++o) eval_bp<N, true>(p, sops + (size_t)o * OP_WORDS, r, &reg);
+        for (int o = o0; o < o0 + n; ++o) eval_bp<N, true, MAT>(p, sops + (size_t)o * OP_WORDS, r, &reg);
     }
 }
 // a lane owns a replica and walks the ops of the range in order: no barriers, no cross-lane dependencies, every wavefront evaluates the same op for 64
 // replicas with unit-stride loads — the schedule of LARGE batches (from a few waves per SIMD on it is bound by the messages' HBM traffic, not by latency)
-template <int N, int PHASE>
+template <int N, int PHASE, bool MAT = false>
 __global__ void __launch_bounds__(64) k_tree_walk(TreeParams p, int op0, int op1) {
     const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= p.R) return;
-    for (int o = op0; o < op1; ++o) eval_op<N, PHASE>(p, p.ops + (size_t)o * OP_WORDS, r);
+    for (int o = op0; o < op1; ++o) eval_op<N, PHASE, MAT>(p, p.ops + (size_t)o * OP_WORDS, r);
 }
 }  // namespace tree
 }  // namespace rxhip

@@ -447,6 +447,13 @@ __device__ __forceinline__ void load_value(const Env<NT>& E, int off, bool slot,
     if (slot) load_vec<NT, ES1>(E.L, E.val(off), E.p.es, d, v);
     else load_vec<NT, true>(E.L, E.p.cpool + off, 1, d, v);
 }
+// the matrix of a `*` node (element (i, j) at i · si + j · sj of a row-major block): the constant at cpool + off, or (slot: F_MAT_SLOT / F_MAT_B_SLOT) this
+// replica's own matrix in the value slot `off` — straight into the register tiles, the layout load_mat gives the constant
+template <int NT, bool ES1>
+__device__ __forceinline__ void load_amat(const Env<NT>& E, int off, bool slot, int rows, int cols, int si, int sj, Mat<NT>& m) {
+    if (slot) load_mat<NT, ES1>(E.L, E.val(off), E.p.es, rows, cols, si, sj, m);
+    else load_mat<NT, true>(E.L, E.p.cpool + off, 1, rows, cols, si, sj, m);
+}
 template <int NT>
 __device__ __forceinline__ bool any_nan(const Vec<NT>& v) {
     bool bad = false;
@@ -456,9 +463,9 @@ __device__ __forceinline__ bool any_nan(const Vec<NT>& v) {
 }
 
 // A marginal as the second phase reads it (tree_wave_kernels.hpp load_marginal): mean, covariance (want_cov), log|V| — of the slot `off`, or (push) of its IMAGE
-// under the constant d × du matrix at cpool + aoff: (A m, A V Aᵀ); ldoff ≥ 0: a square map, log|A V Aᵀ| = log|V| + cpool[ldoff]
+// under the constant d × du matrix at cpool + aoff: (A m, A V Aᵀ); ldoff ≥ 0: a square map, log|A V Aᵀ| = log|V| + cpool[ldoff]; aslot: the replica's own matrix (load_amat)
 template <int NT, bool ES1>
-__device__ __forceinline__ double load_marginal(const Env<NT>& E, int off, bool push, int aoff, int du, int d, bool want_cov, Vec<NT>& m, Mat<NT>& V, int ldoff = -1) {
+__device__ __forceinline__ double load_marginal(const Env<NT>& E, int off, bool push, int aoff, int du, int d, bool want_cov, Vec<NT>& m, Mat<NT>& V, int ldoff = -1, bool aslot = false) {
     const double* b = E.marg(off);
     const long long es = E.p.es;
     if (!push) {
@@ -468,7 +475,7 @@ __device__ __forceinline__ double load_marginal(const Env<NT>& E, int off, bool 
         return b[(long long)(d + d * (d + 1) / 2) * es];
     }
     Mat<NT> at;   // Aᵀ (du × d): element (i, j) = A[j][i] at j · du + i
-    load_mat<NT, true>(E.L, E.p.cpool + aoff, 1, du, d, 1, du, at);
+    load_amat<NT, ES1>(E, aoff, aslot, du, d, 1, du, at);
     VecK<NT> mu;
     load_veck<NT, ES1>(E.L, b, es, du, mu);
     m = matvec_t<NT>(at, mu);
@@ -486,9 +493,10 @@ __device__ __forceinline__ double load_marginal(const Env<NT>& E, int off, bool 
 }
 
 // the sweep (ops up to OP_MARGINAL): tree_wave_kernels.hpp eval_bp, op for op
-template <int NT, bool ES1>
+template <int NT, bool ES1, bool MAT = false>
 __device__ __forceinline__ void eval_bp(const Env<NT>& E, const int* __restrict__ w) {
     const int op = w[W_OP], d = w[W_D0], fl = w[W_FLAGS];
+    const int flm = MAT ? fl : 0;   // (MAT = false — a program without a data matrix: the loaders' slot branch is compiled out, the instance is the constant-only one)
     const Lane<NT>& L = E.L;
     const long long es = E.p.es;
     bool ok = true;
@@ -496,7 +504,7 @@ __device__ __forceinline__ void eval_bp(const Env<NT>& E, const int* __restrict_
     case OP_DERIVE_MUL: {
         const int d1 = w[W_D1];
         Mat<NT> at;
-        load_mat<NT, true>(L, E.p.cpool + w[W_C0], 1, d1, d, 1, d1, at);
+        load_amat<NT, ES1>(E, w[W_C0], flm & F_MAT_SLOT, d1, d, 1, d1, at);
         VecK<NT> x;
         if (fl & F_VAL_SLOT) load_veck<NT, ES1>(L, E.val(w[W_VAL]), es, d1, x);
         else load_veck<NT, true>(L, E.p.cpool + w[W_VAL], 1, d1, x);
@@ -559,7 +567,7 @@ __device__ __forceinline__ void eval_bp(const Env<NT>& E, const int* __restrict_
         Vec<NT> v;
         Mat<NT> V, at, Y, Vo;
         ok = load_msg<NT, ES1>(E, w[W_IN0], fl & F_IN0_WP, false, d1, v, V);
-        load_mat<NT, true>(L, E.p.cpool + w[W_C0], 1, d1, d, 1, d1, at);   // Aᵀ
+        load_amat<NT, ES1>(E, w[W_C0], flm & F_MAT_SLOT, d1, d, 1, d1, at);   // Aᵀ
         const Vec<NT> m = matvec_t<NT>(at, to_k<NT>(L, v));
         const int n16 = tiles<NT>(d > d1 ? d : d1);
         mul<NT>(Y, V, at, n16);     // V Aᵀ
@@ -571,7 +579,7 @@ __device__ __forceinline__ void eval_bp(const Env<NT>& E, const int* __restrict_
         Vec<NT> v;
         Mat<NT> Lm, a, Y, Lo;
         ok = load_msg<NT, ES1>(E, w[W_IN0], fl & F_IN0_WP, true, d, v, Lm);
-        load_mat<NT, true>(L, E.p.cpool + w[W_C0], 1, d, d1, d1, 1, a);   // A
+        load_amat<NT, ES1>(E, w[W_C0], flm & F_MAT_SLOT, d, d1, d1, 1, a);   // A
         const Vec<NT> xo = matvec_t<NT>(a, to_k<NT>(L, v));
         const int n16 = tiles<NT>(d > d1 ? d : d1);
         mul<NT>(Y, Lm, a, n16);     // Λ A
@@ -670,9 +678,10 @@ __device__ __forceinline__ void eval_bp(const Env<NT>& E, const int* __restrict_
 // the second phase: Bethe terms, residual moments, q(W) updates — tree_wave_kernels.hpp eval_fe, op for op
 // HEAVY = false: the instance without the joint-marginal algebra (OP_FE_NOISE2M, OP_FE_ADD2) and the q(W) update — the terms of a chain's observation nodes, the
 // entropies, the sums: half the registers, twice the wavefronts per SIMD (the host launches a level's ops by opcode class: tree_engine.hip launch_wave_phase)
-template <int NT, bool ES1, int HEAVY = 1>   // 1: every op; 0: the light ops; 2: OP_FE_NOISE2M alone (the joint term of a chain's transitions: its own register budget)
+template <int NT, bool ES1, int HEAVY = 1, bool MAT = false>   // 1: every op; 0: the light ops; 2: OP_FE_NOISE2M alone (the joint term of a chain's transitions: its own register budget)
 __device__ __forceinline__ void eval_fe(const Env<NT>& E, const int* __restrict__ w) {
     const int op = w[W_OP], d = w[W_D0], fl = w[W_FLAGS];
+    const int flm = MAT ? fl : 0;   // (MAT = false — a program without a data matrix: the loaders' slot branch is compiled out, the instance is the constant-only one)
     const Lane<NT>& L = E.L;
     const long long es = E.p.es;
     const int n16 = tiles<NT>(d);
@@ -681,7 +690,7 @@ __device__ __forceinline__ void eval_fe(const Env<NT>& E, const int* __restrict_
     case OP_MARG_PUSH: {   // the stored marginal of an `A * x` output, formed when a caller asks for it
         Vec<NT> m;
         Mat<NT> V;
-        const double ldV = load_marginal<NT, ES1>(E, w[W_IN0], true, w[W_C0], w[W_D1], d, true, m, V, w[W_IN1]);
+        const double ldV = load_marginal<NT, ES1>(E, w[W_IN0], true, w[W_C0], w[W_D1], d, true, m, V, w[W_IN1], flm & F_MAT_SLOT);
         double* b = E.marg(w[W_OUT]);
         store_vec<NT, ES1>(L, b, es, d, m);
         store_sym<NT, ES1>(L, b + (long long)d * es, es, d, V);
@@ -692,8 +701,8 @@ __device__ __forceinline__ void eval_fe(const Env<NT>& E, const int* __restrict_
         // Cov(a − b) = P⁻¹ + D V_b Dᵀ with D = P⁻¹ W − I — formed from Dᵀ = W P⁻¹ − I alone: D (V_b Dᵀ)
         Vec<NT> mb, ma, v0;
         Mat<NT> Vb, P, W, Dt, Y, dummy;
-        const double ldVb = load_marginal<NT, ES1>(E, w[W_VAL2], fl & F_PUSH_B, w[W_IN2], w[W_N], d, true, mb, Vb, (fl & F_PUSH_B) ? w[W_D1] : -1);
-        (void)load_marginal<NT, ES1>(E, w[W_VAL], fl & F_PUSH_A, w[W_IN1], w[W_LIST], d, false, ma, dummy);
+        const double ldVb = load_marginal<NT, ES1>(E, w[W_VAL2], fl & F_PUSH_B, w[W_IN2], w[W_N], d, true, mb, Vb, (fl & F_PUSH_B) ? w[W_D1] : -1, flm & F_MAT_B_SLOT);
+        (void)load_marginal<NT, ES1>(E, w[W_VAL], fl & F_PUSH_A, w[W_IN1], w[W_LIST], d, false, ma, dummy, -1, flm & F_MAT_SLOT);
         if (w[W_IN0] >= 0) ok = load_msg<NT, ES1>(E, w[W_IN0], fl & F_IN0_WP, true, d, v0, P);
         else zero<NT>(P);
         const double el = load_noise<NT, ES1>(E, w, d, false, W);
@@ -732,7 +741,7 @@ __device__ __forceinline__ void eval_fe(const Env<NT>& E, const int* __restrict_
         Vec<NT> v0, v1;
         Mat<NT> V, W;
         if (op == OP_FE_NOISE1) {
-            const double ldV = load_marginal<NT, ES1>(E, w[W_IN0], fl & F_PUSH_A, w[W_IN1], w[W_D1], d, true, v0, V, (fl & F_PUSH_A) ? w[W_IN2] : -1);
+            const double ldV = load_marginal<NT, ES1>(E, w[W_IN0], fl & F_PUSH_A, w[W_IN1], w[W_D1], d, true, v0, V, (fl & F_PUSH_A) ? w[W_IN2] : -1, flm & F_MAT_SLOT);
             H = 0.5 * (d * (T_LOG2PI + 1.0) + ldV);
             if (fl & F_FOLD_ENT) H *= (double)(1 - w[W_OUT]);
             load_value<NT, ES1>(E, w[W_VAL], fl & F_VAL_SLOT, d, v1);
@@ -758,7 +767,7 @@ __device__ __forceinline__ void eval_fe(const Env<NT>& E, const int* __restrict_
         if (fl & F_PUSH_A) {
             Vec<NT> m;
             Mat<NT> V;
-            ldV = load_marginal<NT, ES1>(E, w[W_IN0], true, w[W_C0], w[W_D1], d, true, m, V, w[W_IN1]);
+            ldV = load_marginal<NT, ES1>(E, w[W_IN0], true, w[W_C0], w[W_D1], d, true, m, V, w[W_IN1], flm & F_MAT_SLOT);
         } else
             ldV = E.marg(w[W_IN0])[(long long)(d + d * (d + 1) / 2) * es];
         if (threadIdx.x == 0) *E.term(w[W_TERM]) = (double)w[W_N] * 0.5 * (d * (T_LOG2PI + 1.0) + ldV);
@@ -841,7 +850,7 @@ __device__ __forceinline__ void eval_fe(const Env<NT>& E, const int* __restrict_
 
 // One launch per level: a wavefront (a workgroup of 64) per item (op, replica).  Storage as TreeParams says: element k of slot `off` of replica r at
 // (off + k)·es + r·rs_<array> — the engines above d = 8 store a replica's slots contiguously (es = 1), rxhip_rule_eval's one-node schedules replica-fastest.
-template <int PHASE, int NT, bool ES1>
+template <int PHASE, int NT, bool ES1, bool MAT = false>
 __global__ void __launch_bounds__(64) k_tile_ops(TreeParams p, int op0, int op1) {
     __shared__ Scratch<NT> scratch;
     const Lane<NT> L = make_lane<NT>();
@@ -850,14 +859,14 @@ __global__ void __launch_bounds__(64) k_tile_ops(TreeParams p, int op0, int op1)
         const long long o = it / p.R;
         const Env<NT> E{L, scratch, p, it - o * p.R};
         const int* w = p.ops + (size_t)(op0 + o) * OP_WORDS;
-        if (PHASE == 0) eval_bp<NT, ES1>(E, w);
-        else if (PHASE == 1) eval_fe<NT, ES1, 1>(E, w);
-        else if (PHASE == 2) eval_fe<NT, ES1, 0>(E, w);
-        else eval_fe<NT, ES1, 2>(E, w);
+        if (PHASE == 0) eval_bp<NT, ES1, MAT>(E, w);
+        else if (PHASE == 1) eval_fe<NT, ES1, 1, MAT>(E, w);
+        else if (PHASE == 2) eval_fe<NT, ES1, 0, MAT>(E, w);
+        else eval_fe<NT, ES1, 2, MAT>(E, w);
     }
 }
 // a wavefront owns a replica and walks the ops of the range in order (every op's inputs were written by this wavefront or before the launch)
-template <int PHASE, int NT, bool ES1>
+template <int PHASE, int NT, bool ES1, bool MAT = false>
 __global__ void __launch_bounds__(64) k_tile_walk(TreeParams p, int op0, int op1) {
     __shared__ Scratch<NT> scratch;
     const Lane<NT> L = make_lane<NT>();
@@ -865,8 +874,8 @@ __global__ void __launch_bounds__(64) k_tile_walk(TreeParams p, int op0, int op1
         const Env<NT> E{L, scratch, p, r};
         for (int o = op0; o < op1; ++o) {
             const int* w = p.ops + (size_t)o * OP_WORDS;
-            if (PHASE == 0) eval_bp<NT, ES1>(E, w);
-            else eval_fe<NT, ES1>(E, w);
+            if (PHASE == 0) eval_bp<NT, ES1, MAT>(E, w);
+            else eval_fe<NT, ES1, 1, MAT>(E, w);
             __syncthreads();   // (one wavefront: a workgroup-scope fence — this op's stores before the next op's loads by other lanes)
         }
     }

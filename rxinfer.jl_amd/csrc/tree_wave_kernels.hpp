@@ -207,6 +207,25 @@ __device__ __forceinline__ void l_cmat(const Ctx& c, int M, const double* cp, in
     each(c, rows, cols, [&](int i, int j) { wlds[M + i * LD + j] = cp[i * cols + j]; });
 #endif
 }
+// the matrix of a `*` node staged where the constant is: l_cmat, or (slot: F_MAT_SLOT / F_MAT_B_SLOT) this replica's own rows×cols matrix from the value slot `off`
+template <int DC>
+__device__ __forceinline__ void l_amat(const Ctx& c, int M, const TreeParams& p, int off, bool slot, int rows, int cols, long long r) {
+    if (!slot) {
+        l_cmat<DC>(c, M, p.cpool + off, rows, cols);
+        return;
+    }
+    const int LD = c.LD;
+    const double* b = p.val + r * p.rs_val;
+    const long long es = p.es;
+#ifndef RXHIP_HOST_EMUL
+    batch<(DC * DC + WL - 1) / WL>(c, rows * cols, [&](int e) { return b[((long long)off + e) * es]; }, [&](int e, double x) {
+        const int i = e / cols;
+        wlds[M + i * LD + e - i * cols] = x;
+    });
+#else
+    each(c, rows, cols, [&](int i, int j) { wlds[M + i * LD + j] = b[((long long)off + i * cols + j) * es]; });
+#endif
+}
 __device__ __forceinline__ void zero_mat(const Ctx& c, int M, int d) {
     const int LD = c.LD;
     each(c, d, d, [&](int i, int j) { wlds[M + i * LD + j] = 0.0; });
@@ -705,7 +724,7 @@ __device__ __forceinline__ void load_value(const Ctx& c, const TreeParams& p, in
 // the item when an image's covariance is wanted: callers form images first).  A singular image: log|V| = −∞.
 template <int DC>
 __device__ __forceinline__ double load_marginal(const Ctx& c, const TreeParams& p, int off, bool push, int aoff, int du, int d, long long r, bool want_cov, int vm, int vt, int MV,
-                                                int TA, int TB, int TC, int ldoff = -1) {
+                                                int TA, int TB, int TC, int ldoff = -1, bool aslot = false) {
     const int LD = c.LD;
     if (!push) {
         l_vec(c, vm, p.marg, off, d, p.es, r * p.rs_marg);
@@ -718,7 +737,7 @@ __device__ __forceinline__ double load_marginal(const Ctx& c, const TreeParams& 
         return ldV;
     }
     l_vec(c, vt, p.marg, off, du, p.es, r * p.rs_marg);
-    l_cmat<DC>(c, TA, p.cpool + aoff, d, du);
+    l_amat<DC>(c, TA, p, aoff, aslot, d, du, r);
     if (want_cov) l_sym<DC>(c, TB, p.marg, off + du, du, p.es, r * p.rs_marg);
     w_sync();
     matvec(c, vm, TA, LD, 1, vt, d, du);
@@ -735,16 +754,17 @@ __device__ __forceinline__ double load_marginal(const Ctx& c, const TreeParams& 
 }
 
 // the sweep (ops up to OP_MARGINAL): the rules of tree_kernels.hpp's eval_bp, op for op
-template <int DC>
+template <int DC, bool MAT = MAT_DEFAULT>
 __device__ __forceinline__ void eval_bp(const Ctx& c, const TreeParams& p, const int* __restrict__ w, long long r) {
     const int op = w[W_OP], d = w[W_D0], fl = w[W_FLAGS], LD = c.LD;
+    const int flm = MAT ? fl : 0;   // (MAT = false — a program without a data matrix: the loaders' slot branch is compiled out, the instance is the constant-only one)
     const int M0 = c.M(0), M1 = c.M(1), M2 = c.M(2), M3 = c.M(3);
     const int v0 = c.v(0), v1 = c.v(1), v2 = c.v(2);
     bool ok = true;
     switch (op) {
     case OP_DERIVE_MUL: {
         const int d1 = w[W_D1];
-        l_cmat<DC>(c, M0, p.cpool + w[W_C0], d, d1);
+        l_amat<DC>(c, M0, p, w[W_C0], flm & F_MAT_SLOT, d, d1, r);
         load_value(c, p, w[W_VAL], fl & F_VAL_SLOT, d1, r, v0);
         matvec(c, v1, M0, LD, 1, v0, d, d1);
         s_vec(c, p.val, w[W_OUT], d, p.es, r * p.rs_val, v1);
@@ -809,7 +829,7 @@ __device__ __forceinline__ void eval_bp(const Ctx& c, const TreeParams& p, const
     case OP_MUL_OUT: {
         const int d1 = w[W_D1];
         ok = load_msg<DC>(c, p, w[W_IN0], fl & F_IN0_WP, false, d1, r, v0, M0);
-        l_cmat<DC>(c, M1, p.cpool + w[W_C0], d, d1);
+        l_amat<DC>(c, M1, p, w[W_C0], flm & F_MAT_SLOT, d, d1, r);
         w_sync();
         matvec(c, v1, M1, LD, 1, v0, d, d1);
         matmul<DC>(c, M2, M1, false, M0, false, d, d1, d1);   // A V
@@ -819,7 +839,7 @@ __device__ __forceinline__ void eval_bp(const Ctx& c, const TreeParams& p, const
     case OP_MUL_IN: {
         const int d1 = w[W_D1];
         ok = load_msg<DC>(c, p, w[W_IN0], fl & F_IN0_WP, true, d, r, v0, M0);
-        l_cmat<DC>(c, M1, p.cpool + w[W_C0], d, d1);
+        l_amat<DC>(c, M1, p, w[W_C0], flm & F_MAT_SLOT, d, d1, r);
         w_sync();
         matvec(c, v1, M1, 1, LD, v0, d1, d);              // Aᵀ ξ
         matmul<DC>(c, M2, M1, true, M0, false, d1, d, d);     // Aᵀ Λ
@@ -915,9 +935,10 @@ __device__ __forceinline__ void eval_bp(const Ctx& c, const TreeParams& p, const
 }
 
 // the second phase: Bethe terms, residual moments, q(W) updates — tree_kernels.hpp's eval_fe, op for op
-template <int DC>
+template <int DC, bool MAT = MAT_DEFAULT>
 __device__ __forceinline__ void eval_fe(const Ctx& c, const TreeParams& p, const int* __restrict__ w, long long r) {
     const int op = w[W_OP], d = w[W_D0], fl = w[W_FLAGS], LD = c.LD;
+    const int flm = MAT ? fl : 0;   // (MAT = false — a program without a data matrix: the loaders' slot branch is compiled out, the instance is the constant-only one)
     const int M0 = c.M(0), M1 = c.M(1), M2 = c.M(2), M3 = c.M(3);
     const int v0 = c.v(0), v1 = c.v(1), v2 = c.v(2), v3 = c.v(3), v4 = c.v(4);
     bool ok = true;
@@ -972,7 +993,7 @@ __device__ __forceinline__ void eval_fe(const Ctx& c, const TreeParams& p, const
         if (c.lane == 0) p.term[(long long)w[W_TERM] * p.es + r * p.rs_term] = term;
     } break;
     case OP_MARG_PUSH: {   // the stored marginal of an `A * x` output, formed when a caller asks for it
-        const double ldV = load_marginal<DC>(c, p, w[W_IN0], true, w[W_C0], w[W_D1], d, r, true, v0, v1, M0, M1, M2, M3, w[W_IN1]);
+        const double ldV = load_marginal<DC>(c, p, w[W_IN0], true, w[W_C0], w[W_D1], d, r, true, v0, v1, M0, M1, M2, M3, w[W_IN1], flm & F_MAT_SLOT);
         s_vec(c, p.marg, w[W_OUT], d, p.es, r * p.rs_marg, v0);
         s_sym<DC>(c, p.marg, w[W_OUT] + d, d, p.es, r * p.rs_marg, M0);
         if (c.lane == 0) p.marg[(long long)(w[W_OUT] + d + d * (d + 1) / 2) * p.es + r * p.rs_marg] = ldV;
@@ -981,8 +1002,8 @@ __device__ __forceinline__ void eval_fe(const Ctx& c, const TreeParams& p, const
         // tree_kernels.hpp OP_FE_NOISE2M, op for op: the joint of a Gaussian node's two interfaces from ONE inbound message (side a) and the two marginals —
         // P = L_a + W, log|J| = log|P| − log|V_b|, Cov(a − b) = P⁻¹ + (P⁻¹W − I) V_b (P⁻¹W − I)ᵀ.  V_b → M2 first (an image needs every tile), then P⁻¹ → M0,
         // D = P⁻¹W − I → M3, D V_b → M1, E → M0.
-        const double ldVb = load_marginal<DC>(c, p, w[W_VAL2], fl & F_PUSH_B, w[W_IN2], w[W_N], d, r, true, v2, v4, M2, M0, M1, M3, (fl & F_PUSH_B) ? w[W_D1] : -1);   // m_b → v2
-        (void)load_marginal<DC>(c, p, w[W_VAL], fl & F_PUSH_A, w[W_IN1], w[W_LIST], d, r, false, v1, v4, M0, M0, M1, M3);             // m_a → v1
+        const double ldVb = load_marginal<DC>(c, p, w[W_VAL2], fl & F_PUSH_B, w[W_IN2], w[W_N], d, r, true, v2, v4, M2, M0, M1, M3, (fl & F_PUSH_B) ? w[W_D1] : -1, flm & F_MAT_B_SLOT);   // m_b → v2
+        (void)load_marginal<DC>(c, p, w[W_VAL], fl & F_PUSH_A, w[W_IN1], w[W_LIST], d, r, false, v1, v4, M0, M0, M1, M3, -1, flm & F_MAT_SLOT);             // m_a → v1
         if (w[W_IN0] >= 0) ok = load_msg<DC>(c, p, w[W_IN0], fl & F_IN0_WP, true, d, r, v0, M0);
         else zero_mat(c, M0, d);
         const double el = load_noise<DC>(c, p, w, d, r, false, M1);
@@ -1027,7 +1048,7 @@ __device__ __forceinline__ void eval_fe(const Ctx& c, const TreeParams& p, const
     case OP_FE_NOISE0: {
         double H = 0.0;
         if (op == OP_FE_NOISE1) {   // (the marginal first: an image of another marginal needs every tile)
-            const double ldV = load_marginal<DC>(c, p, w[W_IN0], fl & F_PUSH_A, w[W_IN1], w[W_D1], d, r, true, v0, v4, M0, M1, M2, M3, (fl & F_PUSH_A) ? w[W_IN2] : -1);
+            const double ldV = load_marginal<DC>(c, p, w[W_IN0], fl & F_PUSH_A, w[W_IN1], w[W_D1], d, r, true, v0, v4, M0, M1, M2, M3, (fl & F_PUSH_A) ? w[W_IN2] : -1, flm & F_MAT_SLOT);
             H = 0.5 * (d * (T_LOG2PI + 1.0) + ldV);
             if (fl & F_FOLD_ENT) H *= (double)(1 - w[W_OUT]);
             load_value(c, p, w[W_VAL], fl & F_VAL_SLOT, d, r, v1);
@@ -1052,7 +1073,7 @@ __device__ __forceinline__ void eval_fe(const Ctx& c, const TreeParams& p, const
     } break;
     case OP_FE_ENT: {
         double ldV;
-        if (fl & F_PUSH_A) ldV = load_marginal<DC>(c, p, w[W_IN0], true, w[W_C0], w[W_D1], d, r, true, v0, v4, M0, M1, M2, M3, w[W_IN1]);
+        if (fl & F_PUSH_A) ldV = load_marginal<DC>(c, p, w[W_IN0], true, w[W_C0], w[W_D1], d, r, true, v0, v4, M0, M1, M2, M3, w[W_IN1], flm & F_MAT_SLOT);
         else ldV = p.marg[(w[W_IN0] + d + d * (d + 1) / 2) * p.es + r * p.rs_marg];
         if (c.lane == 0) p.term[(long long)w[W_TERM] * p.es + r * p.rs_term] = (double)w[W_N] * 0.5 * (d * (T_LOG2PI + 1.0) + ldV);
     } break;
@@ -1130,10 +1151,10 @@ __device__ __forceinline__ void eval_fe(const Ctx& c, const TreeParams& p, const
     if (!ok && c.lane == 0) atomicOr(p.status, 1);
 }
 
-template <int PHASE, int DC>
+template <int PHASE, int DC, bool MAT = false>
 __device__ __forceinline__ void eval_op(const Ctx& c, const TreeParams& p, const int* __restrict__ w, long long r) {
-    if (PHASE == 0) eval_bp<DC>(c, p, w, r);
-    else eval_fe<DC>(c, p, w, r);
+    if (PHASE == 0) eval_bp<DC, MAT>(c, p, w, r);
+    else eval_fe<DC, MAT>(c, p, w, r);
 }
 
 #ifndef RXHIP_HOST_EMUL
@@ -1141,23 +1162,23 @@ __device__ __forceinline__ void eval_op(const Ctx& c, const TreeParams& p, const
 // (TreeParams): the engines of this kernel store a replica's slots CONTIGUOUSLY (es = 1, rs = the array's doubles per replica), so that the 64 lanes of the
 // wavefront that loads a message read 64 consecutive doubles — with the replica-fastest layout of the register kernels (es = RS, rs = 1; still what
 // rxhip_rule_eval's one-node schedules use) every lane touched a 128-byte line of its own and 15/16 of the HBM traffic was other replicas' data
-template <int PHASE, int DC>
+template <int PHASE, int DC, bool MAT = false>
 __global__ void __launch_bounds__(WL, DC <= 16 ? 2 : 1) k_wave_ops(TreeParams p, int op0, int op1, int dmax) {
     const Ctx c = make_ctx(dmax);
     const long long total = (long long)(op1 - op0) * p.R;
     for (long long it = blockIdx.x; it < total; it += gridDim.x) {
         const long long o = it / p.R, r = it - o * p.R;
-        eval_op<PHASE, DC>(c, p, p.ops + (size_t)(op0 + o) * OP_WORDS, r);
+        eval_op<PHASE, DC, MAT>(c, p, p.ops + (size_t)(op0 + o) * OP_WORDS, r);
         __syncthreads();   // (one wavefront: a fence — the next item reuses the workspace)
     }
 }
 // a wavefront owns a replica and walks the ops of the range in order (every op's inputs were written by this wavefront or before the launch)
-template <int PHASE, int DC>
+template <int PHASE, int DC, bool MAT = false>
 __global__ void __launch_bounds__(WL, DC <= 16 ? 2 : 1) k_wave_walk(TreeParams p, int op0, int op1, int dmax) {
     const Ctx c = make_ctx(dmax);
     for (long long r = blockIdx.x; r < p.R; r += gridDim.x)
         for (int o = op0; o < op1; ++o) {
-            eval_op<PHASE, DC>(c, p, p.ops + (size_t)o * OP_WORDS, r);
+            eval_op<PHASE, DC, MAT>(c, p, p.ops + (size_t)o * OP_WORDS, r);
             __syncthreads();   // (a workgroup-scope fence: the op's stores to global memory before the next op's loads by other lanes)
         }
 }

@@ -239,6 +239,13 @@ function fix_shapes!(t::GraphTables)
                 r > 0 && (want[ids[1]] = r; want[ids[2]] = r)
             elseif code == Int32(2)                             # out = A * in
                 t.var_rows[ids[2]] > 0 && (want[ids[1]] = t.var_rows[ids[2]]; want[ids[3]] = t.var_cols[ids[2]])
+                # a DATA matrix (`x[i] * b` with x in `data = (…)`; `dot(x[i], b)` is the 1 × d case): its shape from the output's and the input's dimensions —
+                # the node-array executor loads it per replica (include/rxhip.h "typeof(*) with a constant or a DATA matrix"), no fallback.
+                # (Only once BOTH neighbours have rows: a model in which the output's dimension could be had from A alone leaves A at the 1 × 1
+                #  default below, and the engine answers RXHIP_ERR_BADARG "data matrix is 1 x 1, not …" — not UnsupportedGraph — for it.)
+                if t.var_rows[ids[2]] == 0 && t.var_kind[ids[2]] == RXHIP_VARKIND_DATA && t.var_rows[ids[1]] > 0 && t.var_rows[ids[3]] > 0
+                    t.var_rows[ids[2]] = t.var_rows[ids[1]]; t.var_cols[ids[2]] = t.var_rows[ids[3]]; changed = true
+                end
             elseif code == Int32(13)
                 r = maximum(t.var_rows[ids]); r > 0 && (for i in ids; want[i] = r; end)
             elseif code == Int32(10)                            # NormalMixture: out as m[1]
@@ -372,7 +379,7 @@ function ReactiveMP.new_observation!(v::HIPDataVariable, value)
     slot = g.data_slot[v.id]
     if g.family === :tree   # ragged observations: every data variable at its own offset of the staging vector
         ismissing(value) && error("the node-array executor takes no missing observations; use options = (backend = :reactivemp,)")
-        vals = value isa Real ? (Float64(value),) : value
+        vals = value isa Real ? (Float64(value),) : value isa AbstractMatrix ? transpose(value) : value   # (a data matrix of `*`: row-major, rxhip_tree_set_data)
         o = g.tree.data_offsets[slot]
         @inbounds for (k, x) in enumerate(vals)
             g.staging[o + k] = x

@@ -712,7 +712,7 @@ function tree_layout(t)
     offs, o = Int[], 0
     for id in data
         push!(offs, o)
-        o += Int(t.var_rows[id + 1])
+        o += Int(t.var_rows[id + 1]) * Int(t.var_cols[id + 1])   # (a data MATRIX — the `A` of a `*` node — is staged row-major: rows·cols values)
     end
     return (family = :tree, data_ids = data, data_offsets = offs, data_total = o, state_ids = rnd, state_dims = Int[Int(t.var_rows[id + 1]) for id in rnd],
             precision_ids = sort!(collect(prec)), scalar_ids = scal, switch_ids = sort!(collect(switch)), probability_ids = sort!(collect(probs)),

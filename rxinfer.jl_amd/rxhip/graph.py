@@ -56,8 +56,9 @@ class GraphBuilder:
     def randomvar(self, dim, name=""):
         return self._var(_lib.VARKIND_RANDOM, dim, name=name)
 
-    def datavar(self, dim, name=""):
-        return self._var(_lib.VARKIND_DATA, dim, name=name)
+    def datavar(self, dim, name="", cols=1):
+        """a data variable of `dim` rows; cols > 1 (or 1 × 1 on the `A` interface of `*`): a data MATRIX dim × cols, set per replica row-major (TreeEngine.set_data)"""
+        return self._var(_lib.VARKIND_DATA, dim, cols, name=name)
 
     def constvar(self, value, name=""):
         v = np.atleast_1d(np.asarray(value, dtype=np.float64))
@@ -120,7 +121,7 @@ class GraphBuilder:
                 val = np.asarray(v["value"], dtype=np.float64)
                 i = gb.constvar(val.reshape(v["rows"], v["cols"]) if v["cols"] > 1 else val, name=v.get("name", ""))
             else:
-                i = (gb.randomvar if v["kind"] == "random" else gb.datavar)(v["rows"], name=v.get("name", ""))
+                i = gb.randomvar(v["rows"], name=v.get("name", "")) if v["kind"] == "random" else gb.datavar(v["rows"], name=v.get("name", ""), cols=int(v.get("cols", 1)))
             if "init" in v:
                 gb.initialize(i, INIT_FAMILIES[v["init"]["family"]], v["init"]["params"])
             if "msg_init" in v:
@@ -343,6 +344,52 @@ def two_branch_chain_graph(T, A, B1, B2, P, Q1, Q2, m0, V0):
             ys.append(y)
         xs.append(x)
     return gb, xs, ys
+
+
+def linreg_graph(N, x=None, d=1, dy=1, prior_a=(0.0, 1.0), prior_b=(0.0, 1.0), noise_var=1.0, init=None, x_as_data=True):
+    """RxInfer's linear regression (test/models/regression/linreg_tests.jl): a ~ N(prior_a), b ~ N(prior_b), y[i] ~ Normal(mean = x[i] * b + a, var = noise_var),
+    i = 1 … N — a loopy graph that `init` cuts: {"a" | "b": (mean, var | cov)} message initialisations `μ(a)` / `μ(b)`.  d = dy = 1: scalar nodes; otherwise
+    y[i] ~ MvNormal(X[i] * b + a, Σ) with b of dimension d, a and y of dimension dy, X[i] a dy × d matrix, the priors as (mean [·], cov [·][·]), noise_var Σ [dy][dy].
+    x_as_data=True: every x[i] is a DATA matrix of the `*` node, as the reference passes it (`data = (x = …, y = …)`) — each replica sets its own regressors with
+    TreeEngine.set_data (row-major dy·d values per x[i]); x_as_data=False: x ([N] or [N][dy][d]) is baked into the graph as constants, the same for every replica.
+    Returns (builder, y data variables, x data variables — [] for constants —, dict(a=, b=, t=[…] the products x[i] * b, s=[…] the sums))."""
+    if not x_as_data:
+        x = np.asarray(x, float)
+        if x.shape[0] != N:
+            raise ValueError("x must hold N regressors")
+        if x.ndim == 3:
+            dy, d = x.shape[1], x.shape[2]
+    vec = d > 1 or dy > 1
+    gb = GraphBuilder()
+    a, b = gb.randomvar(dy, name="a"), gb.randomvar(d, name="b")
+    if vec:
+        gb.mvnormal_mean_cov(a, gb.constvar(np.asarray(prior_a[0], float)), gb.constvar(np.asarray(prior_a[1], float)))
+        gb.mvnormal_mean_cov(b, gb.constvar(np.asarray(prior_b[0], float)), gb.constvar(np.asarray(prior_b[1], float)))
+    else:
+        gb.node(_lib.NODE_NORMAL_MEAN_VARIANCE, a, gb.constvar(prior_a[0]), gb.constvar(prior_a[1]))
+        gb.node(_lib.NODE_NORMAL_MEAN_VARIANCE, b, gb.constvar(prior_b[0]), gb.constvar(prior_b[1]))
+    ts, ss, ys, xv = [], [], [], []
+    for i in range(N):
+        t, s, y = gb.randomvar(dy), gb.randomvar(dy), gb.datavar(dy, name="y")
+        if x_as_data:
+            xi = gb.datavar(dy, name="x", cols=d)
+            xv.append(xi)
+        else:
+            xi = gb.constvar(x[i] if vec else float(x[i]))
+        gb.node(_lib.NODE_MULTIPLY, t, xi, b)
+        gb.node(_lib.NODE_ADD, s, t, a)
+        if vec:
+            gb.mvnormal_mean_cov(y, s, gb.constvar(np.asarray(noise_var, float)))
+        else:
+            gb.node(_lib.NODE_NORMAL_MEAN_VARIANCE, y, s, gb.constvar(noise_var))
+        ts.append(t); ss.append(s); ys.append(y)
+    for k, mv in (init or {}).items():
+        var = a if k == "a" else b
+        if vec:
+            gb.initialize_message(var, _lib.INIT_MVNORMAL, np.concatenate([np.ravel(mv[0]), np.ravel(mv[1])]))
+        else:
+            gb.initialize_message(var, _lib.INIT_NORMAL, mv)
+    return gb, ys, xv, dict(a=a, b=b, t=ts, s=ss)
 
 
 def lgssm_noise_graph(T, A, B, P, m0, V0, nu0, S0, init=None, prior_through_transition=False, gamma=None):

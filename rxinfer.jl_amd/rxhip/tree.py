@@ -80,10 +80,11 @@ class TreeEngine:
         self.close()
 
     def set_data(self, variables, values):
-        """variables: data variable ids; values: [replica][Σ rows] (the rows of the variables side by side, in list order)"""
+        """variables: data variable ids; values: [replica][Σ rows] (the rows of the variables side by side, in list order; a data matrix — the `A` of a `*`
+        node, GraphBuilder.datavar(rows, cols=…) — takes rows·cols values, row-major)"""
         v = np.ascontiguousarray(variables, dtype=np.int64)
         x = _c(values).reshape(self.n_replicas, -1)
-        rows = int(sum(self.gb.rows[i] for i in v))
+        rows = int(sum(self.gb.rows[i] * self.gb.cols[i] for i in v))
         if x.shape[1] != rows:
             raise ValueError(f"values must be [replicas][{rows}]")
         self._chk(_lib.lib().rxhip_tree_set_data(self._h, v.ctypes.data_as(c_int64_p), len(v), x.ctypes.data_as(c_double_p)))
