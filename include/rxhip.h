@@ -522,6 +522,54 @@ rxhip_status rxhip_tree_continue(rxhip_engine* e, int32_t on);
 /* rxhip_run, rxhip_get_free_energy (sum over the replicas, per iteration), rxhip_get_free_energy_per_chain (per replica, last iteration),
  * rxhip_counters, rxhip_sync, rxhip_get_stream, rxhip_last_error, rxhip_destroy apply as to every engine. */
 
+/* Streaming — replaces the per-observation loop of src/inference/streaming.jl:341-407 for a one-step graph of the executor (the HGF step graph of
+ * test/models/statespace/hgf_tests.jl:9-31, a Kalman step whose prior mean and variance are data, online regression): a series of T observations goes up
+ * once; feedback, VMP iterations, history and free energy run on the device with no host synchronisation between observations.  The chain engines' twin
+ * is rxhip_run_filter / rxhip_filter_step.
+ * The feedback table replaces the `@autoupdates` specification of src/inference/autoupdates.jl (`m, v = mean_var(q(x))`, hgf_tests.jl:46-49): before the
+ * iterations of every observation the value of data variable `target` is taken from the current marginal of Gaussian random variable `source`.
+ *   RXHIP_AU_MEAN        its mean; dim(target) = dim(source), any dimension the executor runs
+ *   RXHIP_AU_VAR         its variance            } scalars on both sides: what the Gaussian nodes with a data-valued variance / precision consume
+ *   RXHIP_AU_PRECISION   1 / its variance        }
+ * RXHIP_ERR_BADARG with the offending variable in the text: a target that is not a data variable or is the data matrix of a `*` node, a source that is not a
+ * Gaussian random variable, a dimension mismatch, a target listed twice, an unknown kind.  RXHIP_ERR_UNSUPPORTED, and said so in the text: a covariance /
+ * precision MATRIX as feedback (VAR / PRECISION of a vector source) and the parameters of a Gamma / Wishart / discrete marginal (`shape(q(τ))`,
+ * `params(q(θ))`: a source that is a precision or discrete variable) — the executor has no data-valued matrix covariance or Gamma prior to receive them. */
+typedef enum { RXHIP_AU_MEAN = 0, RXHIP_AU_VAR = 1, RXHIP_AU_PRECISION = 2 } rxhip_autoupdate_kind;
+typedef struct { int64_t target; int64_t source; int32_t kind; int32_t reserved; } rxhip_autoupdate;
+/* host only, no device: would the engine of `g` take this table?  Failures as above (or those of rxhip_tree_plan for the graph); text: rxhip_lowering_error() */
+rxhip_status rxhip_tree_check_autoupdates(const rxhip_graph_desc* g, const rxhip_autoupdate* au, int64_t n);
+/* the table of every later rxhip_tree_stream; n = 0 clears it (a stream then runs the host loop WITHOUT feedback) */
+rxhip_status rxhip_tree_set_autoupdates(rxhip_engine* e, const rxhip_autoupdate* au, int64_t n);
+/* series: host [T][replica][rows of vars[0] | rows of vars[1] | …] — rxhip_tree_set_data's layout, once per observation.  Per observation t, in the order of
+ * streaming.jl:341-407 (the autoupdates are fetched ONCE per observation and held through its iterations):
+ *   1. every target ← its source's current marginal;   2. the data variables `vars` ← series[t];
+ *   3. `iterations` VMP iterations exactly as rxhip_run runs them on a continued engine: q(W), γ of GCV nodes, mean-field marginals and loop messages are
+ *      carried from observation to observation (rxhip_tree_continue(1) between the runs of the host loop);
+ *   4. the marginals (mean, covariance) of `history_vars` (Gaussian random variables) and the iterations' free energies are appended to device-resident history.
+ * Before the first observation of a fresh engine — or of any call on an engine with rxhip_tree_continue off — the state is the `@initialization` state and the
+ * feedback reads the sources' `@initialization` marginals (rxhip_graph_desc.var_init*; a source without one: RXHIP_ERR_BADARG naming it, as the reference's
+ * "The initial value for `θ` has not been specified", test/models/iid/beta_bernoulli_tests.jl:35-41).  On an engine that has run with rxhip_tree_continue on, it reads
+ * the current marginals and the state goes on: two calls of T1 and T2 observations equal one of T1 + T2, bit for bit.  A source whose marginal is an image
+ * marginal (the output of `A * x`) has it formed before the feedback, as rxhip_tree_get_marginals forms it.
+ * A data variable of the graph must be in `vars`, a target, or set before (rxhip_tree_set_data: it keeps its value; else RXHIP_ERR_STATE); a target in `vars`, a
+ * variable listed twice or a history variable that is not Gaussian is RXHIP_ERR_BADARG.  NaN in the series is `missing` on an engine created with
+ * allow_missing and RXHIP_ERR_BADARG without, NaN in a data matrix always — the rule of rxhip_tree_set_data.  T = 0 is a no-op.  History memory is
+ * T × Σ (d + d(d+1)/2) × replicas doubles: RXHIP_ERR_BADARG with the byte count when it cannot be allocated.
+ * The call enqueues all T observations on the engine's stream (every schedule and kernel family; the launch-per-level schedule replays the HIP graph rxhip_run
+ * captured) and synchronises once at the end; the not-positive-definite status is that of the whole series.  Afterwards rxhip_tree_get_marginals / _precision /
+ * _discrete, rxhip_get_free_energy and rxhip_get_free_energy_per_chain answer as after the last rxhip_run of the host loop (the last observation);
+ * rxhip_counters counts all observations of the stream calls that continue one another; rxhip_tree_info.last_iteration_ms is the device time of the call ÷
+ * (T · iterations), step kernels included. */
+rxhip_status rxhip_tree_stream(rxhip_engine* e, const int64_t* vars, int64_t n_vars, const double* series, int64_t T, int32_t iterations, int32_t want_free_energy,
+                               const int64_t* history_vars, int64_t n_history);
+/* what the last rxhip_tree_stream recorded after each observation's iterations (replaces `keephistory` / the `history` of the streaming engine,
+ * src/inference/streaming.jl:341-407): mean [T][var][replica][d], cov [T][var][replica][d][d] of its history_vars in list order (either pointer may be NULL) */
+rxhip_status rxhip_tree_get_history(rxhip_engine* e, double* mean, double* cov);
+/* fe [T][iterations] of the last rxhip_tree_stream that asked for it: every iteration's free energy, summed over the replicas in the engine's fixed order
+ * (the `free_energy_history` of streaming.jl, per observation) */
+rxhip_status rxhip_tree_get_stream_free_energy(rxhip_engine* e, double* fe);
+
 /* One rule, evaluated on the device for a batch of inputs — the fine-grained A/B hook of SURVEY §8(b): what
  * `@rule NodeType(:iface, Marginalisation) (m_… , q_…)` returns for the given inbound message(s) and constants
  * (test/inference/inference_tests.jl:2049-2066 redirects a node to custom rule code the same way).  Runs the executor's own op on a one-node

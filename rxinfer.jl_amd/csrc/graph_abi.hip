@@ -148,6 +148,34 @@ rxhip_status rxhip_tree_continue(rxhip_engine* e, int32_t on) {
     rxhip::tree::set_continue(e->tree, on != 0);
     return RXHIP_OK;
 }
+rxhip_status rxhip_tree_check_autoupdates(const rxhip_graph_desc* g, const rxhip_autoupdate* au, int64_t n) {
+    std::string err;
+    rxhip_lower::last_asymmetry() = 0.0;
+    const rxhip_status st = rxhip::tree::check_autoupdates(g, au, n, err);
+    if (st) rxhip_lower::last_error() = err;   // (no handle to hang the text on: rxhip_lowering_error() returns it)
+    return st;
+}
+rxhip_status rxhip_tree_set_autoupdates(rxhip_engine* e, const rxhip_autoupdate* au, int64_t n) {
+    if (!e || !e->tree) return e ? fail(e, RXHIP_ERR_BADARG, "rxhip_tree_set_autoupdates: not an engine of the node-array executor") : RXHIP_ERR_BADARG;
+    e->err.clear();
+    return rxhip::tree::set_autoupdates(e->tree, au, n, e->err);
+}
+rxhip_status rxhip_tree_stream(rxhip_engine* e, const int64_t* vars, int64_t n_vars, const double* series, int64_t T, int32_t iterations, int32_t want_free_energy,
+                               const int64_t* history_vars, int64_t n_history) {
+    if (!e || !e->tree) return e ? fail(e, RXHIP_ERR_BADARG, "rxhip_tree_stream: not an engine of the node-array executor") : RXHIP_ERR_BADARG;
+    e->err.clear();
+    return rxhip::tree::stream(e->tree, vars, n_vars, series, T, iterations, want_free_energy, history_vars, n_history, e->err);
+}
+rxhip_status rxhip_tree_get_history(rxhip_engine* e, double* mean, double* cov) {
+    if (!e || !e->tree) return e ? fail(e, RXHIP_ERR_BADARG, "rxhip_tree_get_history: not an engine of the node-array executor") : RXHIP_ERR_BADARG;
+    e->err.clear();
+    return rxhip::tree::get_history(e->tree, mean, cov, e->err);
+}
+rxhip_status rxhip_tree_get_stream_free_energy(rxhip_engine* e, double* fe) {
+    if (!e || !e->tree) return e ? fail(e, RXHIP_ERR_BADARG, "rxhip_tree_get_stream_free_energy: not an engine of the node-array executor") : RXHIP_ERR_BADARG;
+    e->err.clear();
+    return rxhip::tree::get_stream_free_energy(e->tree, fe, e->err);
+}
 rxhip_status rxhip_rule_eval(const rxhip_rule_call* call, int32_t device) {
     std::string err;
     const rxhip_status st = rxhip::tree::rule_eval(call, device, err);

@@ -138,6 +138,10 @@ struct Program {
     int n_loop = 0;
     long long loop_doubles = 0;
     std::vector<double> loop_init;     // [loop_doubles] D of every loop message, in the form the message is stored in
+    // the `@initialization` marginals of the Gaussian variables as given (Normal / MvNormal): what the feedback of a stream reads before the first observation
+    // (tree_engine.hip stream; src/inference/streaming.jl:341-407 fetches the autoupdates from the initial marginals then)
+    std::vector<int> ginit_off;        // per variable: offset into ginit of mean[d] | cov[d][d], −1 without one
+    std::vector<double> ginit;
 };
 
 struct Compiler {
@@ -1069,6 +1073,20 @@ struct Compiler {
         }
     }
 
+    // every Gaussian variable's `@initialization` marginal, kept as given: the source of a stream's first feedback (Program.ginit)
+    void init_gauss() {
+        P.ginit_off.assign(nv, -1);
+        if (!g->var_init_family || !g->var_init) return;
+        for (int64_t v = 0; v < nv; ++v) {
+            if (P.vclass[v] != VC_GAUSS || g->var_init[v] < 0) continue;
+            const int fam = g->var_init_family[v], d = P.dim[v];
+            if (!(fam == RXHIP_INIT_MVNORMAL || (fam == RXHIP_INIT_NORMAL && d == 1))) continue;
+            const double* q = g->const_pool + g->var_init[v];
+            P.ginit_off[v] = (int)P.ginit.size();
+            P.ginit.insert(P.ginit.end(), q, q + d + (size_t)d * d);
+        }
+    }
+
     void emit_all() {
         // derived values first (their own dependency order)
         {
@@ -1889,6 +1907,7 @@ struct Compiler {
         allocate();
         init_precision();
         init_marginals();
+        init_gauss();
         emit_all();
         finish();
         count();

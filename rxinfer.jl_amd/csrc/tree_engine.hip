@@ -11,6 +11,9 @@
 //   5. slots of the replica-fastest device arrays, the constant pool (matrices, Σ | W | log|W| blocks inverted once on the host, priors).
 // run(): per iteration either one launch per level over all (op, replica) items, or ONE launch in which a workgroup walks all levels for its
 // replicas (deep narrow graphs: a chain is three levels per time step and a launch per level would cost more than the level).
+// stream(): T observations of a one-step graph in one call — per observation the step kernel of tree_stream_kernels.hpp (the `@autoupdates` feedback from the
+// marginals and observation t of the uploaded series into the value slots), the iterations exactly as run() enqueues them on a continued engine, the step kernel
+// again (the history marginals); one synchronisation at the end (src/inference/streaming.jl:341-407).
 #include "tree_engine.hpp"
 
 #include <hip/hip_runtime.h>
@@ -27,6 +30,7 @@
 #include "graph_lowering.hpp"  // last_asymmetry
 #include "launch_tables.hpp"   // hook_env
 #include "tree_kernels.hpp"
+#include "tree_stream_kernels.hpp"
 #include "tree_wave.hpp"
 #include "tree_compiler.hpp"   // Program, Compiler: the graph compiler (host only)
 
@@ -60,6 +64,13 @@ struct Engine {
     uint64_t runs = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double last_iteration_ms = 0.0;
+    // streaming (rxhip_tree_set_autoupdates / rxhip_tree_stream): the feedback table, and what the last stream left on the device
+    std::vector<rxhip_autoupdate> autoupdates;
+    double *d_hist = nullptr, *d_sfe = nullptr;   // history [T][rows][R] (or [T][R][rows]: elem_fast), free energy [T][iterations]
+    std::vector<int64_t> hist_vars;
+    long long hist_T = 0, hist_rows = 0, sfe_T = 0;
+    int sfe_iterations = 0;
+    uint64_t stream_iterations = 0;   // Σ observations × iterations of the stream calls that continue one another (0: the last call was rxhip_run)
 };
 
 namespace {
@@ -282,6 +293,76 @@ void launch(const Engine* e, const TreeParams& p, int l0, int l1) {
     default: launch_levels<8>(e, p, l0, l1); break;   // (registers for 4x4 blocks: the 8x8 instance spills — it exists so that such graphs run at all)
     }
 }
+
+// The pieces of a run that rxhip_run and rxhip_tree_stream share: the same launches in the same order, so that a stream's iterations ARE a continued run's.
+// A run starts from the @initialization marginals (iterations re-push the data: src/inference/batch.jl:391-430)
+// — unless the caller drives the loop one iteration per call (rxhip_tree_continue): then only the first run does
+void start_state(const Engine* e, const TreeParams& p) {
+    const Program& P = e->prog;
+    if (e->cont && e->ran) return;
+    if (P.prec_doubles > 0) {
+        const long long total = P.prec_doubles * e->RS;
+        hipLaunchKernelGGL(k_tree_broadcast, dim3((unsigned)std::min<long long>((total + 255) / 256, 4096)), dim3(256), 0, e->stream, e->d_prec, (const double*)e->d_prec_init,
+                           (long long)P.prec_doubles, e->RS, e->elem_fast ? 1 : 0);
+    }
+    if (P.has_mf) {   // the marginals the mean-field rules read in the first iteration
+        const long long total = P.marg_doubles * e->RS;
+        hipLaunchKernelGGL(k_tree_broadcast, dim3((unsigned)std::min<long long>((total + 255) / 256, 4096)), dim3(256), 0, e->stream, e->d_marg, (const double*)e->d_marg_init,
+                           (long long)P.marg_doubles, e->RS, e->elem_fast ? 1 : 0);
+    }
+    if (P.n_loop) {   // the message initialisations the first iteration's readers of the loop messages take
+        const unsigned loop_blocks = (unsigned)std::min<long long>((P.loop_doubles * e->R + 255) / 256, 4096);
+        hipLaunchKernelGGL(k_tree_carry, dim3(loop_blocks), dim3(256), 0, e->stream, e->d_msg, (const double*)e->d_loop_init, P.loop_doubles, e->R, p.es, p.rs_msg);
+    }
+}
+// without the free energy on a graph without precision variables the sweep ends with the marginals
+int last_level(const Engine* e, int want_fe) {
+    const Program& P = e->prog;
+    return (!want_fe && P.prec_doubles == 0) ? P.fe_level : (P.lazy_level >= 0 ? P.lazy_level : P.n_levels);
+}
+// the launch-per-level schedule's iteration as an instantiated HIP graph (nullptr: direct launches), captured once per (free energy wanted, last level)
+hipGraphExec_t sweep_graph(Engine* e, const TreeParams& p, int want_fe, int l_end) {
+    if (!e->use_graph) return nullptr;
+    const int wf = want_fe ? 1 : 0;
+    if (e->gexec[wf] && e->g_lend[wf] != l_end) { (void)hipGraphExecDestroy(e->gexec[wf]); e->gexec[wf] = nullptr; }
+    if (!e->gexec[wf]) {
+        hipGraph_t gr = nullptr;
+        if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+            launch(e, p, 0, l_end);
+            if (hipStreamEndCapture(e->stream, &gr) == hipSuccess && gr && hipGraphInstantiate(&e->gexec[wf], gr, nullptr, nullptr, 0) == hipSuccess) e->g_lend[wf] = l_end;
+            else e->gexec[wf] = nullptr;
+            if (gr) (void)hipGraphDestroy(gr);
+        }
+        (void)hipGetLastError();
+        if (!e->gexec[wf]) e->use_graph = false;   // (the direct launches are the same kernels: nothing is lost but the launch overhead)
+    }
+    return e->gexec[wf];
+}
+// one VMP iteration on the engine's stream; its free energy (summed over the replicas) into *fe_out
+hipError_t enqueue_iteration(const Engine* e, const TreeParams& p, hipGraphExec_t gx, int l_end, int want_fe, double* fe_out) {
+    const Program& P = e->prog;
+    if (gx) {
+        const hipError_t he = hipGraphLaunch(gx, e->stream);
+        if (he != hipSuccess) return he;
+    } else
+        launch(e, p, 0, l_end);
+    if (P.n_loop) {   // the loop messages just computed become what the next iteration (or a continued run) reads
+        const unsigned loop_blocks = (unsigned)std::min<long long>((P.loop_doubles * e->R + 255) / 256, 4096);
+        hipLaunchKernelGGL(k_tree_carry, dim3(loop_blocks), dim3(256), 0, e->stream, e->d_msg, (const double*)nullptr, P.loop_doubles, e->R, p.es, p.rs_msg);
+    }
+    if (want_fe) {   // Σ over replicas of term[root]: chunks of FE_CHUNK into partials, the partials (≤ FE_CHUNK of them: up to 16.7 M replicas) into the iteration's slot
+        const unsigned nb = (unsigned)((e->R + FE_CHUNK - 1) / FE_CHUNK);
+        const double* root = e->d_term + (size_t)P.fe_root * (e->elem_fast ? 1 : e->RS);
+        const long long stride = e->elem_fast ? P.term_slots : 1;
+        if (nb == 1)
+            hipLaunchKernelGGL(k_tree_fe_total, dim3(1), dim3(256), 0, e->stream, root, stride, e->R, e->d_fe_rep, fe_out);
+        else {
+            hipLaunchKernelGGL(k_tree_fe_total, dim3(nb), dim3(256), 0, e->stream, root, stride, e->R, e->d_fe_rep, e->d_fe_part);
+            hipLaunchKernelGGL(k_tree_fe_total, dim3(1), dim3(256), 0, e->stream, (const double*)e->d_fe_part, 1ll, (long long)nb, (double*)nullptr, fe_out);
+        }
+    }
+    return hipSuccess;
+}
 }  // namespace
 
 rxhip_status create(const rxhip_graph_desc* g, int device, void* stream, Engine** out, std::string& err) {
@@ -438,7 +519,7 @@ void destroy(Engine* e) {
     DevScope ds(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     for (void* q : {(void*)e->d_sops, (void*)e->d_strands, (void*)e->d_ops, (void*)e->d_aux, (void*)e->d_lvl, (void*)e->d_status, (void*)e->d_cpool, (void*)e->d_msg, (void*)e->d_marg, (void*)e->d_val, (void*)e->d_prec,
-                    (void*)e->d_term, (void*)e->d_stat, (void*)e->d_prec_init, (void*)e->d_marg_init, (void*)e->d_loop_init, (void*)e->d_fe_rep, (void*)e->d_fe_hist, (void*)e->d_fe_part})
+                    (void*)e->d_term, (void*)e->d_stat, (void*)e->d_prec_init, (void*)e->d_marg_init, (void*)e->d_loop_init, (void*)e->d_fe_rep, (void*)e->d_fe_hist, (void*)e->d_fe_part, (void*)e->d_hist, (void*)e->d_sfe})
         if (q) (void)hipFree(q);
     for (hipGraphExec_t x : e->gexec) if (x) (void)hipGraphExecDestroy(x);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
@@ -509,7 +590,6 @@ rxhip_status run(Engine* e, int iterations, int want_fe, std::string& err) {
     if (!e || iterations < 1) { err = "run: iterations must be positive"; return RXHIP_ERR_BADARG; }
     if (!e->have_data) { err = "run before every data variable has been set"; return RXHIP_ERR_STATE; }
     DevScope ds(e->device);
-    const Program& P = e->prog;
     if (iterations > e->fe_cap) {
         TCHK(hipStreamSynchronize(e->stream));
         if (e->d_fe_hist) TCHK(hipFree(e->d_fe_hist));
@@ -518,61 +598,13 @@ rxhip_status run(Engine* e, int iterations, int want_fe, std::string& err) {
         e->fe_cap = iterations;
     }
     TCHK(hipMemsetAsync(e->d_status, 0, sizeof(int), e->stream));
-    // a run starts from the @initialization marginals (iterations re-push the data: src/inference/batch.jl:391-430)
-    // — unless the caller drives the loop one iteration per call (rxhip_tree_continue): then only the first run does
-    if (P.prec_doubles > 0 && !(e->cont && e->ran)) {
-        const long long total = P.prec_doubles * e->RS;
-        hipLaunchKernelGGL(k_tree_broadcast, dim3((unsigned)std::min<long long>((total + 255) / 256, 4096)), dim3(256), 0, e->stream, e->d_prec, (const double*)e->d_prec_init,
-                           (long long)P.prec_doubles, e->RS, e->elem_fast ? 1 : 0);
-    }
-    if (P.has_mf && !(e->cont && e->ran)) {   // the marginals the mean-field rules read in the first iteration
-        const long long total = P.marg_doubles * e->RS;
-        hipLaunchKernelGGL(k_tree_broadcast, dim3((unsigned)std::min<long long>((total + 255) / 256, 4096)), dim3(256), 0, e->stream, e->d_marg, (const double*)e->d_marg_init,
-                           (long long)P.marg_doubles, e->RS, e->elem_fast ? 1 : 0);
-    }
     const TreeParams p = params_of(e, want_fe);
-    const long long loop_items = P.loop_doubles * e->R;
-    const unsigned loop_blocks = (unsigned)std::min<long long>((loop_items + 255) / 256, 4096);
-    if (P.n_loop && !(e->cont && e->ran))   // the message initialisations the first iteration's readers of the loop messages take
-        hipLaunchKernelGGL(k_tree_carry, dim3(loop_blocks), dim3(256), 0, e->stream, e->d_msg, (const double*)e->d_loop_init, P.loop_doubles, e->R, p.es, p.rs_msg);
-    // without the free energy on a graph without precision variables the sweep ends with the marginals
-    const int l_end = (!want_fe && P.prec_doubles == 0) ? P.fe_level : (P.lazy_level >= 0 ? P.lazy_level : P.n_levels);
+    start_state(e, p);
+    const int l_end = last_level(e, want_fe);
     if (!e->ev0) { TCHK(hipEventCreate(&e->ev0)); TCHK(hipEventCreate(&e->ev1)); }
-    hipGraphExec_t gx = nullptr;
-    if (e->use_graph) {
-        const int wf = want_fe ? 1 : 0;
-        if (e->gexec[wf] && e->g_lend[wf] != l_end) { (void)hipGraphExecDestroy(e->gexec[wf]); e->gexec[wf] = nullptr; }
-        if (!e->gexec[wf]) {
-            hipGraph_t gr = nullptr;
-            if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                launch(e, p, 0, l_end);
-                if (hipStreamEndCapture(e->stream, &gr) == hipSuccess && gr && hipGraphInstantiate(&e->gexec[wf], gr, nullptr, nullptr, 0) == hipSuccess) e->g_lend[wf] = l_end;
-                else e->gexec[wf] = nullptr;
-                if (gr) (void)hipGraphDestroy(gr);
-            }
-            (void)hipGetLastError();
-            if (!e->gexec[wf]) e->use_graph = false;   // (the direct launches below are the same kernels: nothing is lost but the launch overhead)
-        }
-        gx = e->gexec[wf];
-    }
+    const hipGraphExec_t gx = sweep_graph(e, p, want_fe, l_end);
     TCHK(hipEventRecord(e->ev0, e->stream));
-    for (int it = 0; it < iterations; ++it) {
-        if (gx) TCHK(hipGraphLaunch(gx, e->stream));
-        else launch(e, p, 0, l_end);
-        if (P.n_loop)   // the loop messages just computed become what the next iteration (or a continued run) reads
-            hipLaunchKernelGGL(k_tree_carry, dim3(loop_blocks), dim3(256), 0, e->stream, e->d_msg, (const double*)nullptr, P.loop_doubles, e->R, p.es, p.rs_msg);
-        if (want_fe) {   // Σ over replicas of term[root]: chunks of FE_CHUNK into partials, the partials (≤ FE_CHUNK of them: up to 16.7 M replicas) into the iteration's slot
-            const unsigned nb = (unsigned)((e->R + FE_CHUNK - 1) / FE_CHUNK);
-            const double* root = e->d_term + (size_t)P.fe_root * (e->elem_fast ? 1 : e->RS);
-            const long long stride = e->elem_fast ? P.term_slots : 1;
-            if (nb == 1)
-                hipLaunchKernelGGL(k_tree_fe_total, dim3(1), dim3(256), 0, e->stream, root, stride, e->R, e->d_fe_rep, e->d_fe_hist + it);
-            else {
-                hipLaunchKernelGGL(k_tree_fe_total, dim3(nb), dim3(256), 0, e->stream, root, stride, e->R, e->d_fe_rep, e->d_fe_part);
-                hipLaunchKernelGGL(k_tree_fe_total, dim3(1), dim3(256), 0, e->stream, (const double*)e->d_fe_part, 1ll, (long long)nb, (double*)nullptr, e->d_fe_hist + it);
-            }
-        }
-    }
+    for (int it = 0; it < iterations; ++it) TCHK(enqueue_iteration(e, p, gx, l_end, want_fe, e->d_fe_hist + it));
     TCHK(hipEventRecord(e->ev1, e->stream));
     TCHK(hipGetLastError());
     TCHK(hipStreamSynchronize(e->stream));
@@ -586,6 +618,7 @@ rxhip_status run(Engine* e, int iterations, int want_fe, std::string& err) {
     e->push_done = false;
     e->last_iterations = iterations;
     e->last_want_fe = want_fe;
+    e->stream_iterations = 0;
     ++e->runs;
     if (status & 1) { err = "a message or marginal precision was not positive definite"; return RXHIP_ERR_NOT_POSDEF; }
     if (want_fe) {
@@ -722,7 +755,8 @@ rxhip_status get_free_energy_per_replica(Engine* e, double* per_replica, std::st
     return RXHIP_OK;
 }
 void counters(Engine* e, uint64_t* rule_calls, uint64_t* products, uint64_t* marginals) {
-    const uint64_t k = (uint64_t)e->R * (uint64_t)std::max(1, e->last_iterations);
+    // (after rxhip_tree_stream: all observations of the stream calls that continue one another)
+    const uint64_t k = (uint64_t)e->R * (e->stream_iterations ? e->stream_iterations : (uint64_t)std::max(1, e->last_iterations));
     if (rule_calls) *rule_calls = e->prog.rule_calls * k;
     if (products) *products = e->prog.products * k;
     if (marginals) *marginals = e->prog.marginals * k;
@@ -757,6 +791,349 @@ void* stream_of(Engine* e) { return (void*)e->stream; }
 rxhip_status sync(Engine* e, std::string& err) {
     DevScope ds(e->device);
     TCHK(hipStreamSynchronize(e->stream));
+    return RXHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// streaming (include/rxhip.h "Streaming"): the loop of src/inference/streaming.jl:341-407 on the device
+namespace {
+const char* au_kind_name(int k) { return k == RXHIP_AU_MEAN ? "mean" : k == RXHIP_AU_VAR ? "var" : "precision"; }
+// would this engine take the feedback table?  (src/inference/autoupdates.jl: `target = f(q(source))`)
+rxhip_status validate_autoupdates(const Program& P, const rxhip_autoupdate* au, int64_t n, std::string& err) {
+    if (n < 0 || (n > 0 && !au)) { err = "autoupdates: null table"; return RXHIP_ERR_BADARG; }
+    const int64_t nv = (int64_t)P.vclass.size();
+    std::vector<char> seen((size_t)nv, 0);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t t = au[i].target, s = au[i].source;
+        const int k = au[i].kind;
+        const std::string at = "autoupdate " + std::to_string(i) + ": ";
+        if (k != RXHIP_AU_MEAN && k != RXHIP_AU_VAR && k != RXHIP_AU_PRECISION) {
+            err = at + "unknown kind " + std::to_string(k) + " for target variable " + std::to_string(t) + " (RXHIP_AU_MEAN, RXHIP_AU_VAR or RXHIP_AU_PRECISION)";
+            return RXHIP_ERR_BADARG;
+        }
+        if (t < 0 || t >= nv || P.vclass[t] != VC_DATA) { err = at + "target variable " + std::to_string(t) + " is not a data variable"; return RXHIP_ERR_BADARG; }
+        if (P.is_mat[t]) { err = at + "target variable " + std::to_string(t) + " is the data matrix of a `*` node"; return RXHIP_ERR_BADARG; }
+        if (s >= 0 && s < nv && (P.vclass[s] == VC_PREC || P.vclass[s] == VC_CAT || P.vclass[s] == VC_DIR)) {
+            err = at + "source variable " + std::to_string(s) + " is not Gaussian: the parameters of a Gamma / Wishart / discrete marginal (`shape(q(τ))`, `params(q(θ))`) as feedback "
+                       "are not supported — the executor has no data-valued prior of those families to receive them";
+            return RXHIP_ERR_UNSUPPORTED;
+        }
+        if (s < 0 || s >= nv || P.vclass[s] != VC_GAUSS) { err = at + "source variable " + std::to_string(s) + " is not a Gaussian random variable"; return RXHIP_ERR_BADARG; }
+        if (k != RXHIP_AU_MEAN && P.dim[s] != 1) {
+            err = at + au_kind_name(k) + " of source variable " + std::to_string(s) + " (dimension " + std::to_string(P.dim[s]) +
+                  "): a covariance / precision MATRIX as feedback is not supported — the executor has no data-valued matrix covariance to receive it";
+            return RXHIP_ERR_UNSUPPORTED;
+        }
+        if (P.dim[t] != P.dim[s]) {
+            err = at + "target variable " + std::to_string(t) + " has dimension " + std::to_string(P.dim[t]) + ", the " + au_kind_name(k) + " of source variable " + std::to_string(s) + " has " +
+                  std::to_string(P.dim[s]);
+            return RXHIP_ERR_BADARG;
+        }
+        if (seen[t]) { err = at + "target variable " + std::to_string(t) + " is listed twice"; return RXHIP_ERR_BADARG; }
+        seen[t] = 1;
+    }
+    return RXHIP_OK;
+}
+}  // namespace
+
+rxhip_status check_autoupdates(const rxhip_graph_desc* g, const rxhip_autoupdate* au, int64_t n, std::string& err) {
+    if (!g) { err = "null argument"; return RXHIP_ERR_BADARG; }
+    Program P;
+    try {
+        Compiler c(g, P);
+        c.compile();
+    } catch (const Fail& f) {
+        err = f.msg;
+        return f.st;
+    } catch (const std::exception& ex) {
+        err = ex.what();
+        return RXHIP_ERR_BADARG;
+    }
+    return validate_autoupdates(P, au, n, err);
+}
+
+rxhip_status set_autoupdates(Engine* e, const rxhip_autoupdate* au, int64_t n, std::string& err) {
+    if (!e) { err = "null engine"; return RXHIP_ERR_BADARG; }
+    if (rxhip_status st = validate_autoupdates(e->prog, au, n, err)) return st;
+    e->autoupdates.assign(au, au + (n > 0 ? n : 0));
+    return RXHIP_OK;
+}
+
+rxhip_status stream(Engine* e, const int64_t* vars, int64_t n_vars, const double* series, int64_t T, int iterations, int want_fe, const int64_t* history_vars, int64_t n_history,
+                    std::string& err) {
+    if (!e || n_vars < 0 || (n_vars > 0 && !vars) || T < 0 || n_history < 0 || (n_history > 0 && !history_vars)) { err = "stream: null or negative argument"; return RXHIP_ERR_BADARG; }
+    if (iterations < 1) { err = "stream: iterations must be positive"; return RXHIP_ERR_BADARG; }
+    const Program& P = e->prog;
+    const int64_t nv = (int64_t)P.vclass.size();
+    // which data variables this call feeds: the feedback targets, then the series' variables
+    std::vector<char> fed((size_t)nv, 0);
+    for (const rxhip_autoupdate& a : e->autoupdates) fed[a.target] = 1;
+    long long rows = 0;
+    for (int64_t i = 0; i < n_vars; ++i) {
+        const int64_t v = vars[i];
+        if (v < 0 || v >= nv || P.vclass[v] != VC_DATA) { err = "stream: variable " + std::to_string(v) + " is not a data variable"; return RXHIP_ERR_BADARG; }
+        if (fed[v] == 1) { err = "stream: variable " + std::to_string(v) + " is the target of an autoupdate and cannot be streamed as data too"; return RXHIP_ERR_BADARG; }
+        if (fed[v]) { err = "stream: variable " + std::to_string(v) + " is listed twice"; return RXHIP_ERR_BADARG; }
+        fed[v] = 2;
+        rows += P.val_width[v];
+    }
+    for (int64_t i = 0; i < n_history; ++i) {
+        const int64_t v = history_vars[i];
+        if (v < 0 || v >= nv || P.vclass[v] != VC_GAUSS) { err = "stream: history variable " + std::to_string(v) + " is not a random Gaussian variable"; return RXHIP_ERR_BADARG; }
+    }
+    if (T == 0) return RXHIP_OK;
+    if (rows > 0 && !series) { err = "stream: null series"; return RXHIP_ERR_BADARG; }
+    for (size_t i = 0; i < P.data_vars.size(); ++i)
+        if (!e->data_set[i] && !fed[P.data_vars[i]]) { err = "stream: data variable " + std::to_string(P.data_vars[i]) + " is neither streamed, nor fed back, nor set before"; return RXHIP_ERR_STATE; }
+    const bool fresh = !(e->cont && e->ran);   // the first feedback reads the @initialization marginals (streaming.jl fetches the autoupdates before the first observation's iterations)
+    bool src_push = false, hist_push = false;
+    for (const rxhip_autoupdate& a : e->autoupdates) {
+        if (fresh && P.ginit_off[a.source] < 0) {
+            err = "stream: the initial value for variable " + std::to_string(a.source) + " has not been specified: an autoupdate reads q(" + std::to_string(a.source) +
+                  ") before the first observation — give it an @initialization marginal (Normal / MvNormal)";
+            return RXHIP_ERR_BADARG;
+        }
+        src_push = src_push || P.is_push[a.source];
+    }
+    for (int64_t i = 0; i < n_history; ++i) hist_push = hist_push || P.is_push[history_vars[i]];
+
+    DevScope ds(e->device);
+    const long long R = e->R;
+    const bool ef = e->elem_fast;
+    // the row tables of the two steps, and the feedback's initial values
+    std::vector<StreamRow> pre, post;
+    std::vector<double> init;
+    for (const rxhip_autoupdate& a : e->autoupdates) {
+        const int d = P.dim[a.source];
+        const double* q = P.ginit_off[a.source] >= 0 ? P.ginit.data() + P.ginit_off[a.source] : nullptr;
+        if (a.kind == RXHIP_AU_MEAN) {
+            for (int k = 0; k < d; ++k) {
+                pre.push_back(StreamRow{P.val_off[a.target] + k, P.marg_off[a.source] + k, SR_MEAN, (int)init.size()});
+                init.push_back(q ? q[k] : 0.0);
+            }
+        } else {   // (scalars: the marginal slot is mean | variance | log-determinant)
+            pre.push_back(StreamRow{P.val_off[a.target], P.marg_off[a.source] + 1, a.kind == RXHIP_AU_VAR ? SR_VAR : SR_PRECISION, (int)init.size()});
+            init.push_back(q ? q[1] : 1.0);
+        }
+    }
+    {
+        int col = 0;
+        for (int64_t i = 0; i < n_vars; ++i)
+            for (int k = 0; k < P.val_width[vars[i]]; ++k) pre.push_back(StreamRow{P.val_off[vars[i]] + k, col++, SR_SERIES, 0});
+    }
+    long long hrows = 0;
+    for (int64_t i = 0; i < n_history; ++i) {
+        const int d = P.dim[history_vars[i]], w = d + d * (d + 1) / 2;   // mean | packed covariance
+        for (int k = 0; k < w; ++k) post.push_back(StreamRow{(int)(hrows + k), P.marg_off[history_vars[i]] + k, SR_HISTORY, 0});
+        hrows += w;
+    }
+
+    TCHK(hipStreamSynchronize(e->stream));
+    // what the previous stream left is replaced
+    for (double** q : {&e->d_hist, &e->d_sfe}) {
+        if (*q) (void)hipFree(*q);
+        *q = nullptr;
+    }
+    e->hist_T = e->sfe_T = 0;
+    e->hist_vars.clear();
+    double* d_series = nullptr;
+    StreamRow *d_pre = nullptr, *d_post = nullptr;
+    double* d_init = nullptr;
+    auto release = [&]() {
+        for (void* q : {(void*)d_series, (void*)d_pre, (void*)d_post, (void*)d_init})
+            if (q) (void)hipFree(q);
+    };
+    auto fail_with = [&](rxhip_status st) { release(); return st; };
+    if (n_history > 0) {
+        const size_t bytes = sizeof(double) * (size_t)T * (size_t)hrows * (size_t)R;
+        if (hipMalloc(&e->d_hist, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            e->d_hist = nullptr;
+            err = "stream: the history of " + std::to_string(T) + " observations needs " + std::to_string(bytes) + " bytes of device memory, which could not be allocated";
+            return fail_with(RXHIP_ERR_BADARG);
+        }
+    }
+    if (want_fe && hipMalloc(&e->d_sfe, sizeof(double) * (size_t)T * (size_t)iterations) != hipSuccess) { e->d_sfe = nullptr; err = "stream: hipMalloc failed"; return fail_with(RXHIP_ERR_HIP); }
+    if (iterations > e->fe_cap) {
+        if (e->d_fe_hist) (void)hipFree(e->d_fe_hist);
+        e->d_fe_hist = nullptr;
+        e->fe_cap = 0;
+        if (hipMalloc(&e->d_fe_hist, sizeof(double) * (size_t)iterations) != hipSuccess) { err = "stream: hipMalloc failed"; return fail_with(RXHIP_ERR_HIP); }
+        e->fe_cap = iterations;
+    }
+    rxhip_status st;
+    if ((st = upload(&d_pre, pre, err)) || (st = upload(&d_post, post, err)) || (st = upload(&d_init, init, err))) return fail_with(st);
+    // the series: up as it is, in blocks of observations of at most 256 MB, and transposed ONCE into the value slots' layout — replica-fastest: column k of
+    // observation t and replica r at [k][t][r]; a replica's slots contiguous: [t][r][k]
+    const long long es_ser = ef ? 1 : (long long)T * R, rs_ser = ef ? rows : 1;
+    if (rows > 0) {
+        const size_t sbytes = sizeof(double) * (size_t)T * (size_t)R * (size_t)rows;
+        if (hipMalloc(&d_series, sbytes) != hipSuccess) {
+            (void)hipGetLastError();
+            d_series = nullptr;
+            err = "stream: the series of " + std::to_string(T) + " observations needs " + std::to_string(sbytes) + " bytes of device memory, which could not be allocated";
+            return fail_with(RXHIP_ERR_BADARG);
+        }
+        if (hipMemset(e->d_status, 0, sizeof(int)) != hipSuccess) { err = "stream: hipMemset failed"; return fail_with(RXHIP_ERR_HIP); }
+        const long long per_obs = R * rows, blk = std::max<long long>(1, std::min<long long>(T, ((256ll << 20) / 8) / std::max<long long>(1, per_obs)));
+        double* d_tmp = nullptr;
+        if (hipMalloc(&d_tmp, sizeof(double) * (size_t)blk * (size_t)per_obs) != hipSuccess) { err = "stream: hipMalloc failed"; return fail_with(RXHIP_ERR_HIP); }
+        bool bad = false;
+        for (long long t0 = 0; t0 < T && !bad; t0 += blk) {
+            const long long nt = std::min<long long>(blk, T - t0), nr = nt * R;   // (observation, replica) pairs of this block: the scatter's "replicas"
+            if (hipMemcpy(d_tmp, series + (size_t)t0 * per_obs, sizeof(double) * (size_t)nt * per_obs, hipMemcpyHostToDevice) != hipSuccess) { bad = true; break; }
+            long long col = 0;
+            for (int64_t i = 0; i < n_vars;) {   // runs of data values / of data matrices: the scatter reports NaN in the two with different bits, as set_data does
+                int64_t j = i;
+                long long width = 0;
+                while (j < n_vars && P.is_mat[vars[j]] == P.is_mat[vars[i]]) { width += P.val_width[vars[j]]; ++j; }
+                const dim3 grid((unsigned)((nr + 31) / 32), (unsigned)((width + 31) / 32));
+                hipLaunchKernelGGL(k_tree_scatter, grid, dim3(256), 0, e->stream, d_series + (size_t)col * es_ser + (size_t)t0 * R * rs_ser, (const double*)d_tmp, nr, es_ser, rs_ser, rows, col, width,
+                                   e->d_status, P.is_mat[vars[i]] ? 4 : 2);
+                col += width;
+                i = j;
+            }
+            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess) bad = true;
+        }
+        (void)hipFree(d_tmp);
+        if (bad) { err = "stream: copying the series to the device failed"; return fail_with(RXHIP_ERR_HIP); }
+        int flag = 0;
+        if (hipMemcpy(&flag, e->d_status, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess || hipMemset(e->d_status, 0, sizeof(int)) != hipSuccess) { err = "stream: reading the status word failed"; return fail_with(RXHIP_ERR_HIP); }
+        if (flag & 4) { err = "stream: a data matrix of the series holds NaN or Inf — the matrix of a `*` node cannot be `missing`"; return fail_with(RXHIP_ERR_BADARG); }
+        if ((flag & 2) && !e->allow_missing) {
+            err = "stream: the series holds NaN or Inf — `missing` observations need an engine created with rxhip_graph_desc.allow_missing";
+            return fail_with(RXHIP_ERR_BADARG);
+        }
+    }
+    if (hipMemsetAsync(e->d_status, 0, sizeof(int), e->stream) != hipSuccess) { err = "stream: hipMemsetAsync failed"; return fail_with(RXHIP_ERR_HIP); }
+
+    const TreeParams p = params_of(e, want_fe);
+    start_state(e, p);
+    const int l_end = last_level(e, want_fe);
+    if (!e->ev0 && (hipEventCreate(&e->ev0) != hipSuccess || hipEventCreate(&e->ev1) != hipSuccess)) { err = "stream: hipEventCreate failed"; return fail_with(RXHIP_ERR_HIP); }
+    const hipGraphExec_t gx = sweep_graph(e, p, want_fe, l_end);
+    StreamStep c{};
+    c.R = R; c.by_replica = ef ? 1 : 0;
+    c.val = e->d_val; c.es_val = p.es; c.rs_val = p.rs_val;
+    c.marg = e->d_marg; c.es_marg = p.es; c.rs_marg = p.rs_marg;
+    c.es_ser = es_ser; c.rs_ser = rs_ser;
+    c.es_hist = ef ? 1 : R; c.rs_hist = ef ? hrows : 1;
+    auto step = [&](const StreamRow* tab, size_t n) {
+        c.rows = tab; c.n_rows = (int)n;
+        const long long items = (long long)n * R;
+        hipLaunchKernelGGL(k_tree_stream_step, dim3((unsigned)std::min<long long>((items + 255) / 256, 4096)), dim3(256), 0, e->stream, c);
+    };
+    auto push_images = [&]() {   // the image marginals (OP_MARG_PUSH) of the last sweep, as rxhip_tree_get_marginals forms them on demand
+        launch(e, params_of(e, 0), P.lazy_level, P.lazy_level + 1);
+        e->push_done = true;
+    };
+    hipError_t he = hipEventRecord(e->ev0, e->stream);
+    for (int64_t t = 0; t < T && he == hipSuccess; ++t) {
+        const bool from_init = fresh && t == 0;
+        if (src_push && !from_init && !e->push_done && P.lazy_level >= 0) push_images();
+        c.init = from_init ? d_init : nullptr;
+        c.series = d_series ? d_series + (size_t)t * R * rs_ser : nullptr;
+        c.hist = nullptr;
+        if (!pre.empty()) step(d_pre, pre.size());
+        for (int it = 0; it < iterations && he == hipSuccess; ++it) he = enqueue_iteration(e, p, gx, l_end, want_fe, want_fe ? e->d_sfe + (size_t)t * iterations + it : nullptr);
+        e->push_done = false;
+        if (hist_push && P.lazy_level >= 0) push_images();
+        if (!post.empty()) {
+            c.hist = e->d_hist + (size_t)t * (size_t)hrows * (size_t)R;
+            step(d_post, post.size());
+        }
+    }
+    if (he == hipSuccess) he = hipEventRecord(e->ev1, e->stream);
+    if (he == hipSuccess && want_fe)   // rxhip_get_free_energy afterwards: the last observation's row
+        he = hipMemcpyAsync(e->d_fe_hist, e->d_sfe + (size_t)(T - 1) * iterations, sizeof(double) * (size_t)iterations, hipMemcpyDeviceToDevice, e->stream);
+    if (he == hipSuccess) he = hipGetLastError();
+    const hipError_t hs = hipStreamSynchronize(e->stream);   // the ONE synchronisation of the call
+    if (he == hipSuccess) he = hs;
+    release();
+    if (he != hipSuccess) { err = std::string("stream: ") + hipGetErrorString(he); return RXHIP_ERR_HIP; }
+    {
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, e->ev0, e->ev1) == hipSuccess) e->last_iteration_ms = (double)ms / ((double)T * iterations);   // (step kernels included)
+    }
+    int status = 0;
+    TCHK(hipMemcpy(&status, e->d_status, sizeof(int), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < P.data_vars.size(); ++i)
+        if (fed[P.data_vars[i]]) e->data_set[i] = 1;
+    e->have_data = true;
+    e->stream_iterations = (fresh ? 0 : e->stream_iterations) + (uint64_t)T * (uint64_t)iterations;
+    e->ran = true;
+    e->last_iterations = iterations;
+    e->last_want_fe = want_fe;
+    e->runs += (uint64_t)T;
+    e->hist_T = n_history > 0 ? T : 0;
+    e->hist_rows = hrows;
+    e->hist_vars.assign(history_vars, history_vars + n_history);
+    e->sfe_T = want_fe ? T : 0;
+    e->sfe_iterations = iterations;
+    if (status & 1) { err = "a message or marginal precision was not positive definite"; return RXHIP_ERR_NOT_POSDEF; }
+    if (want_fe) {
+        std::vector<double> h((size_t)T * iterations);
+        TCHK(hipMemcpy(h.data(), e->d_sfe, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+        for (double v : h)
+            if (!std::isfinite(v)) { err = "free energy is not finite"; return RXHIP_ERR_NONFINITE_FE; }
+    }
+    return RXHIP_OK;
+}
+
+// the history of the last stream into [T][var][replica][d] / [T][var][replica][d][d]: one gather per observation on the device (the kernel of get_marginals over
+// that observation's block), blocks of observations of at most 256 MB of results
+rxhip_status get_history(Engine* e, double* mean, double* cov, std::string& err) {
+    if (!e) { err = "null engine"; return RXHIP_ERR_BADARG; }
+    if (e->hist_T <= 0 || !e->d_hist) { err = "get_history: no history — call rxhip_tree_stream with history variables first"; return RXHIP_ERR_STATE; }
+    if (!mean && !cov) return RXHIP_OK;
+    DevScope ds(e->device);
+    const Program& P = e->prog;
+    const long long R = e->R, T = e->hist_T;
+    const size_t n = e->hist_vars.size();
+    std::vector<GatherVar> gv(n);
+    size_t nm = 0, nc = 0;
+    int off = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const int d = P.dim[e->hist_vars[i]];
+        gv[i].off = off; gv[i].d = d; gv[i].clamped = 0;
+        gv[i].mo = (long long)nm; gv[i].co = (long long)nc;
+        nm += (size_t)R * d; nc += (size_t)R * d * d;
+        off += d + d * (d + 1) / 2;
+    }
+    const size_t cap = (256u << 20) / 8;
+    const long long blk = std::max<long long>(1, std::min<long long>(T, (long long)(cap / std::max<size_t>(1, nc))));
+    GatherVar* d_gv = nullptr;
+    double *d_m = nullptr, *d_c = nullptr;
+    auto freeall = [&]() { for (void* q : {(void*)d_gv, (void*)d_m, (void*)d_c}) if (q) (void)hipFree(q); };
+    hipError_t he = hipStreamSynchronize(e->stream);
+    if (he == hipSuccess) he = hipMalloc(&d_gv, sizeof(GatherVar) * n);
+    if (he == hipSuccess) he = hipMemcpy(d_gv, gv.data(), sizeof(GatherVar) * n, hipMemcpyHostToDevice);
+    if (he == hipSuccess && mean) he = hipMalloc(&d_m, sizeof(double) * nm * (size_t)blk);
+    if (he == hipSuccess && cov) he = hipMalloc(&d_c, sizeof(double) * nc * (size_t)blk);
+    const long long es = e->elem_fast ? 1 : R, rs = e->elem_fast ? e->hist_rows : 1;
+    for (long long t0 = 0; t0 < T && he == hipSuccess; t0 += blk) {
+        const long long nt = std::min(blk, T - t0);
+        for (long long t = t0; t < t0 + nt; ++t) {
+            const long long items = (long long)n * ((R + 255) / 256);
+            hipLaunchKernelGGL(k_tree_gather, dim3((unsigned)std::min<long long>(items, 1 << 20)), dim3(256), 0, e->stream, (const double*)(e->d_hist + (size_t)t * e->hist_rows * R), (const double*)e->d_val,
+                               (const GatherVar*)d_gv, (int)n, R, es, rs, 1ll, d_m ? d_m + (size_t)(t - t0) * nm : nullptr, d_c ? d_c + (size_t)(t - t0) * nc : nullptr);
+        }
+        he = hipGetLastError();
+        if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+        if (he == hipSuccess && mean) he = hipMemcpy(mean + (size_t)t0 * nm, d_m, sizeof(double) * nm * (size_t)nt, hipMemcpyDeviceToHost);
+        if (he == hipSuccess && cov) he = hipMemcpy(cov + (size_t)t0 * nc, d_c, sizeof(double) * nc * (size_t)nt, hipMemcpyDeviceToHost);
+    }
+    freeall();
+    if (he != hipSuccess) { err = std::string("get_history: ") + hipGetErrorString(he); return RXHIP_ERR_HIP; }
+    return RXHIP_OK;
+}
+
+rxhip_status get_stream_free_energy(Engine* e, double* fe, std::string& err) {
+    if (!e || !fe) { err = "null argument"; return RXHIP_ERR_BADARG; }
+    if (e->sfe_T <= 0 || !e->d_sfe) { err = "no free energy: call rxhip_tree_stream with want_free_energy first"; return RXHIP_ERR_STATE; }
+    DevScope ds(e->device);
+    TCHK(hipStreamSynchronize(e->stream));
+    TCHK(hipMemcpy(fe, e->d_sfe, sizeof(double) * (size_t)e->sfe_T * (size_t)e->sfe_iterations, hipMemcpyDeviceToHost));
     return RXHIP_OK;
 }
 

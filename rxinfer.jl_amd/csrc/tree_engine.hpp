@@ -25,6 +25,13 @@ void counters(Engine* e, uint64_t* rule_calls, uint64_t* products, uint64_t* mar
 void info(Engine* e, rxhip_tree_info* out);
 // on: every later run() continues from the q(W) the previous run ended with (rxhip_tree_continue)
 void set_continue(Engine* e, bool on);
+// streaming (include/rxhip.h "Streaming"): the feedback table, T observations with feedback / iterations / history / free energy on the device, the read-backs
+rxhip_status check_autoupdates(const rxhip_graph_desc* g, const rxhip_autoupdate* au, int64_t n, std::string& err);   // host only
+rxhip_status set_autoupdates(Engine* e, const rxhip_autoupdate* au, int64_t n, std::string& err);
+rxhip_status stream(Engine* e, const int64_t* vars, int64_t n_vars, const double* series, int64_t T, int iterations, int want_fe, const int64_t* history_vars, int64_t n_history,
+                    std::string& err);
+rxhip_status get_history(Engine* e, double* mean, double* cov, std::string& err);
+rxhip_status get_stream_free_energy(Engine* e, double* fe, std::string& err);
 int device_of(Engine* e);
 void* stream_of(Engine* e);
 rxhip_status sync(Engine* e, std::string& err);

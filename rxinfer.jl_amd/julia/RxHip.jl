@@ -894,6 +894,49 @@ function tree_discrete(e::Engine, id::Integer)
     return out[1:K[]]
 end
 
+# mirrors rxhip_autoupdate (kind: 0 mean, 1 variance, 2 precision = 1 / variance — RXHIP_AU_*)
+struct Autoupdate
+    target::Int64
+    source::Int64
+    kind::Int32
+    reserved::Int32
+end
+
+"""The `@autoupdates` of a streamed model (`rxhip_tree_set_autoupdates`): before every observation of `tree_stream!` data variable `target` takes the
+mean / variance / precision of the current q(`source`) (0-based ids).  An empty table clears it."""
+function tree_set_autoupdates!(e::Engine, table::Vector{Autoupdate})
+    GC.@preserve table check(e, ccall((:rxhip_tree_set_autoupdates, librxhip), Int32, (Ptr{Cvoid}, Ptr{Autoupdate}, Int64), e.handle, table, length(table)))
+end
+
+"""`T` observations in one call (`rxhip_tree_stream`): `series` holds, observation after observation and replica after replica, the values of the data
+variables `ids` side by side; feedback, iterations, history and free energy stay on the device (the loop of src/inference/streaming.jl:341-407)."""
+function tree_stream!(e::Engine, ids::Vector{Int64}, series::Vector{Float64}, T::Integer; iterations::Integer = 1, free_energy::Bool = true,
+                      history::Vector{Int64} = Int64[])
+    GC.@preserve ids series history check(e, ccall((:rxhip_tree_stream, librxhip), Int32,
+        (Ptr{Cvoid}, Ptr{Int64}, Int64, Ptr{Float64}, Int64, Int32, Int32, Ptr{Int64}, Int64),
+        e.handle, ids, length(ids), series, T, iterations, free_energy ? 1 : 0, history, length(history)))
+end
+
+"""What the last `tree_stream!` recorded (`rxhip_tree_get_history`) for its history variables of dimensions `dims` over `T` observations: per variable a
+vector over time of means and of covariance matrices (replica 1)."""
+function tree_history(e::Engine, dims::Vector{Int}, T::Integer)
+    R = e.n_chains
+    sm, sc = R * sum(dims), R * sum(d -> d * d, dims)
+    mean, cov = Vector{Float64}(undef, T * sm), Vector{Float64}(undef, T * sc)
+    GC.@preserve mean cov check(e, ccall((:rxhip_tree_get_history, librxhip), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), e.handle, mean, cov))
+    ms, Vs = [Vector{Vector{Float64}}() for _ in dims], [Vector{Matrix{Float64}}() for _ in dims]
+    for t in 0:(T - 1)   # [T][var][replica][d] / [T][var][replica][d][d], row-major: replica 1 of every variable
+        mo, co = t * sm, t * sc
+        for (i, d) in enumerate(dims)
+            push!(ms[i], mean[(mo + 1):(mo + d)])
+            push!(Vs[i], collect(transpose(reshape(cov[(co + 1):(co + d * d)], d, d))))
+            mo += R * d
+            co += R * d * d
+        end
+    end
+    return ms, Vs
+end
+
 """One message rule on the device (`rxhip_rule_eval`): the A/B hook next to `ReactiveMP.@call_rule`.  `a`: d × n, `B`: d × d × n (column-major
 Julia arrays of symmetric matrices: the C side reads them row-major, the same bytes)."""
 function rule_eval(node_type::Integer, iface::Integer, constant, a::Matrix{Float64}, B::Array{Float64, 3}; a2 = nothing, B2 = nothing,

@@ -126,6 +126,13 @@ class RuleCall(ctypes.Structure):   # rxhip_rule_call
                 ("in2_B", c_double_p), ("out_form", ctypes.c_int32), ("out_a", c_double_p), ("out_B", c_double_p)]
 
 
+AU_MEAN, AU_VAR, AU_PRECISION = 0, 1, 2
+
+
+class Autoupdate(ctypes.Structure):   # rxhip_autoupdate
+    _fields_ = [("target", ctypes.c_int64), ("source", ctypes.c_int64), ("kind", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 # every symbol include/rxhip.h declares: (name, restype, argtypes)
 _H = ctypes.c_void_p
 SYMBOLS = [
@@ -136,6 +143,11 @@ SYMBOLS = [
     ("rxhip_tree_get_discrete", ctypes.c_int32, [_H, ctypes.c_int64, c_double_p, ctypes.POINTER(ctypes.c_int32)]),
     ("rxhip_tree_get_info", ctypes.c_int32, [_H, ctypes.POINTER(TreeInfo)]),
     ("rxhip_tree_continue", ctypes.c_int32, [_H, ctypes.c_int32]),
+    ("rxhip_tree_check_autoupdates", ctypes.c_int32, [ctypes.POINTER(GraphDesc), ctypes.POINTER(Autoupdate), ctypes.c_int64]),
+    ("rxhip_tree_set_autoupdates", ctypes.c_int32, [_H, ctypes.POINTER(Autoupdate), ctypes.c_int64]),
+    ("rxhip_tree_stream", ctypes.c_int32, [_H, c_int64_p, ctypes.c_int64, c_double_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, c_int64_p, ctypes.c_int64]),
+    ("rxhip_tree_get_history", ctypes.c_int32, [_H, c_double_p, c_double_p]),
+    ("rxhip_tree_get_stream_free_energy", ctypes.c_int32, [_H, c_double_p]),
     ("rxhip_rule_eval", ctypes.c_int32, [ctypes.POINTER(RuleCall), ctypes.c_int32]),
     ("rxhip_lgssm_create", ctypes.c_int32, [ctypes.POINTER(LgssmDesc), ctypes.POINTER(_H)]),
     ("rxhip_lgssm_noise_create", ctypes.c_int32, [ctypes.POINTER(LgssmDesc), ctypes.POINTER(NoisePrior), ctypes.POINTER(_H)]),

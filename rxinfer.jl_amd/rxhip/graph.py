@@ -716,11 +716,13 @@ def iid_normal_graph(N, mean, variance, shape, rate=None, init=None, scale=None)
 
 
 def hgf_step_graph(kappa, omega, z_variance, y_variance, q_zt=(0.0, 5.0), q_xt=(0.0, 5.0), n_gh=31):
-    """The one-step graph of test/models/statespace/hgf_tests.jl:9-31 with its `@initialization` and GCV meta."""
+    """The one-step graph of test/models/statespace/hgf_tests.jl:9-31 with its `@initialization` and GCV meta.  names["autoupdates"]: the `@autoupdates` of
+    hgf_tests.jl:46-49 as the table TreeEngine.set_autoupdates takes (`zt_min_mean, zt_min_var = mean_var(q(zt))`, the same for xt)."""
     gb = GraphBuilder()
     zt_min, xt_min, zt, xt = gb.randomvar(1), gb.randomvar(1), gb.randomvar(1), gb.randomvar(1)
-    gb.node(_lib.NODE_NORMAL_MEAN_VARIANCE, zt_min, gb.datavar(1), gb.datavar(1))
-    gb.node(_lib.NODE_NORMAL_MEAN_VARIANCE, xt_min, gb.datavar(1), gb.datavar(1))
+    zm, zv, xm, xv = gb.datavar(1), gb.datavar(1), gb.datavar(1), gb.datavar(1)
+    gb.node(_lib.NODE_NORMAL_MEAN_VARIANCE, zt_min, zm, zv)
+    gb.node(_lib.NODE_NORMAL_MEAN_VARIANCE, xt_min, xm, xv)
     gb.node(_lib.NODE_NORMAL_MEAN_VARIANCE, zt, zt_min, gb.constvar(z_variance))
     gb.node(_lib.NODE_GCV, xt, xt_min, zt, gb.constvar(kappa), gb.constvar(omega))
     y = gb.datavar(1)
@@ -728,7 +730,7 @@ def hgf_step_graph(kappa, omega, z_variance, y_variance, q_zt=(0.0, 5.0), q_xt=(
     gb.initialize(zt, _lib.INIT_NORMAL, q_zt)
     gb.initialize(xt, _lib.INIT_NORMAL, q_xt)
     gb.gh_points = n_gh
-    return gb, dict(zt=zt, xt=xt, y=y)
+    return gb, dict(zt=zt, xt=xt, y=y, autoupdates=[(zm, zt, "mean"), (zv, zt, "var"), (xm, xt, "mean"), (xv, xt, "var")])
 
 
 def lower_gmm(g):

@@ -93,6 +93,50 @@ class TreeEngine:
         self._chk(_lib.lib().rxhip_run(self._h, int(iterations), int(bool(free_energy))))
         self._iters = int(iterations)
 
+    def set_autoupdates(self, table):
+        """The `@autoupdates` of a streamed model (rxhip_tree_set_autoupdates): [(target, source, "mean" | "var" | "precision"), …] — before every observation of
+        stream() data variable `target` takes the mean / variance / 1 ÷ variance of the current q(source).  [] clears the table."""
+        arr = autoupdate_table(table)
+        self._chk(_lib.lib().rxhip_tree_set_autoupdates(self._h, arr.ptr, len(arr)))
+
+    def stream(self, variables, series, iterations=1, free_energy=True, history=()):
+        """T observations in one call (rxhip_tree_stream), feedback / iterations / history / free energy on the device: series [T][replica][Σ rows of variables]
+        (set_data's layout per observation).  Returns {"history": {var: (mean [T][R][d], cov [T][R][d][d])}, "free_energy": [T][iterations] (None without)}."""
+        v = np.ascontiguousarray(variables, dtype=np.int64)
+        h = np.ascontiguousarray(history, dtype=np.int64)
+        R = self.n_replicas
+        rows = int(sum(self.gb.rows[i] * self.gb.cols[i] for i in v))
+        x = _c(series)
+        T = int(x.shape[0]) if x.ndim > 0 else 0
+        x = x.reshape(T, R, -1) if T else x.reshape(0, R, rows)
+        if x.shape[2] != rows:
+            raise ValueError(f"series must be [T][replicas][{rows}]")
+        L = _lib.lib()
+        self._chk(L.rxhip_tree_stream(self._h, v.ctypes.data_as(c_int64_p), len(v), x.ctypes.data_as(c_double_p), T, int(iterations), int(bool(free_energy)),
+                                      h.ctypes.data_as(c_int64_p), len(h)))
+        if T:
+            self._iters = int(iterations)
+        out = {"history": {}, "free_energy": None}
+        dims = [self.gb.rows[i] for i in h]
+        if T and len(h):
+            sm, sc = sum(dims), sum(d * d for d in dims)
+            mean, cov = np.empty((T, R * sm)), np.empty((T, R * sc))
+            self._chk(L.rxhip_tree_get_history(self._h, mean.ctypes.data_as(c_double_p), cov.ctypes.data_as(c_double_p)))
+            mo = co = 0
+            for i, d in zip(h, dims):
+                out["history"][int(i)] = (mean[:, mo:mo + R * d].reshape(T, R, d).copy(), cov[:, co:co + R * d * d].reshape(T, R, d, d).copy())
+                mo += R * d
+                co += R * d * d
+        else:
+            for i, d in zip(h, dims):
+                out["history"][int(i)] = (np.empty((0, R, d)), np.empty((0, R, d, d)))
+        if free_energy:
+            fe = np.empty((T, int(iterations)))
+            if T:
+                self._chk(L.rxhip_tree_get_stream_free_energy(self._h, fe.ctypes.data_as(c_double_p)))
+            out["free_energy"] = fe
+        return out
+
     def marginals(self, variables):
         """{variable: (mean [replica][d], cov [replica][d][d])}"""
         v = np.ascontiguousarray(variables, dtype=np.int64)
@@ -137,6 +181,40 @@ class TreeEngine:
         r, p, m = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
         self._chk(_lib.lib().rxhip_counters(self._h, ctypes.byref(r), ctypes.byref(p), ctypes.byref(m)))
         return dict(rule_calls=r.value, products=p.value, marginals=m.value)
+
+
+_AU_KINDS = {"mean": _lib.AU_MEAN, "var": _lib.AU_VAR, "precision": _lib.AU_PRECISION}
+
+
+def autoupdate_table(table):
+    """[(target, source, kind), …] as an array of rxhip_autoupdate; kind: "mean" | "var" | "precision" (or the integer of include/rxhip.h)"""
+    table = list(table)
+    arr = (_lib.Autoupdate * max(1, len(table)))()
+    for i, (t, s, k) in enumerate(table):
+        if isinstance(k, str) and k not in _AU_KINDS:
+            raise ValueError(f"autoupdate kind {k!r}: 'mean', 'var' or 'precision'")
+        arr[i].target, arr[i].source, arr[i].kind = int(t), int(s), _AU_KINDS[k] if isinstance(k, str) else int(k)
+    return _AuTable(arr, len(table))
+
+
+class _AuTable:
+    """a ctypes array of rxhip_autoupdate and the table's length (a ctypes array cannot have length 0); .ptr is the pointer argument"""
+
+    def __init__(self, arr, n):
+        self.arr, self.n, self.ptr = arr, n, ctypes.cast(arr, ctypes.POINTER(_lib.Autoupdate))
+
+    def __len__(self):
+        return self.n
+
+
+def check_autoupdates(gb, table, n_replicas=1, allow_missing=False):
+    """Would TreeEngine(gb).set_autoupdates(table) take the table?  Host only, no GPU (rxhip_tree_check_autoupdates); raises RxHipError where it would not."""
+    g, keep = gb.tables(n_replicas=n_replicas, allow_missing=allow_missing)
+    arr = autoupdate_table(table)
+    L = _lib.lib()
+    st = L.rxhip_tree_check_autoupdates(ctypes.byref(g), arr.ptr, len(arr))
+    if st != _lib.OK:
+        raise RxHipError(st, L.rxhip_lowering_error().decode() or L.rxhip_status_string(st).decode())
 
 
 def plan(gb, n_replicas=1, allow_missing=False):
