@@ -44,6 +44,7 @@ extern "C" {
  *     RXHIP_BACKWARD_LANES=1    one-pass schedule: the backward sweep of the four-phase schedule instead of the table-driven one
  *     RXHIP_MEAN_RECORDS=1      one-pass schedule: a filtered-mean record per time index instead of the reverse filter from checkpoints
  *     RXHIP_MEAN_CHECKPOINT=K   one-pass schedule: the reverse filter with checkpoint stride K (1, 2, 4, … 32) whatever its bound says
+ *     RXHIP_BOUNDARY_KERNEL=1   reverse-filter schedule: the boundary scan as a launch of its own instead of inside the sweep's waves (read at every run)
  *     RXHIP_SMALL_SWEEP=0       few short chains: the five launches of the four-phase schedule instead of k_small_sweep (one launch)
  *     RXHIP_ELEM_FULL=1         per-chain models at d, dy <= 4: every recursion of the sweep in full to the end of every segment (no frozen tails, full records)
  *     RXHIP_NOISE_MOMENTS_PASS=1  unknown-noise engines: the residual second moments by a separate pass over the posteriors instead of inside the backward sweep

@@ -1767,6 +1767,36 @@ __global__ void __launch_bounds__(64) k_boundary_scan(Params p, const CstArgFor<
 // LDS in chunks of 64 segments (the recursion is latency-bound: a scalar or global load per step would
 // cost more than the arithmetic), and the per-chain element vectors are prefetched one segment ahead.
 constexpr int SCAN_TAB_CHUNK = 64;  // segments per LDS chunk
+// One step of either recursion (M1, M2 / N1, N2: the [D][D] blocks of the segment's ScanLayout row).  k_boundary_scan_tab and the boundary
+// prologue of k_backward_sh_rev both call these, so the two produce the same bits.
+template <int D>
+__device__ __forceinline__ void scan_prefix_step(const double* __restrict__ M1, const double* __restrict__ M2, const double (&b)[D], const double (&eta)[D],
+                                                 double (&m)[D]) {   // m(b_{s+1}) = b_s + M1_s m(b_s) + M2_s η_s
+    double mn[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        double acc = b[i];
+#pragma unroll
+        for (int k = 0; k < D; ++k) acc += M1[i * D + k] * m[k] + M2[i * D + k] * eta[k];
+        mn[i] = acc;
+    }
+#pragma unroll
+    for (int i = 0; i < D; ++i) m[i] = mn[i];
+}
+template <int D>
+__device__ __forceinline__ void scan_suffix_step(const double* __restrict__ N1, const double* __restrict__ N2, const double (&b)[D], const double (&eta)[D],
+                                                 double (&xi)[D]) {   // ξβ(b_s) = η_s + N1_s ξβ(b_{s+1}) − N2_s b_s
+    double xn[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        double acc = eta[i];
+#pragma unroll
+        for (int k = 0; k < D; ++k) acc += N1[i * D + k] * xi[k] - N2[i * D + k] * b[k];
+        xn[i] = acc;
+    }
+#pragma unroll
+    for (int i = 0; i < D; ++i) xi[i] = xn[i];
+}
 // one wavefront = 64 chains in one role; `tbl` (SCAN_TAB_CHUNK · ScanLayout::SIZE doubles) is private to it: the staging is ordered by
 // wave-level fences (LDS executes a wave's accesses in order)
 template <int D, int DY, bool FE, int CH = SCAN_TAB_CHUNK>
@@ -1843,16 +1873,7 @@ __device__ __forceinline__ void boundary_scan_tab_body(const Params& p, const Cs
                     eta[i] = en[i];
                 }
                 if (s + 1 < S - 1) load_el(s + 1, bn, en);
-                double mn[D];
-#pragma unroll
-                for (int i = 0; i < D; ++i) {
-                    double acc = b[i];
-#pragma unroll
-                    for (int k = 0; k < D; ++k) acc += t[SL::M1 + i * D + k] * m[k] + t[SL::M2 + i * D + k] * eta[k];
-                    mn[i] = acc;
-                }
-#pragma unroll
-                for (int i = 0; i < D; ++i) m[i] = mn[i];
+                scan_prefix_step<D>(t + SL::M1, t + SL::M2, b, eta, m);
             }
         }
     } else {
@@ -1881,16 +1902,7 @@ __device__ __forceinline__ void boundary_scan_tab_body(const Params& p, const Cs
                     eta[i] = en[i];
                 }
                 if (s - 1 >= 1) load_el(s - 1, bn, en);
-                double xn[D];
-#pragma unroll
-                for (int i = 0; i < D; ++i) {
-                    double acc = eta[i];
-#pragma unroll
-                    for (int k = 0; k < D; ++k) acc += t[SL::N1 + i * D + k] * xi[k] - t[SL::N2 + i * D + k] * b[k];
-                    xn[i] = acc;
-                }
-#pragma unroll
-                for (int i = 0; i < D; ++i) xi[i] = xn[i];
+                scan_suffix_step<D>(t + SL::N1, t + SL::N2, b, eta, xi);
 #pragma unroll
                 for (int i = 0; i < NS; ++i) Lm.v[i] = tp[SL::LB + i];
                 if (live) store_soa<D>(p.beta, s, p.n_chains, chain, xi, Lm);
@@ -3411,6 +3423,135 @@ __global__ void __launch_bounds__(64) k_backward_sh(Params p, const double* __re
 }
 
 
+// The boundary recursion inside the sweep (k_backward_sh_rev).  A wave of segment `seg` needs two vectors per chain from phase 2: the filtered
+// mean m(b_seg) at its segment start and the backward message mean ξβ(b_{seg+1}) at its end.  Both are recursions over the segment elements
+// (b, η) that k_forward0 left in `elem`, so the wave computes them itself — the prefix over segments 0 … seg−1, the suffix over S−1 … seg+1 —
+// with the step functions of k_boundary_scan_tab (the same bits), and the separate launch with its 16 waves and its one memory latency per
+// segment goes.  The element vectors do not depend on the recursion: a ring of BND_RING segments is loaded ahead, so the dependent chain is
+// FMAs only.  The two d×d maps of a step come from the ScanLayout rows through LDS, in double-buffered chunks of BND_CHUNK segments that are
+// fetched into registers a chunk ahead.  Everything here is dead before the step loop of the sweep.
+constexpr int BND_RING = 8;
+constexpr int BND_CHUNK = 8;    // a multiple of BND_RING: the ring slot of a step is a compile-time constant
+template <int D>
+struct BndStage {
+    static constexpr int ROW = 2 * D * D;            // M1, M2 (prefix) or N1, N2 (suffix) of one segment
+    static constexpr int N = BND_CHUNK * ROW;        // doubles per LDS buffer
+    static constexpr int PPL = (N + 63) / 64;        // … per lane
+};
+// `count` steps from segment `first` (upwards: prefix, downwards: suffix), all wave-uniform; v: the recursion's vector
+template <int D, bool SUF>
+__device__ __forceinline__ void boundary_chain(const Params& p, const long long chain0, const unsigned lane, const int first, const int count,
+                                               double (*__restrict__ lds)[BndStage<D>::N], double (&v)[D]) {
+    using SL = ScanLayout<D>;
+    using BS = BndStage<D>;
+    static_assert(BND_CHUNK % BND_RING == 0, "ring slots must be compile-time");
+    static_assert(SL::M2 == SL::M1 + D * D && SL::N2 == SL::N1 + D * D, "the two maps of a step are one contiguous block of a row");
+    constexpr int OFF = SUF ? SL::N1 : SL::M1;
+    if (count <= 0) return;
+    auto seg_of = [&](int q) { return SUF ? first - q : first + q; };
+    double eb[BND_RING][2 * D];
+    // Buffer loads: the descriptor (base of the segment's element, wave-uniform) and the row offset stay in scalar registers and the lane
+    // offset is ONE 32-bit register; as plain pointers every load of the ring kept a 64-bit address of its own alive.  The descriptor's
+    // range is the rest of the element from the wave's first chain on (2·D·n_chains·8 < 2³² for any batch that fits a device).
+    const unsigned rowb = (unsigned)p.n_chains * 8u;
+    const unsigned nrec = 2u * D * rowb - (unsigned)chain0 * 8u;
+    auto load_el = [&](int q, double (&e)[2 * D]) {
+        const double* base = p.elem + ((long long)seg_of(q) * 2 * D) * p.n_chains + chain0;
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(base), 0, (int)nrec, 0x00020000);
+#pragma unroll
+        for (int i = 0; i < 2 * D; ++i) e[i] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(lane * 8u), (int)(i * rowb), 0));
+    };
+    double tr[BS::PPL];
+    auto fetch = [&](int q0) {
+#pragma unroll
+        for (int k = 0; k < BS::PPL; ++k) {
+            const int idx = k * 64 + (int)lane;
+            const int q = q0 + idx / BS::ROW;
+            tr[k] = (idx < BS::N && q < count) ? p.scan[(long long)seg_of(q) * SL::SIZE + OFF + idx % BS::ROW] : 0.0;
+        }
+    };
+    auto stash = [&](int b) {
+#pragma unroll
+        for (int k = 0; k < BS::PPL; ++k) {
+            const int idx = k * 64 + (int)lane;
+            if (idx < BS::N) lds[b][idx] = tr[k];
+        }
+    };
+#pragma unroll
+    for (int j = 0; j < BND_RING; ++j)
+        if (j < count) load_el(j, eb[j]);
+    fetch(0);
+    stash(0);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    int b = 0;
+    for (int q0 = 0; q0 < count; q0 += BND_CHUNK, b ^= 1) {
+        if (q0 + BND_CHUNK < count) fetch(q0 + BND_CHUNK);
+#pragma unroll
+        for (int u = 0; u < BND_CHUNK; ++u) {
+            const int q = q0 + u;
+            if (q < count) {
+                double bb[D], eta[D];
+#pragma unroll
+                for (int i = 0; i < D; ++i) {
+                    bb[i] = eb[u % BND_RING][i];
+                    eta[i] = eb[u % BND_RING][D + i];
+                }
+                if (q + BND_RING < count) load_el(q + BND_RING, eb[u % BND_RING]);
+                __builtin_amdgcn_sched_barrier(0);   // the refill stays behind the use of its slot: hoisted, it would double the ring's registers
+                const double* t = &lds[b][u * BS::ROW];
+                if constexpr (SUF) scan_suffix_step<D>(t, t + D * D, bb, eta, v);
+                else scan_prefix_step<D>(t, t + D * D, bb, eta, v);
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (q0 + BND_CHUNK < count) stash(b ^ 1);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+// What k_boundary_scan_tab leaves for segment `seg` and the wave's 64 chains, computed and stored by the wave itself: fstart[seg] and
+// beta[seg + 1] (k_fe_seg reads the former after the sweep), and from the waves of segment 0 the t = 0 update: its record, V_f(0) and its
+// evidence term (fe: slot 0 of fe_part).  No two waves write the same word.
+template <int D, int DY>
+__device__ __forceinline__ void boundary_in_sweep(const Params& p, const CPtr c, const long long seg, const long long chain, const int lane, const bool fe,
+                                                  double (*__restrict__ lds)[BndStage<D>::N], double (&mseg)[D], double (&xb)[D]) {
+    using CL = CstLayout<D, DY>;
+    using SL = ScanLayout<D>;
+    constexpr int NS = Dim<D>::NS;
+    {
+        double mp[D], yv[DY];
+        Sym<D> Vp, V;
+#pragma unroll
+        for (int i = 0; i < D; ++i) mp[i] = c[CL::M1 + i];
+#pragma unroll
+        for (int i = 0; i < NS; ++i) Vp.v[i] = c[CL::V1 + i];
+        load_y<DY>(p.y, 0, p.n_chains, chain, yv);
+        bool ok = true;
+        double quad = 0.0, detprod = 1.0;
+        obs_update<D, DY, true>(c, mp, Vp, yv, mseg, V, ok, quad, detprod);
+        if (seg == 0) {
+            store_filt_sh<D>(p, 0, chain, mseg, V);
+            if (fe) p.fe_part[chain] = -0.5 * (quad + log(detprod));
+            if (!ok) atomicOr(p.status, ST_NOT_POSDEF);
+        }
+    }
+    boundary_chain<D, false>(p, chain - lane, (unsigned)lane, 0, (int)seg, lds, mseg);
+#pragma unroll
+    for (int i = 0; i < D; ++i) xb[i] = 0.0;
+    boundary_chain<D, true>(p, chain - lane, (unsigned)lane, p.S - 1, p.S - 1 - (int)seg, lds, xb);
+    const double* row = p.scan + seg * SL::SIZE;
+    Sym<D> Vb, Lb;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        Vb.v[i] = row[SL::VB + i];
+        Lb.v[i] = (seg == p.S - 1) ? 0.0 : row[SL::LB + i];
+    }
+    store_soa<D>(p.fstart, seg, p.n_chains, chain, mseg, Vb);
+    store_soa<D>(p.beta, seg + 1, p.n_chains, chain, xb, Lb);
+}
+
 // Phase 4 for shared-model batches on the reverse-filter schedule: k_forward0<…, true> left z only at checkpoints (every K steps
 // of a segment and at its end), and this sweep rebuilds every other filtered mean by running the filter BACKWARD in time.
 // With V_p V_f⁻¹ = I + V_p B'Q⁻¹B the Kalman update inverts exactly:
@@ -3420,9 +3561,11 @@ __global__ void __launch_bounds__(64) k_backward_sh(Params p, const double* __re
 // (table row t: E_t, V_p(t+1) in the F slot, G_t, V_s(t)).  The reverse chain restarts from every checkpoint (m_f = z + N_t m_seg)
 // and from m_seg at the segment start, so it never runs more than K − 1 steps; K is chosen at creation from the bound the
 // table kernels fold (REV_AMP_LIMIT).  Covariance stores and the table-row stream are those of k_backward_sh.
+// bnd: 0 — m_seg and ξβ come from a k_boundary_scan_tab launch before this one; 1 / 2 — the wave computes them in its prologue
+// (boundary_in_sweep; 2: with the evidence term of the t = 0 update).
 template <int D, int DY>
 __global__ void __launch_bounds__(64) k_backward_sh_rev(Params p, const double* __restrict__ gtab, const double* __restrict__ segend,
-                                                        const CstArg<CstLayout<D, DY>::SIZE> cb) {
+                                                        const CstArg<CstLayout<D, DY>::SIZE> cb, const int bnd) {
     using ST = SmoothTab<D>;
     using CL = CstLayout<D, DY>;
     constexpr int MP2 = DimM<D>::MP2;
@@ -3435,6 +3578,7 @@ __global__ void __launch_bounds__(64) k_backward_sh_rev(Params p, const double* 
     constexpr int NCP = 32 * D * D;          // … of the 64 covariances
     __shared__ double2 tbuf[2][NPC];
     __shared__ double mtile[64 * D];
+    __shared__ double bndbuf[2][BndStage<D>::N];
     const int lane = threadIdx.x;
     const long long g0 = (long long)blockIdx.x * 64;  // n_chains % 64 == 0: the wave holds 64 chains of ONE segment
     const long long seg = g0 / p.n_chains;
@@ -3462,13 +3606,16 @@ __global__ void __launch_bounds__(64) k_backward_sh_rev(Params p, const double* 
 
     double mf[D], ms[D];
     {
-        const double* q = p.fstart + (seg * Dim<D>::NP) * p.n_chains + chain;
-        const double* bq = p.beta + ((seg + 1) * Dim<D>::NP) * p.n_chains + chain;
         double xb[D];
+        if (bnd) boundary_in_sweep<D, DY>(p, c, seg, chain, lane, bnd == 2, bndbuf, mseg, xb);
+        else {
+            const double* q = p.fstart + (seg * Dim<D>::NP) * p.n_chains + chain;
+            const double* bq = p.beta + ((seg + 1) * Dim<D>::NP) * p.n_chains + chain;
 #pragma unroll
-        for (int i = 0; i < D; ++i) {
-            mseg[i] = q[i * p.n_chains];
-            xb[i] = bq[i * p.n_chains];
+            for (int i = 0; i < D; ++i) {
+                mseg[i] = q[i * p.n_chains];
+                xb[i] = bq[i * p.n_chains];
+            }
         }
         if (len > 0) {
             double2 r[MP2];

@@ -2897,7 +2897,13 @@ static rxhip_status run_impl(rxhip_engine* e, int32_t iterations, int32_t want_f
             e->vt->seg_elements(p, e->stream);
             if ((st = prof_end(e))) return st;
         }
-        if (!e->dense && !small_now) {
+        // Reverse-filter sweep of a shared-model batch: every wave of k_backward_sh_rev runs the boundary recursion for its own segment and chains
+        // (boundary_in_sweep), so the scan is no launch of its own and k_fe_seg, which reads the segment-start means, follows the sweep.
+        // RXHIP_BOUNDARY_KERNEL=1 keeps the separate launch: the comparison arm of tests/test_boundary_in_sweep_gpu.py.
+        const char* bnd_env = hook_env("RXHIP_BOUNDARY_KERNEL");
+        const bool bnd_in_sweep = fused && e->uniform && e->d_scan && e->d_gtab && e->ck_log2 > 0 && e->S > 0 && !e->noise && !e->masked &&
+                                  !(bnd_env && std::atoi(bnd_env) != 0);
+        if (!e->dense && !small_now && !bnd_in_sweep) {
             if ((st = prof_begin(e, RXHIP_K_BOUNDARY_SCAN))) return st;
             if (e->uniform && (e->d_scan || e->S == 0)) e->vt->boundary_scan_tab(p, e->h_cst0.data(), fe, e->stream);
             else e->vt->boundary_scan(p, e->h_cst0.data(), e->uniform, fe, e->stream);
@@ -2908,14 +2914,15 @@ static rxhip_status run_impl(rxhip_engine* e, int32_t iterations, int32_t want_f
                 if ((st = prof_begin(e, RXHIP_K_FORWARD))) return st;
                 e->vt->forward(p, e->h_cst0.data(), e->uniform, fe, e->stream);
                 if ((st = prof_end(e))) return st;
-            } else if (fe)
+            } else if (fe && !bnd_in_sweep)
                 e->vt->fe_seg(p, e->stream);
             if (!filter) {
                 if ((st = prof_begin(e, RXHIP_K_BACKWARD))) return st;
-                if (fused && e->d_gtab) e->vt->backward_sh(p, e->h_cst0.data(), e->d_gtab, e->d_segend, e->ck_log2 > 0, e->stream);
+                if (fused && e->d_gtab) e->vt->backward_sh(p, e->h_cst0.data(), e->d_gtab, e->d_segend, e->ck_log2 > 0, bnd_in_sweep ? (fe ? 2 : 1) : 0, e->stream);
                 else e->vt->backward(p, e->h_cst0.data(), e->uniform, e->stream);
                 if ((st = prof_end(e))) return st;
             }
+            if (fe && bnd_in_sweep) e->vt->fe_seg(p, e->stream);
         }
         if (e->noise) {   // q(W) of every chain from this sweep's q(x); its free-energy slot; the constants of the next sweep
             np.iteration = it;

@@ -101,8 +101,9 @@ struct Launch {
         hipLaunchKernelGGL((k_smooth_tab_chain<D>), dim3(nblk(q.S, 64)), dim3(64), 0, s, q);
         hipLaunchKernelGGL((k_smooth_tab_apply<D>), dim3(nblk(nblocks, 64)), dim3(64), 0, s, q);
     }
-    static void backward_sh(const Params& p, const double* hc, const double* gtab, const double* segend, bool rev, hipStream_t s) {
-        if (rev) hipLaunchKernelGGL((k_backward_sh_rev<D, DY>), dim3((unsigned)(p.n_chains / 64 * p.S)), dim3(64), 0, s, p, gtab, segend, carg(hc));
+    // bnd (reverse-filter sweep only): 0 — a boundary-scan launch came before; 1 / 2 — the sweep's waves run the boundary recursion themselves (2: + free energy)
+    static void backward_sh(const Params& p, const double* hc, const double* gtab, const double* segend, bool rev, int bnd, hipStream_t s) {
+        if (rev) hipLaunchKernelGGL((k_backward_sh_rev<D, DY>), dim3((unsigned)(p.n_chains / 64 * p.S)), dim3(64), 0, s, p, gtab, segend, carg(hc), bnd);
         else hipLaunchKernelGGL((k_backward_sh<D>), dim3((unsigned)(p.n_chains / 64 * p.S)), dim3(64), 0, s, p, gtab, segend);
     }
     static void forecast(const PredictParams& p, hipStream_t s) {
