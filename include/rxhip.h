@@ -39,12 +39,16 @@ extern "C" {
  *   RXHIP_TEST_HOOKS=1   enables the schedule switches below.  Without it NONE of them is read: a host's environment cannot change the
  *                        schedule behind a result.  All of them select between schedules that compute the same posteriors and free energy
  *                        (the parity tests run both sides); they exist so that one schedule can check another and for A/B timings.
+ *                        The switches of the state-space engines (all below but RXHIP_ENGINE_POOL, RXHIP_FE_RESID_VALU and RXHIP_TREE_*) are read
+ *                        ONCE, by rxhip_lgssm_create / rxhip_lgssm_noise_create (csrc/lgssm_plan.hpp ScheduleHooks::read), and hold for the
+ *                        engine's life: a later change of the environment reaches engines created afterwards only.  They are part of the
+ *                        engine pool's key.
  *     RXHIP_ONE_PASS=0|1        d, dy <= 4 shared-model batches: force the four-phase / the one-pass table-driven schedule (default: by size)
  *     RXHIP_ONE_SEGMENT=1       d, dy <= 4 masked / per-step engines: one segment per chain
  *     RXHIP_BACKWARD_LANES=1    one-pass schedule: the backward sweep of the four-phase schedule instead of the table-driven one
  *     RXHIP_MEAN_RECORDS=1      one-pass schedule: a filtered-mean record per time index instead of the reverse filter from checkpoints
  *     RXHIP_MEAN_CHECKPOINT=K   one-pass schedule: the reverse filter with checkpoint stride K (1, 2, 4, … 32) whatever its bound says
- *     RXHIP_BOUNDARY_KERNEL=1   reverse-filter schedule: the boundary scan as a launch of its own instead of inside the sweep's waves (read at every run)
+ *     RXHIP_BOUNDARY_KERNEL=1   reverse-filter schedule: the boundary scan as a launch of its own instead of inside the sweep's waves
  *     RXHIP_SMALL_SWEEP=0       few short chains: the five launches of the four-phase schedule instead of k_small_sweep (one launch)
  *     RXHIP_ELEM_FULL=1         per-chain models at d, dy <= 4: every recursion of the sweep in full to the end of every segment (no frozen tails, full records)
  *     RXHIP_NOISE_MOMENTS_PASS=1  unknown-noise engines: the residual second moments by a separate pass over the posteriors instead of inside the backward sweep

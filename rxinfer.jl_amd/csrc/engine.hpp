@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/rxhip.h"
+#include "lgssm_plan.hpp"
 #include "tree_engine.hpp"
 
 namespace rxhip {
@@ -55,6 +56,7 @@ struct rxhip_engine : rxhip_engine_life {
     size_t arena_bytes = 0;
     bool in_arena(const void* q) const { return arena && (const char*)q >= arena && (const char*)q < arena + arena_bytes; }
     // description
+    rxhip::plan::ScheduleHooks hooks;   // state-space engines: the test hooks as rxhip_lgssm_create found them — every schedule decision of the engine's life reads these
     int d = 0, dy = 0;
     int dpad = 0;  // dense path: d rounded up to a multiple of 16 (kernel dimension); == d otherwise
     long long T = 0, n_chains = 0;

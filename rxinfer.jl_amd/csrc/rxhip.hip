@@ -28,6 +28,7 @@
 #include "model_envelope.hpp"
 
 using namespace rxhip;
+using plan::ScheduleHooks;
 
 // The kernels templated on a dimension live in translation units of their own (launch_tables.hpp: tu_lgssm.hip per state dimension,
 // tu_dense.hip per MFMA tile count); this file reaches them through LgssmVtbl / DenseVtbl.
@@ -810,10 +811,6 @@ static rxhip_status build_model_tables(rxhip_engine* e, int mdl, const rxhip_lgs
 // dense path (d multiple of 16, ≤ 64): host-side per-model tables and launches
 // any state dimension up to 64: the MFMA path runs on d rounded up to a multiple of 16, the extra dimensions are
 // decoupled padding (A = 0, P = V0 = I, m0 = 0, B = 0: posterior N(0, I), no contribution to the free energy)
-static bool small_sweep_off() {   // RXHIP_SMALL_SWEEP=0 (test hook): the five launches of the four-phase schedule instead of k_small_sweep
-    const char* v = hook_env("RXHIP_SMALL_SWEEP");
-    return v && std::atoi(v) == 0;
-}
 static bool dense_supported(int d, int dy) { return d >= 1 && d <= 64 && dy >= 1 && dy <= 64; }
 static int dense_pad(int d) { return (d + 15) / 16 * 16; }
 
@@ -853,7 +850,7 @@ static void dense_schedule_ints(rxhip_engine* e) {
 
 static bool dense_tab_on_device(const rxhip_engine* e) {
     // d ≥ 32: below, the host recursions take well under a millisecond (and a 16×16 model padded into these kernels would not be faster)
-    return e->nt >= 2 && e->dyk <= e->dpad && !hook_env("RXHIP_HOST_TABLES");
+    return e->nt >= 2 && e->dyk <= e->dpad && !e->hooks.host_tables;
 }
 
 // ---- `missing` observations on the MFMA path, parallel in time (dense_mseg_kernels.hpp) -------------------------------------
@@ -866,7 +863,7 @@ static rxhip_status mseg_setup(rxhip_engine* e, const rxhip_lgssm_desc* ds) {
     const bool stepm = ds->step_model != nullptr && ds->n_models > 1;
     const bool chainm = !stepm && ds->chain_model != nullptr && ds->n_models > 1;   // one model per chain (with `missing` values: else the fully observed MFMA path has them)
     if (!(ds->allow_missing || stepm) || (ds->chain_model && !chainm) || (!stepm && !chainm && ds->n_models != 1) || e->T < 2 ||
-        hook_env("RXHIP_GSEQ") || ((stepm || chainm) && hook_env("RXHIP_STEPM_GSEQ")))
+        e->hooks.gseq || ((stepm || chainm) && e->hooks.stepm_gseq))
         return RXHIP_OK;
     // the masked kernels work on d×d tiles that also hold the observation-space matrices: pad to the larger of d and dy
     e->m_dpad = 16 * ((std::max(e->d, e->dy) + 15) / 16);
@@ -883,8 +880,7 @@ static rxhip_status mseg_setup(rxhip_engine* e, const rxhip_lgssm_desc* ds) {
     // the machine on their own: ONE segment per chain — the sweep kernels run the whole chain, no element pass and no boundary recursion.
     long long S = 1;
     // RXHIP_MSEG_SCAN = sequential | log: the boundary recursion as one / two sequential levels, or in ⌈log₂ S⌉ rounds (default: the cheaper one)
-    const char* scan_env = hook_env("RXHIP_MSEG_SCAN");
-    const int scan_mode = hook_env("RXHIP_MSEG_ONE_LEVEL") ? 1 : scan_env && !std::strcmp(scan_env, "sequential") ? 1 : scan_env && !std::strcmp(scan_env, "log") ? 2 : 0;
+    const int scan_mode = e->hooks.mseg_one_level ? 1 : e->hooks.mseg_scan;
     auto hs_fits = [&](long long s) { return (double)C * (double)s * (MSEG_WS + 9 + 12) * MM * 8.0 <= 6e9; };   // scratch + elements + four generations
     auto hs_rounds_of = [](long long s) { int r = 0; while ((1LL << r) <= s - 2) ++r; return r; };
     const double f = (double)(e->m_nt - 1) / 3.0, c_s = 8.0 + f * 13.0, c_g = 15.0 + f * 35.0;
@@ -894,8 +890,7 @@ static rxhip_status mseg_setup(rxhip_engine* e, const rxhip_lgssm_desc* ds) {
     const double conc = e->m_nt == 1 ? 2048.0 : e->m_nt == 2 ? 1024.0 : 512.0;
     const double conc_c = conc, c_c = 8.0 + f * 22.0;    // a round of fused compositions: 30 µs at d = 64 with a CU to itself, 44 µs when workgroups share one
     // log-depth recursion over ⌈s / g⌉ entries of g segments: km_fold (g − 1 compositions in a row), the rounds, km_apply, km_inner (g − 1 steps)
-    const char* grp_env = hook_env("RXHIP_MSEG_GROUP");
-    const int grp_forced = grp_env ? std::atoi(grp_env) : 0;
+    const int grp_forced = e->hooks.mseg_group;
     auto log_cost = [&](long long s, int g) {
         const double n = std::ceil((double)s / (double)g), wv = std::ceil(2.0 * (double)C * n / conc_c), wf = std::ceil((double)C * n / conc_c);
         const double sh2 = 2.0 * (double)C * n > 0.5 * conc_c ? 1.45 : 1.0, sh1 = (double)C * n > 0.5 * conc_c ? 1.45 : 1.0;   // workgroups that share a CU
@@ -910,8 +905,7 @@ static rxhip_status mseg_setup(rxhip_engine* e, const rxhip_lgssm_desc* ds) {
     };
     {
         const double c_e = 10.0 + f * 22.0, c_f = 5.7 + f * 21.0;   // fused element step (32 µs at d = 64 with every CU busy), forward + backward sweep step
-        const char* w8_env = hook_env("RXHIP_WAVE8");
-        const bool w8_ok = e->m_nt == 1 && e->d <= 8 && !stepm && !chainm && !(w8_env && std::atoi(w8_env) == 0);
+        const bool w8_ok = e->m_nt == 1 && e->d <= 8 && !stepm && !chainm && !e->hooks.wave8_off;
         auto cost = [&](long long s_asked) {
             // (the segments that s_asked turns into once the segment length is an integer: ⌈(T − 1) / L⌉ of length L = ⌈(T − 1) / s_asked⌉)
             const long long Lq = ((long long)T - 1 + s_asked - 1) / s_asked, s = ((long long)T - 1 + Lq - 1) / Lq;
@@ -950,7 +944,7 @@ static rxhip_status mseg_setup(rxhip_engine* e, const rxhip_lgssm_desc* ds) {
     e->m_hs = 0; e->m_hs_rounds = 0;
     {   // the boundary recursion of this S: sequential (one level, or two from 16 segments on) or log-depth, by the same cost figures
         double seq = (double)S * c_s * std::ceil(2.0 * (double)C / conc);
-        if (S >= 16 && !hook_env("RXHIP_MSEG_ONE_LEVEL")) {
+        if (S >= 16 && !e->hooks.mseg_one_level) {
             const double sg = std::ceil(std::sqrt((double)S)), ng = std::ceil((double)S / sg);
             seq = (sg * c_g + (ng + 2.0 * sg) * c_s) * std::ceil((double)C * ng / conc);
         }
@@ -964,7 +958,7 @@ static rxhip_status mseg_setup(rxhip_engine* e, const rxhip_lgssm_desc* ds) {
             e->m_hs_rounds = hs_rounds_of(e->m_hs_n);
         }
     }
-    if (!e->m_hs && S >= 16 && !hook_env("RXHIP_MSEG_ONE_LEVEL")) {
+    if (!e->m_hs && S >= 16 && !e->hooks.mseg_one_level) {
         int sg = 1;
         while ((long long)sg * sg < S) ++sg;
         e->m_sg = sg;
@@ -990,7 +984,7 @@ static rxhip_status mseg_setup(rxhip_engine* e, const rxhip_lgssm_desc* ds) {
     {
         size_t free_b = 0, total_b = 0;
         bool fits = hipMemGetInfo(&free_b, &total_b) == hipSuccess && (double)off[21] <= 0.9 * (double)free_b;
-        if (const char* cap = hook_env("RXHIP_MSEG_MAX_BYTES")) fits = fits && off[21] <= std::strtoull(cap, nullptr, 10);
+        fits = fits && off[21] <= e->hooks.mseg_max_bytes;
         if (!fits || hipMalloc(&e->mseg_block, off[21]) != hipSuccess) {
             (void)hipGetLastError();
             e->mseg_block = nullptr;
@@ -1078,12 +1072,9 @@ static rxhip_status mseg_run(rxhip_engine* e, bool fe, bool filter) {
     if (e->m_chainm) { dp.models = e->m_modtab; dp.chain_model = e->d_chain_model; }   // the sweep kernels' own per-chain lookup (dense_model)
     // chains that run as ONE segment (they fill the chip on their own) at d ≤ 8: the sweep inside one wavefront per chain
     // (dense8_kernels.hpp; smoothing runs of one model; RXHIP_WAVE8=0: the MFMA kernels, which stay the checker)
-    {
-        const char* w8 = hook_env("RXHIP_WAVE8");
-        dp.wave8 = (e->mS == 1 && e->m_nt == 1 && e->d <= 8 && !e->m_stepm && !e->m_chainm && !filter && !(w8 && std::atoi(w8) == 0)) ? 1 : 0;
-        e->m_wave8_last = dp.wave8 != 0;
-        if (dp.wave8) mp.rec = K8_REC;   // km_gy writes B′Q⁻¹y_t into the records the in-wave kernels read
-    }
+    dp.wave8 = (e->mS == 1 && e->m_nt == 1 && e->d <= 8 && !e->m_stepm && !e->m_chainm && !filter && !e->hooks.wave8_off) ? 1 : 0;
+    e->m_wave8_last = dp.wave8 != 0;
+    if (dp.wave8) mp.rec = K8_REC;   // km_gy writes B′Q⁻¹y_t into the records the in-wave kernels read
     rxhip_status st;
     if ((st = prof_begin(e, RXHIP_K_SEG_AGGREGATE))) return st;
     dense_vt(e->m_nt)->mseg_sweep(mp, dp, fe, filter, e->stream);
@@ -1513,7 +1504,7 @@ static bool engine_pool_on() {
     const char* v = hook_env("RXHIP_ENGINE_POOL");
     return !(v && std::atoi(v) == 0);
 }
-static bool engine_pool_key(const rxhip_lgssm_desc* ds, std::string& key) {
+static bool engine_pool_key(const rxhip_lgssm_desc* ds, const ScheduleHooks& hooks, std::string& key) {
     key.clear();
     if (!engine_pool_on()) return false;
     if (ds->d > 4 || ds->dy > 4 || ds->n_models != 1 || ds->chain_model || ds->step_model || ds->state_offset || ds->obs_offset || ds->allow_missing ||
@@ -1526,12 +1517,7 @@ static bool engine_pool_key(const rxhip_lgssm_desc* ds, std::string& key) {
     put(hdr, sizeof hdr);
     const size_t d = (size_t)ds->d, dy = (size_t)ds->dy;
     put(ds->A, 8 * d * d); put(ds->B, 8 * dy * d); put(ds->P, 8 * d * d); put(ds->Q, 8 * dy * dy); put(ds->m0, 8 * d); put(ds->V0, 8 * d * d);
-    for (const char* name : {"RXHIP_ONE_PASS", "RXHIP_ONE_SEGMENT", "RXHIP_SMALL_SWEEP", "RXHIP_BACKWARD_LANES", "RXHIP_HOST_TABLES", "RXHIP_MEAN_RECORDS",
-                             "RXHIP_MEAN_CHECKPOINT"}) {   // schedule hooks read at creation
-        const char* v = hook_env(name);
-        key.push_back('|');
-        if (v) key.append(v);
-    }
+    hooks.append_key(key);   // every schedule hook: an engine of another schedule is another engine
     return true;
 }
 static void free_all(rxhip_engine* e);
@@ -1719,9 +1705,9 @@ rxhip_status rxhip_set_conditioning_guard(int32_t enabled) {
     conditioning_guard().store(enabled ? 1 : 0);
     return RXHIP_OK;
 }
-rxhip_status rxhip_lgssm_create(const rxhip_lgssm_desc* ds, rxhip_engine** out) {
-    if (!out) return RXHIP_ERR_BADARG;
-    *out = nullptr;
+// ---- rxhip_lgssm_create in pieces: the descriptor, the conditioning envelope, the engine pool, the engine's description and schedule
+// (lgssm_plan.hpp), then one helper per kernel family (create_gseq, create_dense, create_lanes)
+static rxhip_status validate_desc(const rxhip_lgssm_desc* ds, const LgssmVtbl** vt_out, bool* dense_out) {
     if (!ds || ds->d <= 0 || ds->dy <= 0 || ds->T <= 0 || ds->n_chains <= 0 || ds->n_models <= 0 || !ds->A ||
         !ds->B || !ds->P || !ds->Q || !ds->m0 || !ds->V0)
         return RXHIP_ERR_BADARG;
@@ -1737,76 +1723,73 @@ rxhip_status rxhip_lgssm_create(const rxhip_lgssm_desc* ds, rxhip_engine** out) 
         for (long long t = 0; t < ds->T + ds->horizon; ++t)
             if (ds->step_model[t] < 0 || ds->step_model[t] >= ds->n_models) return RXHIP_ERR_BADARG;
     }
-    if (dense && conditioning_guard().load()) {   // the information-form schedules of d > 4 are validated inside an envelope of model conditioning (model_envelope.hpp)
-        const size_t dd = (size_t)ds->d * ds->d, bd = (size_t)ds->dy * ds->d, qq = (size_t)ds->dy * ds->dy;
-        const double limit = ds->d <= 16 ? envelope::ENVELOPE_ONE_TILE : envelope::ENVELOPE_TILES;
-        for (int m = 0; m < ds->n_models; ++m) {
-            // (per-step models: every model against the prior of the chain; a model that is never the first sees V0 only through this bound)
-            const double k = envelope::kappa(ds->d, ds->dy, ds->A + m * dd, ds->B + m * bd, ds->P + m * dd, ds->Q + m * qq, ds->V0 + (ds->step_model ? (size_t)ds->step_model[0] * dd : m * dd),
-                                             ds->prior_through_transition != 0);
-            if (std::isfinite(k) && k > limit) {
-                char buf[400];
-                std::snprintf(buf, sizeof buf,
-                              "model %d: conditioning kappa = %.3g of its filtered precisions is beyond %.0e, the envelope the information-form chain schedules of d = %d are "
-                              "validated for (csrc/model_envelope.hpp); the node-array executor holds such models (rxhip_create hands the graph to it; rxhip_set_conditioning_guard(0) "
-                              "switches this check off)",
-                              m, k, limit, ds->d);
-                rxhip_lower::last_error() = buf;
-                return RXHIP_ERR_UNSUPPORTED;
-            }
+    *vt_out = vt;
+    *dense_out = dense;
+    return RXHIP_OK;
+}
+// the information-form schedules of d > 4 are validated inside an envelope of model conditioning (model_envelope.hpp)
+static rxhip_status check_envelope(const rxhip_lgssm_desc* ds) {
+    const size_t dd = (size_t)ds->d * ds->d, bd = (size_t)ds->dy * ds->d, qq = (size_t)ds->dy * ds->dy;
+    const double limit = ds->d <= 16 ? envelope::ENVELOPE_ONE_TILE : envelope::ENVELOPE_TILES;
+    for (int m = 0; m < ds->n_models; ++m) {
+        // (per-step models: every model against the prior of the chain; a model that is never the first sees V0 only through this bound)
+        const double k = envelope::kappa(ds->d, ds->dy, ds->A + m * dd, ds->B + m * bd, ds->P + m * dd, ds->Q + m * qq, ds->V0 + (ds->step_model ? (size_t)ds->step_model[0] * dd : m * dd),
+                                         ds->prior_through_transition != 0);
+        if (std::isfinite(k) && k > limit) {
+            char buf[400];
+            std::snprintf(buf, sizeof buf,
+                          "model %d: conditioning kappa = %.3g of its filtered precisions is beyond %.0e, the envelope the information-form chain schedules of d = %d are "
+                          "validated for (csrc/model_envelope.hpp); the node-array executor holds such models (rxhip_create hands the graph to it; rxhip_set_conditioning_guard(0) "
+                          "switches this check off)",
+                          m, k, limit, ds->d);
+            rxhip_lower::last_error() = buf;
+            return RXHIP_ERR_UNSUPPORTED;
         }
     }
-    std::string pkey;
-    if (engine_pool_key(ds, pkey)) {   // a parked engine of exactly this descriptor: as good as new (engine pool above)
-        rxhip_engine* hit = nullptr;
-        {
-            EnginePool& ep = engine_pool();
-            std::lock_guard<std::mutex> g(ep.m);
-            for (size_t i = ep.idle.size(); i-- > 0;)
-                if (ep.idle[i]->pool_key == pkey) { hit = ep.idle[i]; ep.idle.erase(ep.idle.begin() + (long)i); break; }
-        }
-        if (hit) {
-            if (!hit->own_y) hit->d_y = nullptr;   // (a caller's device pointer of the previous life)
-            static_cast<rxhip_engine_life&>(*hit) = rxhip_engine_life{};   // every per-owner field at once (engine.hpp)
-            *out = hit;
-            return RXHIP_OK;
-        }
+    return RXHIP_OK;
+}
+// a parked engine of exactly this descriptor and these hooks: as good as new (engine pool above)
+static rxhip_engine* engine_pool_take(const std::string& pkey) {
+    rxhip_engine* hit = nullptr;
+    {
+        EnginePool& ep = engine_pool();
+        std::lock_guard<std::mutex> g(ep.m);
+        for (size_t i = ep.idle.size(); i-- > 0;)
+            if (ep.idle[i]->pool_key == pkey) { hit = ep.idle[i]; ep.idle.erase(ep.idle.begin() + (long)i); break; }
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return RXHIP_ERR_NO_DEVICE;
-
-    rxhip_engine* e = new rxhip_engine();
-    *out = e;  // returned even on failure so that rxhip_last_error is readable; caller destroys
-    e->pool_key = pkey;
+    if (hit) {
+        if (!hit->own_y) hit->d_y = nullptr;   // (a caller's device pointer of the previous life)
+        static_cast<rxhip_engine_life&>(*hit) = rxhip_engine_life{};   // every per-owner field at once (engine.hpp)
+    }
+    return hit;
+}
+// the engine's description: schedule fields from the planner, host copies of what later entry points need
+static rxhip_status create_describe(rxhip_engine* e, const rxhip_lgssm_desc* ds, const LgssmVtbl* vt, bool dense) {
+    plan::Shape sh;
+    sh.d = ds->d; sh.dy = ds->dy; sh.T = ds->T; sh.n_chains = ds->n_chains; sh.n_models = ds->n_models; sh.segments = ds->segments;
+    sh.dense = dense; sh.allow_missing = ds->allow_missing != 0; sh.step_model = ds->step_model != nullptr; sh.chain_model = ds->chain_model != nullptr;
+    const plan::Flags fl = plan::static_flags(sh, e->hooks);
+    const plan::Segmentation sg = plan::segmentation(sh, fl, e->hooks);
     e->vt = vt;
     e->dense = dense;
-    e->dpad = dense ? dense_pad(ds->d) : ds->d;
-    e->nt = e->dpad / 16;
+    e->dpad = fl.dpad;
+    e->nt = fl.nt;
     e->d = ds->d;
     e->dy = ds->dy;
     e->T = ds->T;
     e->n_chains = ds->n_chains;
     e->n_models = ds->n_models;
     e->ptt = ds->prior_through_transition ? 1 : 0;
-    e->uniform = (ds->n_models == 1);
-    if (ds->allow_missing) {
-        // `missing` observations change the covariances per chain and per time index: no table of the time-parallel schedule
-        // survives.  The chain runs as ONE segment (sequential in time, parallel over chains) on the per-chain-record kernels.
-        if (dense) e->gseq = true;  // any d, dy ≤ 64: one workgroup per chain, sequential in time (gseq_kernels.hpp)
-        e->masked = true;
-        e->sequential = true;
-        e->uniform = false;
-    }
-    if (ds->step_model) {
-        // time-varying A_t, P_t, B_t, Q_t: the tables of the time-parallel schedule assume one model along the chain
-        if (dense) e->gseq = true;
-        e->sequential = true;
-        e->uniform = false;
-    }
-    // Per-chain models take the same table-free route: per-position gain tables PER MODEL were 256 B per lane and step of
-    // streamed traffic (26 GB per sweep at C2 with n_models = n_chains — more than the observations and posteriors together);
-    // computing the element in the lane costs less than reading it (measured: k_seg_aggregate 5.97 ms -> k_seg_elements)
-    if (!dense && !e->uniform) e->sequential = true;
+    e->uniform = fl.uniform;
+    e->gseq = fl.gseq;
+    e->masked = fl.masked;
+    e->sequential = fl.sequential;
+    e->pack = fl.pack;
+    e->wg_chains = fl.wg_chains;
+    e->dyk = fl.dyk;
+    e->S = sg.S;
+    e->L = sg.L;
+    e->Llast = sg.Llast;
     if (ds->horizon < 0) return fail(e, RXHIP_ERR_BADARG, "horizon must be non-negative");
     e->H = ds->horizon;
     if (ds->state_offset || ds->obs_offset) {
@@ -1840,337 +1823,313 @@ rxhip_status rxhip_lgssm_create(const rxhip_lgssm_desc* ds, rxhip_engine** out) 
             std::memcpy(&e->h_bq[(size_t)m * (nb + nq) + nb], ds->Q + (size_t)m * nq, sizeof(double) * nq);
         }
     }
-    // d ≤ 8: two chains per 16×16 tile (block-diagonal pair) instead of one chain padded to 16 — twice the chains per
-    // workgroup for the same MFMA work.  Needs an even batch (the pair is formed from neighbours in memory).
-    e->pack = (dense && !e->gseq && ds->d <= 8 && ds->dy <= 32 && ds->n_chains % 2 == 0 && ds->n_models == 1 && !hook_env("RXHIP_NO_PACK")) ? 2 : 1;
-    e->wg_chains = ds->n_chains / e->pack;
-    e->dyk = ds->dy * e->pack;
-    if (ds->device >= 0) {
-        if (ds->device >= ndev) return fail(e, RXHIP_ERR_BADARG, "device %d out of range (%d visible)", ds->device, ndev);
-        e->device = ds->device;
-    } else
-        HIPCHK(e, hipGetDevice(&e->device));
-    SET_DEVICE(e);
-    if (ds->stream) {
-        e->stream = (hipStream_t)ds->stream;
-    } else {
-        HIPCHK(e, stream_acquire(e->device, &e->stream));
-        e->own_stream = true;
+    return RXHIP_OK;
+}
+// dense engines: [n_models][m0 | V0] at user level (sequential schedule, rxhip_filter_step)
+static std::vector<double> dense_prior(const rxhip_engine* e, const rxhip_lgssm_desc* ds) {
+    std::vector<double> prior;
+    const size_t Du = (size_t)e->d, np = Du + Du * Du;
+    prior.resize((size_t)e->n_models * np);
+    for (int m = 0; m < e->n_models; ++m) {
+        std::memcpy(&prior[(size_t)m * np], ds->m0 + (size_t)m * Du, sizeof(double) * Du);
+        std::memcpy(&prior[(size_t)m * np + Du], ds->V0 + (size_t)m * Du * Du, sizeof(double) * Du * Du);
     }
-
-    // time segmentation: two (chain, segment) lanes per SIMD lane slot — 256 CUs × 4 SIMDs × 2 waves × 64 lanes.
-    // Once the forward message is stored compactly the backward kernel is issue-bound at one wave per SIMD
-    // (measured at C2: 4.7 ms with 64 segments, 3.9–4.0 ms with 128…512); the boundary scan is cheap.
-    // Dense (MFMA) path: one workgroup of NT wavefronts per (chain, segment).  At d = 49…64 the forward kernel keeps two
-    // matrices in LDS and 254 registers, so TWO workgroups share a CU (one wavefront of each per SIMD): measured at C3,
-    // forward 0.72 -> 0.58 ms with 500 instead of 250 segments (750: 0.62).  The smaller tiles leave room for more, and the
-    // kernels are latency-bound, so
-    // more resident workgroups pay until the per-segment prologue dominates (measured, scripts/time_mid_dims.py:
-    // d = 16, 512 chains, T = 1000: 4.27 ms with 2 workgroups per CU, 2.22 ms with 48; d = 32, 128 chains: 4.86 -> 3.02 ms).
-    // d ≥ 48: two workgroups fit a CU; a time-invariant chain gets four workgroups' worth of segments, because most of them leave the sweep kernels
-    // after two or three steps (their matrices repeat: kd_forward_info FROZEN) and the sweep is as long as the segments that do not — measured at C3
-    // (scripts/time_c3_clean.py, C3_SEGMENTS): 0.578 ms with 715 segments, 0.553 with 909, 0.547 – 0.557 with 1000, 0.559 with 1111, 0.605 with 1429
-    // (with three repeats required before a segment leaves: 0.670 with 500, 0.612 with 715, 0.626 with 1000)
-    const bool dense_frozen = dense && e->nt >= 3 && e->uniform && !e->masked && ds->step_model == nullptr && !e->gseq;
-    const int dense_wg_per_cu = !dense ? 0 : e->nt == 1 ? 48 : e->nt == 2 ? 8 : dense_frozen ? 4 : 2;
-    const long long steps = e->T - 1;  // transitions
-    bool small_short = false;
-    if (steps <= 0) {
-        e->S = 0;
-        e->L = 1;
-        e->Llast = 1;
-    } else {
-        long long S_target = (e->sequential && hook_env("RXHIP_ONE_SEGMENT")) ? 1 : ds->segments > 0 ? ds->segments
-                             : dense ? (256 * dense_wg_per_cu + e->wg_chains - 1) / e->wg_chains
-                                     : (131072 + e->n_chains - 1) / e->n_chains;
-        if (ds->segments <= 0 && !dense) {
-            // few chains: the lanes do not fill the machine and the sweep is a latency chain of L steps through three
-            // kernels (≈0.86 µs per step, fitted at d = 2) plus S sequential boundary steps (≈0.26 µs each):
-            // S* = sqrt(steps · 0.86 / 0.26).  (measured, one chain, d = 2, T = 50 000: 1.18 ms with L = 16, S = 3125.)
-            const long long s_lat = (long long)std::ceil(std::sqrt(3.3 * (double)steps));
-            if (S_target > s_lat) S_target = s_lat;
-            // a few chains whose lanes fit ONE workgroup run the whole sweep in one launch (k_small_sweep: chains · S ≤ 256, ≤ 64 chains):
-            // take fewer, slightly longer segments for that where it costs at most a few steps of latency
-            const long long cap = e->n_chains <= 16 ? 256 / e->n_chains : 0;
-            if (cap >= 1 && S_target > cap && (steps + cap - 1) / cap <= 32) S_target = cap;
-            // … and with its boundary recursion in log depth (boundary_scan_par_body) the segments of that schedule can be SHORT: as many as
-            // fit the workgroup, down to 3 steps each (measured, scripts/time_small_segments.py)
-            if (cap >= 1 && (steps + cap - 1) / cap <= 32 && e->uniform && !e->masked && ds->step_model == nullptr && !small_sweep_off()) {
-                S_target = std::min<long long>(cap, std::max<long long>(1, steps / 3));
-                small_short = true;
+    return prior;
+}
+// d > 4 with `missing` observations or per-step constants — no tables: the user-level constants, the priors, the outputs
+static rxhip_status create_gseq(rxhip_engine* e, const rxhip_lgssm_desc* ds) {
+    const std::vector<double> prior = dense_prior(e, ds);
+    e->S = 0; e->L = 1; e->Llast = 1;
+    once_per_device(0, e->device, [] {
+        (void)hipFuncSetAttribute((const void*)k_gseq_forward, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
+        (void)hipFuncSetAttribute((const void*)k_gseq_backward, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
+    });
+    const size_t CU = (size_t)e->n_chains, Du = (size_t)e->d;
+    ArenaPlan ap;
+    ap.upload(&e->d_user, e->h_user.data(), sizeof(double) * e->h_user.size());
+    ap.upload(&e->d_prior, prior.data(), sizeof(double) * prior.size());
+    if (ds->chain_model) ap.upload(&e->d_chain_model, ds->chain_model, sizeof(int) * CU);
+    if (ds->step_model) ap.upload(&e->d_step_model, ds->step_model, sizeof(int) * (size_t)(e->T + e->H));
+    if (!e->h_mu.empty()) {
+        ap.upload(&e->d_mu, e->h_mu.data(), sizeof(double) * e->h_mu.size());
+        ap.upload(&e->d_nu, e->h_nu.data(), sizeof(double) * e->h_nu.size());
+        ap.upload(&e->d_cx, e->h_cx.data(), sizeof(double) * e->h_cx.size());
+        ap.upload(&e->d_cy_raw, e->h_cy.data(), sizeof(double) * e->h_cy.size());
+    }
+    ap.zeroed(&e->d_status, sizeof(int));
+    ap.zeroed(&e->d_fe_part, sizeof(double) * CU);
+    e->fe_total_cap = 16;
+    ap.zeroed(&e->d_fe_total, sizeof(double) * e->fe_total_cap);
+    ap.plain(&e->d_fe_blocks, sizeof(double) * ((CU + 63) / 64));
+    ap.plain(&e->d_fe_chain, sizeof(double) * CU);
+    ap.plain(&e->d_mean, sizeof(double) * (size_t)e->Tout() * CU * Du);
+    ap.plain(&e->d_cov, sizeof(double) * (size_t)e->Tout() * CU * Du * Du);
+    if (rxhip_status st = arena_commit(e, ap)) return st;
+    if (rxhip_status st = mseg_setup(e, ds)) return st;
+    return RXHIP_OK;
+}
+// kernel-level model of a packed engine: blockdiag(M8, M8) with M8 the model padded to 8 decoupled dimensions
+// (A = 0, P = V0 = I, m0 = 0, B = 0 there: posterior N(0, I), no contribution to the free energy)
+static void pack_pair_model(const rxhip_engine* e, const rxhip_lgssm_desc* ds, std::vector<double> (&buf)[6], rxhip_lgssm_desc& dk) {
+    std::vector<double>&pA = buf[0], &pB = buf[1], &pP = buf[2], &pQ = buf[3], &pm = buf[4], &pV = buf[5];
+    const int du = ds->d, dyu = ds->dy, dyk = e->dyk;
+    pA.assign(256, 0.0); pP.assign(256, 0.0); pV.assign(256, 0.0); pm.assign(16, 0.0);
+    pB.assign((size_t)dyk * 16, 0.0); pQ.assign((size_t)dyk * dyk, 0.0);
+    for (int b = 0; b < 2; ++b) {
+        for (int i = 0; i < 8; ++i)
+            for (int j = 0; j < 8; ++j) {
+                const bool in = i < du && j < du;
+                const size_t o = (size_t)(8 * b + i) * 16 + 8 * b + j;
+                pA[o] = in ? ds->A[(size_t)i * du + j] : 0.0;
+                pP[o] = in ? ds->P[(size_t)i * du + j] : (i == j ? 1.0 : 0.0);
+                pV[o] = in ? ds->V0[(size_t)i * du + j] : (i == j ? 1.0 : 0.0);
             }
+        for (int i = 0; i < du; ++i) pm[8 * b + i] = ds->m0[i];
+        for (int r = 0; r < dyu; ++r) {
+            for (int j = 0; j < du; ++j) pB[(size_t)(dyu * b + r) * 16 + 8 * b + j] = ds->B[(size_t)r * du + j];
+            for (int q = 0; q < dyu; ++q) pQ[(size_t)(dyu * b + r) * dyk + dyu * b + q] = ds->Q[(size_t)r * dyu + q];
         }
-        // Batches of one model on the model / data split (below: e->split): the data pass is vectors only, one workgroup per 4·(64/d) chains
-        // of a segment, so the machine fills through MORE segments, and the per-model tables are a recursion over the segment LENGTH
-        // (kt_gains, kt_agg: sequential in L).  Segments of ≈32 steps, at most 128 of them (measured, scripts/time_split_segments.py:
-        // d = 64 × 64 chains × T = 1000: sweep 1.60 -> 1.21 ms and first touch 23 -> 8.5 ms with 32 instead of 8 segments; d = 32 × 256:
-        // 1.25 -> 1.09 ms, 10.6 -> 4.5 ms; d = 8 × 1024: 0.48 -> 0.46 ms).
+    }
+    dk.d = 16; dk.dy = dyk; dk.n_chains = e->wg_chains;
+    dk.A = pA.data(); dk.B = pB.data(); dk.P = pP.data(); dk.Q = pQ.data(); dk.m0 = pm.data(); dk.V0 = pV.data();
+}
+// the tables of one model of the MFMA path, built by the device builder (d ≥ 32) or on the host, then shared through the table cache
+static rxhip_status dense_tables_build(rxhip_engine* e, const rxhip_lgssm_desc& dm, int mdl, std::vector<unsigned char>& key, StageTrace& tr, DenseTables** out) {
+    const size_t Sg = (size_t)(e->S > 0 ? e->S : 1), D = (size_t)e->dpad;
+    rxhip_status st = RXHIP_OK;
+    DenseTables* dt = nullptr;
+    dense_schedule_ints(e);
+    const bool on_dev = dense_tab_on_device(e);
+    std::vector<double> cst, tab, scanm, qtab;
+    std::vector<int> canon;
+    const DenseCst cl = DenseCst::make((int)D, e->dyk);
+    const size_t MMd = D * D, dyp4 = (size_t)((e->dyk + 3) & ~3);
+    size_t nb[6];
+    if (on_dev) {
+        nb[0] = (size_t)cl.size; nb[1] = (size_t)2 * e->L * dyp4 * 2 * D; nb[2] = Sg * 6 * MMd; nb[3] = 2 * Sg * MMd;
+        nb[4] = Sg * 2 * MMd; nb[5] = (4 * Sg + 1) / 2;
+    } else {
+        st = build_dense_tables(e, &dm, cst, tab, scanm, qtab, canon);
+        if (st) return st;
+        tr.mark("dense: host tables", STAGE_TABLES_HOST);
+        nb[0] = cst.size(); nb[1] = tab.size(); nb[2] = scanm.size(); nb[3] = qtab.size(); nb[4] = Sg * 2 * MMd; nb[5] = (canon.size() + 1) / 2;
+    }
+    dt = new DenseTables;
+    dt->key.swap(key);
+    dt->device = e->device;
+    dt->agg_oc = e->agg_oc; dt->agg_kc = e->agg_kc; dt->scan_sg = e->scan_sg; dt->scan_ng = e->scan_ng;
+    size_t off[7] = {0};
+    for (int q = 0; q < 6; ++q) off[q + 1] = off[q] + ArenaPlan::al(sizeof(double) * (nb[q] ? nb[q] : 1));
+    dt->bytes = off[6];
+    if (hipMalloc(&dt->block, dt->bytes) != hipSuccess) { delete dt; return fail(e, RXHIP_ERR_HIP, "hipMalloc of %zu bytes (model tables) failed", off[6]); }
+    tr.mark("dense: table block (hipMalloc)", STAGE_ALLOC);
+    double** dst[5] = {&dt->d_cst, &dt->d_tab, &dt->d_scanm, &dt->d_qtab, &dt->d_bnd};
+    hipError_t up = hipSuccess;
+    for (int q = 0; q < 5; ++q) *dst[q] = (double*)(dt->block + off[q]);
+    dt->d_canon = (int*)(dt->block + off[5]);
+    // device build: padded inputs | workspace | two status words, ONE temporary allocation (freed when the tables are done); the
+    // inputs travel through a pinned block and the status words come back into it
+    DevTmp tab_ws;
+    const size_t nin = 5 * MMd + D, nws = on_dev ? TabWs::doubles((int)D, e->L) : 0;
+    PinnedTmp pin(sizeof(double) * (nin + 2));
+    if (!pin.p) { (void)hipFree(dt->block); delete dt; return fail(e, RXHIP_ERR_HIP, "hipHostMalloc of the staging block failed"); }
+    int* h_st = reinterpret_cast<int*>(pin.p + nin);   // [0]: table builders, [2]: boundary inverses
+    h_st[0] = h_st[2] = 0;
+    up = hipMalloc(&tab_ws.p, sizeof(double) * ((on_dev ? nin : 0) + nws + 2));
+    int* d_st = up == hipSuccess ? reinterpret_cast<int*>((double*)tab_ws.p + (on_dev ? nin : 0) + nws) : nullptr;
+    if (up == hipSuccess) up = hipMemsetAsync(d_st, 0, 2 * sizeof(double), e->stream);
+    tr.mark("dense: temporary workspace (hipMalloc)", STAGE_ALLOC);
+    if (on_dev) {
+        // the model padded to d×d (copies only): A | P | V0 | B | Q | m0 — B, Q padded to d rows, Q = I on the padding diagonal
+        double* hin = pin.p;
+        std::memset(hin, 0, sizeof(double) * nin);
+        const int du = dm.d, dyu = dm.dy;
+        for (int i = 0; i < (int)D; ++i)
+            for (int j = 0; j < (int)D; ++j) {
+                const bool in = i < du && j < du;
+                hin[(size_t)i * D + j] = in ? dm.A[(size_t)i * du + j] : 0.0;
+                hin[MMd + (size_t)i * D + j] = in ? dm.P[(size_t)i * du + j] : (i == j ? 1.0 : 0.0);
+                hin[2 * MMd + (size_t)i * D + j] = in ? dm.V0[(size_t)i * du + j] : (i == j ? 1.0 : 0.0);
+                hin[3 * MMd + (size_t)i * D + j] = (i < dyu && j < du) ? dm.B[(size_t)i * du + j] : 0.0;
+                hin[4 * MMd + (size_t)i * D + j] = (i < dyu && j < dyu) ? dm.Q[(size_t)i * dyu + j] : (i == j && i >= dyu ? 1.0 : 0.0);
+            }
+        for (int i = 0; i < du; ++i) hin[5 * MMd + i] = dm.m0[i];
+        if (up == hipSuccess) up = hipMemcpyAsync(tab_ws.p, hin, sizeof(double) * nin, hipMemcpyHostToDevice, e->stream);
+        if (up == hipSuccess) up = hipMemsetAsync(dt->d_tab, 0, sizeof(double) * nb[1], e->stream);   // the padded k rows of the aggregation maps
+        if (up == hipSuccess) up = hipMemsetAsync(dt->d_cst, 0, sizeof(double) * nb[0], e->stream);
+        TabParams tp{};
+        tp.d = (int)D; tp.dy = e->dyk; tp.ptt = e->ptt; tp.T = e->T; tp.L = e->L; tp.Llast = e->Llast; tp.S = e->S; tp.sg = e->scan_sg; tp.ng = e->scan_ng;
+        tp.in = (const double*)tab_ws.p; tp.ws = (double*)tab_ws.p + nin; tp.cst = dt->d_cst; tp.tab = dt->d_tab; tp.scanm = dt->d_scanm;
+        tp.qtab = dt->d_qtab; tp.canon = dt->d_canon; tp.status = d_st;
+        if (up == hipSuccess) {
+            { const int nt_prep = e->nt; up = once_per_device_checked(110 + nt_prep, e->device, [nt_prep] { return dense_vt(nt_prep)->tab_prepare(); }); }
+            if (up == hipSuccess) up = dense_vt(e->nt)->tab_build(tp, e->stream);
+        }
+        tr.mark("dense: device tables (enqueued)", STAGE_TABLES_DEVICE);
+    } else {
+        const std::vector<double>* src[4] = {&cst, &tab, &scanm, &qtab};
+        for (int q = 0; q < 4 && up == hipSuccess; ++q)
+            up = hipMemcpyAsync(*dst[q], src[q]->data(), sizeof(double) * src[q]->size(), hipMemcpyHostToDevice, e->stream);
+        if (up == hipSuccess) up = hipMemcpyAsync(dt->d_canon, canon.data(), sizeof(int) * canon.size(), hipMemcpyHostToDevice, e->stream);
+    }
+    if (up == hipSuccess && e->S > 0) {  // data-independent inverses at the segment boundaries: once per model, on the device
+        DenseParams dp{};
+        dp.S = e->S; dp.d = e->dpad; dp.dy = e->dyk; dp.scanm = dt->d_scanm; dp.bnd = dt->d_bnd; dp.canon = dt->d_canon;
+        dp.status = d_st + 2;
+        DENSE_DISPATCH(e->nt, prepare_bnd(dp, e->stream));
+        up = hipGetLastError();
+    }
+    // ONE wait for the builders and the boundary inverses, then both status words out of pinned memory
+    if (up == hipSuccess) up = hipMemcpyAsync(h_st, d_st, 2 * sizeof(double), hipMemcpyDeviceToHost, e->stream);
+    if (up == hipSuccess) up = hipStreamSynchronize(e->stream);   // (the host vectors of the host builder die at the end of this scope)
+    tr.mark(on_dev ? "dense: device tables + bnd (wait)" : "dense: table upload + bnd", on_dev ? STAGE_TABLES_DEVICE : STAGE_UPLOAD);
+    if (up == hipSuccess && (h_st[0] || h_st[2])) {
+        (void)hipFree(dt->block);
+        delete dt;
+        return fail(e, RXHIP_ERR_NOT_POSDEF, h_st[0] ? "model %d: a covariance of the model or of its filter recursion is not positive definite"
+                                                     : "model %d: a boundary covariance / precision is not positive definite", mdl);
+    }
+    if (up != hipSuccess) {
+        (void)hipFree(dt->block);
+        delete dt;
+        return fail(e, RXHIP_ERR_HIP, "upload of the model tables failed: %s", hipGetErrorString(up));
+    }
+    dense_tables_insert(dt);
+    *out = dt;
+    return RXHIP_OK;
+}
+// d > 4, fully observed, one model per chain: the MFMA path
+static rxhip_status create_dense(rxhip_engine* e, const rxhip_lgssm_desc* ds) {
+    const std::vector<double> prior = dense_prior(e, ds);
+    StageTrace tr(e->stage_ms);
+    hipError_t herr = hipSuccess;
+    { const int nt_prep = e->nt; herr = once_per_device_checked(100 + nt_prep, e->device, [nt_prep] { return dense_vt(nt_prep)->prepare(); }); }
+    if (herr != hipSuccess) return fail(e, RXHIP_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+    const size_t C = (size_t)e->wg_chains, CU = (size_t)e->n_chains, T = (size_t)e->T, Sg = (size_t)(e->S > 0 ? e->S : 1),
+                 D = (size_t)e->dpad, Du = (size_t)e->d;
+    // kernel-level model: the user's, or — packed — a block-diagonal pair
+    rxhip_lgssm_desc dk = *ds;
+    std::vector<double> packed[6];
+    if (e->pack == 2) pack_pair_model(e, ds, packed, dk);
+    // the tables of every model: shared with every other engine of the same model and schedule on this device
+    rxhip_status st = RXHIP_OK;
+    for (int mdl = 0; mdl < e->n_models; ++mdl) {
+        rxhip_lgssm_desc dm = dk;  // model `mdl` at kernel level (a packed pair has one model by construction)
+        if (e->pack == 1) {
+            dm.A = ds->A + (size_t)mdl * Du * Du; dm.B = ds->B + (size_t)mdl * e->dy * Du; dm.P = ds->P + (size_t)mdl * Du * Du;
+            dm.Q = ds->Q + (size_t)mdl * e->dy * e->dy; dm.m0 = ds->m0 + (size_t)mdl * Du; dm.V0 = ds->V0 + (size_t)mdl * Du * Du;
+        }
+        std::vector<unsigned char> key;
         {
-            const char* sp_env = hook_env("RXHIP_DENSE_SPLIT");
-            const bool split_eligible = dense && !e->gseq && ds->n_models == 1 && (sp_env ? std::atoi(sp_env) != 0 : e->wg_chains >= 4);
-            if (split_eligible && ds->segments <= 0) S_target = std::max(S_target, std::min<long long>(128, (steps + 31) / 32));
+            const long long hdr[9] = {e->d, e->dy, e->T, e->S, e->L, e->Llast, e->ptt, e->dpad, e->pack};
+            auto put = [&](const void* q, size_t n) { const unsigned char* b = (const unsigned char*)q; key.insert(key.end(), b, b + n); };
+            put(hdr, sizeof hdr);
+            const size_t o = (size_t)mdl;  // the USER's model bytes identify the tables
+            put(ds->A + o * Du * Du, sizeof(double) * Du * Du); put(ds->B + o * e->dy * Du, sizeof(double) * e->dy * Du);
+            put(ds->P + o * Du * Du, sizeof(double) * Du * Du); put(ds->Q + o * e->dy * e->dy, sizeof(double) * e->dy * e->dy);
+            put(ds->m0 + o * Du, sizeof(double) * Du); put(ds->V0 + o * Du * Du, sizeof(double) * Du * Du);
         }
-        if (S_target < 1) S_target = 1;
-        long long L = (steps + S_target - 1) / S_target;
-        const long long Lmin = ds->segments > 0 ? 1 : small_short ? 3 : 8;
-        if (L < Lmin) L = Lmin;
-        if (L > steps) L = steps;
-        e->L = L;
-        e->S = (int)((steps + L - 1) / L);
-        e->Llast = steps - (long long)(e->S - 1) * L;
+        DenseTables* dt = dense_tables_acquire(key, e->device);
+        if (!dt) {
+            if ((st = dense_tables_build(e, dm, mdl, key, tr, &dt))) return st;
+        } else {
+            e->agg_oc = dt->agg_oc; e->agg_kc = dt->agg_kc; e->scan_sg = dt->scan_sg; e->scan_ng = dt->scan_ng;
+            tr.mark("dense: tables from cache", STAGE_TABLES_HOST);
+        }
+        e->dts.push_back(dt);  // released in free_all, whatever happens below
     }
-
-    std::vector<double> prior;  // dense engines: [n_models][m0 | V0] at user level (sequential schedule, rxhip_filter_step)
-    if (dense) {
-        const size_t Du = (size_t)e->d, np = Du + Du * Du;
-        prior.resize((size_t)e->n_models * np);
-        for (int m = 0; m < e->n_models; ++m) {
-            std::memcpy(&prior[(size_t)m * np], ds->m0 + (size_t)m * Du, sizeof(double) * Du);
-            std::memcpy(&prior[(size_t)m * np + Du], ds->V0 + (size_t)m * Du * Du, sizeof(double) * Du * Du);
-        }
+    {
+        DenseTables* dt = e->dts[0];
+        e->d_cst = dt->d_cst; e->d_tab = dt->d_tab; e->d_scanm = dt->d_scanm; e->d_qtab = dt->d_qtab; e->d_bnd = dt->d_bnd;
+        e->d_canon = dt->d_canon;
     }
-    if (e->gseq) {  // no tables: the user-level constants, the priors, the outputs
-        e->S = 0; e->L = 1; e->Llast = 1;
-        once_per_device(0, e->device, [] {
-            (void)hipFuncSetAttribute((const void*)k_gseq_forward, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_gseq_backward, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
-        });
-        const size_t CU = (size_t)e->n_chains, Du = (size_t)e->d;
-        ArenaPlan ap;
-        ap.upload(&e->d_user, e->h_user.data(), sizeof(double) * e->h_user.size());
-        ap.upload(&e->d_prior, prior.data(), sizeof(double) * prior.size());
-        if (ds->chain_model) ap.upload(&e->d_chain_model, ds->chain_model, sizeof(int) * CU);
-        if (ds->step_model) ap.upload(&e->d_step_model, ds->step_model, sizeof(int) * (size_t)(e->T + e->H));
-        if (!e->h_mu.empty()) {
-            ap.upload(&e->d_mu, e->h_mu.data(), sizeof(double) * e->h_mu.size());
-            ap.upload(&e->d_nu, e->h_nu.data(), sizeof(double) * e->h_nu.size());
-            ap.upload(&e->d_cx, e->h_cx.data(), sizeof(double) * e->h_cx.size());
-            ap.upload(&e->d_cy_raw, e->h_cy.data(), sizeof(double) * e->h_cy.size());
-        }
-        ap.zeroed(&e->d_status, sizeof(int));
-        ap.zeroed(&e->d_fe_part, sizeof(double) * CU);
-        e->fe_total_cap = 16;
-        ap.zeroed(&e->d_fe_total, sizeof(double) * e->fe_total_cap);
-        ap.plain(&e->d_fe_blocks, sizeof(double) * ((CU + 63) / 64));
-        ap.plain(&e->d_fe_chain, sizeof(double) * CU);
-        ap.plain(&e->d_mean, sizeof(double) * (size_t)e->Tout() * CU * Du);
-        ap.plain(&e->d_cov, sizeof(double) * (size_t)e->Tout() * CU * Du * Du);
-        if (rxhip_status st = arena_commit(e, ap)) return st;
-        if (rxhip_status st = mseg_setup(e, ds)) return st;
-        return RXHIP_OK;
+    std::vector<DenseModel> hmodels;
+    if (e->n_models > 1)
+        for (DenseTables* dt : e->dts) hmodels.push_back(DenseModel{dt->d_cst, dt->d_tab, dt->d_scanm, dt->d_qtab, dt->d_bnd, dt->d_canon});
+    ArenaPlan ap;
+    if (e->n_models > 1) {
+        ap.upload(&e->d_models, hmodels.data(), sizeof(DenseModel) * hmodels.size());
+        ap.upload(&e->d_chain_model, ds->chain_model, sizeof(int) * CU);
     }
-    if (dense) {
-        StageTrace tr(e->stage_ms);
-        hipError_t herr = hipSuccess;
-        { const int nt_prep = e->nt; herr = once_per_device_checked(100 + nt_prep, e->device, [nt_prep] { return dense_vt(nt_prep)->prepare(); }); }
-        if (herr != hipSuccess) return fail(e, RXHIP_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-        const size_t C = (size_t)e->wg_chains, CU = (size_t)e->n_chains, T = (size_t)e->T, Sg = (size_t)(e->S > 0 ? e->S : 1),
-                     D = (size_t)e->dpad, Du = (size_t)e->d;
-        // kernel-level model: the user's, or — packed — blockdiag(M8, M8) with M8 the model padded to 8 decoupled dimensions
-        // (A = 0, P = V0 = I, m0 = 0, B = 0 there: posterior N(0, I), no contribution to the free energy)
-        rxhip_lgssm_desc dk = *ds;
-        std::vector<double> pA, pB, pP, pQ, pm, pV;
-        if (e->pack == 2) {
-            const int du = ds->d, dyu = ds->dy, dyk = e->dyk;
-            pA.assign(256, 0.0); pP.assign(256, 0.0); pV.assign(256, 0.0); pm.assign(16, 0.0);
-            pB.assign((size_t)dyk * 16, 0.0); pQ.assign((size_t)dyk * dyk, 0.0);
-            for (int b = 0; b < 2; ++b) {
-                for (int i = 0; i < 8; ++i)
-                    for (int j = 0; j < 8; ++j) {
-                        const bool in = i < du && j < du;
-                        const size_t o = (size_t)(8 * b + i) * 16 + 8 * b + j;
-                        pA[o] = in ? ds->A[(size_t)i * du + j] : 0.0;
-                        pP[o] = in ? ds->P[(size_t)i * du + j] : (i == j ? 1.0 : 0.0);
-                        pV[o] = in ? ds->V0[(size_t)i * du + j] : (i == j ? 1.0 : 0.0);
-                    }
-                for (int i = 0; i < du; ++i) pm[8 * b + i] = ds->m0[i];
-                for (int r = 0; r < dyu; ++r) {
-                    for (int j = 0; j < du; ++j) pB[(size_t)(dyu * b + r) * 16 + 8 * b + j] = ds->B[(size_t)r * du + j];
-                    for (int q = 0; q < dyu; ++q) pQ[(size_t)(dyu * b + r) * dyk + dyu * b + q] = ds->Q[(size_t)r * dyu + q];
-                }
-            }
-            dk.d = 16; dk.dy = dyk; dk.n_chains = e->wg_chains;
-            dk.A = pA.data(); dk.B = pB.data(); dk.P = pP.data(); dk.Q = pQ.data(); dk.m0 = pm.data(); dk.V0 = pV.data();
-        }
-        // the tables of every model: shared with every other engine of the same model and schedule on this device
-        rxhip_status st = RXHIP_OK;
-        for (int mdl = 0; mdl < e->n_models; ++mdl) {
-            rxhip_lgssm_desc dm = dk;  // model `mdl` at kernel level (a packed pair has one model by construction)
-            if (e->pack == 1) {
-                dm.A = ds->A + (size_t)mdl * Du * Du; dm.B = ds->B + (size_t)mdl * e->dy * Du; dm.P = ds->P + (size_t)mdl * Du * Du;
-                dm.Q = ds->Q + (size_t)mdl * e->dy * e->dy; dm.m0 = ds->m0 + (size_t)mdl * Du; dm.V0 = ds->V0 + (size_t)mdl * Du * Du;
-            }
-            std::vector<unsigned char> key;
-            {
-                const long long hdr[9] = {e->d, e->dy, e->T, e->S, e->L, e->Llast, e->ptt, e->dpad, e->pack};
-                auto put = [&](const void* q, size_t n) { const unsigned char* b = (const unsigned char*)q; key.insert(key.end(), b, b + n); };
-                put(hdr, sizeof hdr);
-                const size_t o = (size_t)mdl;  // the USER's model bytes identify the tables
-                put(ds->A + o * Du * Du, sizeof(double) * Du * Du); put(ds->B + o * e->dy * Du, sizeof(double) * e->dy * Du);
-                put(ds->P + o * Du * Du, sizeof(double) * Du * Du); put(ds->Q + o * e->dy * e->dy, sizeof(double) * e->dy * e->dy);
-                put(ds->m0 + o * Du, sizeof(double) * Du); put(ds->V0 + o * Du * Du, sizeof(double) * Du * Du);
-            }
-            DenseTables* dt = dense_tables_acquire(key, e->device);
-            if (!dt) {
-                dense_schedule_ints(e);
-                const bool on_dev = dense_tab_on_device(e);
-                std::vector<double> cst, tab, scanm, qtab;
-                std::vector<int> canon;
-                const DenseCst cl = DenseCst::make((int)D, e->dyk);
-                const size_t MMd = D * D, dyp4 = (size_t)((e->dyk + 3) & ~3);
-                size_t nb[6];
-                if (on_dev) {
-                    nb[0] = (size_t)cl.size; nb[1] = (size_t)2 * e->L * dyp4 * 2 * D; nb[2] = Sg * 6 * MMd; nb[3] = 2 * Sg * MMd;
-                    nb[4] = Sg * 2 * MMd; nb[5] = (4 * Sg + 1) / 2;
-                } else {
-                    st = build_dense_tables(e, &dm, cst, tab, scanm, qtab, canon);
-                    if (st) return st;
-                    tr.mark("dense: host tables", STAGE_TABLES_HOST);
-                    nb[0] = cst.size(); nb[1] = tab.size(); nb[2] = scanm.size(); nb[3] = qtab.size(); nb[4] = Sg * 2 * MMd; nb[5] = (canon.size() + 1) / 2;
-                }
-                dt = new DenseTables;
-                dt->key.swap(key);
-                dt->device = e->device;
-                dt->agg_oc = e->agg_oc; dt->agg_kc = e->agg_kc; dt->scan_sg = e->scan_sg; dt->scan_ng = e->scan_ng;
-                size_t off[7] = {0};
-                for (int q = 0; q < 6; ++q) off[q + 1] = off[q] + ArenaPlan::al(sizeof(double) * (nb[q] ? nb[q] : 1));
-                dt->bytes = off[6];
-                if (hipMalloc(&dt->block, dt->bytes) != hipSuccess) { delete dt; return fail(e, RXHIP_ERR_HIP, "hipMalloc of %zu bytes (model tables) failed", off[6]); }
-                tr.mark("dense: table block (hipMalloc)", STAGE_ALLOC);
-                double** dst[5] = {&dt->d_cst, &dt->d_tab, &dt->d_scanm, &dt->d_qtab, &dt->d_bnd};
-                hipError_t up = hipSuccess;
-                for (int q = 0; q < 5; ++q) *dst[q] = (double*)(dt->block + off[q]);
-                dt->d_canon = (int*)(dt->block + off[5]);
-                // device build: padded inputs | workspace | two status words, ONE temporary allocation (freed when the tables are done); the
-                // inputs travel through a pinned block and the status words come back into it
-                DevTmp tab_ws;
-                const size_t nin = 5 * MMd + D, nws = on_dev ? TabWs::doubles((int)D, e->L) : 0;
-                PinnedTmp pin(sizeof(double) * (nin + 2));
-                if (!pin.p) { (void)hipFree(dt->block); delete dt; return fail(e, RXHIP_ERR_HIP, "hipHostMalloc of the staging block failed"); }
-                int* h_st = reinterpret_cast<int*>(pin.p + nin);   // [0]: table builders, [2]: boundary inverses
-                h_st[0] = h_st[2] = 0;
-                up = hipMalloc(&tab_ws.p, sizeof(double) * ((on_dev ? nin : 0) + nws + 2));
-                int* d_st = up == hipSuccess ? reinterpret_cast<int*>((double*)tab_ws.p + (on_dev ? nin : 0) + nws) : nullptr;
-                if (up == hipSuccess) up = hipMemsetAsync(d_st, 0, 2 * sizeof(double), e->stream);
-                tr.mark("dense: temporary workspace (hipMalloc)", STAGE_ALLOC);
-                if (on_dev) {
-                    // the model padded to d×d (copies only): A | P | V0 | B | Q | m0 — B, Q padded to d rows, Q = I on the padding diagonal
-                    double* hin = pin.p;
-                    std::memset(hin, 0, sizeof(double) * nin);
-                    const int du = dm.d, dyu = dm.dy;
-                    for (int i = 0; i < (int)D; ++i)
-                        for (int j = 0; j < (int)D; ++j) {
-                            const bool in = i < du && j < du;
-                            hin[(size_t)i * D + j] = in ? dm.A[(size_t)i * du + j] : 0.0;
-                            hin[MMd + (size_t)i * D + j] = in ? dm.P[(size_t)i * du + j] : (i == j ? 1.0 : 0.0);
-                            hin[2 * MMd + (size_t)i * D + j] = in ? dm.V0[(size_t)i * du + j] : (i == j ? 1.0 : 0.0);
-                            hin[3 * MMd + (size_t)i * D + j] = (i < dyu && j < du) ? dm.B[(size_t)i * du + j] : 0.0;
-                            hin[4 * MMd + (size_t)i * D + j] = (i < dyu && j < dyu) ? dm.Q[(size_t)i * dyu + j] : (i == j && i >= dyu ? 1.0 : 0.0);
-                        }
-                    for (int i = 0; i < du; ++i) hin[5 * MMd + i] = dm.m0[i];
-                    if (up == hipSuccess) up = hipMemcpyAsync(tab_ws.p, hin, sizeof(double) * nin, hipMemcpyHostToDevice, e->stream);
-                    if (up == hipSuccess) up = hipMemsetAsync(dt->d_tab, 0, sizeof(double) * nb[1], e->stream);   // the padded k rows of the aggregation maps
-                    if (up == hipSuccess) up = hipMemsetAsync(dt->d_cst, 0, sizeof(double) * nb[0], e->stream);
-                    TabParams tp{};
-                    tp.d = (int)D; tp.dy = e->dyk; tp.ptt = e->ptt; tp.T = e->T; tp.L = e->L; tp.Llast = e->Llast; tp.S = e->S; tp.sg = e->scan_sg; tp.ng = e->scan_ng;
-                    tp.in = (const double*)tab_ws.p; tp.ws = (double*)tab_ws.p + nin; tp.cst = dt->d_cst; tp.tab = dt->d_tab; tp.scanm = dt->d_scanm;
-                    tp.qtab = dt->d_qtab; tp.canon = dt->d_canon; tp.status = d_st;
-                    if (up == hipSuccess) {
-                        { const int nt_prep = e->nt; up = once_per_device_checked(110 + nt_prep, e->device, [nt_prep] { return dense_vt(nt_prep)->tab_prepare(); }); }
-                        if (up == hipSuccess) up = dense_vt(e->nt)->tab_build(tp, e->stream);
-                    }
-                    tr.mark("dense: device tables (enqueued)", STAGE_TABLES_DEVICE);
-                } else {
-                    const std::vector<double>* src[4] = {&cst, &tab, &scanm, &qtab};
-                    for (int q = 0; q < 4 && up == hipSuccess; ++q)
-                        up = hipMemcpyAsync(*dst[q], src[q]->data(), sizeof(double) * src[q]->size(), hipMemcpyHostToDevice, e->stream);
-                    if (up == hipSuccess) up = hipMemcpyAsync(dt->d_canon, canon.data(), sizeof(int) * canon.size(), hipMemcpyHostToDevice, e->stream);
-                }
-                if (up == hipSuccess && e->S > 0) {  // data-independent inverses at the segment boundaries: once per model, on the device
-                    DenseParams dp{};
-                    dp.S = e->S; dp.d = e->dpad; dp.dy = e->dyk; dp.scanm = dt->d_scanm; dp.bnd = dt->d_bnd; dp.canon = dt->d_canon;
-                    dp.status = d_st + 2;
-                    DENSE_DISPATCH(e->nt, prepare_bnd(dp, e->stream));
-                    up = hipGetLastError();
-                }
-                // ONE wait for the builders and the boundary inverses, then both status words out of pinned memory
-                if (up == hipSuccess) up = hipMemcpyAsync(h_st, d_st, 2 * sizeof(double), hipMemcpyDeviceToHost, e->stream);
-                if (up == hipSuccess) up = hipStreamSynchronize(e->stream);   // (the host vectors of the host builder die at the end of this scope)
-                tr.mark(on_dev ? "dense: device tables + bnd (wait)" : "dense: table upload + bnd", on_dev ? STAGE_TABLES_DEVICE : STAGE_UPLOAD);
-                if (up == hipSuccess && (h_st[0] || h_st[2])) {
-                    (void)hipFree(dt->block);
-                    delete dt;
-                    return fail(e, RXHIP_ERR_NOT_POSDEF, h_st[0] ? "model %d: a covariance of the model or of its filter recursion is not positive definite"
-                                                                 : "model %d: a boundary covariance / precision is not positive definite", mdl);
-                }
-                if (up != hipSuccess) {
-                    (void)hipFree(dt->block);
-                    delete dt;
-                    return fail(e, RXHIP_ERR_HIP, "upload of the model tables failed: %s", hipGetErrorString(up));
-                }
-                dense_tables_insert(dt);
+    ap.plain(&e->d_loc, sizeof(double) * C * 2 * Sg * D);
+    ap.plain(&e->d_aggpart, sizeof(double) * C * (size_t)e->agg_kc * Sg * 2 * D);
+    ap.zeroed(&e->d_status, sizeof(int));
+    // smoothing runs use 2S slots (forward + backward parts) + one per workgroup of kd_fe_resid
+    ap.zeroed(&e->d_fe_part, sizeof(double) * (2 * Sg + 2 + (size_t)fe_resid_blocks(e->T, e->dpad, e->dyk)) * CU);
+    e->fe_total_cap = 16;
+    ap.zeroed(&e->d_fe_total, sizeof(double) * e->fe_total_cap);
+    ap.plain(&e->d_fe_blocks, sizeof(double) * ((CU + 63) / 64));
+    ap.plain(&e->d_filt, sizeof(double) * C * T * dense_rec(e->nt));
+    ap.plain(&e->d_vend, sizeof(double) * C * Sg * dense_tri(e->nt));
+    ap.upload(&e->d_user, e->h_user.data(), sizeof(double) * e->h_user.size());
+    ap.upload(&e->d_prior, prior.data(), sizeof(double) * prior.size());
+    if (!e->h_mu.empty()) {
+        ap.upload(&e->d_mu, e->h_mu.data(), sizeof(double) * e->h_mu.size());
+        ap.upload(&e->d_nu, e->h_nu.data(), sizeof(double) * e->h_nu.size());
+        ap.upload(&e->d_cx, e->h_cx.data(), sizeof(double) * e->h_cx.size());
+        ap.upload(&e->d_cy_raw, e->h_cy.data(), sizeof(double) * e->h_cy.size());
+    }
+    ap.plain(&e->d_mean, sizeof(double) * (size_t)e->Tout() * CU * Du);
+    ap.plain(&e->d_cov, sizeof(double) * (size_t)e->Tout() * CU * Du * Du);
+    ap.plain(&e->d_elem, sizeof(double) * C * Sg * 2 * D);
+    ap.plain(&e->d_fstart_m, sizeof(double) * C * Sg * D);
+    ap.plain(&e->d_beta_xi, sizeof(double) * C * (Sg + 1) * D);
+    ap.plain(&e->d_fe_chain, sizeof(double) * CU);
+    e->split = e->n_models == 1 && e->S > 0 && plan::split_wanted(e->wg_chains, e->hooks);   // the model / data split (lgssm_plan.hpp)
+    if (e->split) {
+        const int nt_split = e->nt;
+        once_per_device(16 + nt_split, e->device, [nt_split] { (void)dense_vt(nt_split)->split_prepare(); });
+        ap.plain(&e->d_dtab, sizeof(double) * T * 3 * D * D);
+        ap.plain(&e->d_vlast, sizeof(double) * D * D);
+        ap.plain(&e->d_vstab, sizeof(double) * T * Du * Du);
+        ap.plain(&e->d_fe_const, sizeof(double) * 2 * Sg);
+    }
+    if ((st = arena_commit(e, ap))) return st;
+    tr.mark("dense: work buffers");   // (arena_commit accounts its own stages)
+    return RXHIP_OK;
+}
+// the per-time-index maps of the one-pass schedule: data-independent, once per engine
+static rxhip_status lanes_time_tables(rxhip_engine* e, bool rev_cand, int ck_forced) {
+    const LgssmVtbl* vt = e->vt;
+    TimeTabParams q{};
+    q.T = e->T; q.L = e->L; q.pos = e->d_pos; q.scan = e->d_scan; q.mtab = e->d_mtab; q.ntab = e->d_ntab; q.vtab = e->d_vtab;
+    q.status = e->d_status;
+    HIPCHK(e, hipEventCreate(&e->ev_tab0));
+    HIPCHK(e, hipEventCreate(&e->ev_tab1));
+    HIPCHK(e, hipEventRecord(e->ev_tab0, e->stream));
+    vt->time_tables(q, e->stream);
+    if (e->d_gtab) {
+        SmoothTabParams sq{};
+        sq.T = e->T; sq.L = e->L; sq.S = e->S; sq.vtab = e->d_vtab; sq.ntab = e->d_ntab; sq.scan = e->d_scan;
+        sq.gtab = e->d_gtab; sq.segend = e->d_segend; sq.blk = e->d_sblk; sq.status = e->d_status;
+        sq.rev = rev_cand ? 1 : 0; sq.amp = e->d_amp; sq.ainv = e->d_ainv; sq.ckfail = e->d_ckfail;
+        vt->smooth_tables(sq, e->h_cst0.data(), e->stream);
+        if (rev_cand) {   // the largest stride whose windows all pass the bound (one word: a bit per failing stride 8, 16, 32)
+            int ckfail = 0;
+            HIPCHK(e, hipMemcpyAsync(&ckfail, e->d_ckfail, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+            HIPCHK(e, hipStreamSynchronize(e->stream));
+            e->ck_log2 = 0;
+            if (ck_forced) {
+                while ((1 << e->ck_log2) < ck_forced) ++e->ck_log2;
             } else {
-                e->agg_oc = dt->agg_oc; e->agg_kc = dt->agg_kc; e->scan_sg = dt->scan_sg; e->scan_ng = dt->scan_ng;
-                tr.mark("dense: tables from cache", STAGE_TABLES_HOST);
+                for (int k = 2; k >= 0 && !e->ck_log2; --k)
+                    if (!((ckfail >> k) & 1)) e->ck_log2 = 3 + k;
             }
-            e->dts.push_back(dt);  // released in free_all, whatever happens below
+            if (!e->ck_log2) {   // no admissible stride: the records schedule, whose F slot holds F_t (rebuild the rows)
+                sq.rev = 0;
+                vt->smooth_tables(sq, e->h_cst0.data(), e->stream);
+            }
         }
-        {
-            DenseTables* dt = e->dts[0];
-            e->d_cst = dt->d_cst; e->d_tab = dt->d_tab; e->d_scanm = dt->d_scanm; e->d_qtab = dt->d_qtab; e->d_bnd = dt->d_bnd;
-            e->d_canon = dt->d_canon;
-        }
-        std::vector<DenseModel> hmodels;
-        if (e->n_models > 1)
-            for (DenseTables* dt : e->dts) hmodels.push_back(DenseModel{dt->d_cst, dt->d_tab, dt->d_scanm, dt->d_qtab, dt->d_bnd, dt->d_canon});
-        ArenaPlan ap;
-        if (e->n_models > 1) {
-            ap.upload(&e->d_models, hmodels.data(), sizeof(DenseModel) * hmodels.size());
-            ap.upload(&e->d_chain_model, ds->chain_model, sizeof(int) * CU);
-        }
-        ap.plain(&e->d_loc, sizeof(double) * C * 2 * Sg * D);
-        ap.plain(&e->d_aggpart, sizeof(double) * C * (size_t)e->agg_kc * Sg * 2 * D);
-        ap.zeroed(&e->d_status, sizeof(int));
-        // smoothing runs use 2S slots (forward + backward parts) + one per workgroup of kd_fe_resid
-        ap.zeroed(&e->d_fe_part, sizeof(double) * (2 * Sg + 2 + (size_t)fe_resid_blocks(e->T, e->dpad, e->dyk)) * CU);
-        e->fe_total_cap = 16;
-        ap.zeroed(&e->d_fe_total, sizeof(double) * e->fe_total_cap);
-        ap.plain(&e->d_fe_blocks, sizeof(double) * ((CU + 63) / 64));
-        ap.plain(&e->d_filt, sizeof(double) * C * T * dense_rec(e->nt));
-        ap.plain(&e->d_vend, sizeof(double) * C * Sg * dense_tri(e->nt));
-        ap.upload(&e->d_user, e->h_user.data(), sizeof(double) * e->h_user.size());
-        ap.upload(&e->d_prior, prior.data(), sizeof(double) * prior.size());
-        if (!e->h_mu.empty()) {
-            ap.upload(&e->d_mu, e->h_mu.data(), sizeof(double) * e->h_mu.size());
-            ap.upload(&e->d_nu, e->h_nu.data(), sizeof(double) * e->h_nu.size());
-            ap.upload(&e->d_cx, e->h_cx.data(), sizeof(double) * e->h_cx.size());
-            ap.upload(&e->d_cy_raw, e->h_cy.data(), sizeof(double) * e->h_cy.size());
-        }
-        ap.plain(&e->d_mean, sizeof(double) * (size_t)e->Tout() * CU * Du);
-        ap.plain(&e->d_cov, sizeof(double) * (size_t)e->Tout() * CU * Du * Du);
-        ap.plain(&e->d_elem, sizeof(double) * C * Sg * 2 * D);
-        ap.plain(&e->d_fstart_m, sizeof(double) * C * Sg * D);
-        ap.plain(&e->d_beta_xi, sizeof(double) * C * (Sg + 1) * D);
-        ap.plain(&e->d_fe_chain, sizeof(double) * CU);
-        // One model for at least four workgroups' worth of chains: the matrices of the information-form smoother are computed
-        // once (model pass on one chain), every sweep is vectors only (d = 8 × 1024 chains × T = 1000: 1.86 -> 0.77 ms;
-        // d = 64 × 64 chains: 5.70 -> 1.92 ms).  RXHIP_DENSE_SPLIT=0/1 overrides (tests).
-        {
-            const char* sp_env = hook_env("RXHIP_DENSE_SPLIT");
-            e->split = e->n_models == 1 && e->S > 0 && (sp_env ? std::atoi(sp_env) != 0 : e->wg_chains >= 4);
-        }
-        if (e->split) {
-            const int nt_split = e->nt;
-            once_per_device(16 + nt_split, e->device, [nt_split] { (void)dense_vt(nt_split)->split_prepare(); });
-            ap.plain(&e->d_dtab, sizeof(double) * T * 3 * D * D);
-            ap.plain(&e->d_vlast, sizeof(double) * D * D);
-            ap.plain(&e->d_vstab, sizeof(double) * T * Du * Du);
-            ap.plain(&e->d_fe_const, sizeof(double) * 2 * Sg);
-        }
-        if ((st = arena_commit(e, ap))) return st;
-        tr.mark("dense: work buffers");   // (arena_commit accounts its own stages)
-        return RXHIP_OK;
     }
+    HIPCHK(e, hipEventRecord(e->ev_tab1, e->stream));
+    // no synchronisation here: the table kernels are ordered before every sweep on the engine's stream, and a covariance
+    // that is not positive definite raises the status flag the first run reports (RXHIP_ERR_NOT_POSDEF)
+    HIPCHK(e, hipGetLastError());
+    return RXHIP_OK;
+}
+// d, dy ≤ 4: a lane per (chain, segment)
+static rxhip_status create_lanes(rxhip_engine* e, const rxhip_lgssm_desc* ds) {
+    const LgssmVtbl* vt = e->vt;
     // per-model tables
     const size_t NP = (size_t)e->d + (size_t)e->d * (e->d + 1) / 2;
     const size_t NP2 = (NP + 1) / 2;
@@ -2178,12 +2137,7 @@ rxhip_status rxhip_lgssm_create(const rxhip_lgssm_desc* ds, rxhip_engine** out) 
     std::vector<double> cst((size_t)e->n_models * vt->cst_size), tab((size_t)e->n_models * Ltab * vt->tab_size + 1),
         agg((size_t)e->n_models * 2 * vt->agg_size), scan;
     FusedTables ft;
-    // The one-pass schedule (k_forward0 + table-driven backward sweep) pays where the sweep is bandwidth-bound.  A few chains
-    // are a latency chain of L steps either way, and its tables cost 30 µs more at creation (measured, one chain, T = 10⁴:
-    // 0.41 against 0.38 ms end to end), so small problems keep the two-pass schedule.  RXHIP_ONE_PASS=0/1 overrides (tests).
-    const char* op_env = hook_env("RXHIP_ONE_PASS");
-    const bool want_fused = e->uniform && e->S > 0 &&
-                            (op_env ? std::atoi(op_env) != 0 : (double)e->n_chains * (double)e->T >= 4194304.0);
+    const bool want_fused = plan::want_fused(e->uniform, e->S, e->n_chains, e->T, e->hooks);
     StageTrace tr(e->stage_ms);
     for (int m = 0; m < e->n_models; ++m) {
         rxhip_status st = build_model_tables(e, m, ds, cst.data() + (size_t)m * vt->cst_size,
@@ -2210,26 +2164,18 @@ rxhip_status rxhip_lgssm_create(const rxhip_lgssm_desc* ds, rxhip_engine** out) 
         ap.upload(&e->d_cy_raw, e->h_cy.data(), sizeof(double) * e->h_cy.size());
     }
     if (e->uniform && !scan.empty()) ap.upload(&e->d_scan, scan.data(), sizeof(double) * scan.size());
-    // Reverse-filter candidates (k_backward_sh_rev): the table-driven backward sweep, no more observation than
-    // state components (the observations it reads instead of the z records are not larger).  The stride is chosen below, once
-    // the tables exist; RXHIP_MEAN_RECORDS=1 keeps a record per time index, RXHIP_MEAN_CHECKPOINT=K forces the stride K.
-    const char* rec_env = hook_env("RXHIP_MEAN_RECORDS");
-    const char* ck_env = hook_env("RXHIP_MEAN_CHECKPOINT");
-    int ck_forced = 0;
-    if (ck_env) {
-        ck_forced = std::atoi(ck_env);
-        if (ck_forced < 1 || ck_forced > 32 || (ck_forced & (ck_forced - 1)))
-            return fail(e, RXHIP_ERR_BADARG, "RXHIP_MEAN_CHECKPOINT=%s: a power of two from 1 to 32", ck_env);
-    }
-    const bool rev_cand = e->fused && C % 64 == 0 && !hook_env("RXHIP_BACKWARD_LANES") && e->dy <= e->d && e->T > 1 &&
-                          !(rec_env && std::atoi(rec_env) != 0);
+    // (reverse-filter candidates: plan::rev_cand; the stride is chosen in lanes_time_tables, once the tables exist)
+    const int ck_forced = e->hooks.mean_checkpoint;
+    if (ck_forced && (ck_forced < 1 || ck_forced > 32 || (ck_forced & (ck_forced - 1))))
+        return fail(e, RXHIP_ERR_BADARG, "RXHIP_MEAN_CHECKPOINT=%s: a power of two from 1 to 32", e->hooks.mean_checkpoint_text.s);
+    const bool rev_cand = plan::rev_cand(e->fused, e->n_chains, e->d, e->dy, e->T, e->hooks);
     if (e->fused) {
         ap.upload(&e->d_ftab, ft.ftab.data(), sizeof(double) * ft.ftab.size());
         ap.upload(&e->d_pos, ft.pos.data(), sizeof(double) * ft.pos.size());
         ap.upload(&e->d_fseg, ft.fseg.data(), sizeof(double) * ft.fseg.size());
         ap.plain(&e->d_mtab, sizeof(double) * T * vt->mt_row);
         ap.plain(&e->d_ntab, sizeof(double) * T * vt->mt_row);
-        if (C % 64 == 0 && !hook_env("RXHIP_BACKWARD_LANES")) {
+        if (plan::gtab_tables(e->n_chains, e->hooks)) {
             ap.plain(&e->d_gtab, sizeof(double) * T * vt->gt_row);
             ap.plain(&e->d_segend, sizeof(double) * Sg * vt->se_size);
             ap.plain(&e->d_sblk, sizeof(double) * Sg * (size_t)smooth_blocks_per_segment(e->L) * 3 * e->d * e->d);
@@ -2266,41 +2212,8 @@ rxhip_status rxhip_lgssm_create(const rxhip_lgssm_desc* ds, rxhip_engine** out) 
     }
     if (rxhip_status st = arena_commit(e, ap)) return st;
     tr.mark("lanes: arena", -1);   // (accounted by arena_commit itself)
-    if (e->fused) {  // the per-time-index maps of the one-pass schedule: data-independent, once per engine
-        TimeTabParams q{};
-        q.T = e->T; q.L = e->L; q.pos = e->d_pos; q.scan = e->d_scan; q.mtab = e->d_mtab; q.ntab = e->d_ntab; q.vtab = e->d_vtab;
-        q.status = e->d_status;
-        HIPCHK(e, hipEventCreate(&e->ev_tab0));
-        HIPCHK(e, hipEventCreate(&e->ev_tab1));
-        HIPCHK(e, hipEventRecord(e->ev_tab0, e->stream));
-        vt->time_tables(q, e->stream);
-        if (e->d_gtab) {
-            SmoothTabParams sq{};
-            sq.T = e->T; sq.L = e->L; sq.S = e->S; sq.vtab = e->d_vtab; sq.ntab = e->d_ntab; sq.scan = e->d_scan;
-            sq.gtab = e->d_gtab; sq.segend = e->d_segend; sq.blk = e->d_sblk; sq.status = e->d_status;
-            sq.rev = rev_cand ? 1 : 0; sq.amp = e->d_amp; sq.ainv = e->d_ainv; sq.ckfail = e->d_ckfail;
-            vt->smooth_tables(sq, e->h_cst0.data(), e->stream);
-            if (rev_cand) {   // the largest stride whose windows all pass the bound (one word: a bit per failing stride 8, 16, 32)
-                int ckfail = 0;
-                HIPCHK(e, hipMemcpyAsync(&ckfail, e->d_ckfail, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-                HIPCHK(e, hipStreamSynchronize(e->stream));
-                e->ck_log2 = 0;
-                if (ck_forced) {
-                    while ((1 << e->ck_log2) < ck_forced) ++e->ck_log2;
-                } else {
-                    for (int k = 2; k >= 0 && !e->ck_log2; --k)
-                        if (!((ckfail >> k) & 1)) e->ck_log2 = 3 + k;
-                }
-                if (!e->ck_log2) {   // no admissible stride: the records schedule, whose F slot holds F_t (rebuild the rows)
-                    sq.rev = 0;
-                    vt->smooth_tables(sq, e->h_cst0.data(), e->stream);
-                }
-            }
-        }
-        HIPCHK(e, hipEventRecord(e->ev_tab1, e->stream));
-        // no synchronisation here: the table kernels are ordered before every sweep on the engine's stream, and a covariance
-        // that is not positive definite raises the status flag the first run reports (RXHIP_ERR_NOT_POSDEF)
-        HIPCHK(e, hipGetLastError());
+    if (e->fused) {
+        if (rxhip_status st = lanes_time_tables(e, rev_cand, ck_forced)) return st;
         tr.mark("lanes: device tables (enqueued)", STAGE_TABLES_DEVICE);
     }
     if (rev_cand) {   // z records: one slot per checkpoint (+ the t = 0 record of the boundary scan), or one per time index
@@ -2310,6 +2223,46 @@ rxhip_status rxhip_lgssm_create(const rxhip_lgssm_desc* ds, rxhip_engine** out) 
         HIPCHK(e, hipMalloc(&e->d_filt, sizeof(double) * slots * MP2 * 2 * (((C + 63) / 64) * 64)));
     }
     return RXHIP_OK;
+}
+
+rxhip_status rxhip_lgssm_create(const rxhip_lgssm_desc* ds, rxhip_engine** out) {
+    if (!out) return RXHIP_ERR_BADARG;
+    *out = nullptr;
+    const LgssmVtbl* vt = nullptr;
+    bool dense = false;
+    if (rxhip_status st = validate_desc(ds, &vt, &dense)) return st;
+    if (dense && conditioning_guard().load())
+        if (rxhip_status st = check_envelope(ds)) return st;
+    const ScheduleHooks hooks = ScheduleHooks::read(hook_env);   // once per engine: every later decision reads e->hooks
+    std::string pkey;
+    if (engine_pool_key(ds, hooks, pkey))
+        if (rxhip_engine* hit = engine_pool_take(pkey)) {
+            *out = hit;
+            return RXHIP_OK;
+        }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return RXHIP_ERR_NO_DEVICE;
+
+    rxhip_engine* e = new rxhip_engine();
+    *out = e;  // returned even on failure so that rxhip_last_error is readable; caller destroys
+    e->pool_key = pkey;
+    e->hooks = hooks;
+    if (rxhip_status st = create_describe(e, ds, vt, dense)) return st;
+    if (ds->device >= 0) {
+        if (ds->device >= ndev) return fail(e, RXHIP_ERR_BADARG, "device %d out of range (%d visible)", ds->device, ndev);
+        e->device = ds->device;
+    } else
+        HIPCHK(e, hipGetDevice(&e->device));
+    SET_DEVICE(e);
+    if (ds->stream) {
+        e->stream = (hipStream_t)ds->stream;
+    } else {
+        HIPCHK(e, stream_acquire(e->device, &e->stream));
+        e->own_stream = true;
+    }
+    if (e->gseq) return create_gseq(e, ds);
+    if (dense) return create_dense(e, ds);
+    return create_lanes(e, ds);
 }
 
 
@@ -2694,6 +2647,301 @@ rxhip_status rxhip_run_filter(rxhip_engine* e, int32_t want_fe) {
     if (st) return st;
     return rxhip_sync(e);
 }
+// What one call of run_impl runs, resolved ONCE from the engine, `filter` and `want_fe` (and the engine's hooks): the iteration loop dispatches on
+// these fields and evaluates no schedule predicate of its own.
+enum class RunFamily { Mseg, Gseq, DenseSplit, Dense, OnePass, SmallSweep, FourPhase, Elements };
+struct RunPlan {
+    RunFamily family = RunFamily::Elements;
+    bool filter = false, fe = false;
+    bool segments = false;        // S > 0: there is a sweep beyond the boundary scan
+    bool info = false;            // MFMA path: the information-form kernels (smoothing runs with S > 0), which evaluate the free energy themselves
+    bool elem_full = false, no_frozen = false;   // fixed-point exits off (rxhip_set_fixed_point_exits, RXHIP_ELEM_FULL / RXHIP_NO_FROZEN)
+    bool noise_in_sweep = false;  // an unknown observation-noise precision: the backward sweep leaves the residual second moments per (segment, chain) behind
+    bool tinv_records = false;    // mean-only forward records behind the fixed point of V_f (k_forward_tinv / k_backward_tinv)
+    bool bnd_in_sweep = false;    // reverse-filter sweep: the boundary recursion inside the waves of k_backward_sh_rev, no scan launch
+    bool scan_tab = false;        // lanes: the table-driven boundary scan (boundary_scan_tab) instead of the general one
+    bool backward_sh = false;     // lanes: the table-driven backward sweep (k_backward_sh / k_backward_sh_rev) instead of the lanes' own
+    bool elements_pass = false;   // Elements: several segments, their elements computed in the lane (k_seg_elements)
+    int fe_slots = 0;             // partial free-energy slots per chain the reduction sums (Params::S of k_fe_few / k_fe_chain)
+    double* fe_part = nullptr;    // … and where they are
+};
+static RunPlan resolve_run(const rxhip_engine* e, bool filter, bool fe) {
+    const ScheduleHooks& h = e->hooks;
+    RunPlan pl;
+    pl.filter = filter;
+    pl.fe = fe;
+    pl.segments = e->S > 0;
+    pl.info = !filter && e->S > 0;
+    pl.noise_in_sweep = e->noise && !e->dense && e->S > 0 && !filter && !h.noise_moments_pass;
+    pl.elem_full = e->full_recursions || h.elem_full;
+    pl.no_frozen = e->full_recursions || h.no_frozen;
+    // per-chain, time-invariant models on long segments: mean-only forward records behind the fixed point of V_f (k_forward_tinv / k_backward_tinv)
+    // (any segment length: interior segments start ON the fixed point; an unknown-noise engine's models are time-invariant within a sweep, and its
+    //  separate moment pass — the test hook — reads posteriors, not records)
+    pl.tinv_records = !e->dense && !e->uniform && e->d_elemx && !e->masked && !e->d_step_model && !filter && e->n_chains % 64 == 0 && e->S > 0 && !pl.elem_full &&
+                      (!e->noise || pl.noise_in_sweep);
+    const bool fused = e->fused && !filter;
+    // k_small_sweep (lgssm_kernels.hpp): the whole four-phase sweep of a small problem in one launch.  Per-kernel profiling keeps the separate
+    // launches (there is nothing to time separately in one kernel); RXHIP_SMALL_SWEEP=0 forces them (the tests compare the two bit for bit).
+    const bool small = !h.small_sweep_off && !e->dense && !fused && e->uniform && !e->sequential && !e->masked && e->d_scan && e->S > 0 &&
+                       e->n_chains <= 16 && e->n_chains * (long long)e->S <= 256 && !e->profiling;   // (≤ 16 chains: the free-energy reduction of k_fe_few)
+    // `missing` observations / per-step constants at d > 4 on the masked MFMA schedule (smoothing; filtering runs: the same sweep, then the
+    // filtered moments from its records) unless the sequential schedule is asked for as the checker of filtering runs
+    const bool mseg = e->gseq && e->mseg && !(filter && h.filter_gseq);
+    pl.family = mseg ? RunFamily::Mseg : e->gseq ? RunFamily::Gseq : e->dense ? (pl.info && e->split ? RunFamily::DenseSplit : RunFamily::Dense)
+                : fused ? RunFamily::OnePass : small ? RunFamily::SmallSweep : (e->S > 0 && !e->sequential) ? RunFamily::FourPhase : RunFamily::Elements;
+    // Reverse-filter sweep of a shared-model batch: every wave of k_backward_sh_rev runs the boundary recursion for its own segment and chains
+    // (boundary_in_sweep), so the scan is no launch of its own and k_fe_seg, which reads the segment-start means, follows the sweep.
+    // RXHIP_BOUNDARY_KERNEL=1 keeps the separate launch: the comparison arm of tests/test_boundary_in_sweep_gpu.py.
+    pl.bnd_in_sweep = fused && e->uniform && e->d_scan && e->d_gtab && e->ck_log2 > 0 && e->S > 0 && !e->noise && !e->masked && !h.boundary_kernel;
+    pl.scan_tab = e->uniform && (e->d_scan || e->S == 0);
+    pl.backward_sh = fused && e->d_gtab;
+    pl.elements_pass = pl.family == RunFamily::Elements && e->d_elemx;   // masked / per-step schedules with several segments
+    pl.fe_slots = e->S + (e->noise ? 1 : 0);   // + the Wishart slot
+    pl.fe_part = e->d_fe_part;
+    if (mseg) {   // slots of kd_forward_info / kd_backward_info / kd_fe_resid over the mseg segments
+        pl.fe_part = e->m_fe_part;
+        pl.fe_slots = 2 * e->mS - 1 + (int)mseg_resid_slots(e->T, e->m_dpad, e->dy, e->m_stepm, e->m_models);
+    }
+    // residual quadratic forms at the smoothed means (parallel over all steps), then 2S partial slots of kd_forward_info / kd_backward_info + kd_fe_resid's
+    if (e->dense && !e->gseq && pl.info) pl.fe_slots = 2 * e->S - 1 + fe_resid_blocks(e->T, e->dpad, e->dyk);
+    return pl;
+}
+static Params fill_params(const rxhip_engine* e, const RunPlan& pl) {
+    Params p;
+    p.T = e->T;
+    p.n_chains = e->n_chains;
+    p.S = e->S;
+    p.L = e->L;
+    p.n_models = e->n_models;
+    p.y = e->d_y;
+    p.filt = e->d_filt;
+    p.nb64 = (e->n_chains + 63) / 64;
+    p.ck_log2 = e->ck_log2;
+    p.nck = e->nck;
+    p.ainv = e->d_ainv;
+    p.vtab = e->d_vtab;
+    p.scan = e->d_scan;
+    p.mean = e->d_mean;
+    p.cov = e->d_cov;
+    p.cst = e->d_cst;
+    p.tab = e->d_tab;
+    p.agg = e->d_agg;
+    p.chain_model = e->d_chain_model;
+    p.elem = e->d_elem;
+    p.fstart = e->d_fstart;
+    p.beta = e->d_beta;
+    p.fe_part = e->d_fe_part;
+    p.fe_chain = e->d_fe_chain;
+    p.fe_total = e->d_fe_total;
+    p.status = e->d_status;
+    p.filter = pl.filter ? 1 : 0;
+    p.masked = e->masked ? 1 : 0;
+    p.step_model = e->d_step_model;
+    p.elemx = e->d_elemx;
+    p.noise_B = pl.noise_in_sweep ? e->n_B : nullptr;
+    p.noise_part = pl.noise_in_sweep ? e->n_part : nullptr;
+    p.elem_full = pl.elem_full ? 1 : 0;
+    p.tinv_records = pl.tinv_records ? 1 : 0;
+    const bool fused = pl.family == RunFamily::OnePass;
+    p.ftab = fused ? e->d_ftab : nullptr; p.mtab = fused ? e->d_mtab : nullptr; p.ntab = fused ? e->d_ntab : nullptr;
+    p.fseg = fused ? e->d_fseg : nullptr; p.fe_const = e->fe_const;
+    p.fe_scale = pl.filter ? 1.0 / (double)e->T : 1.0;
+    return p;
+}
+static DenseParams fill_dense_params(const rxhip_engine* e, const RunPlan& pl) {
+    DenseParams dp{};
+    if (!(e->dense && !e->gseq)) return dp;
+    dp.T = e->T; dp.n_chains = e->wg_chains; dp.S = e->S; dp.L = e->L; dp.d = e->dpad; dp.d_out = e->d; dp.dy = e->dyk;
+    dp.pack = e->pack; dp.d_sub = 8; dp.dy_sub = e->dy;
+    dp.models = e->n_models > 1 ? e->d_models : nullptr; dp.chain_model = e->d_chain_model;
+    dp.y = e->d_y; dp.filt = e->d_filt; dp.vend = e->d_vend; dp.mean = e->d_mean; dp.cov = e->d_cov; dp.cst = e->d_cst; dp.tab = e->d_tab;
+    dp.bnd = e->d_bnd; dp.qtab = e->d_qtab; dp.canon = e->d_canon; dp.loc = e->d_loc; dp.sg = e->scan_sg; dp.ng = e->scan_ng;
+    dp.aggpart = e->d_aggpart; dp.agg_oc = e->agg_oc; dp.agg_kc = e->agg_kc; dp.Llast = e->Llast;
+    dp.scanm = e->d_scanm; dp.elem = e->d_elem; dp.fstart_m = e->d_fstart_m; dp.beta_xi = e->d_beta_xi;
+    dp.fe_part = e->d_fe_part; dp.status = e->d_status;
+    dp.filter = pl.filter ? 1 : 0;
+    dp.no_frozen = pl.no_frozen ? 1 : 0;
+    return dp;
+}
+// a run starts from the @initialization marginal of W (iterations re-push the data: batch.jl:391-430)
+static rxhip_status fill_noise_params(rxhip_engine* e, const RunPlan& pl, int32_t iterations, NoiseParams& np) {
+    if (pl.filter) return fail(e, RXHIP_ERR_BADARG, "run_filter: an engine with an unknown noise precision has no streaming twin");
+    const bool noise_in_sweep = pl.noise_in_sweep;
+    np.T = e->T; np.n_chains = e->n_chains; np.S = e->S; np.y = e->d_y; np.mean = e->d_mean; np.cov = e->d_cov; np.B = e->n_B;
+    np.cst = e->d_cst; np.prior = e->n_prior; np.state = e->n_state; np.fe_part = e->d_fe_part; np.status = e->d_status;
+    np.part = e->n_part; np.slices = noise_in_sweep ? e->S : e->n_slices; np.moments_in_sweep = noise_in_sweep ? 1 : 0;
+    if (iterations > e->n_hist_cap) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        if (e->n_hist) HIPCHK(e, hipFree(e->n_hist));
+        e->n_hist = nullptr;
+        HIPCHK(e, hipMalloc(&e->n_hist, sizeof(double) * (size_t)iterations * (size_t)e->n_chains * (1 + (size_t)e->dy * e->dy)));
+        e->n_hist_cap = iterations;
+    }
+    np.hist = e->n_hist;
+    if (!(e->noise_continue && e->ran)) e->vt->noise_reset(np, e->stream);
+    return RXHIP_OK;
+}
+
+static rxhip_status run_mseg(rxhip_engine* e, const RunPlan& pl) {
+    if (rxhip_status st = mseg_run(e, pl.fe, pl.filter)) return st;
+    e->records_hold_gains = !pl.filter && !e->m_wave8_last;   // (the in-wave d ≤ 8 sweep keeps records of its own shape)
+    return RXHIP_OK;
+}
+static rxhip_status run_gseq(rxhip_engine* e, const RunPlan& pl) {
+    rxhip_status st;
+    const bool fe = pl.fe, filter = pl.filter;
+    GseqParams gq{};
+    gq.T = e->T; gq.n_chains = e->n_chains; gq.d = e->d; gq.dy = e->dy; gq.ptt = e->ptt; gq.fe = fe ? 1 : 0; gq.y = e->d_y;
+    gq.mean = e->d_mean; gq.cov = e->d_cov; gq.user = e->d_user; gq.prior = e->d_prior; gq.chain_model = e->d_chain_model;
+    gq.step_model = e->d_step_model; gq.fe_part = e->d_fe_part; gq.status = e->d_status;
+    const size_t lds = gseq_lds_bytes(e->d, e->dy);
+    if ((st = prof_begin(e, RXHIP_K_FORWARD))) return st;
+    hipLaunchKernelGGL(k_gseq_forward, dim3((unsigned)e->n_chains), dim3(256), lds, e->stream, gq);
+    if ((st = prof_end(e))) return st;
+    if (!filter && e->T > 1) {
+        if ((st = prof_begin(e, RXHIP_K_BACKWARD))) return st;
+        hipLaunchKernelGGL(k_gseq_backward, dim3((unsigned)e->n_chains), dim3(256), lds, e->stream, gq);
+        if ((st = prof_end(e))) return st;
+    }
+    return RXHIP_OK;
+}
+static rxhip_status run_dense(rxhip_engine* e, const RunPlan& pl, const DenseParams& dp, bool was_cov_current) {
+    rxhip_status st;
+    const bool fe = pl.fe, info = pl.info;
+    if (pl.segments) {
+        if ((st = prof_begin(e, RXHIP_K_SEG_AGGREGATE))) return st;
+        DENSE_DISPATCH(e->nt, seg_aggregate(dp, e->stream));
+        if ((st = prof_end(e))) return st;
+    }
+    // smoothing runs with S > 0 evaluate the free energy in the forward / backward kernels (information form);
+    // filtering runs and single-observation chains keep the evidence terms of the scan + covariance-form forward kernel
+    if ((st = prof_begin(e, RXHIP_K_BOUNDARY_SCAN))) return st;
+    DENSE_DISPATCH(e->nt, boundary_scan(dp, fe && !info, e->stream));
+    if ((st = prof_end(e))) return st;
+    if (pl.family == RunFamily::DenseSplit) {
+        SplitParams sq{};
+        sq.p = dp; sq.D = e->dpad; sq.rec = dense_rec(e->nt); sq.dtab = e->d_dtab; sq.vlast = e->d_vlast; sq.vstab = e->d_vstab;
+        sq.fe_const = e->d_fe_const;
+        if (!e->split_ready) {  // the model pass: the full kernels on ONE workgroup chain, their records -> tables
+            DenseParams mp = dp;
+            mp.vlast = e->d_vlast;
+            mp.full_records = 1;   // kd_split_tables reads the matrices of every time index
+            DENSE_DISPATCH(e->nt, forward_info(mp, true, e->stream, 1));
+            DENSE_DISPATCH(e->nt, backward_info(mp, true, e->stream, 1));
+            hipLaunchKernelGGL(kd_split_tables, dim3((unsigned)e->T), dim3(256), 0, e->stream, sq);
+            hipLaunchKernelGGL(kd_split_save, dim3(256), dim3(256), 0, e->stream, sq, (long long)e->n_chains);
+            e->split_ready = true;
+        }
+        if ((st = prof_begin(e, RXHIP_K_FORWARD))) return st;
+        const long long per_wg = 4 * (64 / e->dpad);  // chains of one segment per workgroup
+        const dim3 lds_grid((unsigned)((e->wg_chains + per_wg - 1) / per_wg), (unsigned)e->S);
+        dense_vt(e->nt)->split_forward(sq, lds_grid, e->stream);
+        if ((st = prof_end(e))) return st;
+        if ((st = prof_begin(e, RXHIP_K_BACKWARD))) return st;
+        dense_vt(e->nt)->split_backward(sq, lds_grid, e->stream);
+        // covariances: every sweep, or (mode 1) when somebody asks for them; the constant free-energy slots every sweep
+        const bool lazy = e->cov_mode == 1 && e->H == 0;
+        if (lazy && was_cov_current) e->cov_current = true;   // nothing in this schedule touches the array
+        else if (lazy) e->cov_pending = true;
+        hipLaunchKernelGGL(kd_split_broadcast, dim3(lazy ? 64 : 2048), dim3(256), 0, e->stream, sq, (long long)e->n_chains, fe ? 1 : 0, lazy ? 0 : 1);
+        if ((st = prof_end(e))) return st;
+    } else if (pl.segments) {
+        if ((st = prof_begin(e, RXHIP_K_FORWARD))) return st;
+        if (info) { DENSE_DISPATCH(e->nt, forward_info(dp, fe, e->stream, -1)); }
+        else { DENSE_DISPATCH(e->nt, forward(dp, fe, e->stream)); }
+        if ((st = prof_end(e))) return st;
+        if (info) {
+            if ((st = prof_begin(e, RXHIP_K_BACKWARD))) return st;
+            DENSE_DISPATCH(e->nt, backward_info(dp, fe, e->stream, -1));
+            e->records_hold_gains = e->pack == 1;
+            if ((st = prof_end(e))) return st;
+        }
+    }
+    return RXHIP_OK;
+}
+static rxhip_status run_lanes(rxhip_engine* e, const RunPlan& pl, const Params& p) {
+    rxhip_status st;
+    const bool fe = pl.fe, fused = pl.family == RunFamily::OnePass, bnd_in_sweep = pl.bnd_in_sweep;
+    if (fused) {  // one pass over the observations: known-start recursion + z_t records + evidence parts
+        if ((st = prof_begin(e, RXHIP_K_FORWARD))) return st;
+        e->vt->forward0(p, e->h_cst0.data(), fe, e->ck_log2 > 0, e->stream);
+        if ((st = prof_end(e))) return st;
+    } else if (pl.family == RunFamily::SmallSweep) {   // a few chains, a short series: aggregate, boundary scan, forward, backward and the free energy in ONE launch
+        e->vt->small_sweep(p, e->h_cst0.data(), fe, e->stream);
+        return RXHIP_OK;
+    } else if (pl.family == RunFamily::FourPhase) {
+        if ((st = prof_begin(e, RXHIP_K_SEG_AGGREGATE))) return st;
+        e->vt->seg_aggregate(p, e->h_cst0.data(), e->uniform, e->stream);
+        if ((st = prof_end(e))) return st;
+    } else if (pl.elements_pass) {  // masked / per-step schedules with several segments: the elements are computed in the lane
+        if ((st = prof_begin(e, RXHIP_K_SEG_AGGREGATE))) return st;
+        e->vt->seg_elements(p, e->stream);
+        if ((st = prof_end(e))) return st;
+    }
+    if (!bnd_in_sweep) {
+        if ((st = prof_begin(e, RXHIP_K_BOUNDARY_SCAN))) return st;
+        if (pl.scan_tab) e->vt->boundary_scan_tab(p, e->h_cst0.data(), fe, e->stream);
+        else e->vt->boundary_scan(p, e->h_cst0.data(), e->uniform, fe, e->stream);
+        if ((st = prof_end(e))) return st;
+    }
+    if (pl.segments) {
+        if (!fused) {
+            if ((st = prof_begin(e, RXHIP_K_FORWARD))) return st;
+            e->vt->forward(p, e->h_cst0.data(), e->uniform, fe, e->stream);
+            if ((st = prof_end(e))) return st;
+        } else if (fe && !bnd_in_sweep)
+            e->vt->fe_seg(p, e->stream);
+        if (!pl.filter) {
+            if ((st = prof_begin(e, RXHIP_K_BACKWARD))) return st;
+            if (pl.backward_sh) e->vt->backward_sh(p, e->h_cst0.data(), e->d_gtab, e->d_segend, e->ck_log2 > 0, bnd_in_sweep ? (fe ? 2 : 1) : 0, e->stream);
+            else e->vt->backward(p, e->h_cst0.data(), e->uniform, e->stream);
+            if ((st = prof_end(e))) return st;
+        }
+        if (fe && bnd_in_sweep) e->vt->fe_seg(p, e->stream);
+    }
+    return RXHIP_OK;
+}
+// after the sweep of every family: q(W) of a noise engine, the free-energy reduction, known inputs, the unobserved tail
+static rxhip_status run_tail(rxhip_engine* e, const RunPlan& pl, const Params& p, const DenseParams& dp, NoiseParams& np, int it) {
+    rxhip_status st;
+    if (e->noise) {   // q(W) of every chain from this sweep's q(x); its free-energy slot; the constants of the next sweep
+        np.iteration = it;
+        e->vt->noise_update(np, e->stream);
+    }
+    if (pl.fe && pl.family != RunFamily::SmallSweep) {
+        if ((st = prof_begin(e, RXHIP_K_FE_REDUCE))) return st;
+        const int nb = (int)((e->n_chains + 63) / 64);
+        Params pr = p;
+        pr.S = pl.fe_slots;
+        pr.fe_part = pl.fe_part;
+        if (pl.info && (pl.family == RunFamily::Dense || pl.family == RunFamily::DenseSplit)) launch_fe_resid(dp, e->stream);
+        if (e->n_chains <= 16) {
+            hipLaunchKernelGGL(k_fe_few, dim3(1), dim3(256), 0, e->stream, pr);
+        } else {
+            hipLaunchKernelGGL(k_fe_chain, dim3(nb), dim3(256), 0, e->stream, pr, e->d_fe_blocks);
+            hipLaunchKernelGGL(k_fe_total, dim3(1), dim3(256), 0, e->stream, p, (const double*)e->d_fe_blocks, nb);
+        }
+        if ((st = prof_end(e))) return st;
+    }
+    if (e->d_mu) {  // known inputs: back from x − μ to x (the free-energy terms above are invariant under the shift)
+        hipLaunchKernelGGL(k_shift_rows, dim3(2048), dim3(256), 0, e->stream, e->d_mean, (const double*)e->d_mu, e->T, e->n_chains, e->d, 1.0, e->off_chain ? 1 : 0);
+    }
+    if (e->H > 0 && e->dense) {  // the unobserved tail on the MFMA path: generic-dimension forecast, one workgroup per chain
+        GenericParams gp{};
+        gp.T = e->T; gp.H = e->H; gp.n_chains = e->n_chains; gp.d = e->d; gp.dy = e->dy; gp.mean = e->d_mean; gp.cov = e->d_cov;
+        gp.user = e->d_user; gp.cx = e->d_cx; gp.off_chain = e->off_chain ? 1 : 0; gp.chain_model = e->d_chain_model; gp.step_model = e->d_step_model; gp.status = e->d_status;
+        hipLaunchKernelGGL(k_forecast_generic, dim3((unsigned)e->n_chains), dim3(256), generic_forecast_lds(e->d), e->stream, gp);
+    }
+    if (e->H > 0 && !e->dense) {  // the unobserved tail: forward messages from the last filtered (= smoothed) belief
+        PredictParams pp{};
+        pp.T = e->T; pp.H = e->H; pp.n_chains = e->n_chains; pp.mean = e->d_mean; pp.cov = e->d_cov; pp.cst = e->d_cst;
+        pp.chain_model = e->d_chain_model; pp.step_model = e->d_step_model; pp.status = e->d_status; pp.cx = e->d_cx; pp.off_chain = e->off_chain ? 1 : 0;
+        e->vt->forecast(pp, e->stream);
+    }
+    return RXHIP_OK;
+}
+
 static rxhip_status run_impl(rxhip_engine* e, int32_t iterations, int32_t want_fe, bool filter) {
     if (!e) return RXHIP_ERR_BADARG;
     if (e->kind == 2) return rxhip::hgf_run_async(e, iterations, want_fe);
@@ -2725,247 +2973,28 @@ static rxhip_status run_impl(rxhip_engine* e, int32_t iterations, int32_t want_f
         e->fe_total_cap = iterations;
         HIPCHK(e, hipMalloc(&e->d_fe_total, sizeof(double) * e->fe_total_cap));
     }
-    Params p;
-    p.T = e->T;
-    p.n_chains = e->n_chains;
-    p.S = e->S;
-    p.L = e->L;
-    p.n_models = e->n_models;
-    p.y = e->d_y;
-    p.filt = e->d_filt;
-    p.nb64 = (e->n_chains + 63) / 64;
-    p.ck_log2 = e->ck_log2;
-    p.nck = e->nck;
-    p.ainv = e->d_ainv;
-    p.vtab = e->d_vtab;
-    p.scan = e->d_scan;
-    p.mean = e->d_mean;
-    p.cov = e->d_cov;
-    p.cst = e->d_cst;
-    p.tab = e->d_tab;
-    p.agg = e->d_agg;
-    p.chain_model = e->d_chain_model;
-    p.elem = e->d_elem;
-    p.fstart = e->d_fstart;
-    p.beta = e->d_beta;
-    p.fe_part = e->d_fe_part;
-    p.fe_chain = e->d_fe_chain;
-    p.fe_total = e->d_fe_total;
-    p.status = e->d_status;
-    p.filter = filter ? 1 : 0;
-    p.masked = e->masked ? 1 : 0;
-    p.step_model = e->d_step_model;
-    p.elemx = e->d_elemx;
-    // an unknown observation-noise precision: the backward sweep leaves the residual second moments per (segment, chain) behind
-    const bool noise_in_sweep = e->noise && !e->dense && e->S > 0 && !filter && !hook_env("RXHIP_NOISE_MOMENTS_PASS");
-    p.noise_B = noise_in_sweep ? e->n_B : nullptr;
-    p.noise_part = noise_in_sweep ? e->n_part : nullptr;
-    p.elem_full = (e->full_recursions || hook_env("RXHIP_ELEM_FULL")) ? 1 : 0;
-    // per-chain, time-invariant models on long segments: mean-only forward records behind the fixed point of V_f (k_forward_tinv / k_backward_tinv)
-    // (any segment length: interior segments start ON the fixed point; an unknown-noise engine's models are time-invariant within a sweep, and its
-    //  separate moment pass — the test hook — reads posteriors, not records)
-    p.tinv_records = (!e->dense && !e->uniform && e->d_elemx && !e->masked && !e->d_step_model && !filter && e->n_chains % 64 == 0 && e->S > 0 && !p.elem_full &&
-                      (!e->noise || noise_in_sweep)) ? 1 : 0;
-    const bool fused = e->fused && !filter;
-    p.ftab = fused ? e->d_ftab : nullptr; p.mtab = fused ? e->d_mtab : nullptr; p.ntab = fused ? e->d_ntab : nullptr;
-    p.fseg = fused ? e->d_fseg : nullptr; p.fe_const = e->fe_const;
-    p.fe_scale = filter ? 1.0 / (double)e->T : 1.0;
     const bool fe = want_fe != 0;
-    // k_small_sweep (lgssm_kernels.hpp): the whole four-phase sweep of a small problem in one launch.  Per-kernel profiling keeps the separate
-    // launches (there is nothing to time separately in one kernel); RXHIP_SMALL_SWEEP=0 forces them (the tests compare the two bit for bit).
-    const bool small_off = small_sweep_off();
-    const bool small_now = !small_off && !e->dense && !fused && e->uniform && !e->sequential && !e->masked && e->d_scan && e->S > 0 &&
-                           e->n_chains <= 16 && e->n_chains * (long long)e->S <= 256 && !e->profiling;   // (≤ 16 chains: the free-energy reduction of k_fe_few)
-    rxhip_status st;
-    DenseParams dp{};
-    if (e->dense && !e->gseq) {
-        dp.T = e->T; dp.n_chains = e->wg_chains; dp.S = e->S; dp.L = e->L; dp.d = e->dpad; dp.d_out = e->d; dp.dy = e->dyk;
-        dp.pack = e->pack; dp.d_sub = 8; dp.dy_sub = e->dy;
-        dp.models = e->n_models > 1 ? e->d_models : nullptr; dp.chain_model = e->d_chain_model;
-        dp.y = e->d_y; dp.filt = e->d_filt; dp.vend = e->d_vend; dp.mean = e->d_mean; dp.cov = e->d_cov; dp.cst = e->d_cst; dp.tab = e->d_tab;
-        dp.bnd = e->d_bnd; dp.qtab = e->d_qtab; dp.canon = e->d_canon; dp.loc = e->d_loc; dp.sg = e->scan_sg; dp.ng = e->scan_ng;
-        dp.aggpart = e->d_aggpart; dp.agg_oc = e->agg_oc; dp.agg_kc = e->agg_kc; dp.Llast = e->Llast;
-        dp.scanm = e->d_scanm; dp.elem = e->d_elem; dp.fstart_m = e->d_fstart_m; dp.beta_xi = e->d_beta_xi;
-        dp.fe_part = e->d_fe_part; dp.status = e->d_status;
-        dp.filter = p.filter;
-        dp.no_frozen = (e->full_recursions || hook_env("RXHIP_NO_FROZEN")) ? 1 : 0;
-    }
+    const RunPlan pl = resolve_run(e, filter, fe);
+    Params p = fill_params(e, pl);
+    const DenseParams dp = fill_dense_params(e, pl);
     NoiseParams np{};
-    if (e->noise) {   // a run starts from the @initialization marginal of W (iterations re-push the data: batch.jl:391-430)
-        if (filter) return fail(e, RXHIP_ERR_BADARG, "run_filter: an engine with an unknown noise precision has no streaming twin");
-        np.T = e->T; np.n_chains = e->n_chains; np.S = e->S; np.y = e->d_y; np.mean = e->d_mean; np.cov = e->d_cov; np.B = e->n_B;
-        np.cst = e->d_cst; np.prior = e->n_prior; np.state = e->n_state; np.fe_part = e->d_fe_part; np.status = e->d_status;
-        np.part = e->n_part; np.slices = noise_in_sweep ? e->S : e->n_slices; np.moments_in_sweep = noise_in_sweep ? 1 : 0;
-        if (iterations > e->n_hist_cap) {
-            HIPCHK(e, hipStreamSynchronize(e->stream));
-            if (e->n_hist) HIPCHK(e, hipFree(e->n_hist));
-            e->n_hist = nullptr;
-            HIPCHK(e, hipMalloc(&e->n_hist, sizeof(double) * (size_t)iterations * (size_t)e->n_chains * (1 + (size_t)e->dy * e->dy)));
-            e->n_hist_cap = iterations;
-        }
-        np.hist = e->n_hist;
-        if (!(e->noise_continue && e->ran)) e->vt->noise_reset(np, e->stream);
-    }
+    if (e->noise)
+        if (rxhip_status st = fill_noise_params(e, pl, iterations, np)) return st;
     for (int it = 0; it < iterations; ++it) {
         p.iteration = it;
         // an unknown-noise engine writes the posteriors of a run's LAST iteration only (rxhip_get_marginals is defined as that; the moments q(W) needs
         // are formed inside the sweep): 160 B/U of stores per earlier iteration that nothing ever read
-        p.skip_marginals = (noise_in_sweep && it + 1 < iterations) ? 1 : 0;
-        // `missing` observations / per-step constants at d > 4 on the masked MFMA schedule (smoothing; filtering runs: the same sweep, then the
-        // filtered moments from its records) unless the sequential schedule is asked for as the checker of filtering runs
-        const bool mseg_now = e->gseq && e->mseg && !(filter && hook_env("RXHIP_FILTER_GSEQ"));
-        if (mseg_now) {
-            if ((st = mseg_run(e, fe, filter))) return st;
-            e->records_hold_gains = !filter && !e->m_wave8_last;   // (the in-wave d ≤ 8 sweep keeps records of its own shape)
-        } else if (e->gseq) {
-            GseqParams gq{};
-            gq.T = e->T; gq.n_chains = e->n_chains; gq.d = e->d; gq.dy = e->dy; gq.ptt = e->ptt; gq.fe = fe ? 1 : 0; gq.y = e->d_y;
-            gq.mean = e->d_mean; gq.cov = e->d_cov; gq.user = e->d_user; gq.prior = e->d_prior; gq.chain_model = e->d_chain_model;
-            gq.step_model = e->d_step_model; gq.fe_part = e->d_fe_part; gq.status = e->d_status;
-            const size_t lds = gseq_lds_bytes(e->d, e->dy);
-            if ((st = prof_begin(e, RXHIP_K_FORWARD))) return st;
-            hipLaunchKernelGGL(k_gseq_forward, dim3((unsigned)e->n_chains), dim3(256), lds, e->stream, gq);
-            if ((st = prof_end(e))) return st;
-            if (!filter && e->T > 1) {
-                if ((st = prof_begin(e, RXHIP_K_BACKWARD))) return st;
-                hipLaunchKernelGGL(k_gseq_backward, dim3((unsigned)e->n_chains), dim3(256), lds, e->stream, gq);
-                if ((st = prof_end(e))) return st;
-            }
-        } else if (e->dense) {
-            if (e->S > 0) {
-                if ((st = prof_begin(e, RXHIP_K_SEG_AGGREGATE))) return st;
-                DENSE_DISPATCH(e->nt, seg_aggregate(dp, e->stream));
-                if ((st = prof_end(e))) return st;
-            }
-            // smoothing runs with S > 0 evaluate the free energy in the forward / backward kernels (information form);
-            // filtering runs and single-observation chains keep the evidence terms of the scan + covariance-form forward kernel
-            const bool info = !filter && e->S > 0;
-            if ((st = prof_begin(e, RXHIP_K_BOUNDARY_SCAN))) return st;
-            DENSE_DISPATCH(e->nt, boundary_scan(dp, fe && !info, e->stream));
-            if ((st = prof_end(e))) return st;
-            if (e->S > 0 && info && e->split) {
-                SplitParams sq{};
-                sq.p = dp; sq.D = e->dpad; sq.rec = dense_rec(e->nt); sq.dtab = e->d_dtab; sq.vlast = e->d_vlast; sq.vstab = e->d_vstab;
-                sq.fe_const = e->d_fe_const;
-                if (!e->split_ready) {  // the model pass: the full kernels on ONE workgroup chain, their records -> tables
-                    DenseParams mp = dp;
-                    mp.vlast = e->d_vlast;
-                    mp.full_records = 1;   // kd_split_tables reads the matrices of every time index
-                    DENSE_DISPATCH(e->nt, forward_info(mp, true, e->stream, 1));
-                    DENSE_DISPATCH(e->nt, backward_info(mp, true, e->stream, 1));
-                    hipLaunchKernelGGL(kd_split_tables, dim3((unsigned)e->T), dim3(256), 0, e->stream, sq);
-                    hipLaunchKernelGGL(kd_split_save, dim3(256), dim3(256), 0, e->stream, sq, (long long)e->n_chains);
-                    e->split_ready = true;
-                }
-                if ((st = prof_begin(e, RXHIP_K_FORWARD))) return st;
-                const long long per_wg = 4 * (64 / e->dpad);  // chains of one segment per workgroup
-                const dim3 lds_grid((unsigned)((e->wg_chains + per_wg - 1) / per_wg), (unsigned)e->S);
-                dense_vt(e->nt)->split_forward(sq, lds_grid, e->stream);
-                if ((st = prof_end(e))) return st;
-                if ((st = prof_begin(e, RXHIP_K_BACKWARD))) return st;
-                dense_vt(e->nt)->split_backward(sq, lds_grid, e->stream);
-                // covariances: every sweep, or (mode 1) when somebody asks for them; the constant free-energy slots every sweep
-                const bool lazy = e->cov_mode == 1 && e->H == 0;
-                if (lazy && was_cov_current) e->cov_current = true;   // nothing in this schedule touches the array
-                else if (lazy) e->cov_pending = true;
-                hipLaunchKernelGGL(kd_split_broadcast, dim3(lazy ? 64 : 2048), dim3(256), 0, e->stream, sq, (long long)e->n_chains, fe ? 1 : 0, lazy ? 0 : 1);
-                if ((st = prof_end(e))) return st;
-            } else if (e->S > 0) {
-                if ((st = prof_begin(e, RXHIP_K_FORWARD))) return st;
-                if (info) { DENSE_DISPATCH(e->nt, forward_info(dp, fe, e->stream, -1)); }
-                else { DENSE_DISPATCH(e->nt, forward(dp, fe, e->stream)); }
-                if ((st = prof_end(e))) return st;
-                if (info) {
-                    if ((st = prof_begin(e, RXHIP_K_BACKWARD))) return st;
-                    DENSE_DISPATCH(e->nt, backward_info(dp, fe, e->stream, -1));
-                    e->records_hold_gains = e->pack == 1;
-                    if ((st = prof_end(e))) return st;
-                }
-            }
-        } else if (fused) {  // one pass over the observations: known-start recursion + z_t records + evidence parts
-            if ((st = prof_begin(e, RXHIP_K_FORWARD))) return st;
-            e->vt->forward0(p, e->h_cst0.data(), fe, e->ck_log2 > 0, e->stream);
-            if ((st = prof_end(e))) return st;
-        } else if (small_now) {   // a few chains, a short series: aggregate, boundary scan, forward, backward and the free energy in ONE launch
-            e->vt->small_sweep(p, e->h_cst0.data(), fe, e->stream);
-        } else if (e->S > 0 && !e->sequential) {
-            if ((st = prof_begin(e, RXHIP_K_SEG_AGGREGATE))) return st;
-            e->vt->seg_aggregate(p, e->h_cst0.data(), e->uniform, e->stream);
-            if ((st = prof_end(e))) return st;
-        } else if (e->d_elemx) {  // masked / per-step schedules with several segments: the elements are computed in the lane
-            if ((st = prof_begin(e, RXHIP_K_SEG_AGGREGATE))) return st;
-            e->vt->seg_elements(p, e->stream);
-            if ((st = prof_end(e))) return st;
+        p.skip_marginals = (pl.noise_in_sweep && it + 1 < iterations) ? 1 : 0;
+        rxhip_status st;
+        switch (pl.family) {
+            case RunFamily::Mseg: st = run_mseg(e, pl); break;
+            case RunFamily::Gseq: st = run_gseq(e, pl); break;
+            case RunFamily::DenseSplit:
+            case RunFamily::Dense: st = run_dense(e, pl, dp, was_cov_current); break;
+            default: st = run_lanes(e, pl, p); break;
         }
-        // Reverse-filter sweep of a shared-model batch: every wave of k_backward_sh_rev runs the boundary recursion for its own segment and chains
-        // (boundary_in_sweep), so the scan is no launch of its own and k_fe_seg, which reads the segment-start means, follows the sweep.
-        // RXHIP_BOUNDARY_KERNEL=1 keeps the separate launch: the comparison arm of tests/test_boundary_in_sweep_gpu.py.
-        const char* bnd_env = hook_env("RXHIP_BOUNDARY_KERNEL");
-        const bool bnd_in_sweep = fused && e->uniform && e->d_scan && e->d_gtab && e->ck_log2 > 0 && e->S > 0 && !e->noise && !e->masked &&
-                                  !(bnd_env && std::atoi(bnd_env) != 0);
-        if (!e->dense && !small_now && !bnd_in_sweep) {
-            if ((st = prof_begin(e, RXHIP_K_BOUNDARY_SCAN))) return st;
-            if (e->uniform && (e->d_scan || e->S == 0)) e->vt->boundary_scan_tab(p, e->h_cst0.data(), fe, e->stream);
-            else e->vt->boundary_scan(p, e->h_cst0.data(), e->uniform, fe, e->stream);
-            if ((st = prof_end(e))) return st;
-        }
-        if (!e->dense && e->S > 0 && !small_now) {
-            if (!fused) {
-                if ((st = prof_begin(e, RXHIP_K_FORWARD))) return st;
-                e->vt->forward(p, e->h_cst0.data(), e->uniform, fe, e->stream);
-                if ((st = prof_end(e))) return st;
-            } else if (fe && !bnd_in_sweep)
-                e->vt->fe_seg(p, e->stream);
-            if (!filter) {
-                if ((st = prof_begin(e, RXHIP_K_BACKWARD))) return st;
-                if (fused && e->d_gtab) e->vt->backward_sh(p, e->h_cst0.data(), e->d_gtab, e->d_segend, e->ck_log2 > 0, bnd_in_sweep ? (fe ? 2 : 1) : 0, e->stream);
-                else e->vt->backward(p, e->h_cst0.data(), e->uniform, e->stream);
-                if ((st = prof_end(e))) return st;
-            }
-            if (fe && bnd_in_sweep) e->vt->fe_seg(p, e->stream);
-        }
-        if (e->noise) {   // q(W) of every chain from this sweep's q(x); its free-energy slot; the constants of the next sweep
-            np.iteration = it;
-            e->vt->noise_update(np, e->stream);
-        }
-        if (fe && !small_now) {
-            if ((st = prof_begin(e, RXHIP_K_FE_REDUCE))) return st;
-            const int nb = (int)((e->n_chains + 63) / 64);
-            Params pr = p;
-            if (e->noise) pr.S = p.S + 1;   // + the Wishart slot
-            if (mseg_now) {   // slots of kd_forward_info / kd_backward_info / kd_fe_resid over the mseg segments
-                pr.fe_part = e->m_fe_part;
-                pr.S = 2 * e->mS - 1 + (int)mseg_resid_slots(e->T, e->m_dpad, e->dy, e->m_stepm, e->m_models);
-            }
-            if (e->dense && !e->gseq && !filter && e->S > 0) {
-                // residual quadratic forms at the smoothed means (parallel over all steps), then 2S partial slots of
-                // kd_forward_info / kd_backward_info + kd_fe_resid's
-                launch_fe_resid(dp, e->stream);
-                pr.S = 2 * e->S - 1 + fe_resid_blocks(e->T, e->dpad, e->dyk);
-            }
-            if (e->n_chains <= 16) {
-                hipLaunchKernelGGL(k_fe_few, dim3(1), dim3(256), 0, e->stream, pr);
-            } else {
-                hipLaunchKernelGGL(k_fe_chain, dim3(nb), dim3(256), 0, e->stream, pr, e->d_fe_blocks);
-                hipLaunchKernelGGL(k_fe_total, dim3(1), dim3(256), 0, e->stream, p, (const double*)e->d_fe_blocks, nb);
-            }
-            if ((st = prof_end(e))) return st;
-        }
-        if (e->d_mu) {  // known inputs: back from x − μ to x (the free-energy terms above are invariant under the shift)
-            hipLaunchKernelGGL(k_shift_rows, dim3(2048), dim3(256), 0, e->stream, e->d_mean, (const double*)e->d_mu, e->T, e->n_chains, e->d, 1.0, e->off_chain ? 1 : 0);
-        }
-        if (e->H > 0 && e->dense) {  // the unobserved tail on the MFMA path: generic-dimension forecast, one workgroup per chain
-            GenericParams gp{};
-            gp.T = e->T; gp.H = e->H; gp.n_chains = e->n_chains; gp.d = e->d; gp.dy = e->dy; gp.mean = e->d_mean; gp.cov = e->d_cov;
-            gp.user = e->d_user; gp.cx = e->d_cx; gp.off_chain = e->off_chain ? 1 : 0; gp.chain_model = e->d_chain_model; gp.step_model = e->d_step_model; gp.status = e->d_status;
-            hipLaunchKernelGGL(k_forecast_generic, dim3((unsigned)e->n_chains), dim3(256), generic_forecast_lds(e->d), e->stream, gp);
-        }
-        if (e->H > 0 && !e->dense) {  // the unobserved tail: forward messages from the last filtered (= smoothed) belief
-            PredictParams pp{};
-            pp.T = e->T; pp.H = e->H; pp.n_chains = e->n_chains; pp.mean = e->d_mean; pp.cov = e->d_cov; pp.cst = e->d_cst;
-            pp.chain_model = e->d_chain_model; pp.step_model = e->d_step_model; pp.status = e->d_status; pp.cx = e->d_cx; pp.off_chain = e->off_chain ? 1 : 0;
-            e->vt->forecast(pp, e->stream);
-        }
+        if (!st) st = run_tail(e, pl, p, dp, np, it);
+        if (st) return st;
     }
     HIPCHK(e, hipGetLastError());
     e->last_iterations = iterations;
@@ -3278,7 +3307,7 @@ rxhip_status rxhip_get_node_marginals(rxhip_engine* e, int32_t node_type, double
         gq.chain_model = e->d_chain_model; gq.step_model = e->d_step_model; gq.fe_part = nullptr; gq.status = e->d_status;
         // After a sweep of the information-form kernels (one chain per tile, no model / data split) the smoother gains are still in the
         // records: the cross-covariances are one product per time index.  Otherwise: the sequential re-run.
-        const bool from_records = e->records_hold_gains && !hook_env("RXHIP_JOINTS_GSEQ");
+        const bool from_records = e->records_hold_gains && !e->hooks.joints_gseq;
         if (from_records) {
             DenseParams cp{};
             const int nt = e->mseg ? e->m_nt : e->nt;
