@@ -760,10 +760,12 @@ rxhip_status rxhip_gmm_update(rxhip_engine* e, int32_t want_free_energy);
  * Multivariate Gaussian mixture, mean-field VMP (reference model test/models/mixtures/gmm_multivariate_tests.jl:6-32):
  *     m[k] ~ MvNormal(mean = mu0[k], cov = S0[k]);  w[k] ~ Wishart(nu0[k], V0[k]);  s ~ Dirichlet(alpha0);
  *     z[i] ~ Categorical(s);  y[i] ~ NormalMixture(switch = z[i], m = m, p = w)           (w: precision matrices)
- * d = 1…4; K ≤ 16 (d ≤ 2) or K ≤ 8 (d = 3, 4).  init_*: the `@initialization` marginals q(m[k]) = N(mean, cov),
+ * d = 1…4: K ≤ 16 (d ≤ 2) or K ≤ 8 (d = 3, 4), statistics of a lane in registers.  d = 5…32: K ≤ 16, the pass on the fp64 matrix cores
+ * (csrc/mvgmm_dense_kernels.hpp).  Anything else is RXHIP_ERR_UNSUPPORTED.  init_*: the `@initialization` marginals q(m[k]) = N(mean, cov),
  * q(w[k]) = Wishart(nu, V), q(s) = Dirichlet.  Same handle protocol as the univariate engine: rxhip_set_data(RXHIP_VAR_Y,
  * y [N][d], N*d, 0), rxhip_run / the split-phase rxhip_gmm_begin_run, _accumulate, _statistics_device, _update (statistics:
- * K'(1 + d + d(d+1)/2) + 1 doubles), rxhip_get_free_energy, rxhip_gmm_get_responsibilities.
+ * K'(1 + d + d(d+1)/2) + 1 doubles: per component Σπ | Σπy | Σπyy' packed lower, then Σ_i H[q(z_i)]; K' = K padded to 4, 8, 16 at d ≤ 4,
+ * K' = K at d ≥ 5), rxhip_get_free_energy, rxhip_gmm_get_responsibilities.
  * rxhip_gmm_get_history: hist[iterations][K][2 + d + 2d²] = per component  mean[d] | cov[d][d] | nu | V[d][d] | alpha.
  * ------------------------------------------------------------------------------------------ */
 typedef struct {

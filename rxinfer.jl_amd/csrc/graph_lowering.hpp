@@ -998,7 +998,7 @@ inline rxhip_status lower_mvgmm(const rxhip_graph_desc* g, MvGmm& M) {
         if (!mix.empty() || s_prior >= 0) return unsupported("iid observation nodes next to a mixture");
         const long long mvar = iface(g, iid[0], 1), pvar = iface(g, iid[0], 2);
         const int d = g->var_rows[iface(g, iid[0], 0)];
-        if (d < 1 || d > 4) return unsupported("iid multivariate Gaussian with an unsupported dimension");
+        if (d < 1 || d > 32) return unsupported("iid multivariate Gaussian with an unsupported dimension");
         if (g->var_kind[mvar] != RXHIP_VARKIND_RANDOM || g->var_kind[pvar] != RXHIP_VARKIND_RANDOM) return unsupported("iid Gaussian with a known mean or precision");
         for (long long f : iid) {
             if (iface(g, f, 1) != mvar || iface(g, f, 2) != pvar || g->var_rows[iface(g, f, 0)] != d) return unsupported("observation nodes do not share mean and precision");
@@ -1042,7 +1042,7 @@ inline rxhip_status lower_mvgmm(const rxhip_graph_desc* g, MvGmm& M) {
     if (mix.empty() || s_prior < 0) return unsupported("no NormalMixture nodes / no switch prior");
     const int K = (n_iface(g, mix[0]) - 2) / 2;
     const int d = g->var_rows[iface(g, mix[0], 0)];
-    if (K < 1 || K > 16 || n_iface(g, mix[0]) != 2 + 2 * K || d < 1 || d > 4) return unsupported("mixture with an unsupported number of components / dimension");
+    if (K < 1 || K > 16 || n_iface(g, mix[0]) != 2 + 2 * K || d < 1 || d > 32) return unsupported("mixture with an unsupported number of components / dimension");
     std::vector<long long> mv(K), wv(K);
     for (int k = 0; k < K; ++k) { mv[k] = iface(g, mix[0], 2 + k); wv[k] = iface(g, mix[0], 2 + K + k); }
     long long used = 1;

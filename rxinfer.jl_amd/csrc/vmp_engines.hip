@@ -16,6 +16,7 @@
 #include "hgf_kernels.hpp"
 #pragma clang diagnostic pop
 #include "mvgmm_kernels.hpp"
+#include "mvgmm_dense_kernels.hpp"
 #include "engine.hpp"
 
 using namespace rxhip;
@@ -62,6 +63,23 @@ static int mvg_kt(int d, int K) {
         case 304: MvgLaunch<3, 4>::CALL; break;  case 308: MvgLaunch<3, 8>::CALL; break;                                          \
         case 404: MvgLaunch<4, 4>::CALL; break;  default: MvgLaunch<4, 8>::CALL; break;                                           \
     }
+// d = 5…32 (mvgmm_dense_kernels.hpp): d and K are runtime values, the pass is templated on the tile count ⌈d/16⌉ only
+struct MvdLaunch {
+    static void init(const MvgParams& p, int d, hipStream_t s) { hipLaunchKernelGGL(k_mvgd_init, dim3(p.K), dim3(64), 0, s, p, d); }
+    static void pass(MvgParams p, int d, bool resp, hipStream_t s) {
+        p.write_resp = resp ? 1 : 0;
+        if (mvd_tiles(d) == 1) hipLaunchKernelGGL((k_mvgd_pass<1>), dim3(p.nblocks), dim3(256), 0, s, p, d);
+        else hipLaunchKernelGGL((k_mvgd_pass<2>), dim3(p.nblocks), dim3(256), 0, s, p, d);
+    }
+    static void reduce(const MvgParams& p, int nq, hipStream_t s) { hipLaunchKernelGGL(k_mvg_reduce, dim3(nq), dim3(256), 0, s, p, nq); }
+    static void update(const MvgParams& p, int d, bool fe, hipStream_t s) {
+        if (fe) {
+            hipLaunchKernelGGL((k_mvgd_update<true>), dim3(p.K), dim3(64), 0, s, p, d);
+            hipLaunchKernelGGL(k_mvgd_fe, dim3(1), dim3(64), 0, s, p, d);
+        } else
+            hipLaunchKernelGGL((k_mvgd_update<false>), dim3(p.K), dim3(64), 0, s, p, d);
+    }
+};
 
 
 static GmmParams gmm_params(rxhip_engine* e) {
@@ -165,9 +183,10 @@ rxhip_status rxhip_mvgmm_create(const rxhip_mvgmm_desc* ds, rxhip_engine** out) 
     if (!ds || ds->N <= 0 || ds->K <= 0 || ds->d <= 0 || !ds->mu0 || !ds->S0 || !ds->nu0 || !ds->V0 || !ds->alpha0 ||
         !ds->init_m_mean || !ds->init_m_cov || !ds->init_w_nu || !ds->init_w_V || !ds->init_s_alpha)
         return RXHIP_ERR_BADARG;
-    if (ds->d > 4 || mvg_kt(ds->d, ds->K) == 0) return RXHIP_ERR_UNSUPPORTED;
-    const int d = ds->d, dd = d * d, K = ds->K, KT = mvg_kt(d, K);
-    const int SZ = 2 + d + 2 * dd, PRI = d + 2 * dd + 4, STAT = 1 + d + d * (d + 1) / 2, DRV = 1 + d * (d + 1) / 2 + d;
+    const bool dense = ds->d > 4;   // d = 5…32 on the matrix cores (mvgmm_dense_kernels.hpp): no component padding, K ≤ 16
+    if (dense ? (ds->d > MVD_DMAX || ds->K > MVD_KMAX) : mvg_kt(ds->d, ds->K) == 0) return RXHIP_ERR_UNSUPPORTED;
+    const int d = ds->d, dd = d * d, K = ds->K, KT = dense ? K : mvg_kt(d, K);
+    const int SZ = 2 + d + 2 * dd, PRI = d + 2 * dd + 4, STAT = 1 + d + d * (d + 1) / 2, DRV = dense ? mvd_drv_stride(d) : 1 + d * (d + 1) / 2 + d;
     for (int k = 0; k < K; ++k)
         if (!(ds->nu0[k] > d - 1) || !(ds->init_w_nu[k] > d - 1) || !(ds->alpha0[k] > 0) || !(ds->init_s_alpha[k] > 0)) return RXHIP_ERR_NOT_POSDEF;
     int ndev = 0;
@@ -191,8 +210,9 @@ rxhip_status rxhip_mvgmm_create(const rxhip_mvgmm_desc* ds, rxhip_engine** out) 
         HIPCHK(e, stream_acquire(e->device, &e->stream));
         e->own_stream = true;
     }
-    long long nb = (e->g.N + 255) / 256;
-    if (nb > 1024) nb = 1024;
+    long long nb = dense ? (e->g.N + MVD_TP - 1) / MVD_TP : (e->g.N + 255) / 256;
+    const long long nb_cap = dense ? MVD_GRID_CAP : 1024;
+    if (nb > nb_cap) nb = nb_cap;
     e->g.nblocks = (int)nb;
     // prior block per component: mu0 | S0⁻¹ | nu0 | V0⁻¹ | alpha0 | log|S0| | log|V0|   (inverses / log-determinants once, here)
     std::vector<double> prior((size_t)K * PRI), init((size_t)K * SZ), tmp(dd);
@@ -220,7 +240,7 @@ rxhip_status rxhip_mvgmm_create(const rxhip_mvgmm_desc* ds, rxhip_engine** out) 
     HIPCHK(e, hipMalloc(&e->g.d_par, sizeof(double) * init.size()));
     HIPCHK(e, hipMalloc(&e->g.d_drv, sizeof(double) * (size_t)KT * DRV));
     HIPCHK(e, hipMalloc(&e->g.d_partial, sizeof(double) * (size_t)nb * e->g.nq));
-    HIPCHK(e, hipMalloc(&e->g.d_totals, sizeof(double) * e->g.nq));
+    HIPCHK(e, hipMalloc(&e->g.d_totals, sizeof(double) * (e->g.nq + (dense ? K : 0))));   // dense: the components' free-energy terms behind the statistics
     HIPCHK(e, hipMemcpy(e->g.d_prior, prior.data(), sizeof(double) * prior.size(), hipMemcpyHostToDevice));
     HIPCHK(e, hipMemcpy(e->g.d_init, init.data(), sizeof(double) * init.size(), hipMemcpyHostToDevice));
     if (e->g.materialize) HIPCHK(e, hipMalloc(&e->g.d_resp, sizeof(double) * (size_t)e->g.N * K));
@@ -248,7 +268,9 @@ rxhip_status rxhip_gmm_begin_run(rxhip_engine* e, int32_t iterations) {
     HIPCHK(e, hipMemcpyAsync(e->g.d_par, e->g.d_init, sizeof(double) * e->g.state_size, hipMemcpyDeviceToDevice, e->stream));
     e->g.it = 0;
     e->g.iterations = iterations;
-    if (e->g.mvd) {
+    if (e->g.mvd > 4) {
+        MvdLaunch::init(mvg_params(e), e->g.mvd, e->stream);
+    } else if (e->g.mvd) {
         MvgParams p = mvg_params(e);
         MVG_DISPATCH(e->g.mvd, e->g.KT, init(p, e->stream));
     } else {
@@ -267,7 +289,9 @@ rxhip_status rxhip_gmm_accumulate(rxhip_engine* e) {
     const bool resp = e->g.materialize && e->g.it == e->g.iterations - 1;
     rxhip_status st;
     if ((st = prof_begin(e, RXHIP_K_GMM_PASS))) return st;
-    if (e->g.mvd) {
+    if (e->g.mvd > 4) {
+        MvdLaunch::pass(mvg_params(e), e->g.mvd, resp, e->stream);
+    } else if (e->g.mvd) {
         MvgParams p = mvg_params(e);
         MVG_DISPATCH(e->g.mvd, e->g.KT, pass(p, resp, e->stream));
     } else {
@@ -276,7 +300,9 @@ rxhip_status rxhip_gmm_accumulate(rxhip_engine* e) {
     }
     if ((st = prof_end(e))) return st;
     if ((st = prof_begin(e, RXHIP_K_GMM_REDUCE))) return st;
-    if (e->g.mvd) {
+    if (e->g.mvd > 4) {
+        MvdLaunch::reduce(mvg_params(e), e->g.nq, e->stream);
+    } else if (e->g.mvd) {
         MvgParams p = mvg_params(e);
         MVG_DISPATCH(e->g.mvd, e->g.KT, reduce(p, e->stream));
     } else {
@@ -301,7 +327,9 @@ rxhip_status rxhip_gmm_update(rxhip_engine* e, int32_t want_fe) {
     SET_DEVICE(e);
     rxhip_status st;
     if ((st = prof_begin(e, RXHIP_K_GMM_UPDATE))) return st;
-    if (e->g.mvd) {
+    if (e->g.mvd > 4) {
+        MvdLaunch::update(mvg_params(e), e->g.mvd, want_fe != 0, e->stream);
+    } else if (e->g.mvd) {
         MvgParams p = mvg_params(e);
         MVG_DISPATCH(e->g.mvd, e->g.KT, update(p, want_fe != 0, e->stream));
     } else {

@@ -330,7 +330,7 @@ function mixture_history(e::Engine, K::Integer)
     return hist
 end
 
-# mirrors rxhip_mvgmm_desc
+# mirrors rxhip_mvgmm_desc (d = 1…4, or d = 5…32 with K ≤ 16: the same descriptor, the library picks the kernels)
 struct MvGmmDesc
     N::Int64
     K::Int32

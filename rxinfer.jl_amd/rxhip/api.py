@@ -152,6 +152,7 @@ class MultivariateGaussianMixture:
 
 
 def multivariate_gaussian_mixture(prior_mean, prior_cov, prior_nu, prior_scale, prior_alpha=None):
+    """Model spec of the multivariate Gaussian mixture for `infer`: d = 1…4 (K ≤ 16 at d ≤ 2, K ≤ 8 at d = 3, 4) or d = 5…32 with K ≤ 16."""
     m = np.asarray(prior_mean, dtype=np.float64)
     K = m.shape[0]
     return MultivariateGaussianMixture(m, np.asarray(prior_cov, dtype=np.float64), np.asarray(prior_nu, dtype=np.float64),

@@ -455,7 +455,8 @@ class GMMEngine:
 
 
 class MvGMMEngine(GMMEngine):
-    """Mean-field VMP for the multivariate Gaussian mixture, d = 1…4 (include/rxhip.h rxhip_mvgmm_desc).
+    """Mean-field VMP for the multivariate Gaussian mixture (include/rxhip.h rxhip_mvgmm_desc): d = 1…4 (K ≤ 16 at d ≤ 2, K ≤ 8 at d = 3, 4)
+    and d = 5…32 with K ≤ 16 on the fp64 matrix cores.
     priors: mu0 [K][d], S0 [K][d][d], nu0 [K], V0 [K][d][d], alpha0 [K]; init: the same five blocks of the initial marginals."""
 
     def __init__(self, N, mu0, S0, nu0, V0, alpha0, init_m_mean, init_m_cov, init_w_nu, init_w_V, init_s_alpha,
