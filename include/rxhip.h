@@ -834,6 +834,32 @@ typedef struct {
 rxhip_status rxhip_drift_chain_create(const rxhip_drift_chain_desc* desc, rxhip_engine** out);
 
 /* ------------------------------------------------------------------------------------------
+ * Probit state-space model: a scalar Gaussian chain observed through Probit (reference model test/models/statespace/probit_tests.jl:11-18):
+ *     x[1] ~ Normal(m0, v0);  x[k] ~ Normal(a·x[k-1] + c, q)  k = 2…T+1;  y[k-1] ~ Probit(x[k]),  y ∈ {0, 1}, NaN = missing
+ * (the reference test: a = 1, c = 0.1, q = 0.01, m0 = 0, v0 = 100, T = 40) for n_series independent series that share a, c, q, m0, v0.
+ * The Probit node needs the incoming Gaussian message on `in`, so inference is expectation propagation: every observed step carries a Gaussian
+ * site, all empty at the start (the reference's seeded `in` message is not needed: its test asserts the same result for three of them).
+ * One ITERATION (rxhip_run's argument) is a PARALLEL EP update, a defined semantic of this engine (csrc/probit_kernels.hpp): the chain is smoothed
+ * with the current sites, the cavity of every observed step is taken from that one pass, and all sites are replaced together by moment matching
+ * N(x; m, v)·Φ((2y−1)·x).  Posteriors and free energy of iteration i are those of the Gaussian q given the sites after i updates; the free energy
+ * is the Bethe free energy with the Probit average energy by an n_gh-point Gauss–Hermite rule.  Per-iteration values need not equal the
+ * reactive engine's (its update order is sequential); the fixed point does: last(free_energy) = 15.646236967225065 on the reference data.
+ * Same handle protocol as the HGF / drift-chain engines: rxhip_set_data(RXHIP_VAR_Y, y, T*n_series, layout) (anything but 0, 1, NaN:
+ * RXHIP_ERR_BADARG), rxhip_run(e, iterations, want_free_energy), rxhip_get_marginals (d = 1: mean, variance of x[1…T+1], T+1 rows),
+ * rxhip_get_free_energy (per iteration, summed over series), rxhip_get_free_energy_per_chain (last iteration), rxhip_counters, rxhip_destroy.
+ * RXHIP_ERR_BADARG with a text: q ≤ 0, v0 ≤ 0, n_gh outside 1…32.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    int64_t T;
+    int64_t n_series;
+    double a, c, q, m0, v0;
+    int32_t n_gh;          /* Gauss–Hermite points of the Probit average energy, 1..32 */
+    int32_t device;
+    void* stream;
+} rxhip_probit_desc;
+rxhip_status rxhip_probit_create(const rxhip_probit_desc* desc, rxhip_engine** out);
+
+/* ------------------------------------------------------------------------------------------
  * Several GPUs (one process per GPU; chains / series / points shard).  The path's only exchange is the sum
  * over shards of the Bethe free energy (reference: the single `sumreduce` of src/model/plugins/reactivemp_free_energy.jl:99-123
  * over ALL nodes and variables of the model) and, for the mixture, of the responsibility-weighted statistics that
@@ -870,7 +896,8 @@ enum {
     RXHIP_K_GMM_UPDATE = 7,    /* mixture: new marginals of m[k], p[k], s + free energy        */
     RXHIP_K_HGF_FILTER = 8,    /* hierarchical Gaussian filter: all observations × VMP iterations */
     RXHIP_K_DRIFT_CHAIN = 9,   /* noise-free drift chain: time reduction + marginals + free energy */
-    RXHIP_K_COUNT = 10
+    RXHIP_K_PROBIT_SWEEP = 10, /* probit chain: one forward + backward sweep of every series (parallel EP update) */
+    RXHIP_K_COUNT = 11
 };
 /* enable (1) / disable (0) per-kernel HIP-event timing on the engine's stream */
 rxhip_status rxhip_set_profiling(rxhip_engine* e, int32_t enabled);

@@ -1458,6 +1458,8 @@ static void free_all(rxhip_engine* e) {
         if (*b) { (void)hipFree(*b); *b = nullptr; }
     for (double** b : {&e->h.d_out, &e->h.d_fe_series, &e->h.d_gh, &e->h.d_fe_total})
         if (*b) { (void)hipFree(*b); *b = nullptr; }
+    for (double** b : {&e->pb.d_block, &e->pb.d_gh, &e->pb.d_fe_series})
+        if (*b) { (void)hipFree(*b); *b = nullptr; }
     for (double** b : {&e->d_scanm, &e->d_fstart_m, &e->d_beta_xi, &e->d_vend, &e->d_qtab, &e->d_loc, &e->d_aggpart, &e->d_bnd})
         if (*b) { if (!e->in_arena(*b)) (void)hipFree(*b); *b = nullptr; }
     if (e->d_coll) { (void)hipFree(e->d_coll); e->d_coll = nullptr; }
@@ -2528,13 +2530,15 @@ rxhip_status rxhip_set_data(rxhip_engine* e, int32_t var_id, const double* host,
     if (!e) return RXHIP_ERR_BADARG;
     if (var_id == RXHIP_VAR_U) return ingest_inputs(e, host, n, layout);
     if (var_id != RXHIP_VAR_Y) return fail(e, RXHIP_ERR_BADARG, "set_data: variable %d is not a data variable", var_id);
-    return ingest(e, host, n, layout, false);
+    const rxhip_status st = ingest(e, host, n, layout, false);
+    return st == RXHIP_OK && e->kind == 4 ? rxhip::probit_check_data(e) : st;
 }
 rxhip_status rxhip_set_data_device(rxhip_engine* e, int32_t var_id, const double* dev, size_t n, int32_t layout) {
     TREE_GUARD(e);
     if (!e) return RXHIP_ERR_BADARG;
     if (var_id != RXHIP_VAR_Y) return fail(e, RXHIP_ERR_BADARG, "set_data: variable %d is not a data variable", var_id);
-    return ingest(e, dev, n, layout, true);
+    const rxhip_status st = ingest(e, dev, n, layout, true);
+    return st == RXHIP_OK && e->kind == 4 ? rxhip::probit_check_data(e) : st;
 }
 
 // fold finished (kernel start, kernel end) event pairs into the per-kernel sums; with `wait` the stream has been drained and
@@ -2945,6 +2949,10 @@ static rxhip_status run_tail(rxhip_engine* e, const RunPlan& pl, const Params& p
 static rxhip_status run_impl(rxhip_engine* e, int32_t iterations, int32_t want_fe, bool filter) {
     if (!e) return RXHIP_ERR_BADARG;
     if (e->kind == 2) return rxhip::hgf_run_async(e, iterations, want_fe);
+    if (e->kind == 4) {
+        if (filter) return fail(e, RXHIP_ERR_BADARG, "run_filter: not a state-space engine with a streaming twin");
+        return rxhip::probit_run_async(e, iterations, want_fe);
+    }
     if (e->kind == 3) {
         if (filter) return fail(e, RXHIP_ERR_BADARG, "run_filter: not a state-space engine with a streaming twin");
         return drift_run_async(e, iterations, want_fe);
@@ -3149,7 +3157,7 @@ rxhip_status rxhip_get_marginals_device(rxhip_engine* e, int32_t var_id, const d
     TREE_GUARD(e);
     TREE_GUARD(e);
     if (!e) return RXHIP_ERR_BADARG;
-    if (var_id != RXHIP_VAR_X || (e->kind != 0 && e->kind != 3)) return fail(e, RXHIP_ERR_BADARG, "get_marginals: variable %d is not random", var_id);
+    if (var_id != RXHIP_VAR_X || (e->kind != 0 && e->kind != 3 && e->kind != 4)) return fail(e, RXHIP_ERR_BADARG, "get_marginals: variable %d is not random", var_id);
     if (!e->ran) return fail(e, RXHIP_ERR_STATE, "get_marginals: no run yet");
     if (rxhip_status stc = ensure_cov(e)) return stc;   // covariance mode 1: the per-chain array is written now
     if (mean_dev) *mean_dev = e->d_mean;
@@ -3197,7 +3205,7 @@ rxhip_status rxhip_hgf_get_history(rxhip_engine* e, double* z_mean, double* z_va
 rxhip_status rxhip_get_marginals(rxhip_engine* e, int32_t var_id, double* mean, double* cov, int32_t layout) {
     TREE_GUARD(e);
     if (!e) return RXHIP_ERR_BADARG;
-    if (var_id != RXHIP_VAR_X || (e->kind != 0 && e->kind != 3)) return fail(e, RXHIP_ERR_BADARG, "get_marginals: variable %d is not random", var_id);
+    if (var_id != RXHIP_VAR_X || (e->kind != 0 && e->kind != 3 && e->kind != 4)) return fail(e, RXHIP_ERR_BADARG, "get_marginals: variable %d is not random", var_id);
     if (!e->ran) return fail(e, RXHIP_ERR_STATE, "get_marginals: no run yet");
     if (layout != RXHIP_LAYOUT_TIME_CHAIN && layout != RXHIP_LAYOUT_CHAIN_TIME)
         return fail(e, RXHIP_ERR_BADARG, "get_marginals: unknown layout %d", layout);
@@ -3476,7 +3484,7 @@ rxhip_status rxhip_get_marginals_chains(rxhip_engine* e, int32_t var_id, const i
     TREE_GUARD(e);
     TREE_GUARD(e);
     if (!e) return RXHIP_ERR_BADARG;
-    if (var_id != RXHIP_VAR_X || (e->kind != 0 && e->kind != 3)) return fail(e, RXHIP_ERR_BADARG, "get_marginals_chains: variable %d is not random", var_id);
+    if (var_id != RXHIP_VAR_X || (e->kind != 0 && e->kind != 3 && e->kind != 4)) return fail(e, RXHIP_ERR_BADARG, "get_marginals_chains: variable %d is not random", var_id);
     if (!e->ran) return fail(e, RXHIP_ERR_STATE, "get_marginals_chains: no run yet");
     if (!chains || n <= 0) return fail(e, RXHIP_ERR_BADARG, "get_marginals_chains: empty chain list");
     for (int64_t i = 0; i < n; ++i)

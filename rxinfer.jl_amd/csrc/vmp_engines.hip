@@ -1,11 +1,12 @@
 // vmp_engines.hip — the mean-field engines of the pattern-matched families behind the C ABI: the uni- and multivariate Gaussian-mixture engines
 // (csrc/gmm_kernels.hpp, mvgmm_kernels.hpp; SURVEY §8 a9/a10: rxhip_gmm_* / rxhip_mvgmm_create) and the hierarchical Gaussian filter
-// (csrc/hgf_kernels.hpp; a11: rxhip_hgf_create, its run).  The runtime they share with the state-space engines — streams, profiling events,
+// (csrc/hgf_kernels.hpp; a11: rxhip_hgf_create, its run), and the probit chain's batched EP (csrc/probit_kernels.hpp: rxhip_probit_create, its run).  The runtime they share with the state-space engines — streams, profiling events,
 // the engine handle — is rxhip.hip's (engine.hpp).  No kernels of the state-space path live here.
 #include "../../include/rxhip.h"
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -17,6 +18,7 @@
 #pragma clang diagnostic pop
 #include "mvgmm_kernels.hpp"
 #include "mvgmm_dense_kernels.hpp"
+#include "probit_kernels.hpp"
 #include "engine.hpp"
 
 using namespace rxhip;
@@ -400,6 +402,9 @@ static void gauss_hermite_host(int n, double* x, double* w) {
     }
 }
 
+// steps per partial sum of k_probit_energy: PROBIT_ECHUNK unless that would be more chunks than a grid dimension holds
+static long long probit_echunk(long long T) { return std::max<long long>(PROBIT_ECHUNK, (T + 32767) / 32768); }
+
 rxhip_status rxhip_hgf_create(const rxhip_hgf_desc* ds, rxhip_engine** out) {
     if (!out) return RXHIP_ERR_BADARG;
     *out = nullptr;
@@ -442,8 +447,141 @@ rxhip_status rxhip_hgf_create(const rxhip_hgf_desc* ds, rxhip_engine** out) {
     return RXHIP_OK;
 }
 
+rxhip_status rxhip_probit_create(const rxhip_probit_desc* ds, rxhip_engine** out) {
+    if (!out) return RXHIP_ERR_BADARG;
+    *out = nullptr;
+    if (!ds || ds->T <= 0 || ds->n_series <= 0) return RXHIP_ERR_BADARG;
+    rxhip_engine* e = new rxhip_engine();   // from here on every refusal carries a text (rxhip_last_error; the caller destroys the handle)
+    *out = e;
+    e->kind = 4;
+    e->device = -1;
+    if (!(ds->q > 0) || !std::isfinite(ds->q)) return fail(e, RXHIP_ERR_BADARG, "probit: the transition variance q must be positive and finite (got %g)", ds->q);
+    if (!(ds->v0 > 0) || !std::isfinite(ds->v0)) return fail(e, RXHIP_ERR_BADARG, "probit: the prior variance v0 must be positive and finite (got %g)", ds->v0);
+    if (ds->n_gh < 1 || ds->n_gh > 32) return fail(e, RXHIP_ERR_BADARG, "probit: n_gh must be 1 … 32 Gauss-Hermite points (got %d)", ds->n_gh);
+    if (!std::isfinite(ds->a) || !std::isfinite(ds->c) || !std::isfinite(ds->m0)) return fail(e, RXHIP_ERR_BADARG, "probit: a, c and m0 must be finite");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(e, RXHIP_ERR_NO_DEVICE, "no HIP device visible");
+    e->pb.ds = *ds;
+    e->T = ds->T;
+    e->H = 1;   // x has T + 1 entries: the posterior arrays carry one row beyond the observations
+    e->n_chains = ds->n_series;
+    e->d = e->dy = e->dpad = 1;
+    if (ds->device >= 0) {
+        if (ds->device >= ndev) return fail(e, RXHIP_ERR_BADARG, "device %d out of range (%d visible)", ds->device, ndev);
+        e->device = ds->device;
+    } else
+        HIPCHK(e, hipGetDevice(&e->device));
+    SET_DEVICE(e);
+    if (ds->stream) e->stream = (hipStream_t)ds->stream;
+    else {
+        HIPCHK(e, stream_acquire(e->device, &e->stream));
+        e->own_stream = true;
+    }
+    double gh[64] = {0}, gx[32], gw[32];
+    gauss_hermite_host(ds->n_gh, gx, gw);
+    for (int i = 0; i < ds->n_gh; ++i) {
+        gh[i] = gx[i];
+        gh[32 + i] = gw[i] / 1.7724538509055160273;
+    }
+    const size_t C = (size_t)ds->n_series, R = (size_t)ds->T + 1;
+    const size_t chunks = (size_t)((ds->T + probit_echunk(ds->T) - 1) / probit_echunk(ds->T));
+    HIPCHK(e, hipMalloc(&e->pb.d_gh, sizeof(gh)));
+    HIPCHK(e, hipMemcpy(e->pb.d_gh, gh, sizeof(gh), hipMemcpyHostToDevice));
+    // sites ξ | w, forward messages pm | pv ([T+1][series] each), Gaussian free-energy part [series], Probit energies [chunks][series]
+    HIPCHK(e, hipMalloc(&e->pb.d_block, sizeof(double) * (4 * R * C + C + chunks * C)));
+    HIPCHK(e, hipMalloc(&e->d_mean, sizeof(double) * R * C));
+    HIPCHK(e, hipMalloc(&e->d_cov, sizeof(double) * R * C));
+    HIPCHK(e, hipMalloc(&e->d_fe_chain, sizeof(double) * C));
+    e->fe_total_cap = 16;
+    HIPCHK(e, hipMalloc(&e->d_fe_total, sizeof(double) * e->fe_total_cap));
+    HIPCHK(e, hipMalloc(&e->d_status, sizeof(int)));
+    HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
+    return RXHIP_OK;
+}
+
 
 }  // extern "C"
+
+// every observation of a probit engine is 0, 1 or NaN: checked on the device copy, whichever way it arrived
+rxhip_status rxhip::probit_check_data(rxhip_engine* e) {
+    SET_DEVICE(e);
+    const long long n = e->T * e->n_chains;
+    const unsigned nb = (unsigned)std::min<long long>((n + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_probit_check_y, dim3(nb), dim3(256), 0, e->stream, (const double*)e->d_y, n, e->d_status);
+    HIPCHK(e, hipGetLastError());
+    int st = 0;
+    HIPCHK(e, hipMemcpyAsync(&st, e->d_status, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (st & ST_PROBIT_BAD_Y) {
+        HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
+        e->have_data = false;
+        return fail(e, RXHIP_ERR_BADARG, "set_data: a Probit observation is neither 0, 1 nor NaN (missing)");
+    }
+    return RXHIP_OK;
+}
+
+rxhip_status rxhip::probit_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
+    if (iterations <= 0) return fail(e, RXHIP_ERR_BADARG, "run: iterations must be positive");
+    if (!e->have_data) return fail(e, RXHIP_ERR_STATE, "run: no observations (call rxhip_set_data first)");
+    SET_DEVICE(e);
+    const size_t C = (size_t)e->n_chains, R = (size_t)e->T + 1;
+    if (iterations > e->fe_total_cap) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        HIPCHK(e, hipFree(e->d_fe_total));
+        e->d_fe_total = nullptr;
+        e->fe_total_cap = iterations;
+        HIPCHK(e, hipMalloc(&e->d_fe_total, sizeof(double) * e->fe_total_cap));
+    }
+    if (want_fe && iterations > e->pb.fe_cap) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        if (e->pb.d_fe_series) HIPCHK(e, hipFree(e->pb.d_fe_series));
+        e->pb.d_fe_series = nullptr;
+        e->pb.fe_cap = 0;
+        HIPCHK(e, hipMalloc(&e->pb.d_fe_series, sizeof(double) * (size_t)iterations * C));
+        e->pb.fe_cap = iterations;
+    }
+    const rxhip_probit_desc& d = e->pb.ds;
+    ProbitParams p;
+    p.T = e->T; p.n_series = e->n_chains; p.y = e->d_y;
+    p.xi = e->pb.d_block; p.w = p.xi + R * C; p.pm = p.w + R * C; p.pv = p.pm + R * C;
+    p.fe_gauss = p.pv + R * C; p.fe_part = p.fe_gauss + C;
+    p.mean = e->d_mean; p.var = e->d_cov; p.fe_series = e->pb.d_fe_series; p.gh = e->pb.d_gh;
+    p.a = d.a; p.c = d.c; p.q = d.q; p.m0 = d.m0; p.v0 = d.v0; p.n_gh = d.n_gh; p.status = e->d_status;
+    p.echunk = probit_echunk(e->T);
+    const long long chunks = (e->T + p.echunk - 1) / p.echunk;
+    HIPCHK(e, hipMemsetAsync(p.xi, 0, sizeof(double) * 2 * R * C, e->stream));   // every run starts from empty sites
+    const dim3 grid((unsigned)((C + 63) / 64)), egrid((unsigned)((C + 255) / 256), (unsigned)chunks);
+    rxhip_status st;
+    // sweep i = 0 … iterations − 1 performs update i + 1 and (i ≥ 1) sees the marginals of iteration i; the last sweep only reads
+    for (int i = 0; i <= iterations; ++i) {
+        const bool update = i < iterations, last = i == iterations, fe = want_fe && i >= 1;
+        if ((st = prof_begin(e, RXHIP_K_PROBIT_SWEEP))) return st;
+        if (update && !fe) hipLaunchKernelGGL((k_probit_sweep<true, false, false>), grid, dim3(64), 0, e->stream, p);
+        else if (update) hipLaunchKernelGGL((k_probit_sweep<true, true, true>), grid, dim3(64), 0, e->stream, p);
+        else if (fe) hipLaunchKernelGGL((k_probit_sweep<false, true, true>), grid, dim3(64), 0, e->stream, p);
+        else hipLaunchKernelGGL((k_probit_sweep<false, true, false>), grid, dim3(64), 0, e->stream, p);
+        if ((st = prof_end(e))) return st;
+        if (fe) {
+            hipLaunchKernelGGL(k_probit_energy, egrid, dim3(256), 0, e->stream, p);
+            hipLaunchKernelGGL(k_probit_fe, dim3(1), dim3(256), 0, e->stream, p, i - 1, chunks, e->d_fe_total);
+        }
+        (void)last;
+    }
+    if (want_fe)
+        HIPCHK(e, hipMemcpyAsync(e->d_fe_chain, e->pb.d_fe_series + (size_t)(iterations - 1) * C, sizeof(double) * C, hipMemcpyDeviceToDevice, e->stream));
+    HIPCHK(e, hipGetLastError());
+    e->last_iterations = iterations;
+    e->last_want_fe = want_fe != 0;
+    e->ran = true;
+    e->last_filter = false;
+    // reference-equivalent events per series and iteration: a forward and a backward transition message per step, a Probit(:in) message per
+    // observed step (counted as every step: the mask lives on the device); products and marginals at the T + 1 states
+    const uint64_t Cs = (uint64_t)C, T = (uint64_t)e->T, I = (uint64_t)iterations;
+    e->rule_calls = I * Cs * (3 * T + 1);
+    e->products = I * Cs * 2 * (T + 1);
+    e->marginals = I * Cs * (T + 1);
+    return RXHIP_OK;
+}
 
 rxhip_status rxhip::hgf_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
     if (iterations <= 0) return fail(e, RXHIP_ERR_BADARG, "run: iterations must be positive");

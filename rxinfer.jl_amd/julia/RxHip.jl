@@ -460,7 +460,7 @@ function schedule(e::Engine)
     return (segments = Int(s[]), segment_len = Int(l[]))
 end
 
-const RXHIP_K_COUNT = 10   # include/rxhip.h rxhip_kernel_id
+const RXHIP_K_COUNT = 11   # include/rxhip.h rxhip_kernel_id
 "per-kernel device times (`RxInferBenchmarkCallbacks`, src/callbacks/benchmark.jl:99-155): `set_profiling!`, then runs, then `kernel_times`"
 set_profiling!(e::Engine, on::Bool) = check(e, ccall((:rxhip_set_profiling, librxhip), Int32, (Ptr{Cvoid}, Int32), e.handle, Int32(on ? 1 : 0)))
 reset_kernel_times!(e::Engine) = check(e, ccall((:rxhip_reset_kernel_times, librxhip), Int32, (Ptr{Cvoid},), e.handle))

@@ -15,9 +15,9 @@ OK, ERR_BADARG, ERR_UNSUPPORTED, ERR_NOT_POSDEF, ERR_NONFINITE_FE, ERR_HIP, ERR_
 LAYOUT_TIME_CHAIN, LAYOUT_CHAIN_TIME = 0, 1
 VAR_Y, VAR_X, VAR_U = 0, 1, 2
 (K_SEG_AGGREGATE, K_BOUNDARY_SCAN, K_FORWARD, K_BACKWARD, K_FE_REDUCE, K_GMM_PASS, K_GMM_REDUCE, K_GMM_UPDATE, K_HGF_FILTER,
- K_DRIFT_CHAIN, K_COUNT) = range(11)
+ K_DRIFT_CHAIN, K_PROBIT_SWEEP, K_COUNT) = range(12)
 KERNEL_NAMES = ["k_seg_aggregate", "k_boundary_scan", "k_forward", "k_backward", "k_fe_reduce", "k_gmm_pass", "k_gmm_reduce",
-                "k_gmm_update", "k_hgf_filter", "k_drift_chain"]
+                "k_gmm_update", "k_hgf_filter", "k_drift_chain", "k_probit_sweep"]
 
 
 class LgssmDesc(ctypes.Structure):
@@ -105,6 +105,11 @@ class DriftChainDesc(ctypes.Structure):
 class HgfDesc(ctypes.Structure):
     _fields_ = [("T", ctypes.c_int64), ("n_series", ctypes.c_int64)] + [(n, ctypes.c_double) for n in (
         "kappa", "omega", "z_variance", "y_variance", "z0_mean", "z0_var", "x0_mean", "x0_var")] + [
+        ("n_gh", ctypes.c_int32), ("device", ctypes.c_int32), ("stream", ctypes.c_void_p)]
+
+
+class ProbitDesc(ctypes.Structure):
+    _fields_ = [("T", ctypes.c_int64), ("n_series", ctypes.c_int64)] + [(n, ctypes.c_double) for n in ("a", "c", "q", "m0", "v0")] + [
         ("n_gh", ctypes.c_int32), ("device", ctypes.c_int32), ("stream", ctypes.c_void_p)]
 
 
@@ -208,6 +213,7 @@ SYMBOLS = [
     ("rxhip_gmm_update", ctypes.c_int32, [_H, ctypes.c_int32]),
     ("rxhip_hgf_create", ctypes.c_int32, [ctypes.POINTER(HgfDesc), ctypes.POINTER(_H)]),
     ("rxhip_drift_chain_create", ctypes.c_int32, [ctypes.POINTER(DriftChainDesc), ctypes.POINTER(_H)]),
+    ("rxhip_probit_create", ctypes.c_int32, [ctypes.POINTER(ProbitDesc), ctypes.POINTER(_H)]),
     ("rxhip_hgf_get_history", ctypes.c_int32, [_H, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_int32]),
     ("rxhip_set_profiling", ctypes.c_int32, [_H, ctypes.c_int32]),
     ("rxhip_get_kernel_times", ctypes.c_int32, [_H, c_double_p, c_u64_p]),

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RxHipError
-from .engine import DriftChainEngine, GMMEngine, HGFEngine, LGSSMEngine, MvGMMEngine
+from .engine import DriftChainEngine, GMMEngine, HGFEngine, LGSSMEngine, MvGMMEngine, ProbitEngine
 
 
 @dataclass
@@ -211,6 +211,52 @@ def _infer_drift_chain(model, data, iterations, free_energy, options, catch_exce
         if single:
             mean, var = mean[0], var[0]
             fe = fe[0] if fe is not None else None
+        return InferenceResult({"x": NormalMeanVariance(mean, var)}, None, fe, model, None)
+    except Exception as err:
+        if not catch_exception:
+            raise
+        return InferenceResult({}, None, None, model, err)
+    finally:
+        if eng is not None:
+            eng.close()
+
+
+@dataclass
+class ProbitSSM:
+    """`x[1] ~ Normal(prior_mean, prior_var); x[k] ~ Normal(a x[k-1] + c, q); y[k-1] ~ Probit(x[k])`
+    (test/models/statespace/probit_tests.jl:11-18): a scalar Gaussian chain with binary observations, inferred by EP."""
+    a: float
+    c: float
+    q: float
+    prior_mean: float
+    prior_var: float
+    n_gh: int = 32
+
+
+def probit_ssm(a, c, q, prior_mean, prior_var, n_gh=32):
+    return ProbitSSM(float(a), float(c), float(q), float(prior_mean), float(prior_var), int(n_gh))
+
+
+def _infer_probit(model, data, iterations, free_energy, options, catch_exception):
+    """y: [T] or [T][series], entries 0, 1 or NaN (missing).  posteriors["x"] = NormalMeanVariance with mean / var [T+1] (or [T+1][series]);
+    free_energy: one value per parallel-EP iteration (summed over the series of a batch)."""
+    options = _check_options(options)
+    y = np.asarray(data["y"], dtype=np.float64)
+    single = y.ndim == 1
+    if single:
+        y = y[:, None]
+    T, C = y.shape
+    iters = 1 if iterations is None else int(iterations)
+    eng = None
+    try:
+        eng = ProbitEngine(T, model.a, model.c, model.q, model.prior_mean, model.prior_var, n_series=C, n_gh=model.n_gh,
+                           device=int(options.get("device", -1)))
+        eng.set_data(y, layout="time_chain")
+        eng.run(iterations=iters, free_energy=free_energy)
+        mean, var = eng.marginals(layout="time_chain")
+        fe = eng.free_energy() if free_energy else None
+        if single:
+            mean, var = mean[:, 0], var[:, 0]
         return InferenceResult({"x": NormalMeanVariance(mean, var)}, None, fe, model, None)
     except Exception as err:
         if not catch_exception:
@@ -485,6 +531,8 @@ def infer(*, model, data, iterations=None, free_energy=False, options=None, retu
         return _infer_hgf(model, data, iterations, free_energy, options, initialization, catch_exception)
     if isinstance(model, UnivariateDriftChain):
         return _infer_drift_chain(model, data, iterations, free_energy, options, catch_exception)
+    if isinstance(model, ProbitSSM):
+        return _infer_probit(model, data, iterations, free_energy, options, catch_exception)
     if not isinstance(model, LinearGaussianSSM):
         raise TypeError("infer: no device schedule for this model type")
     if model.noise_precision_prior is not None:

@@ -613,6 +613,55 @@ class DriftChainEngine:
     stream = LGSSMEngine.stream
 
 
+class ProbitEngine:
+    """Scalar Gaussian chain observed through Probit, `x[1] ~ Normal(m0, v0); x[k] ~ Normal(a x[k-1] + c, q); y[k-1] ~ Probit(x[k])`
+    (test/models/statespace/probit_tests.jl:11-18), for n_series independent series: batched parallel EP (include/rxhip.h rxhip_probit_desc).
+    `run(iterations)`: that many parallel-EP updates from empty sites; `marginals()`: mean / variance of x[1 … T+1]."""
+
+    def __init__(self, T, a, c, q, m0, v0, n_series=1, n_gh=32, device=-1, stream=None):
+        L = _lib.lib()
+        desc = _lib.ProbitDesc()
+        desc.T, desc.n_series = int(T), int(n_series)
+        desc.a, desc.c, desc.q, desc.m0, desc.v0 = float(a), float(c), float(q), float(m0), float(v0)
+        desc.n_gh, desc.device = int(n_gh), int(device)
+        desc.stream = ctypes.c_void_p(stream) if stream else None
+        self.T, self.n_series, self.n_chains, self.d, self.dy, self.horizon = int(T), int(n_series), int(n_series), 1, 1, 1
+        self._h = ctypes.c_void_p()
+        st = L.rxhip_probit_create(ctypes.byref(desc), ctypes.byref(self._h))
+        if st != _lib.OK:
+            msg = L.rxhip_last_error(self._h).decode() if self._h else L.rxhip_status_string(st).decode()
+            if self._h:
+                L.rxhip_destroy(self._h)
+                self._h = None
+            raise RxHipError(st, msg or L.rxhip_status_string(st).decode())
+        self._iters = 0
+        self._data_ref = None
+
+    _chk = LGSSMEngine._chk
+    close = LGSSMEngine.close
+    __del__ = LGSSMEngine.__del__
+    __enter__ = LGSSMEngine.__enter__
+    __exit__ = LGSSMEngine.__exit__
+    sync = LGSSMEngine.sync
+    run = LGSSMEngine.run
+    run_async = LGSSMEngine.run_async
+    set_data = HGFEngine.set_data
+    set_data_device = HGFEngine.set_data_device
+    free_energy = LGSSMEngine.free_energy
+    free_energy_per_chain = LGSSMEngine.free_energy_per_chain
+    allreduce_free_energy = LGSSMEngine.allreduce_free_energy
+    counters = LGSSMEngine.counters
+    set_profiling = LGSSMEngine.set_profiling
+    reset_kernel_times = LGSSMEngine.reset_kernel_times
+    kernel_times = LGSSMEngine.kernel_times
+    stream = LGSSMEngine.stream
+
+    def marginals(self, layout="time_chain"):
+        """(mean, var) of x[1 … T+1]: [T+1][series] ('time_chain') or [series][T+1] ('chain_time')."""
+        mean, cov = LGSSMEngine.marginals(self, layout)
+        return mean[..., 0], cov[..., 0, 0]
+
+
 class Communicator:
     """RCCL communicator made through the C ABI (rxhip_comm_*): rank 0 calls `Communicator.unique_id()`, the 128 bytes
     travel to the other ranks by any host-side means, every rank constructs `Communicator(nranks, id, rank)`."""
