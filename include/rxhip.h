@@ -66,6 +66,8 @@ extern "C" {
  *     RXHIP_MSEG_MAX_BYTES=n    masked schedule: cap on its record block (an engine that exceeds it stays on the sequential schedule)
  *     RXHIP_WAVE8=0             masked schedule, one segment per chain, d <= 8: the MFMA sweep kernels instead of the in-wave ones
  *     RXHIP_NO_FROZEN=1         MFMA path, time-invariant models at d >= 48: every step of the sweeps in full (no FROZEN / BFROZEN stretches, below)
+ *     RXHIP_COV_EVERY_SWEEP=1   shared-model batches (table-driven backward sweep at d, dy <= 4; model / data split of the MFMA path): every sweep stores the
+ *                               per-chain covariance array, also when the array already holds the same bits (rxhip_set_covariance_mode, mode 0)
  *     RXHIP_TREE_MODE=0|1|2     node-array executor: a launch per level / workgroup-resident levels / a lane (a wavefront above d = 8) per replica walks the
  *                               schedule, for both phases (default: by batch and graph shape, per phase)
  *     RXHIP_TREE_RB=n, RXHIP_TREE_WG=256|512
@@ -924,13 +926,24 @@ rxhip_status rxhip_get_mean_checkpoint_stride(rxhip_engine* e, int32_t* K);
  * replaces: the split `create_model` / inference timing of src/callbacks/benchmark.jl:172-207 */
 rxhip_status rxhip_get_create_stages(rxhip_engine* e, double* ms4);
 /* Posterior covariances of a batch of chains that share ONE model do not depend on the data: they are one [T][d][d] table per model.
- * mode 0 (default): every sweep writes them into the posterior array of every chain — what the reference's marginal actors do
- *   (`src/inference/batch.jl:325-340`: every marginal of every variable, every iteration), and what every BASELINE timing here includes.
+ * mode 0 (default): after every sweep the array holds the posterior covariance of every chain — what the reference's marginal actors
+ *   leave (`src/inference/batch.jl:325-340`: every marginal of every variable, every iteration).  Batches sharing one model (the table-driven
+ *   backward sweep at d, dy <= 4 and the model / data split of the MFMA path, fully observed, no horizon) store it when it is not already
+ *   there: the first smoothing sweep of a handle's life writes the array as every BASELINE timing includes, and later sweeps leave it alone
+ *   for as long as nothing else has written it — the model is a creation argument, so new observations, further runs and further iterations
+ *   cannot change one bit of it.  A filtering run, rxhip_filter_step, rxhip_set_fixed_point_exits and rxhip_set_covariance_mode (either mode)
+ *   make the next smoothing sweep store it again.  The pointers of rxhip_get_marginals_device are `const`: a caller that writes through them
+ *   must call rxhip_set_covariance_mode(e, 0) before the next run.  rxhip_get_covariance_writes counts the sweeps that stored the array.
  * mode 1: shared-model batches on the MFMA path (4 < d ≤ 64, one model, ≥ 4 workgroup chains) keep the table and write the per-chain array
  *   when somebody asks for it (rxhip_get_marginals / _device / _chains, rxhip_lgssm_infer with cov != NULL, predictions, node-local
  *   joints) — at most once until the next run that rewrites it; means and free energy are unaffected.  Every other engine ignores the
  *   mode.  (d = 8 × 1024 chains × T = 1000: 0.56 -> 0.40 ms per sweep; the per-chain copies are 30 % of it.) */
 rxhip_status rxhip_set_covariance_mode(rxhip_engine* e, int32_t mode);
+/* *n: how many times in this handle's life the per-chain covariance array of a state-space engine was stored — by a smoothing sweep (every
+ * iteration of rxhip_run that wrote it; an unknown-noise engine writes it in the last iteration of a run only) or by a materialisation on
+ * request (mode 1 above).  Shared-model batches under the rule of mode 0 count 1 however many sweeps follow the first; every other engine
+ * counts every smoothing sweep.  Filtering runs and rxhip_filter_step are not counted.  Other engines: RXHIP_ERR_UNSUPPORTED. */
+rxhip_status rxhip_get_covariance_writes(rxhip_engine* e, uint64_t* n);
 /* The fixed-point exits of the sweeps ("Fixed-point exits" at the top of this file) per engine.  enabled = 0: every recursion of every later sweep of this
  * engine runs in full to the end of every segment — no frozen stretches on the MFMA path, no mean-only records / early exits of the per-chain d, dy ≤ 4
  * kernels (what RXHIP_NO_FROZEN / RXHIP_ELEM_FULL do under the test hooks, as an API a host can rely on); 1: the default.  The model tables an engine was

@@ -37,7 +37,29 @@ struct rxhip_engine_life {
     bool records_tinv = false;       // the last smoothing run left mean-only forward records behind the fixed point of V_f (Params::tinv_records)
     bool m_wave8_last = false;       // the last masked sweep ran on the in-wave d ≤ 8 kernels
     int cov_mode = 0;                // rxhip_set_covariance_mode (see below)
+    // cov_current: rows 0 … T−1 of d_cov hold what a smoothing sweep of this engine would store — the broadcast of the per-model covariance table
+    // (d_gtab row VS at d, dy ≤ 4; d_vstab on the split schedule of the MFMA path).  A smoothing run of a shared-model batch that finds it set stores
+    // no covariances (run_impl `cov_once`; mode 1 of rxhip_set_covariance_mode: no materialisation).  The state lives HERE and nowhere else: a parked
+    // engine's next owner gets a fresh rxhip_engine_life and pays for its first sweep's stores.  cov_pending: mode 1, the last run left the array to
+    // be materialised (ensure_cov).  Who stores into d_cov, and what keeps the state true:
+    //   run_impl                    clears the flag at the top of EVERY run (smoothing, filtering, any family) and sets it only after the loop of an
+    //                               eligible smoothing run ended without error; every writer below that runs inside run_impl is covered by that
+    //   k_backward_sh(_rev)         the eligible sweep itself: rows 0 … T of its table, the same bits every time
+    //   kd_split_broadcast          the split schedule's copy of d_vstab (run_dense, ensure_cov); its model pass (full MFMA kernels on workgroup chain 0,
+    //                               once per engine, before kd_split_save) runs in the engine's first smoothing sweep, which always stores
+    //   k_boundary_scan(_tab), k_forward, k_small_sweep, k_backward, k_forward0
+    //                               filtering runs, T == 1 and the per-chain schedules: inside run_impl, never eligible (no backward_sh / filter)
+    //   kd_* / km_* / k8_* / k_gseq_*  the other MFMA-path and sequential families: inside run_impl, never eligible
+    //   k_forecast, k_forecast_generic  rows ≥ T, engines with a horizon: never eligible (H == 0 is part of the rule)
+    //   noise engines               compute V_t in the sweep (skip_marginals): never eligible
+    //   rxhip_filter_step           writes its own staging block (d_stream), not d_cov; clears the flag all the same
+    //   k_predict, k_joint(_generic), k_predict_generic, kd_cross_from_records, k_gather_chains, noise moments
+    //                               read d_cov; the getters' sequential re-run (k_gseq_*) writes scratch arrays of its own
+    //   drift / probit / HGF / mixture engines  other kinds: their own run paths, no shared-model sweep
+    // No kernel of a run uses d_cov as scratch, and the arena never overlays it with another buffer (ArenaPlan).  Setters: rxhip_set_covariance_mode and
+    // rxhip_set_fixed_point_exits clear the flag; rxhip_set_data(_device), rxhip_lgssm_set_chain_offsets and the known inputs do not — none enters the table.
     bool cov_pending = false, cov_current = false;
+    uint64_t cov_writes = 0;         // rxhip_get_covariance_writes: smoothing sweeps (and mode-1 materialisations) that stored the per-chain covariance array
     bool noise_continue = false;     // rxhip_lgssm_noise_continue: runs go on from the current q(W) (iteration-at-a-time drivers)
     bool full_recursions = false;    // rxhip_set_fixed_point_exits(e, 0): every recursion of a sweep in full (no frozen stretches, full records)
     // results bookkeeping
@@ -147,8 +169,7 @@ struct rxhip_engine : rxhip_engine_life {
     // MFMA path, a batch that shares one model: matrices once per engine, vectors per sweep (dense_split_kernels.hpp)
     bool split = false, split_ready = false;
     // rxhip_set_covariance_mode: 0 = every sweep writes the covariance of every chain; 1 = shared-model batches on the split schedule write
-    // the per-chain array on request (the values do not depend on the data: one [T][d][d] table per model).  cov_pending: the last run left
-    // the array to be materialised; cov_current: the array holds what a materialisation would write
+    // the per-chain array on request (the values do not depend on the data: one [T][d][d] table per model).  cov_pending / cov_current: rxhip_engine_life
     int m_dpad = 0, m_nt = 0;        // masked schedule: tile dimension 16·⌈max(d, dy)/16⌉ (the engine's own dpad pads d only)
     int m_sg = 0, m_ng = 0;          // masked schedule: groups of the two-level boundary recursion (0: one level)
     int m_models = 1;                // masked schedule: constant blocks (per-step constants: desc.n_models, else 1)

@@ -3279,7 +3279,7 @@ __global__ void __launch_bounds__(64) k_smooth_tab_apply(SmoothTabParams q) {
 }
 
 template <int D>
-__global__ void __launch_bounds__(64) k_backward_sh(Params p, const double* __restrict__ gtab, const double* __restrict__ segend) {
+__global__ void __launch_bounds__(64) k_backward_sh(Params p, const double* __restrict__ gtab, const double* __restrict__ segend, const int write_cov) {
     using ST = SmoothTab<D>;
     constexpr int MP2 = DimM<D>::MP2;
     constexpr int MT = TimeTab<D>::MT;
@@ -3334,7 +3334,9 @@ __global__ void __launch_bounds__(64) k_backward_sh(Params p, const double* __re
             ms[i] = s;
         }
     }
-    // one time index of output: means through the LDS tile, covariances straight from table row `vs`
+    // one time index of output: means through the LDS tile, covariances straight from table row `vs`.  write_cov == 0: the means only — the
+    // per-chain covariance array already holds this engine's table broadcast (rxhip_engine_life::cov_current), and the stores would rewrite
+    // the same bits: 8·D² of the sweep's bytes per (chain, step)
     auto write_out = [&](long long t, const double* vs) {
 #pragma unroll
         for (int i = 0; i < D; ++i) mtile[lane * D + i] = ms[i];
@@ -3348,10 +3350,12 @@ __global__ void __launch_bounds__(64) k_backward_sh(Params p, const double* __re
             const int q = k * 64 + lane;
             if (q < NMP) stream_store(om + q, mtile[2 * q], mtile[2 * q + 1]);
         }
+        if (write_cov) {   // (a kernel argument: one scalar branch per time index)
 #pragma unroll
-        for (int k = 0; k < (NCP + 63) / 64; ++k) {
-            const int q = k * 64 + lane;
-            if (q < NCP) stream_store(oc + q, vs[(2 * q) % (D * D)], vs[(2 * q + 1) % (D * D)]);
+            for (int k = 0; k < (NCP + 63) / 64; ++k) {
+                const int q = k * 64 + lane;
+                if (q < NCP) stream_store(oc + q, vs[(2 * q) % (D * D)], vs[(2 * q + 1) % (D * D)]);
+            }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -3560,12 +3564,12 @@ __device__ __forceinline__ void boundary_in_sweep(const Params& p, const CPtr c,
 //     m_s(t) = E_t m_f(t) + G_t m_s(t+1)
 // (table row t: E_t, V_p(t+1) in the F slot, G_t, V_s(t)).  The reverse chain restarts from every checkpoint (m_f = z + N_t m_seg)
 // and from m_seg at the segment start, so it never runs more than K − 1 steps; K is chosen at creation from the bound the
-// table kernels fold (REV_AMP_LIMIT).  Covariance stores and the table-row stream are those of k_backward_sh.
+// table kernels fold (REV_AMP_LIMIT).  Covariance stores (write_cov) and the table-row stream are those of k_backward_sh.
 // bnd: 0 — m_seg and ξβ come from a k_boundary_scan_tab launch before this one; 1 / 2 — the wave computes them in its prologue
 // (boundary_in_sweep; 2: with the evidence term of the t = 0 update).
 template <int D, int DY>
 __global__ void __launch_bounds__(64) k_backward_sh_rev(Params p, const double* __restrict__ gtab, const double* __restrict__ segend,
-                                                        const CstArg<CstLayout<D, DY>::SIZE> cb, const int bnd) {
+                                                        const CstArg<CstLayout<D, DY>::SIZE> cb, const int bnd, const int write_cov) {
     using ST = SmoothTab<D>;
     using CL = CstLayout<D, DY>;
     constexpr int MP2 = DimM<D>::MP2;
@@ -3647,10 +3651,12 @@ __global__ void __launch_bounds__(64) k_backward_sh_rev(Params p, const double* 
             const int q = k * 64 + lane;
             if (q < NMP) stream_store(om + q, mtile[2 * q], mtile[2 * q + 1]);
         }
+        if (write_cov) {   // (a kernel argument: one scalar branch per time index)
 #pragma unroll
-        for (int k = 0; k < (NCP + 63) / 64; ++k) {
-            const int q = k * 64 + lane;
-            if (q < NCP) stream_store(oc + q, vs[(2 * q) % (D * D)], vs[(2 * q + 1) % (D * D)]);
+            for (int k = 0; k < (NCP + 63) / 64; ++k) {
+                const int q = k * 64 + lane;
+                if (q < NCP) stream_store(oc + q, vs[(2 * q) % (D * D)], vs[(2 * q + 1) % (D * D)]);
+            }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();

@@ -36,7 +36,8 @@ namespace plan {
     X(int, mseg_group, 0)                 /* RXHIP_MSEG_GROUP=g (0: by cost) */                                                         \
     X(unsigned long long, mseg_max_bytes, ~0ULL) /* RXHIP_MSEG_MAX_BYTES=n (all ones: no cap) */                                        \
     X(bool, wave8_off, false)             /* RXHIP_WAVE8=0 */                                                                           \
-    X(bool, no_frozen, false)             /* RXHIP_NO_FROZEN */
+    X(bool, no_frozen, false)             /* RXHIP_NO_FROZEN */                                                                         \
+    X(bool, cov_every_sweep, false)       /* RXHIP_COV_EVERY_SWEEP=1 */
 
 struct Text { char s[16] = {0}; };   // the first 15 characters of a hook's value
 
@@ -79,6 +80,7 @@ struct ScheduleHooks {
         if (const char* v = get("RXHIP_MSEG_MAX_BYTES")) h.mseg_max_bytes = std::strtoull(v, nullptr, 10);
         h.wave8_off = is0("RXHIP_WAVE8");
         h.no_frozen = set("RXHIP_NO_FROZEN");
+        h.cov_every_sweep = not0("RXHIP_COV_EVERY_SWEEP");
         return h;
     }
     // the hooks' part of the engine-pool key: every field, by the list above

@@ -1638,6 +1638,8 @@ rxhip_status rxhip_lgssm_set_offsets(rxhip_engine* e, const double* state_offset
     return rxhip_sync(e);  // the host vectors are the copy sources
 }
 
+// Leaves cov_current (engine.hpp) alone, like the known inputs of creation: offsets shift the means (μ, ν: k_shift_rows on y and on the posterior means),
+// the covariance table of the model does not see them.
 rxhip_status rxhip_lgssm_set_chain_offsets(rxhip_engine* e, const double* state_offset, const double* obs_offset, int32_t layout) {
     TREE_GUARD(e);
     if (!e || e->kind != 0) return RXHIP_ERR_BADARG;
@@ -2525,6 +2527,8 @@ static rxhip_status ingest_inputs(rxhip_engine* e, const double* u, size_t n, in
     return st;
 }
 
+// Neither setter touches cov_current (engine.hpp): observations and data inputs u[t] enter the means and the free energy, never the per-model
+// covariance table (d_gtab / d_vstab are functions of A, B, P, Q, m0, V0 alone) — that new data costs no covariance stores is the point of the rule.
 rxhip_status rxhip_set_data(rxhip_engine* e, int32_t var_id, const double* host, size_t n, int32_t layout) {
     TREE_GUARD(e);
     if (!e) return RXHIP_ERR_BADARG;
@@ -2810,7 +2814,7 @@ static rxhip_status run_gseq(rxhip_engine* e, const RunPlan& pl) {
     }
     return RXHIP_OK;
 }
-static rxhip_status run_dense(rxhip_engine* e, const RunPlan& pl, const DenseParams& dp, bool was_cov_current) {
+static rxhip_status run_dense(rxhip_engine* e, const RunPlan& pl, const DenseParams& dp, bool was_cov_current, bool write_cov) {
     rxhip_status st;
     const bool fe = pl.fe, info = pl.info;
     if (pl.segments) {
@@ -2844,11 +2848,13 @@ static rxhip_status run_dense(rxhip_engine* e, const RunPlan& pl, const DensePar
         if ((st = prof_end(e))) return st;
         if ((st = prof_begin(e, RXHIP_K_BACKWARD))) return st;
         dense_vt(e->nt)->split_backward(sq, lds_grid, e->stream);
-        // covariances: every sweep, or (mode 1) when somebody asks for them; the constant free-energy slots every sweep
+        // covariances: when the array does not hold them already (mode 0: write_cov, the rule of run_impl), or (mode 1) when somebody asks
+        // for them; the constant free-energy slots every sweep
         const bool lazy = e->cov_mode == 1 && e->H == 0;
         if (lazy && was_cov_current) e->cov_current = true;   // nothing in this schedule touches the array
         else if (lazy) e->cov_pending = true;
-        hipLaunchKernelGGL(kd_split_broadcast, dim3(lazy ? 64 : 2048), dim3(256), 0, e->stream, sq, (long long)e->n_chains, fe ? 1 : 0, lazy ? 0 : 1);
+        const bool store = !lazy && write_cov;
+        hipLaunchKernelGGL(kd_split_broadcast, dim3(store ? 2048 : 64), dim3(256), 0, e->stream, sq, (long long)e->n_chains, fe ? 1 : 0, store ? 1 : 0);
         if ((st = prof_end(e))) return st;
     } else if (pl.segments) {
         if ((st = prof_begin(e, RXHIP_K_FORWARD))) return st;
@@ -2864,7 +2870,7 @@ static rxhip_status run_dense(rxhip_engine* e, const RunPlan& pl, const DensePar
     }
     return RXHIP_OK;
 }
-static rxhip_status run_lanes(rxhip_engine* e, const RunPlan& pl, const Params& p) {
+static rxhip_status run_lanes(rxhip_engine* e, const RunPlan& pl, const Params& p, bool write_cov) {
     rxhip_status st;
     const bool fe = pl.fe, fused = pl.family == RunFamily::OnePass, bnd_in_sweep = pl.bnd_in_sweep;
     if (fused) {  // one pass over the observations: known-start recursion + z_t records + evidence parts
@@ -2898,7 +2904,7 @@ static rxhip_status run_lanes(rxhip_engine* e, const RunPlan& pl, const Params& 
             e->vt->fe_seg(p, e->stream);
         if (!pl.filter) {
             if ((st = prof_begin(e, RXHIP_K_BACKWARD))) return st;
-            if (pl.backward_sh) e->vt->backward_sh(p, e->h_cst0.data(), e->d_gtab, e->d_segend, e->ck_log2 > 0, bnd_in_sweep ? (fe ? 2 : 1) : 0, e->stream);
+            if (pl.backward_sh) e->vt->backward_sh(p, e->h_cst0.data(), e->d_gtab, e->d_segend, e->ck_log2 > 0, bnd_in_sweep ? (fe ? 2 : 1) : 0, write_cov, e->stream);
             else e->vt->backward(p, e->h_cst0.data(), e->uniform, e->stream);
             if ((st = prof_end(e))) return st;
         }
@@ -2968,7 +2974,7 @@ static rxhip_status run_impl(rxhip_engine* e, int32_t iterations, int32_t want_f
     if (iterations <= 0) return fail(e, RXHIP_ERR_BADARG, "run: iterations must be positive");
     if (!e->have_data) return fail(e, RXHIP_ERR_STATE, "run: no observations (call rxhip_set_data first)");
     const bool was_cov_current = e->cov_current && !filter;
-    e->cov_current = false;   // any run may rewrite the posterior arrays; the split schedule in mode 1 says otherwise below
+    e->cov_current = false;   // any run may rewrite the posterior arrays; the shared-model smoothing schedules say otherwise below
     e->cov_pending = false;
     e->records_hold_gains = false;
     // the reference refuses to run while a datavar has no value (batch.jl:387-407): so does an engine whose graph has data inputs
@@ -2988,8 +2994,16 @@ static rxhip_status run_impl(rxhip_engine* e, int32_t iterations, int32_t want_f
     NoiseParams np{};
     if (e->noise)
         if (rxhip_status st = fill_noise_params(e, pl, iterations, np)) return st;
+    // Shared-model smoothing sweeps copy the covariances from a per-model table that is built at creation (d_gtab, d_vstab): no data, run or
+    // iteration changes a bit of what they store.  Such a run stores the per-chain array only when it does not hold the broadcast already
+    // (rxhip_engine_life::cov_current, engine.hpp: the writers of d_cov and what keeps the state true).  RXHIP_COV_EVERY_SWEEP=1 (test hook):
+    // every sweep stores it, the comparison arm of tests/test_cov_once_gpu.py.  Mode 1 of the split schedule keeps its own bookkeeping (run_dense).
+    const bool cov_once = !e->hooks.cov_every_sweep && !pl.filter && !e->noise && e->H == 0 &&
+                          ((pl.family == RunFamily::OnePass && pl.backward_sh && pl.segments) || (pl.family == RunFamily::DenseSplit && e->cov_mode == 0));
+    const bool cov_lazy = pl.family == RunFamily::DenseSplit && e->cov_mode == 1 && e->H == 0;
     for (int it = 0; it < iterations; ++it) {
         p.iteration = it;
+        const bool write_cov = !cov_once || (it == 0 && !was_cov_current);
         // an unknown-noise engine writes the posteriors of a run's LAST iteration only (rxhip_get_marginals is defined as that; the moments q(W) needs
         // are formed inside the sweep): 160 B/U of stores per earlier iteration that nothing ever read
         p.skip_marginals = (pl.noise_in_sweep && it + 1 < iterations) ? 1 : 0;
@@ -2998,13 +3012,15 @@ static rxhip_status run_impl(rxhip_engine* e, int32_t iterations, int32_t want_f
             case RunFamily::Mseg: st = run_mseg(e, pl); break;
             case RunFamily::Gseq: st = run_gseq(e, pl); break;
             case RunFamily::DenseSplit:
-            case RunFamily::Dense: st = run_dense(e, pl, dp, was_cov_current); break;
-            default: st = run_lanes(e, pl, p); break;
+            case RunFamily::Dense: st = run_dense(e, pl, dp, was_cov_current, write_cov); break;
+            default: st = run_lanes(e, pl, p, write_cov); break;
         }
         if (!st) st = run_tail(e, pl, p, dp, np, it);
         if (st) return st;
+        if (!filter && !p.skip_marginals && !cov_lazy && write_cov) e->cov_writes += 1;   // rxhip_get_covariance_writes
     }
     HIPCHK(e, hipGetLastError());
+    if (cov_once) e->cov_current = true;   // rows 0 … T−1 hold what the next smoothing sweep would store
     e->last_iterations = iterations;
     e->last_want_fe = fe;
     e->ran = true;
@@ -3037,6 +3053,7 @@ static rxhip_status ensure_cov(rxhip_engine* e) {
     HIPCHK(e, hipGetLastError());
     e->cov_pending = false;
     e->cov_current = true;
+    e->cov_writes += 1;
     return RXHIP_OK;
 }
 rxhip_status rxhip_set_covariance_mode(rxhip_engine* e, int32_t mode) {
@@ -3045,6 +3062,14 @@ rxhip_status rxhip_set_covariance_mode(rxhip_engine* e, int32_t mode) {
     if (mode != 0 && mode != 1) return fail(e, RXHIP_ERR_BADARG, "set_covariance_mode: mode must be 0 (every sweep) or 1 (on request)");
     if (rxhip_status st = ensure_cov(e)) return st;
     e->cov_mode = mode;
+    e->cov_current = false;   // the documented way to force a rewrite (a caller that wrote through rxhip_get_marginals_device): one sweep's stores
+    return RXHIP_OK;
+}
+rxhip_status rxhip_get_covariance_writes(rxhip_engine* e, uint64_t* n) {
+    TREE_GUARD(e);
+    if (!e || !n) return RXHIP_ERR_BADARG;
+    if (e->kind != 0) return fail(e, RXHIP_ERR_UNSUPPORTED, "get_covariance_writes: not a state-space engine");
+    *n = e->cov_writes;
     return RXHIP_OK;
 }
 rxhip_status rxhip_set_fixed_point_exits(rxhip_engine* e, int32_t enabled) {
@@ -3052,6 +3077,7 @@ rxhip_status rxhip_set_fixed_point_exits(rxhip_engine* e, int32_t enabled) {
     if (!e) return RXHIP_ERR_BADARG;
     if (enabled != 0 && enabled != 1) return fail(e, RXHIP_ERR_BADARG, "set_fixed_point_exits: 0 (every recursion in full) or 1 (default)");
     e->full_recursions = enabled == 0;
+    e->cov_current = false;   // (the shared-model tables keep their own convergence tests, so the bits would be the same: one sweep's stores for a rule without exceptions)
     return RXHIP_OK;
 }
 rxhip_status rxhip_sync(rxhip_engine* e) {

@@ -102,9 +102,10 @@ struct Launch {
         hipLaunchKernelGGL((k_smooth_tab_apply<D>), dim3(nblk(nblocks, 64)), dim3(64), 0, s, q);
     }
     // bnd (reverse-filter sweep only): 0 — a boundary-scan launch came before; 1 / 2 — the sweep's waves run the boundary recursion themselves (2: + free energy)
-    static void backward_sh(const Params& p, const double* hc, const double* gtab, const double* segend, bool rev, int bnd, hipStream_t s) {
-        if (rev) hipLaunchKernelGGL((k_backward_sh_rev<D, DY>), dim3((unsigned)(p.n_chains / 64 * p.S)), dim3(64), 0, s, p, gtab, segend, carg(hc), bnd);
-        else hipLaunchKernelGGL((k_backward_sh<D>), dim3((unsigned)(p.n_chains / 64 * p.S)), dim3(64), 0, s, p, gtab, segend);
+    // write_cov: false — the per-chain covariance array already holds the table broadcast, the sweep stores the means only
+    static void backward_sh(const Params& p, const double* hc, const double* gtab, const double* segend, bool rev, int bnd, bool write_cov, hipStream_t s) {
+        if (rev) hipLaunchKernelGGL((k_backward_sh_rev<D, DY>), dim3((unsigned)(p.n_chains / 64 * p.S)), dim3(64), 0, s, p, gtab, segend, carg(hc), bnd, write_cov ? 1 : 0);
+        else hipLaunchKernelGGL((k_backward_sh<D>), dim3((unsigned)(p.n_chains / 64 * p.S)), dim3(64), 0, s, p, gtab, segend, write_cov ? 1 : 0);
     }
     static void forecast(const PredictParams& p, hipStream_t s) {
         hipLaunchKernelGGL((k_forecast<D, DY>), dim3(nblk(p.n_chains, 64)), dim3(64), 0, s, p);

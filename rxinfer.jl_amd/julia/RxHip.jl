@@ -520,9 +520,16 @@ end
 set_fixed_point_exits!(e::Engine, enabled::Bool) =
     check(e, ccall((:rxhip_set_fixed_point_exits, librxhip), Int32, (Ptr{Cvoid}, Int32), e.handle, Int32(enabled ? 1 : 0)))
 
-"0: every sweep writes the covariance of every chain (default); 1: shared-model batches on the MFMA path write the per-chain array on request"
+"0: after every sweep the array holds the covariance of every chain (default; batches sharing one model store it when it is not already there); 1: shared-model batches on the MFMA path write the per-chain array on request"
 set_covariance_mode!(e::Engine, mode::Integer) =
     check(e, ccall((:rxhip_set_covariance_mode, librxhip), Int32, (Ptr{Cvoid}, Int32), e.handle, Int32(mode)))
+
+"how many times in this handle's life the per-chain covariance array was stored (include/rxhip.h rxhip_get_covariance_writes)"
+function covariance_writes(e::Engine)
+    n = Ref{UInt64}(0)
+    check(e, ccall((:rxhip_get_covariance_writes, librxhip), Int32, (Ptr{Cvoid}, Ptr{UInt64}), e.handle, n))
+    return n[]
+end
 
 # ---- generic graph entry: rxhip_graph_desc / rxhip_create (used by HIPInferencePlugin.jl) ----------------------------
 const RXHIP_ERR_UNSUPPORTED = Int32(2)

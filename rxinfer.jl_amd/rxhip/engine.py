@@ -300,9 +300,15 @@ class LGSSMEngine:
         self._chk(_lib.lib().rxhip_set_fixed_point_exits(self._h, 1 if enabled else 0))
 
     def set_covariance_mode(self, mode):
-        """0: every sweep writes the covariance of every chain (default); 1: shared-model batches on the MFMA path write the per-chain
-        array when it is asked for (rxhip_set_covariance_mode)"""
+        """0: after every sweep the array holds the covariance of every chain (default; batches sharing one model store it when it is not
+        already there); 1: shared-model batches on the MFMA path write the per-chain array when it is asked for (rxhip_set_covariance_mode)"""
         self._chk(_lib.lib().rxhip_set_covariance_mode(self._h, int(mode)))
+
+    def covariance_writes(self):
+        """how many times in this handle's life the per-chain covariance array was stored (rxhip_get_covariance_writes)"""
+        n = ctypes.c_uint64()
+        self._chk(_lib.lib().rxhip_get_covariance_writes(self._h, ctypes.byref(n)))
+        return n.value
 
     def schedule(self):
         s, l = ctypes.c_int32(), ctypes.c_int64()
