@@ -801,6 +801,11 @@ rxhip_status rxhip_mvgmm_create(const rxhip_mvgmm_desc* desc, rxhip_engine** out
  * per-event loop (src/inference/streaming.jl:349-407) for this model.
  * rxhip_get_free_energy: per iteration, Σ_series of the mean-over-observations free energy
  * (free_energy_history, src/score/actor.jl:98-104); rxhip_get_free_energy_per_chain: per series, last iteration.
+ * Refusals of rxhip_hgf_create: n_gh < 1 RXHIP_ERR_BADARG, n_gh > 32 RXHIP_ERR_UNSUPPORTED, a variance that is not positive (NaN
+ * included) RXHIP_ERR_NOT_POSDEF — these three without a handle; an infinite variance, or kappa, omega, z0_mean, x0_mean NaN or
+ * infinite: RXHIP_ERR_BADARG with a handle that carries the text (rxhip_last_error) and is to be destroyed.
+ * A non-finite observation is not refused by rxhip_set_data: the run on it ends in RXHIP_ERR_NONFINITE_FE (with or without the free
+ * energy) and its posteriors are not to be used; the status is cleared when it is reported, so new data and another run succeed.
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
     int64_t T;

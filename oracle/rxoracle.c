@@ -1536,13 +1536,18 @@ int rxo_hgf_filter(long long T, const double* y, double kappa, double omega, dou
             const double B = exp(-kappa * qzm + 0.5 * kappa * kappa * qzv);
             const double g = A * B;
             /* @marginalrule GCV(:y_x)(m_y = N(y_t, y_variance), m_x = N(xm, xv), q_z): joint precision / weighted mean */
-            const double l11 = 1.0 / y_variance + g, l22 = 1.0 / xv + g, l12 = -g;
-            const double det = l11 * l22 - l12 * l12;
+            /* det and E(xt − xt_min)² without their cancelling g² terms: with g ≫ 1/y_variance, 1/xv (ω = −6, y variance 100) the textbook
+               forms l11·l22 − g² and v11 + v22 − 2 v12 lose g²/det ≈ 10⁴…10⁵ in relative accuracy per iteration, which the VMP iterations
+               and the filter's feedback then carry to 10⁻⁶ (found against tests/hgf_ref.py; DESIGN.md, HGF) */
+            const double iy = 1.0 / y_variance, ix = 1.0 / xv;
+            const double l11 = iy + g, l22 = ix + g;
+            const double det = iy * ix + g * (iy + ix);
             if (!(det > 0.0)) { rc = RXO_ERR_NOT_POSDEF; goto out; }
-            const double v11 = l22 / det, v22 = l11 / det, v12 = -l12 / det;
-            const double x1 = y[t] / y_variance, x2 = xm / xv;
+            const double v11 = l22 / det, v22 = l11 / det, v12 = g / det;
+            const double x1 = y[t] * iy, x2 = xm * ix;
             const double m1 = v11 * x1 + v12 * x2, m2 = v12 * x1 + v22 * x2;
-            const double psi = (m1 - m2) * (m1 - m2) + v11 + v22 - 2.0 * v12;
+            const double dm = (ix * x1 - iy * x2) / det; /* = m1 − m2 */
+            const double psi = dm * dm + (iy + ix) / det;
             /* @rule GCV(:z)(q_y_x, q_κ, q_ω): ExponentialLinearQuadratic(a = κ, b = ψA, c = −κ, d = 0);
                product with the forward message N(zm, fzv) moment-matched by approximate_meancov (Gauss–Hermite) */
             const double a = kappa, b = psi * A, c = -kappa;
@@ -1581,19 +1586,20 @@ int rxo_hgf_filter(long long T, const double* y, double kappa, double omega, dou
                 for (int i = 0; i < n_gh; ++i) ev += ecs[i] * (epts[i] - em) * (epts[i] - em);
                 ev /= en;
                 if (!(ev > 0.0) || !isfinite(em)) { rc = RXO_ERR_NONFINITE_FE; goto out; }
-                const double wb = 1.0 / z_variance, w00 = 1.0 / ev + wb, w11 = 1.0 / zv + wb;
-                const double dW = w00 * w11 - wb * wb;
-                const double s00 = w11 / dW, s11 = w00 / dW, s01 = wb / dW;
-                const double j0 = s00 * (em / ev) + s01 * (zm / zv), j1 = s01 * (em / ev) + s11 * (zm / zv);
+                const double wb = 1.0 / z_variance, w00 = 1.0 / ev + wb;
+                const double dW = (1.0 / ev) * (1.0 / zv) + wb * (1.0 / ev + 1.0 / zv); /* the same, for q(zt, zt_min) */
+                const double s11 = w00 / dW, s01 = wb / dW;
+                const double j1 = s01 * (em / ev) + s11 * (zm / zv);
                 const double mu_m = j1, var_m = s11;
-                const double e2 = (j0 - j1) * (j0 - j1) + s00 + s11 - 2.0 * s01;
+                const double dj = ((1.0 / zv) * (em / ev) - (1.0 / ev) * (zm / zv)) / dW; /* = j0 − j1 */
+                const double e2 = dj * dj + (1.0 / ev + 1.0 / zv) / dW;
                 double F = 0.0;
                 F += 0.5 * (LOG2PI + log(zv) + ((mu_m - zm) * (mu_m - zm) + var_m) / zv);           /* prior zt_min */
                 F += 0.5 * (LOG2PI + log(xv) + ((m2 - xm) * (m2 - xm) + v22) / xv);                  /* prior xt_min */
                 F += 0.5 * (LOG2PI + log(z_variance) + e2 / z_variance);                             /* transition   */
                 F -= 0.5 * (2.0 * (LOG2PI + 1.0) - log(dW));                                         /* −H[zt,zt_min] */
                 F += 0.5 * (LOG2PI + (qzm * kappa + omega) + psi * A * Bn);                          /* GCV average energy */
-                F -= 0.5 * (2.0 * (LOG2PI + 1.0) + log(v11 * v22 - v12 * v12));                      /* −H[xt,xt_min] */
+                F -= 0.5 * (2.0 * (LOG2PI + 1.0) - log(det));                                        /* −H[xt,xt_min]: det Σ = 1 / det */
                 F += 0.5 * (LOG2PI + log(y_variance) + ((y[t] - m1) * (y[t] - m1) + v11) / y_variance); /* observation */
                 fe[n] += F;
             }

@@ -89,6 +89,11 @@ __global__ void __launch_bounds__(64) k_hgf_filter(HgfParams p) {
         const double fzv = zv + zvar, sc = sqrt(2.0 * fzv);
         const double ixv = rcp_pos(xv), izv = rcp_pos(zv);
         const double x1 = yt * iyvar, x2 = xm * ixv, zx = zm * izv;
+        // det Λ and E(xt − xt_min)² of the joint q(xt, xt_min), precision [[1/yvar + g, −g], [−g, 1/xv + g]], in forms without their cancelling
+        // g² terms: det = piv + g·siv and ψ = (dmn / det)² + siv / det.  With g ≫ 1/yvar, 1/xv (ω = −6, y variance 100: g ≈ 400, det ≈ 8)
+        // l11·l22 − g² and v11 + v22 − 2 v12 lose g²/det ≈ 10⁴…10⁵ in relative accuracy per iteration, and the VMP iterations and the
+        // filter's feedback carry that to 10⁻⁶ of a posterior sd (tests/test_hgf_contract_gpu.py; DESIGN.md, HGF)
+        const double siv = iyvar + ixv, piv = iyvar * ixv, dmn = ixv * x1 - iyvar * x2;
         // point-wise constants of the two cubatures: exp_bounded(−½κ·point) factors out of the iteration loop
         double dx[2], ept[2], lpt[2];
 #pragma unroll
@@ -110,11 +115,12 @@ __global__ void __launch_bounds__(64) k_hgf_filter(HgfParams p) {
             const double B = Bcur;
             const double g = A * B;
             const double l11 = iyvar + g, l22 = ixv + g;
-            const double det = l11 * l22 - g * g;
+            const double det = __builtin_fma(g, siv, piv);
             const double id = rcp_pos(det);
             const double v11 = l22 * id, v22 = l11 * id, v12 = g * id;
             const double m1 = v11 * x1 + v12 * x2, m2 = v12 * x1 + v22 * x2;
-            const double psi = (m1 - m2) * (m1 - m2) + v11 + v22 - 2.0 * v12;
+            const double dm = dmn * id;  // = m1 − m2
+            const double psi = dm * dm + siv * id;
             const double b = psi * A;
             // two cubature points per lane: z-message pdf exp_bounded(−½(κz + b·exp(−κz))) at the forward-message points and (for
             // the free energy) times exp_bounded(z²/2) at the N(0,1) points; first moments taken about zm / 0
@@ -161,13 +167,13 @@ __global__ void __launch_bounds__(64) k_hgf_filter(HgfParams p) {
             // Gaussian moments: mean_var(ExponentialLinearQuadratic) = cubature of pdf(z)·exp(z²/2) against N(0, 1)
             bad = bad || !(f.ev > 0.0) || !is_finite(f.em);
             const double iev = rcp_pos(f.ev);
-            const double w00 = iev + wb, w11 = izv + wb;
-            const double dW = w00 * w11 - wb * wb;
+            const double w00 = iev + wb, swv = iev + izv;
+            const double dW = __builtin_fma(wb, swv, iev * izv);  // the same for q(zt, zt_min): no wb² (wb = 10⁴ at z variance 10⁻⁴) to cancel
             const double idw = rcp_pos(dW);
-            const double s00 = w11 * idw, s11 = w00 * idw, s01 = wb * idw;
+            const double s11 = w00 * idw, s01 = wb * idw;
             const double xo = f.em * iev;
-            const double j0 = s00 * xo + s01 * zx, j1 = s01 * xo + s11 * zx;
-            const double e2 = (j0 - j1) * (j0 - j1) + s00 + s11 - 2.0 * s01;
+            const double j1 = s01 * xo + s11 * zx, dj = (izv * xo - iev * zx) * idw;  // dj = E zt − E zt_min
+            const double e2 = dj * dj + swv * idw;
             double F = fe_t_const;
             F += 0.5 * ((j1 - zm) * (j1 - zm) + s11) * izv;                      // prior zt_min
             F += 0.5 * ((f.m2 - xm) * (f.m2 - xm) + f.v22) * ixv;                // prior xt_min

@@ -411,6 +411,17 @@ rxhip_status rxhip_hgf_create(const rxhip_hgf_desc* ds, rxhip_engine** out) {
     if (!ds || ds->T <= 0 || ds->n_series <= 0 || ds->n_gh < 1) return RXHIP_ERR_BADARG;
     if (ds->n_gh > 32) return RXHIP_ERR_UNSUPPORTED;
     if (!(ds->z_variance > 0) || !(ds->y_variance > 0) || !(ds->z0_var > 0) || !(ds->x0_var > 0)) return RXHIP_ERR_NOT_POSDEF;
+    // non-finite parameters: the kernel's exponential clamps its argument (a NaN included), so nothing downstream would report them
+    const char* nonfinite = !std::isfinite(ds->z_variance) ? "z_variance" : !std::isfinite(ds->y_variance) ? "y_variance" : !std::isfinite(ds->z0_var) ? "z0_var"
+                          : !std::isfinite(ds->x0_var) ? "x0_var" : !std::isfinite(ds->kappa) ? "kappa" : !std::isfinite(ds->omega) ? "omega"
+                          : !std::isfinite(ds->z0_mean) ? "z0_mean" : !std::isfinite(ds->x0_mean) ? "x0_mean" : nullptr;
+    if (nonfinite) {   // (a handle that carries the text, nothing else: the caller destroys it)
+        rxhip_engine* e = new rxhip_engine();
+        *out = e;
+        e->kind = 2;
+        e->device = -1;
+        return fail(e, RXHIP_ERR_BADARG, "hgf: %s must be finite", nonfinite);
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return RXHIP_ERR_NO_DEVICE;
     rxhip_engine* e = new rxhip_engine();

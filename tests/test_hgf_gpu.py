@@ -24,6 +24,15 @@ def hgf_series(n, k, w, zv, yv, seed):
     return z, x, y
 
 
+def _hold(got, ref):
+    """the project's contract per element: means within 1e-6 posterior sd (the reference's variance), variances within 1e-6 relative;
+    got, ref = (zm, zv, xm, xv) of one series"""
+    em = max(float(np.max(np.abs(got[i] - ref[i]) / np.sqrt(ref[i + 1]))) for i in (0, 2))
+    ev = max(float(np.max(np.abs(got[i] - ref[i]) / ref[i])) for i in (1, 3))
+    print(f"mean err {em:.3e} sd, var rel {ev:.3e}")
+    assert all(np.all(np.isfinite(a)) for a in got) and em < 1e-6 and ev < 1e-6, (em, ev)
+
+
 def test_hgf_reference_test_shape():
     """κ = 1, ω = 0, z variance 0.04, y variance 0.01, T = 2000, 10 iterations, GH-31, init N(0, 5) (hgf_tests.jl:94-105)."""
     k, w, zv, yv, n = 1.0, 0.0, 0.2 ** 2, 0.1 ** 2, 2000
@@ -40,6 +49,7 @@ def test_hgf_reference_test_shape():
         ozm, ozv, oxm, oxv, ofe, ocnt = rxoracle.hgf_filter(y[:, s], k, w, zv, yv)
         for a, b in ((zm[:, s], ozm), (zvv[:, s], ozv), (xm[:, s], oxm), (xv[:, s], oxv)):
             assert np.max(np.abs(a - b)) < 1e-6 * np.max(np.abs(b))
+        _hold((zm[:, s], zvv[:, s], xm[:, s], xv[:, s]), (ozm, ozv, oxm, oxv))
         assert abs(fe_s[s] - ofe[-1]) < 1e-8 * abs(ofe[-1])
         fe_sum += ofe
         # the reference test's statistical assertions (hgf_tests.jl:119-133)
@@ -71,6 +81,7 @@ def test_hgf_shapes(S, T, iters, n_gh, layout):
         o = rxoracle.hgf_filter(ys[:, s], k, w, zv, yv, z0=(0.1, 2.0), x0=(-0.2, 3.0), vmp_iters=iters, n_gh=n_gh)
         assert np.max(np.abs(zm[:, s] - o[0])) <= 1e-6 * max(np.max(np.abs(o[0])), 1e-30)
         assert np.max(np.abs(xv[:, s] - o[3])) <= 1e-6 * np.max(np.abs(o[3]))
+        _hold((zm[:, s], zvv[:, s], xm[:, s], xv[:, s]), o[:4])
         fe_sum += o[4]
     assert np.max(np.abs(fe - fe_sum) / np.abs(fe_sum)) < 1e-8
 
