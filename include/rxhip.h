@@ -68,6 +68,9 @@ extern "C" {
  *     RXHIP_NO_FROZEN=1         MFMA path, time-invariant models at d >= 48: every step of the sweeps in full (no FROZEN / BFROZEN stretches, below)
  *     RXHIP_COV_EVERY_SWEEP=1   shared-model batches (table-driven backward sweep at d, dy <= 4; model / data split of the MFMA path): every sweep stores the
  *                               per-chain covariance array, also when the array already holds the same bits (rxhip_set_covariance_mode, mode 0)
+ *     RXHIP_Y_RING=1            reverse-filter schedule: the backward sweep (k_backward_sh_rev) with its observations one step ahead of their use instead of
+ *                               the shipped ring (four steps, Y_RING_SHIPPED in csrc/lgssm_kernels.hpp); the same loop and arithmetic, the comparison arm.  Any other value is refused by
+ *                               rxhip_lgssm_create (RXHIP_ERR_BADARG with a message): the depths are compiled instances, not a parameter
  *     RXHIP_TREE_MODE=0|1|2     node-array executor: a launch per level / workgroup-resident levels / a lane (a wavefront above d = 8) per replica walks the
  *                               schedule, for both phases (default: by batch and graph shape, per phase)
  *     RXHIP_TREE_RB=n, RXHIP_TREE_WG=256|512

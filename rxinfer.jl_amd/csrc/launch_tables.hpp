@@ -50,7 +50,7 @@ struct LgssmVtbl {
     void (*fe_seg)(const Params&, hipStream_t);
     int gt_row, se_size;  // SmoothTab / SegEndTab
     void (*smooth_tables)(const SmoothTabParams&, const double*, hipStream_t);
-    void (*backward_sh)(const Params&, const double*, const double*, const double*, bool, int, bool, hipStream_t);
+    void (*backward_sh)(const Params&, const double*, const double*, const double*, bool, int, bool, int, hipStream_t);
     void (*boundary_scan_tab)(const Params&, const double*, bool, hipStream_t);
     void (*seg_aggregate)(const Params&, const double*, bool, hipStream_t);
     int ex_size;  // ElemX

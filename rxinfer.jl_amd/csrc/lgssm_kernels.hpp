@@ -3567,7 +3567,27 @@ __device__ __forceinline__ void boundary_in_sweep(const Params& p, const CPtr c,
 // table kernels fold (REV_AMP_LIMIT).  Covariance stores (write_cov) and the table-row stream are those of k_backward_sh.
 // bnd: 0 — m_seg and ξβ come from a k_boundary_scan_tab launch before this one; 1 / 2 — the wave computes them in its prologue
 // (boundary_in_sweep; 2: with the evidence term of the t = 0 update).
-template <int D, int DY>
+//
+// Memory operations of the step loop.  s_waitcnt vmcnt counts loads AND stores in issue order, so one wait for the youngest operation
+// drains everything the wave has in flight.  The loop is written so that no such wait is needed on a step that is not a checkpoint:
+//   · nothing that is constant over the loop is read from global memory inside it — A⁻¹ sits in LDS (broadcast ds_read; read through
+//     p.ainv the compiler must assume the mean stores alias it and re-reads it with vector loads, consumed at once, on every step);
+//   · y runs R steps ahead in a register ring (Y_RING_SHIPPED; R = 1 is the comparison arm of RXHIP_Y_RING=1), the table rows one chunk;
+//     both are loaded UNCONDITIONALLY with the step / row index clamped into the wave's own segment (value unused past the end), and the
+//     whole chunks run in a loop without per-step guards, the last len mod U steps after it: every path through the loop body issues
+//     the same operations, and the wait in front of y_{t+1} leaves the R − 1 younger y loads, the table chunk and the stores in flight;
+//   · a checkpoint's record and its N row (one element per lane, broadcast through LDS when its step comes) are loaded together one
+//     window ahead, inside the checkpoint branch.  The wait pass merges paths by the smaller count, which is the plain step's own, so
+//     the branch costs the plain step nothing; the checkpoint step itself still waits for its fresh prefetch (the register allocator
+//     copies the record into place at the branch's end) — one drain per K steps, where there was one per step.
+// RXHIP_Y_RING_DEPTH=1|2|4 builds another depth as the shipped one, like RXHIP_NT_STORES above an A/B switch for a variant library
+// (`make variants/librxhip_ring2.so EXTRA=-DRXHIP_Y_RING_DEPTH=2`, loaded through RXHIP_LIB): how profiles/r13/ring_depths.txt timed depth 2.
+// Every text that names the depth prints Y_RING_SHIPPED; 4 is what ships.
+#ifndef RXHIP_Y_RING_DEPTH
+#define RXHIP_Y_RING_DEPTH 4
+#endif
+constexpr int Y_RING_SHIPPED = RXHIP_Y_RING_DEPTH;   // steps y runs ahead of its use; divides the chunk length, so a step's ring slot is a compile-time constant
+template <int D, int DY, int R>
 __global__ void __launch_bounds__(64) k_backward_sh_rev(Params p, const double* __restrict__ gtab, const double* __restrict__ segend,
                                                         const CstArg<CstLayout<D, DY>::SIZE> cb, const int bnd, const int write_cov) {
     using ST = SmoothTab<D>;
@@ -3580,9 +3600,13 @@ __global__ void __launch_bounds__(64) k_backward_sh_rev(Params p, const double* 
     constexpr int PPL = (NPC + 63) / 64;
     constexpr int NMP = 32 * D;              // 16-byte pieces of the 64 means of a time index
     constexpr int NCP = 32 * D * D;          // … of the 64 covariances
+    static_assert(U % R == 0, "ring slots must be compile-time");
+    static_assert(MT <= 64, "one lane per element of an N row");
     __shared__ double2 tbuf[2][NPC];
     __shared__ double mtile[64 * D];
     __shared__ double bndbuf[2][BndStage<D>::N];
+    __shared__ double ainv[D * D];           // A⁻¹, read once
+    __shared__ double nrow[MT];              // N_t of the checkpoint being restarted from
     const int lane = threadIdx.x;
     const long long g0 = (long long)blockIdx.x * 64;  // n_chains % 64 == 0: the wave holds 64 chains of ONE segment
     const long long seg = g0 / p.n_chains;
@@ -3596,9 +3620,8 @@ __global__ void __launch_bounds__(64) k_backward_sh_rev(Params p, const double* 
     // the checkpoint of time index t ∈ (tb, te]: slot 1 + seg·nck + (t − tb − 1)/K
     auto load_ck = [&](long long t, double2 (&r)[MP2]) { load_filt_m_sh<D>(p, 1 + seg * p.nck + ((t - tb - 1) >> lg), chain, r); };
     double mseg[D];
-    auto ck_mean = [&](const double2 (&r)[MP2], long long t, double (&mf)[D]) {   // m_f(t) = z_t + N_t m_seg
+    auto ck_mean = [&](const double2 (&r)[MP2], const double* N, double (&mf)[D]) {   // m_f(t) = z_t + N_t m_seg
         unpack_m_sh<D>(r, mf);
-        const double* N = p.ntab + t * MT;
 #pragma unroll
         for (int i = 0; i < D; ++i) {
             double s = mf[i];
@@ -3624,7 +3647,7 @@ __global__ void __launch_bounds__(64) k_backward_sh_rev(Params p, const double* 
         if (len > 0) {
             double2 r[MP2];
             load_ck(te, r);
-            ck_mean(r, te, mf);
+            ck_mean(r, p.ntab + te * MT, mf);
         } else {
 #pragma unroll
             for (int i = 0; i < D; ++i) mf[i] = mseg[i];
@@ -3638,6 +3661,8 @@ __global__ void __launch_bounds__(64) k_backward_sh_rev(Params p, const double* 
             ms[i] = s;
         }
     }
+    // (whole groups of 64 pieces are stored without a lane predicate: a predicate the compiler cannot fold is a branch around the store, and the
+    // wait pass then counts the path without it)
     auto write_out = [&](long long t, const double* vs) {
 #pragma unroll
         for (int i = 0; i < D; ++i) mtile[lane * D + i] = ms[i];
@@ -3649,119 +3674,142 @@ __global__ void __launch_bounds__(64) k_backward_sh_rev(Params p, const double* 
 #pragma unroll
         for (int k = 0; k < (NMP + 63) / 64; ++k) {
             const int q = k * 64 + lane;
-            if (q < NMP) stream_store(om + q, mtile[2 * q], mtile[2 * q + 1]);
+            if ((k + 1) * 64 <= NMP || q < NMP) stream_store(om + q, mtile[2 * q], mtile[2 * q + 1]);
         }
         if (write_cov) {   // (a kernel argument: one scalar branch per time index)
 #pragma unroll
             for (int k = 0; k < (NCP + 63) / 64; ++k) {
                 const int q = k * 64 + lane;
-                if (q < NCP) stream_store(oc + q, vs[(2 * q) % (D * D)], vs[(2 * q + 1) % (D * D)]);
+                if ((k + 1) * 64 <= NCP || q < NCP) stream_store(oc + q, vs[(2 * q) % (D * D)], vs[(2 * q + 1) % (D * D)]);
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
     };
     if (seg == p.S - 1) write_out(te, gtab + te * ST::SIZE + ST::VS);
+    if (len <= 0) return;   // (uniform across the wave)
 
-    const double2* g2 = reinterpret_cast<const double2*>(gtab);
-    double2 tr[PPL];
-    auto fetch = [&](long long i0) {
+    const rx_d2v* g2 = reinterpret_cast<const rx_d2v*>(gtab);
+    rx_d2v tr[PPL];   // (a first-class vector: as double2 the unconditional copy is a memcpy into a stack slot)
+    auto fetch = [&](long long i0) {   // the rows of steps i0 … i0 + U − 1, past the segment's last step its row again (never used)
 #pragma unroll
         for (int k = 0; k < PPL; ++k) {
-            const int idx = k * 64 + lane;
+            const int idx = k * 64 + lane < NPC ? k * 64 + lane : NPC - 1;
             const long long r = i0 + idx / RP;  // step index
-            tr[k] = (idx < NPC && r < len) ? g2[(te - 1 - r) * RP + idx % RP] : make_double2(0.0, 0.0);
+            tr[k] = g2[(te - 1 - (r < len ? r : len - 1)) * RP + idx % RP];
         }
     };
     auto stash = [&](int b) {
 #pragma unroll
         for (int k = 0; k < PPL; ++k) {
             const int idx = k * 64 + lane;
-            if (idx < NPC) tbuf[b][idx] = tr[k];
+            if ((k + 1) * 64 <= NPC || idx < NPC) tbuf[b][idx] = make_double2(tr[k].x, tr[k].y);
         }
     };
     fetch(0);
+    if (lane < D * D) ainv[lane] = p.ainv[lane];
     stash(0);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    // the next checkpoint below te (a multiple of K past tb; none when it would be tb itself), prefetched a whole window ahead
-    long long tc = len > 0 ? tb + (((len - 1) >> lg) << lg) : tb;
+    // the next checkpoint below te (a multiple of K past tb; none when it would be tb itself), prefetched a whole window ahead with the one
+    // element of its N row that this lane carries.  Past the last checkpoint the load goes on, to the segment's first one: same operations
+    // on every path, value unused.
+    long long tc = tb + (((len - 1) >> lg) << lg);
     double2 rc[MP2];
-    if (tc > tb) load_ck(tc, rc);
-    double yn[DY];   // y_{t+1} of the next step, one step ahead
-    if (len > 0) load_y<DY>(p.y, te, p.n_chains, chain, yn);
-    int b = 0;
-    for (long long i0 = 0; i0 < len; i0 += U, b ^= 1) {  // `len` is uniform across the wave
-        if (i0 + U < len) fetch(i0 + U);
+    double nc;
+    auto prefetch_ck = [&]() {
+        const long long t = tc > tb ? tc : (tb + K < te ? tb + K : te);
+        load_ck(t, rc);
+        nc = p.ntab[t * MT + (lane < MT ? lane : MT - 1)];
+    };
+    prefetch_ck();
+    // y_{t+1} of step i (t = te − 1 − i) is y[te − i]: slot i mod R of the ring, loaded R steps ahead; past the last step, y[tb + 1] again
+    double yr[R][DY];
+    auto y_index = [&](long long i) { return te - (i < len ? i : len - 1); };
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const long long i = i0 + u;
-            if (i < len) {
-                const long long t = te - 1 - i;
-                const double* row = reinterpret_cast<const double*>(&tbuf[b][0]) + u * ST::SIZE;
-                double yb[DY];
+    for (int r = 0; r < R; ++r) load_y<DY>(p.y, y_index(r), p.n_chains, chain, yr[r]);
+    auto step = [&](const int u, const long long i, const int b) __attribute__((always_inline)) {
+        const long long t = te - 1 - i;
+        const double* row = reinterpret_cast<const double*>(&tbuf[b][0]) + u * ST::SIZE;
+        const double (&yb)[DY] = yr[u % R];
+        double mfn[D];
+        if (t == tb) {   // the start boundary: the scan's own filtered mean
 #pragma unroll
-                for (int k = 0; k < DY; ++k) yb[k] = yn[k];
-                if (t > tb) load_y<DY>(p.y, t, p.n_chains, chain, yn);
-                double mfn[D];
-                if (t == tb) {   // the start boundary: the scan's own filtered mean
+            for (int k = 0; k < D; ++k) mfn[k] = mseg[k];
+        } else if (t == tc) {   // a checkpoint: restart the reverse chain
+            if (lane < MT) nrow[lane] = nc;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            ck_mean(rc, nrow, mfn);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_sched_barrier(0);   // (as for the y slot below: the next record goes into the registers this one has left)
+            tc -= K;
+            prefetch_ck();
+        } else {
+            double w[D], mp[D];
 #pragma unroll
-                    for (int k = 0; k < D; ++k) mfn[k] = mseg[k];
-                } else if (t == tc) {   // a checkpoint: restart the reverse chain
-                    ck_mean(rc, t, mfn);
-                    tc -= K;
-                    if (tc > tb) load_ck(tc, rc);
-                } else {
-                    double w[D], mp[D];
+            for (int a = 0; a < D; ++a) {   // w = B'Q⁻¹B m_f − B'Q⁻¹ y
+                double s = 0.0;
 #pragma unroll
-                    for (int a = 0; a < D; ++a) {   // w = B'Q⁻¹B m_f − B'Q⁻¹ y
-                        double s = 0.0;
+                for (int k = 0; k < D; ++k) s += c[CL::LOBS + sidx(a, k)] * mf[k];
 #pragma unroll
-                        for (int k = 0; k < D; ++k) s += c[CL::LOBS + sidx(a, k)] * mf[k];
+                for (int k = 0; k < DY; ++k) s -= c[CL::G + a * DY + k] * yb[k];
+                w[a] = s;
+            }
 #pragma unroll
-                        for (int k = 0; k < DY; ++k) s -= c[CL::G + a * DY + k] * yb[k];
-                        w[a] = s;
-                    }
+            for (int a = 0; a < D; ++a) {   // m_p(t+1) = m_f(t+1) + V_p(t+1) w
+                double s = mf[a];
 #pragma unroll
-                    for (int a = 0; a < D; ++a) {   // m_p(t+1) = m_f(t+1) + V_p(t+1) w
-                        double s = mf[a];
+                for (int k = 0; k < D; ++k) s += row[ST::F + a * D + k] * w[k];
+                mp[a] = s;
+            }
 #pragma unroll
-                        for (int k = 0; k < D; ++k) s += row[ST::F + a * D + k] * w[k];
-                        mp[a] = s;
-                    }
+            for (int a = 0; a < D; ++a) {   // m_f(t) = A⁻¹ m_p(t+1)
+                double s = 0.0;
 #pragma unroll
-                    for (int a = 0; a < D; ++a) {   // m_f(t) = A⁻¹ m_p(t+1)  (wave-uniform loads, kept out of the VGPRs)
-                        double s = 0.0;
-#pragma unroll
-                        for (int k = 0; k < D; ++k) s += p.ainv[a * D + k] * mp[k];
-                        mfn[a] = s;
-                    }
-                }
-                double mn[D];
-#pragma unroll
-                for (int a = 0; a < D; ++a) {
-                    double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-                    for (int k = 0; k < D; ++k) {
-                        s0 += row[ST::E + a * D + k] * mfn[k];
-                        s1 += row[ST::G + a * D + k] * ms[k];
-                    }
-                    mn[a] = s0 + s1;
-                }
-#pragma unroll
-                for (int a = 0; a < D; ++a) {
-                    ms[a] = mn[a];
-                    mf[a] = mfn[a];
-                }
-                write_out(t, row + ST::VS);
+                for (int k = 0; k < D; ++k) s += ainv[a * D + k] * mp[k];
+                mfn[a] = s;
             }
         }
+        // the slot's refill, behind the last use of its value on every path: issued above it, the new value needs registers of its own and
+        // the loop's back edge copies the whole ring into place — a wait for every load in flight
+        __builtin_amdgcn_sched_barrier(0);
+        load_y<DY>(p.y, y_index(i + R), p.n_chains, chain, yr[u % R]);
+        double mn[D];
+#pragma unroll
+        for (int a = 0; a < D; ++a) {
+            double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+                s0 += row[ST::E + a * D + k] * mfn[k];
+                s1 += row[ST::G + a * D + k] * ms[k];
+            }
+            mn[a] = s0 + s1;
+        }
+#pragma unroll
+        for (int a = 0; a < D; ++a) {
+            ms[a] = mn[a];
+            mf[a] = mfn[a];
+        }
+        write_out(t, row + ST::VS);
+    };
+    int b = 0;
+    long long i0 = 0;
+    for (; i0 + U <= len; i0 += U, b ^= 1) {  // whole chunks (`len` is uniform across the wave)
+        fetch(i0 + U);
+#pragma unroll
+        for (int u = 0; u < U; ++u) step(u, i0 + u, b);
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        if (i0 + U < len) stash(b ^ 1);
+        stash(b ^ 1);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
+#pragma unroll
+    for (int u = 0; u < U - 1; ++u)   // the last len mod U steps
+        if (i0 + u < len) step(u, i0 + u, b);
 }
 
 }  // namespace rxhip

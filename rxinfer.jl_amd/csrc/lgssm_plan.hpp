@@ -37,7 +37,8 @@ namespace plan {
     X(unsigned long long, mseg_max_bytes, ~0ULL) /* RXHIP_MSEG_MAX_BYTES=n (all ones: no cap) */                                        \
     X(bool, wave8_off, false)             /* RXHIP_WAVE8=0 */                                                                           \
     X(bool, no_frozen, false)             /* RXHIP_NO_FROZEN */                                                                         \
-    X(bool, cov_every_sweep, false)       /* RXHIP_COV_EVERY_SWEEP=1 */
+    X(bool, cov_every_sweep, false)       /* RXHIP_COV_EVERY_SWEEP=1 */                                                                 \
+    X(int, y_ring, 0)                     /* RXHIP_Y_RING=1 (0: not set, -1: any other value; rxhip_lgssm_create refuses it) */
 
 struct Text { char s[16] = {0}; };   // the first 15 characters of a hook's value
 
@@ -81,6 +82,7 @@ struct ScheduleHooks {
         h.wave8_off = is0("RXHIP_WAVE8");
         h.no_frozen = set("RXHIP_NO_FROZEN");
         h.cov_every_sweep = not0("RXHIP_COV_EVERY_SWEEP");
+        if (const char* v = get("RXHIP_Y_RING")) h.y_ring = !std::strcmp(v, "1") ? 1 : -1;
         return h;
     }
     // the hooks' part of the engine-pool key: every field, by the list above

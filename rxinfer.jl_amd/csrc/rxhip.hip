@@ -2172,6 +2172,8 @@ static rxhip_status create_lanes(rxhip_engine* e, const rxhip_lgssm_desc* ds) {
     const int ck_forced = e->hooks.mean_checkpoint;
     if (ck_forced && (ck_forced < 1 || ck_forced > 32 || (ck_forced & (ck_forced - 1))))
         return fail(e, RXHIP_ERR_BADARG, "RXHIP_MEAN_CHECKPOINT=%s: a power of two from 1 to 32", e->hooks.mean_checkpoint_text.s);
+    if (e->hooks.y_ring != 0 && e->hooks.y_ring != 1)
+        return fail(e, RXHIP_ERR_BADARG, "RXHIP_Y_RING: 1 (the depth-1 y ring of the reverse-filter sweep) or unset (depth %d)", Y_RING_SHIPPED);
     const bool rev_cand = plan::rev_cand(e->fused, e->n_chains, e->d, e->dy, e->T, e->hooks);
     if (e->fused) {
         ap.upload(&e->d_ftab, ft.ftab.data(), sizeof(double) * ft.ftab.size());
@@ -2904,7 +2906,7 @@ static rxhip_status run_lanes(rxhip_engine* e, const RunPlan& pl, const Params& 
             e->vt->fe_seg(p, e->stream);
         if (!pl.filter) {
             if ((st = prof_begin(e, RXHIP_K_BACKWARD))) return st;
-            if (pl.backward_sh) e->vt->backward_sh(p, e->h_cst0.data(), e->d_gtab, e->d_segend, e->ck_log2 > 0, bnd_in_sweep ? (fe ? 2 : 1) : 0, write_cov, e->stream);
+            if (pl.backward_sh) e->vt->backward_sh(p, e->h_cst0.data(), e->d_gtab, e->d_segend, e->ck_log2 > 0, bnd_in_sweep ? (fe ? 2 : 1) : 0, write_cov, e->hooks.y_ring == 1 ? 1 : Y_RING_SHIPPED, e->stream);
             else e->vt->backward(p, e->h_cst0.data(), e->uniform, e->stream);
             if ((st = prof_end(e))) return st;
         }

@@ -103,8 +103,11 @@ struct Launch {
     }
     // bnd (reverse-filter sweep only): 0 — a boundary-scan launch came before; 1 / 2 — the sweep's waves run the boundary recursion themselves (2: + free energy)
     // write_cov: false — the per-chain covariance array already holds the table broadcast, the sweep stores the means only
-    static void backward_sh(const Params& p, const double* hc, const double* gtab, const double* segend, bool rev, int bnd, bool write_cov, hipStream_t s) {
-        if (rev) hipLaunchKernelGGL((k_backward_sh_rev<D, DY>), dim3((unsigned)(p.n_chains / 64 * p.S)), dim3(64), 0, s, p, gtab, segend, carg(hc), bnd, write_cov ? 1 : 0);
+    // y_ring (reverse-filter sweep only): steps the observations run ahead of their use, 1 or Y_RING_SHIPPED
+    static void backward_sh(const Params& p, const double* hc, const double* gtab, const double* segend, bool rev, int bnd, bool write_cov, int y_ring, hipStream_t s) {
+        const dim3 grid((unsigned)(p.n_chains / 64 * p.S));
+        if (rev && y_ring == 1) hipLaunchKernelGGL((k_backward_sh_rev<D, DY, 1>), grid, dim3(64), 0, s, p, gtab, segend, carg(hc), bnd, write_cov ? 1 : 0);
+        else if (rev) hipLaunchKernelGGL((k_backward_sh_rev<D, DY, Y_RING_SHIPPED>), grid, dim3(64), 0, s, p, gtab, segend, carg(hc), bnd, write_cov ? 1 : 0);
         else hipLaunchKernelGGL((k_backward_sh<D>), dim3((unsigned)(p.n_chains / 64 * p.S)), dim3(64), 0, s, p, gtab, segend, write_cov ? 1 : 0);
     }
     static void forecast(const PredictParams& p, hipStream_t s) {
