@@ -870,6 +870,50 @@ typedef struct {
 rxhip_status rxhip_probit_create(const rxhip_probit_desc* desc, rxhip_engine** out);
 
 /* ------------------------------------------------------------------------------------------
+ * Hidden Markov model with unknown transition and observation matrices (reference model test/models/statespace/hmm_tests.jl:8-24), for each of
+ * n_series independent series:
+ *     A ~ DirichletCollection(prior_A)     K×K, A[i,j] = p(s_t = i | s_{t-1} = j): each COLUMN j is one Dirichlet
+ *     B ~ DirichletCollection(prior_B)     M×K, B[m,i] = p(x_t = m | s_t = i):     each column one Dirichlet
+ *     s_0 ~ Categorical(prior_s0);   s_t ~ DiscreteTransition(s_{t-1}, A);   x_t ~ DiscreteTransition(s_t, B)       t = 1 … T
+ *     q(s_0 … s_T, A, B) = q(s_0 … s_T) q(A) q(B)
+ * Observations are symbol codes 0 … M−1 stored as doubles, NaN = missing.  2 ≤ K ≤ 16, 2 ≤ M ≤ 64.  q(A), q(B) start from init_A, init_B
+ * (NULL: all ones, the reference's vague(DirichletCollection, …)); every run starts there.
+ * One ITERATION (rxhip_run's argument) is a defined semantic of this engine (csrc/hmm_kernels.hpp):
+ *   1. expected-log tables from the current counts: lA[i,j] = ψ(a[i,j]) − ψ(Σ_i a[i,j]), lB likewise; Ã = exp lA, B̃ = exp lB;
+ *   2. scaled forward–backward over s_0 … s_T with π, Ã and B̃[x_t, ·] (a missing step has factor 1): γ_t = q(s_t), log Z̃ = Σ_t log c_t, and the
+ *      statistics N[i,j] = Σ_t ξ_t(i,j), Mstat[m,i] = Σ_{t: x_t = m} γ_t(i);
+ *   3. a ← prior_A + N, b ← prior_B + Mstat.
+ * The posteriors of iteration i are (γ, a, b) after step 3; its free energy is the Bethe free energy at exactly that point:
+ *     F = −log Z̃ + Σ N∘(lA_old − lA_new) + Σ Mstat∘(lB_old − lB_new) + KL(q_new(A)‖p(A)) + KL(q_new(B)‖p(B))        (KL summed over columns)
+ * Per-iteration values depend on this order and need not equal the reactive engine's; the fixed point does (the reference asserts
+ * |last(free_energy) − 60.614480654| < 0.01 after 20 iterations, hmm_tests.jl:95; this iteration gives 60.615293614 there, 60.614432683 at the fixed point).
+ * share_parameters = 1: all series share one q(A) and one q(B) (one HMM fitted to many sequences): N and Mstat are summed over the series in
+ * ascending order before step 3, F = Σ_series(−log Z̃ + the two correction sums) + one pair of KL terms.
+ * per_series = 1 (only with share_parameters = 0): prior_A, prior_B, init_A, init_B hold one set per series, [n_series][K][K] and [n_series][M][K].
+ * Handle protocol: rxhip_set_data(RXHIP_VAR_Y, x, T*n_series, layout) (a value that is neither an integer 0 … M−1 nor NaN: RXHIP_ERR_BADARG,
+ * and the engine does not run on it: RXHIP_ERR_STATE), rxhip_run(e, iterations, want_free_energy), rxhip_hmm_get_states, rxhip_hmm_get_parameters,
+ * rxhip_get_free_energy (per iteration, summed over series), rxhip_get_free_energy_per_chain (last iteration; with shared parameters the
+ * per-series parts, whose sum lacks the KL terms that rxhip_get_free_energy adds once), rxhip_counters, rxhip_destroy.
+ * RXHIP_ERR_BADARG with a text: K or M out of range, T < 1, a count that is not positive and finite, prior_s0 not positive or not summing to
+ * 1 within 1e-12, per_series together with share_parameters.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    int64_t T, n_series;
+    int32_t K, M;
+    const double *prior_A, *prior_B, *prior_s0;   /* [K][K], [M][K] row-major counts > 0; [K] probabilities > 0 summing to 1 within 1e-12 */
+    const double *init_A, *init_B;                /* initial q(A), q(B) counts or NULL = ones */
+    int32_t share_parameters;
+    int32_t per_series;                           /* 1: priors and initial counts are [n_series] sets (not with share_parameters) */
+    int32_t device;
+    void* stream;
+} rxhip_hmm_desc;
+rxhip_status rxhip_hmm_create(const rxhip_hmm_desc* desc, rxhip_engine** out);
+/* q(s_t), t = 0 … T: probs is [T+1][series][K] (RXHIP_LAYOUT_TIME_CHAIN) or [series][T+1][K] (RXHIP_LAYOUT_CHAIN_TIME) */
+rxhip_status rxhip_hmm_get_states(rxhip_engine* e, double* probs, int32_t layout);
+/* the counts of q(A), q(B): [series or 1][K][K], [series or 1][M][K] (1 with shared parameters); either pointer may be NULL */
+rxhip_status rxhip_hmm_get_parameters(rxhip_engine* e, double* A_counts, double* B_counts);
+
+/* ------------------------------------------------------------------------------------------
  * Several GPUs (one process per GPU; chains / series / points shard).  The path's only exchange is the sum
  * over shards of the Bethe free energy (reference: the single `sumreduce` of src/model/plugins/reactivemp_free_energy.jl:99-123
  * over ALL nodes and variables of the model) and, for the mixture, of the responsibility-weighted statistics that

@@ -23,6 +23,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "digamma.hpp"
 #include "lgssm_kernels.hpp"
 
 namespace rxhip {
@@ -47,17 +48,6 @@ struct GmmParams {
     int write_resp;
     int* status;
 };
-
-__device__ __forceinline__ double digamma_dev(double x) {
-    double r = 0.0;
-    while (x < 6.0) {
-        r -= 1.0 / x;
-        x += 1.0;
-    }
-    const double f = 1.0 / (x * x);
-    return r + log(x) - 0.5 / x -
-           f * (1.0 / 12 - f * (1.0 / 120 - f * (1.0 / 252 - f * (1.0 / 240 - f * (1.0 / 132 - f * (691.0 / 32760 - f / 12))))));
-}
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll

@@ -1,6 +1,6 @@
 // vmp_engines.hip — the mean-field engines of the pattern-matched families behind the C ABI: the uni- and multivariate Gaussian-mixture engines
 // (csrc/gmm_kernels.hpp, mvgmm_kernels.hpp; SURVEY §8 a9/a10: rxhip_gmm_* / rxhip_mvgmm_create) and the hierarchical Gaussian filter
-// (csrc/hgf_kernels.hpp; a11: rxhip_hgf_create, its run), and the probit chain's batched EP (csrc/probit_kernels.hpp: rxhip_probit_create, its run).  The runtime they share with the state-space engines — streams, profiling events,
+// (csrc/hgf_kernels.hpp; a11: rxhip_hgf_create, its run), and the probit chain's batched EP (csrc/probit_kernels.hpp: rxhip_probit_create, its run) and the hidden Markov model's forward–backward VMP (csrc/hmm_kernels.hpp: rxhip_hmm_create, its run).  The runtime they share with the state-space engines — streams, profiling events,
 // the engine handle — is rxhip.hip's (engine.hpp).  No kernels of the state-space path live here.
 #include "../../include/rxhip.h"
 
@@ -19,6 +19,7 @@
 #include "mvgmm_kernels.hpp"
 #include "mvgmm_dense_kernels.hpp"
 #include "probit_kernels.hpp"
+#include "hmm_kernels.hpp"
 #include "engine.hpp"
 
 using namespace rxhip;
@@ -510,8 +511,220 @@ rxhip_status rxhip_probit_create(const rxhip_probit_desc* ds, rxhip_engine** out
     return RXHIP_OK;
 }
 
+// the hidden Markov model's parameter block (doubles): π | prior | init | counts | log tables ×2 | Ã B̃ | KL | statistics | their sum | log Z̃
+static HmmParams hmm_params(const rxhip_engine* e) {
+    const size_t C = (size_t)e->n_chains, K = (size_t)e->hm.K, M = (size_t)e->hm.M, KM = (K + M) * K, G = e->hm.shared ? 1 : C;
+    HmmParams p;
+    p.T = e->T; p.n_series = e->n_chains; p.K = e->hm.K; p.M = e->hm.M; p.shared = e->hm.shared;
+    p.x = e->d_y;
+    double* q = e->hm.d_par;
+    p.pi = q; q += 16;
+    p.prior = q; q += G * KM;
+    p.init = q; q += G * KM;
+    p.counts = q; q += G * KM;
+    p.ltab = q; q += 2 * G * KM;
+    p.ttab = q; q += G * KM;
+    p.kl = q; q += G * 2 * K;
+    p.stat = q; q += C * KM;
+    p.stat_sum = q; q += KM;
+    p.logz = q;
+    p.alpha = e->hm.d_alpha; p.gamma = e->hm.d_gamma; p.fe_series = e->hm.d_fe_series; p.status = e->d_status;
+    return p;
+}
+static size_t hmm_param_doubles(size_t C, size_t K, size_t M, bool shared) {
+    const size_t KM = (K + M) * K, G = shared ? 1 : C;
+    return 16 + 6 * G * KM + G * 2 * K + C * KM + KM + C;
+}
+
+rxhip_status rxhip_hmm_create(const rxhip_hmm_desc* ds, rxhip_engine** out) {
+    if (!out) return RXHIP_ERR_BADARG;
+    *out = nullptr;
+    if (!ds) return RXHIP_ERR_BADARG;
+    rxhip_engine* e = new rxhip_engine();   // from here on every refusal carries a text (rxhip_last_error; the caller destroys the handle)
+    *out = e;
+    e->kind = 6;
+    e->device = -1;
+    if (ds->T < 1) return fail(e, RXHIP_ERR_BADARG, "hmm: T must be at least 1 (got %lld)", (long long)ds->T);
+    if (ds->n_series < 1) return fail(e, RXHIP_ERR_BADARG, "hmm: n_series must be at least 1 (got %lld)", (long long)ds->n_series);
+    if (ds->K < 2 || ds->K > hmm::kMaxK) return fail(e, RXHIP_ERR_BADARG, "hmm: K must be 2 … %d states (got %d)", hmm::kMaxK, ds->K);
+    if (ds->M < 2 || ds->M > hmm::kMaxM) return fail(e, RXHIP_ERR_BADARG, "hmm: M must be 2 … %d symbols (got %d)", hmm::kMaxM, ds->M);
+    if (!ds->prior_A || !ds->prior_B || !ds->prior_s0) return fail(e, RXHIP_ERR_BADARG, "hmm: prior_A, prior_B and prior_s0 are required");
+    if (ds->per_series && ds->share_parameters) return fail(e, RXHIP_ERR_BADARG, "hmm: shared parameters have one prior and one initial q, not one per series");
+    const size_t C = (size_t)ds->n_series, K = (size_t)ds->K, M = (size_t)ds->M, KM = (K + M) * K, G = ds->share_parameters ? 1 : C;
+    const size_t sets = ds->per_series ? C : 1;
+    auto positive = [](const double* v, size_t n) {
+        for (size_t i = 0; i < n; ++i)
+            if (!(v[i] > 0.0) || !std::isfinite(v[i])) return false;
+        return true;
+    };
+    if (!positive(ds->prior_A, sets * K * K)) return fail(e, RXHIP_ERR_BADARG, "hmm: every count of prior_A must be positive and finite");
+    if (!positive(ds->prior_B, sets * M * K)) return fail(e, RXHIP_ERR_BADARG, "hmm: every count of prior_B must be positive and finite");
+    if (ds->init_A && !positive(ds->init_A, sets * K * K)) return fail(e, RXHIP_ERR_BADARG, "hmm: every count of init_A must be positive and finite");
+    if (ds->init_B && !positive(ds->init_B, sets * M * K)) return fail(e, RXHIP_ERR_BADARG, "hmm: every count of init_B must be positive and finite");
+    double psum = 0.0;
+    for (size_t i = 0; i < K; ++i) psum += ds->prior_s0[i];
+    if (!positive(ds->prior_s0, K) || !(std::fabs(psum - 1.0) <= 1e-12))
+        return fail(e, RXHIP_ERR_BADARG, "hmm: prior_s0 must be positive probabilities summing to 1 within 1e-12 (sum − 1 = %g)", psum - 1.0);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(e, RXHIP_ERR_NO_DEVICE, "no HIP device visible");
+    e->hm.K = ds->K; e->hm.M = ds->M; e->hm.shared = ds->share_parameters ? 1 : 0;
+    e->T = ds->T;
+    e->H = 1;   // s has T + 1 entries
+    e->n_chains = ds->n_series;
+    e->d = e->dy = e->dpad = 1;
+    if (ds->device >= 0) {
+        if (ds->device >= ndev) return fail(e, RXHIP_ERR_BADARG, "device %d out of range (%d visible)", ds->device, ndev);
+        e->device = ds->device;
+    } else
+        HIPCHK(e, hipGetDevice(&e->device));
+    SET_DEVICE(e);
+    if (ds->stream) e->stream = (hipStream_t)ds->stream;
+    else {
+        HIPCHK(e, stream_acquire(e->device, &e->stream));
+        e->own_stream = true;
+    }
+    // host image of π | prior | init: one set per parameter set g, the K×K block of A and then the M×K block of B
+    std::vector<double> host(16 + 2 * G * KM, 0.0);
+    for (size_t i = 0; i < K; ++i) host[i] = ds->prior_s0[i];
+    for (size_t g = 0; g < G; ++g) {
+        const size_t src = ds->per_series ? g : 0;
+        double *pr = &host[16 + g * KM], *in = &host[16 + G * KM + g * KM];
+        std::memcpy(pr, ds->prior_A + src * K * K, sizeof(double) * K * K);
+        std::memcpy(pr + K * K, ds->prior_B + src * M * K, sizeof(double) * M * K);
+        for (size_t i = 0; i < KM; ++i) in[i] = 1.0;
+        if (ds->init_A) std::memcpy(in, ds->init_A + src * K * K, sizeof(double) * K * K);
+        if (ds->init_B) std::memcpy(in + K * K, ds->init_B + src * M * K, sizeof(double) * M * K);
+    }
+    const size_t R = (size_t)ds->T + 1;
+    HIPCHK(e, hipMalloc(&e->hm.d_par, sizeof(double) * hmm_param_doubles(C, K, M, e->hm.shared != 0)));
+    HIPCHK(e, hipMemcpy(e->hm.d_par, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMalloc(&e->hm.d_alpha, sizeof(double) * R * C * K));
+    HIPCHK(e, hipMalloc(&e->hm.d_gamma, sizeof(double) * R * C * K));
+    HIPCHK(e, hipMalloc(&e->d_fe_chain, sizeof(double) * C));
+    e->fe_total_cap = 32;
+    HIPCHK(e, hipMalloc(&e->d_fe_total, sizeof(double) * e->fe_total_cap));
+    HIPCHK(e, hipMalloc(&e->d_status, sizeof(int)));
+    HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
+    return RXHIP_OK;
+}
+
+rxhip_status rxhip_hmm_get_states(rxhip_engine* e, double* probs, int32_t layout) {
+    if (!e || e->kind != 6) return RXHIP_ERR_BADARG;
+    if (!probs) return fail(e, RXHIP_ERR_BADARG, "hmm_get_states: no output array");
+    if (layout != RXHIP_LAYOUT_TIME_CHAIN && layout != RXHIP_LAYOUT_CHAIN_TIME) return fail(e, RXHIP_ERR_BADARG, "hmm_get_states: unknown layout %d", layout);
+    if (!e->ran) return fail(e, RXHIP_ERR_STATE, "hmm_get_states: no run yet");
+    SET_DEVICE(e);
+    const size_t C = (size_t)e->n_chains, K = (size_t)e->hm.K, R = (size_t)e->T + 1;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (layout == RXHIP_LAYOUT_TIME_CHAIN || C == 1) {
+        HIPCHK(e, hipMemcpy(probs, e->hm.d_gamma, sizeof(double) * R * C * K, hipMemcpyDeviceToHost));
+        return RXHIP_OK;
+    }
+    std::vector<double> tmp(R * C * K);
+    HIPCHK(e, hipMemcpy(tmp.data(), e->hm.d_gamma, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost));
+    for (size_t t = 0; t < R; ++t)
+        for (size_t s = 0; s < C; ++s) std::memcpy(probs + (s * R + t) * K, &tmp[(t * C + s) * K], sizeof(double) * K);
+    return RXHIP_OK;
+}
+
+rxhip_status rxhip_hmm_get_parameters(rxhip_engine* e, double* A_counts, double* B_counts) {
+    if (!e || e->kind != 6) return RXHIP_ERR_BADARG;
+    if (!e->ran) return fail(e, RXHIP_ERR_STATE, "hmm_get_parameters: no run yet");
+    SET_DEVICE(e);
+    const size_t C = (size_t)e->n_chains, K = (size_t)e->hm.K, M = (size_t)e->hm.M, KM = (K + M) * K, G = e->hm.shared ? 1 : C;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    std::vector<double> tmp(G * KM);
+    HIPCHK(e, hipMemcpy(tmp.data(), hmm_params(e).counts, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost));
+    for (size_t g = 0; g < G; ++g) {
+        if (A_counts) std::memcpy(A_counts + g * K * K, &tmp[g * KM], sizeof(double) * K * K);
+        if (B_counts) std::memcpy(B_counts + g * M * K, &tmp[g * KM + K * K], sizeof(double) * M * K);
+    }
+    return RXHIP_OK;
+}
 
 }  // extern "C"
+
+// every observation of a hidden Markov model engine is an integer code 0 … M−1 or NaN: checked on the device copy, whichever way it arrived
+rxhip_status rxhip::hmm_check_data(rxhip_engine* e) {
+    SET_DEVICE(e);
+    const long long n = e->T * e->n_chains;
+    const unsigned nb = (unsigned)std::min<long long>((n + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_hmm_check_x, dim3(nb), dim3(256), 0, e->stream, (const double*)e->d_y, n, e->hm.M, e->d_status);
+    HIPCHK(e, hipGetLastError());
+    int st = 0;
+    HIPCHK(e, hipMemcpyAsync(&st, e->d_status, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (st & ST_HMM_BAD_X) {
+        HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
+        e->have_data = false;
+        return fail(e, RXHIP_ERR_BADARG, "set_data: an observation is neither an integer symbol code 0 … %d nor NaN (missing)", e->hm.M - 1);
+    }
+    return RXHIP_OK;
+}
+
+template <int R>
+static void hmm_launch_sweep(const HmmParams& p, bool out, hipStream_t stream) {
+    const unsigned spw = 64 / R, grid = (unsigned)((p.n_series + spw - 1) / spw);
+    const size_t lds = sizeof(double) * 64 * (size_t)p.M;   // [series in wave][M][R]
+    if (out) hipLaunchKernelGGL((k_hmm_sweep<R, true>), dim3(grid), dim3(64), lds, stream, p);
+    else hipLaunchKernelGGL((k_hmm_sweep<R, false>), dim3(grid), dim3(64), lds, stream, p);
+}
+
+rxhip_status rxhip::hmm_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
+    if (iterations <= 0) return fail(e, RXHIP_ERR_BADARG, "run: iterations must be positive");
+    if (!e->have_data) return fail(e, RXHIP_ERR_STATE, "run: no observations (call rxhip_set_data first)");
+    SET_DEVICE(e);
+    const size_t C = (size_t)e->n_chains;
+    if (iterations > e->fe_total_cap) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        HIPCHK(e, hipFree(e->d_fe_total));
+        e->d_fe_total = nullptr;
+        e->fe_total_cap = iterations;
+        HIPCHK(e, hipMalloc(&e->d_fe_total, sizeof(double) * e->fe_total_cap));
+    }
+    if (want_fe && iterations > e->hm.fe_cap) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        if (e->hm.d_fe_series) HIPCHK(e, hipFree(e->hm.d_fe_series));
+        e->hm.d_fe_series = nullptr;
+        e->hm.fe_cap = 0;
+        HIPCHK(e, hipMalloc(&e->hm.d_fe_series, sizeof(double) * (size_t)iterations * C));
+        e->hm.fe_cap = iterations;
+    }
+    const HmmParams p = hmm_params(e);
+    const int K = p.K, KM = (K + p.M) * K;
+    const long long G = p.shared ? 1 : p.n_series;
+    const unsigned cgrid = (unsigned)((G * 2 * K + 255) / 256), sgrid = (unsigned)((C + 255) / 256);
+    // every run starts from init_A, init_B: their tables go to half 0 of the log tables; iteration i reads half i % 2 and writes the other
+    hipLaunchKernelGGL(k_hmm_tables, dim3(cgrid), dim3(256), 0, e->stream, p, 0);
+    for (int i = 0; i < iterations; ++i) {
+        const bool last = i == iterations - 1;
+        const int cur = (i + 1) & 1;
+        if (K <= 2) hmm_launch_sweep<2>(p, last, e->stream);
+        else if (K <= 4) hmm_launch_sweep<4>(p, last, e->stream);
+        else if (K <= 8) hmm_launch_sweep<8>(p, last, e->stream);
+        else hmm_launch_sweep<16>(p, last, e->stream);
+        if (p.shared) hipLaunchKernelGGL(k_hmm_reduce, dim3((unsigned)((KM + 255) / 256)), dim3(256), 0, e->stream, p);
+        hipLaunchKernelGGL(k_hmm_update, dim3(cgrid), dim3(256), 0, e->stream, p, cur);
+        if (want_fe) {
+            hipLaunchKernelGGL(k_hmm_fe, dim3(sgrid), dim3(256), 0, e->stream, p, i, cur);
+            hipLaunchKernelGGL(k_hmm_fe_total, dim3(1), dim3(256), 0, e->stream, p, i, e->d_fe_total);
+        }
+    }
+    if (want_fe)
+        HIPCHK(e, hipMemcpyAsync(e->d_fe_chain, e->hm.d_fe_series + (size_t)(iterations - 1) * C, sizeof(double) * C, hipMemcpyDeviceToDevice, e->stream));
+    HIPCHK(e, hipGetLastError());
+    e->last_iterations = iterations;
+    e->last_want_fe = want_fe != 0;
+    e->ran = true;
+    e->last_filter = false;
+    // reference-equivalent events per series and iteration: a forward and a backward transition message and an observation message per step, the
+    // messages toward A and B; products and marginals at the T + 1 states and the two matrices
+    const uint64_t Cs = (uint64_t)C, T = (uint64_t)e->T, I = (uint64_t)iterations;
+    e->rule_calls = I * Cs * (3 * T + 2);
+    e->products = I * Cs * 2 * (T + 1);
+    e->marginals = I * Cs * (T + 3);
+    return RXHIP_OK;
+}
 
 // every observation of a probit engine is 0, 1 or NaN: checked on the device copy, whichever way it arrived
 rxhip_status rxhip::probit_check_data(rxhip_engine* e) {

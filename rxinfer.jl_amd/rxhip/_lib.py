@@ -113,6 +113,12 @@ class ProbitDesc(ctypes.Structure):
         ("n_gh", ctypes.c_int32), ("device", ctypes.c_int32), ("stream", ctypes.c_void_p)]
 
 
+class HmmDesc(ctypes.Structure):   # rxhip_hmm_desc
+    _fields_ = [("T", ctypes.c_int64), ("n_series", ctypes.c_int64), ("K", ctypes.c_int32), ("M", ctypes.c_int32)] + [
+        (n, c_double_p) for n in ("prior_A", "prior_B", "prior_s0", "init_A", "init_B")] + [
+        ("share_parameters", ctypes.c_int32), ("per_series", ctypes.c_int32), ("device", ctypes.c_int32), ("stream", ctypes.c_void_p)]
+
+
 class NoisePrior(ctypes.Structure):   # rxhip_noise_prior
     _fields_ = [("nu0", ctypes.c_double), ("S0", c_double_p), ("init_nu", ctypes.c_double), ("init_V", c_double_p)]
 
@@ -214,6 +220,9 @@ SYMBOLS = [
     ("rxhip_hgf_create", ctypes.c_int32, [ctypes.POINTER(HgfDesc), ctypes.POINTER(_H)]),
     ("rxhip_drift_chain_create", ctypes.c_int32, [ctypes.POINTER(DriftChainDesc), ctypes.POINTER(_H)]),
     ("rxhip_probit_create", ctypes.c_int32, [ctypes.POINTER(ProbitDesc), ctypes.POINTER(_H)]),
+    ("rxhip_hmm_create", ctypes.c_int32, [ctypes.POINTER(HmmDesc), ctypes.POINTER(_H)]),
+    ("rxhip_hmm_get_states", ctypes.c_int32, [_H, c_double_p, ctypes.c_int32]),
+    ("rxhip_hmm_get_parameters", ctypes.c_int32, [_H, c_double_p, c_double_p]),
     ("rxhip_hgf_get_history", ctypes.c_int32, [_H, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_int32]),
     ("rxhip_set_profiling", ctypes.c_int32, [_H, ctypes.c_int32]),
     ("rxhip_get_kernel_times", ctypes.c_int32, [_H, c_double_p, c_u64_p]),

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RxHipError
-from .engine import DriftChainEngine, GMMEngine, HGFEngine, LGSSMEngine, MvGMMEngine, ProbitEngine
+from .engine import DriftChainEngine, GMMEngine, HGFEngine, LGSSMEngine, MvGMMEngine, ProbitEngine, HMMEngine
 
 
 @dataclass
@@ -258,6 +258,65 @@ def _infer_probit(model, data, iterations, free_energy, options, catch_exception
         if single:
             mean, var = mean[:, 0], var[:, 0]
         return InferenceResult({"x": NormalMeanVariance(mean, var)}, None, fe, model, None)
+    except Exception as err:
+        if not catch_exception:
+            raise
+        return InferenceResult({}, None, None, model, err)
+    finally:
+        if eng is not None:
+            eng.close()
+
+
+@dataclass
+class HiddenMarkovModel:
+    """`A ~ DirichletCollection(prior_A); B ~ DirichletCollection(prior_B); s_0 ~ Categorical(prior_s0); s[t] ~ DiscreteTransition(s[t-1], A);
+    x[t] ~ DiscreteTransition(s[t], B)` with `q(s, s_0, A, B) = q(s, s_0)q(A)q(B)` (test/models/statespace/hmm_tests.jl:8-24)."""
+    prior_A: np.ndarray
+    prior_B: np.ndarray
+    prior_s0: np.ndarray
+    init_A: Optional[np.ndarray] = None
+    init_B: Optional[np.ndarray] = None
+    share_parameters: bool = False
+
+
+def hidden_markov_model(prior_A, prior_B, prior_s0, init_A=None, init_B=None, share_parameters=False):
+    f = lambda v: None if v is None else np.asarray(v, dtype=np.float64)
+    return HiddenMarkovModel(f(prior_A), f(prior_B), f(prior_s0), f(init_A), f(init_B), bool(share_parameters))
+
+
+def one_hot_to_codes(vectors):
+    """The reference's HMM data are one-hot vectors (hmm_tests.jl:47-52): [..., M] -> symbol codes [...]; a vector that is not one-hot becomes
+    NaN (missing)."""
+    v = np.asarray(vectors, dtype=np.float64)
+    ok = (np.sum(v == 1.0, axis=-1) == 1) & (np.sum(v != 0.0, axis=-1) == 1)
+    return np.where(ok, np.argmax(v, axis=-1).astype(np.float64), np.nan)
+
+
+def _infer_hmm(model, data, iterations, free_energy, options, catch_exception):
+    """x: integer symbol codes [T] or [T][series] (floats with NaN = missing are taken as they are).  posteriors["s"]: probabilities
+    [T+1][K] (or [T+1][series][K]); posteriors["A"], ["B"]: Dirichlet counts [K][K], [M][K] (a leading series axis for an unshared batch);
+    free_energy: one value per iteration (summed over the series of a batch)."""
+    options = _check_options(options)
+    x = np.asarray(data["x"], dtype=np.float64)
+    single = x.ndim == 1
+    if single:
+        x = x[:, None]
+    T, C = x.shape
+    iters = 1 if iterations is None else int(iterations)
+    eng = None
+    try:
+        eng = HMMEngine(T, model.prior_A, model.prior_B, model.prior_s0, model.init_A, model.init_B, n_series=C,
+                        share_parameters=model.share_parameters, device=int(options.get("device", -1)))
+        eng.set_data(x, layout="time_chain")
+        eng.run(iterations=iters, free_energy=free_energy)
+        s = eng.states(layout="time_chain")
+        a, b = eng.parameters()
+        fe = eng.free_energy() if free_energy else None
+        if single:
+            s = s[:, 0]
+        if single or model.share_parameters:
+            a, b = a[0], b[0]
+        return InferenceResult({"s": s, "A": a, "B": b}, None, fe, model, None)
     except Exception as err:
         if not catch_exception:
             raise
@@ -533,6 +592,8 @@ def infer(*, model, data, iterations=None, free_energy=False, options=None, retu
         return _infer_drift_chain(model, data, iterations, free_energy, options, catch_exception)
     if isinstance(model, ProbitSSM):
         return _infer_probit(model, data, iterations, free_energy, options, catch_exception)
+    if isinstance(model, HiddenMarkovModel):
+        return _infer_hmm(model, data, iterations, free_energy, options, catch_exception)
     if not isinstance(model, LinearGaussianSSM):
         raise TypeError("infer: no device schedule for this model type")
     if model.noise_precision_prior is not None:

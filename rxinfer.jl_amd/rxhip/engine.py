@@ -668,6 +668,74 @@ class ProbitEngine:
         return mean[..., 0], cov[..., 0, 0]
 
 
+class HMMEngine:
+    """Hidden Markov model with unknown transition and observation matrices (test/models/statespace/hmm_tests.jl:8-24) for n_series independent
+    series: batched forward–backward VMP (include/rxhip.h rxhip_hmm_desc).  prior_A [K][K] and prior_B [M][K] are Dirichlet counts per COLUMN
+    (A[i, j] = p(s_t = i | s_{t-1} = j), B[m, i] = p(x_t = m | s_t = i)), prior_s0 [K] probabilities; init_A / init_B the initial q (None: ones).
+    Priors and initial counts may carry a leading [n_series] axis (one set per series; not with share_parameters).
+    `run(iterations)`: that many iterations from the initial q; `states()`: q(s_0 … s_T); `parameters()`: the counts of q(A), q(B)."""
+
+    def __init__(self, T, prior_A, prior_B, prior_s0, init_A=None, init_B=None, n_series=1, share_parameters=False, device=-1, stream=None):
+        L = _lib.lib()
+        arrs = [None if v is None else _c(v) for v in (prior_A, prior_B, prior_s0, init_A, init_B)]
+        pA, pB, ps0, iA, iB = arrs
+        if pA.ndim not in (2, 3) or pB.ndim != pA.ndim or pA.shape[-1] != pA.shape[-2] or pB.shape[-1] != pA.shape[-1] or ps0.shape != (pA.shape[-1],):
+            raise ValueError("prior_A must be [K][K], prior_B [M][K], prior_s0 [K] (A and B optionally with a leading series axis)")
+        for name, v, ref in (("init_A", iA, pA), ("init_B", iB, pB)):
+            if v is not None and v.shape != ref.shape:
+                raise ValueError(f"{name} must have the shape of its prior, {ref.shape}")
+        per_series = pA.ndim == 3
+        if per_series and (pA.shape[0] != int(n_series) or pB.shape[0] != int(n_series)):
+            raise ValueError("per-series priors need a leading axis of n_series sets")
+        desc = _lib.HmmDesc()
+        desc.T, desc.n_series, desc.K, desc.M = int(T), int(n_series), int(pA.shape[-1]), int(pB.shape[-2])
+        desc.prior_A, desc.prior_B, desc.prior_s0 = _p(pA), _p(pB), _p(ps0)
+        desc.init_A, desc.init_B = (None if iA is None else _p(iA)), (None if iB is None else _p(iB))
+        desc.share_parameters, desc.per_series, desc.device = int(bool(share_parameters)), int(per_series), int(device)
+        desc.stream = ctypes.c_void_p(stream) if stream else None
+        self.T, self.n_series, self.n_chains, self.K, self.M = int(T), int(n_series), int(n_series), desc.K, desc.M
+        self.share_parameters = bool(share_parameters)
+        self._h = ctypes.c_void_p()
+        st = L.rxhip_hmm_create(ctypes.byref(desc), ctypes.byref(self._h))
+        if st != _lib.OK:
+            msg = L.rxhip_last_error(self._h).decode() if self._h else L.rxhip_status_string(st).decode()
+            if self._h:
+                L.rxhip_destroy(self._h)
+                self._h = None
+            raise RxHipError(st, msg or L.rxhip_status_string(st).decode())
+        self._iters = 0
+        self._data_ref = None
+
+    _chk = LGSSMEngine._chk
+    close = LGSSMEngine.close
+    __del__ = LGSSMEngine.__del__
+    __enter__ = LGSSMEngine.__enter__
+    __exit__ = LGSSMEngine.__exit__
+    sync = LGSSMEngine.sync
+    run = LGSSMEngine.run
+    run_async = LGSSMEngine.run_async
+    set_data = HGFEngine.set_data
+    set_data_device = HGFEngine.set_data_device
+    free_energy = LGSSMEngine.free_energy
+    free_energy_per_chain = LGSSMEngine.free_energy_per_chain
+    counters = LGSSMEngine.counters
+    stream = LGSSMEngine.stream
+
+    def states(self, layout="time_chain"):
+        """q(s_t), t = 0 … T: [T+1][series][K] ('time_chain') or [series][T+1][K] ('chain_time')."""
+        lay = _lib.LAYOUT_TIME_CHAIN if layout == "time_chain" else _lib.LAYOUT_CHAIN_TIME
+        out = np.empty((self.T + 1, self.n_series, self.K) if layout == "time_chain" else (self.n_series, self.T + 1, self.K))
+        self._chk(_lib.lib().rxhip_hmm_get_states(self._h, _p(out), lay))
+        return out
+
+    def parameters(self):
+        """(A counts [series or 1][K][K], B counts [series or 1][M][K]); 1 with shared parameters."""
+        G = 1 if self.share_parameters else self.n_series
+        a, b = np.empty((G, self.K, self.K)), np.empty((G, self.M, self.K))
+        self._chk(_lib.lib().rxhip_hmm_get_parameters(self._h, _p(a), _p(b)))
+        return a, b
+
+
 class Communicator:
     """RCCL communicator made through the C ABI (rxhip_comm_*): rank 0 calls `Communicator.unique_id()`, the 128 bytes
     travel to the other ranks by any host-side means, every rank constructs `Communicator(nranks, id, rank)`."""
