@@ -914,6 +914,60 @@ rxhip_status rxhip_hmm_get_states(rxhip_engine* e, double* probs, int32_t layout
 rxhip_status rxhip_hmm_get_parameters(rxhip_engine* e, double* A_counts, double* B_counts);
 
 /* ------------------------------------------------------------------------------------------
+ * Latent autoregressive model with unknown coefficients and driving-noise precision (reference model test/models/autoregressive/lar_tests.jl:51-76;
+ * its Univariate AR(1) spelling is order 1 of this), for each of n_series independent series, written in scalars: order p (1 … 8), latent
+ * z_{-p+1} … z_T, x_t = (z_t … z_{t-p+1}), x0 = (z_0 … z_{-p+1}):
+ *     γ ~ Gamma(a0, b0);  θ ~ MvNormal(mθ0, Wθ0⁻¹);  x0 ~ MvNormal(m0, W0⁻¹);  x[t] ~ AR(x[t-1], θ, γ): z_t | x_{t-1} ~ N(θᵀx_{t-1}, 1/γ);
+ *     y[t] ~ Normal(c·x[t], τ⁻¹), c = e₁: y_t | z_t ~ N(z_t, 1/τ)            t = 1 … T;          q(x, x0, θ, γ) = q(x, x0) q(θ) q(γ)
+ * The shift rows of the AR node are exact identities (the reference's ARsafe ε is not modelled).  A NaN y_t is missing and contributes no factor.
+ * Every run starts from init q(θ) = N(init_theta_mean, init_theta_cov) and init q(γ) = Gamma(init_gamma_shape, init_gamma_rate); a NULL init
+ * means the prior's own values (the reference's initialisation equals its priors).
+ * One ITERATION (rxhip_run's argument) is a defined semantic of this engine (csrc/lar_kernels.hpp), three exact coordinate updates in the order x, θ, γ:
+ *   1. q(z) = N(m, Λ⁻¹), n = T + p scalars, under the current q(θ) = N(mθ, Vθ), q(γ) = Gamma(a, b), mγ = a/b:  Λ = W0 on the first p scalars
+ *      + Σ_t mγ·G on w_t = (z_t, z_{t-1} … z_{t-p}), G = [[1, −mθᵀ], [−mθ, mθmθᵀ + Vθ]], + τ on the diagonal of every observed z_t;
+ *      h = W0 m0 on x0 + τ y_t on observed z_t.  Λ is banded: Λ = L D Lᵀ, m = Λ⁻¹h, ln det Λ = Σ ln d_i, the band of Σ = Λ⁻¹ up to lag p by the
+ *      selected-inverse recursion.  Statistics: S = Σ_t E[w_t w_tᵀ] (Szz = S_00, Szx = S_0,1:, Sxx = S_1:,1:), E_y = Σ_obs((y_t − m_t)² + Σ_tt),
+ *      N_obs, E_0 = (m_x0 − m0)ᵀW0(m_x0 − m0) + tr(W0 Σ_x0);
+ *   2. q(θ):  Wθ = Wθ0 + mγ Sxx (the old mγ),  Vθ = Wθ⁻¹,  mθ = Vθ(Wθ0 mθ0 + mγ Szx);
+ *   3. q(γ):  a = a0 + T/2,  b = b0 + R/2,  R = Szz − 2 mθᵀSzx + tr((mθmθᵀ + Vθ) Sxx) with the NEW θ.
+ * The posteriors of iteration i are q(z) of step 1 and q(θ), q(γ) after steps 2 and 3; its free energy is the exact variational free energy there:
+ *     F = −½(n ln 2πe − ln det Λ) + ½(p ln 2π − ln det W0 + E_0) + ½(T ln 2π − T(ψ(a) − ln b) + (a/b) R) + ½(N_obs ln 2π − N_obs ln τ + τ E_y)
+ *         + KL(q(θ)‖p(θ)) + KL(q(γ)‖p(γ))
+ * Every update is an exact coordinate step, so F does not rise from one iteration to the next.  Per-iteration values belong to this engine (they
+ * depend on this order and need not equal the reactive engine's); the end of the run does: on the regenerated data of lar_tests.jl:130-158 with
+ * τ = 5, unit priors and 15 iterations this iteration gives 518.918234267 (p = 1; the reference asserts 518.9182342 ± 0.01, lar_tests.jl:171) and
+ * 514.653888437 (p = 5; 514.66086 ± 0.01, lar_tests.jl:202).
+ * share_parameters = 1: one q(θ) and one q(γ) for all series: S is summed over the series in ascending order before steps 2 and 3,
+ * a = a0 + n_series·T/2, F = Σ_series(the first four terms) + the two KL terms once.
+ * Handle protocol: rxhip_set_data(RXHIP_VAR_Y, y, T*n_series, layout) (NaN = missing; ±Inf: RXHIP_ERR_BADARG, and the engine does not run on it:
+ * RXHIP_ERR_STATE), rxhip_run(e, iterations, want_free_energy), rxhip_lar_get_states, rxhip_lar_get_parameters, rxhip_get_free_energy (per
+ * iteration, summed over series), rxhip_get_free_energy_per_chain (last iteration; with shared parameters the per-series parts, whose sum lacks
+ * the KL terms that rxhip_get_free_energy adds once), rxhip_counters, rxhip_destroy.
+ * RXHIP_ERR_BADARG with a text: order outside 1 … 8, T < 1, tau, a shape or a rate that is not positive and finite, a precision or covariance
+ * that is not symmetric (within 1e-12 of its largest entry) positive definite (host Cholesky).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    int64_t T, n_series;
+    int32_t order;                                                /* p, 1 … 8 */
+    double tau;                                                   /* observation precision */
+    const double *prior_theta_mean, *prior_theta_precision;       /* [p], [p][p] */
+    double prior_gamma_shape, prior_gamma_rate;
+    const double *prior_x0_mean, *prior_x0_precision;             /* [p], [p][p]; x0 = (z_0 … z_{-p+1}) */
+    const double *init_theta_mean, *init_theta_cov;               /* [p], [p][p] (a covariance) or NULL = the prior's mean / inverse precision */
+    const double *init_gamma_shape, *init_gamma_rate;             /* one double each or NULL = the prior's */
+    int32_t share_parameters;
+    int32_t device;
+    void* stream;
+} rxhip_lar_desc;
+rxhip_status rxhip_lar_create(const rxhip_lar_desc* desc, rxhip_engine** out);
+/* q(x[t]), t = 1 … T, of the last iteration, assembled from the stored band of Σ: mean [T][series][p], cov [T][series][p][p]
+ * (RXHIP_LAYOUT_TIME_CHAIN) or [series][T][…] (RXHIP_LAYOUT_CHAIN_TIME); either pointer may be NULL */
+rxhip_status rxhip_lar_get_states(rxhip_engine* e, double* mean, double* cov, int32_t layout);
+/* q(θ), q(γ) after EVERY iteration of the last run (the reference keeps KeepEach() for γ and θ): theta_mean [iterations][G][p], theta_cov
+ * [iterations][G][p][p], gamma_shape, gamma_rate [iterations][G], G = n_series (1 with shared parameters); any pointer may be NULL */
+rxhip_status rxhip_lar_get_parameters(rxhip_engine* e, double* theta_mean, double* theta_cov, double* gamma_shape, double* gamma_rate);
+
+/* ------------------------------------------------------------------------------------------
  * Several GPUs (one process per GPU; chains / series / points shard).  The path's only exchange is the sum
  * over shards of the Bethe free energy (reference: the single `sumreduce` of src/model/plugins/reactivemp_free_energy.jl:99-123
  * over ALL nodes and variables of the model) and, for the mixture, of the responsibility-weighted statistics that

@@ -105,7 +105,7 @@ struct rxhip_engine : rxhip_engine_life {
     int* d_status = nullptr;
     double* d_fe_blocks = nullptr;
     // Gaussian-mixture VMP engine (kind == 1)
-    int kind = 0;  // 0: LGSSM, 1: GMM, 2: HGF, 3: noise-free drift chain, 4: probit chain (batched EP, probit_kernels.hpp), 5: the level-scheduled node-array executor (tree_engine.hip; everything lives behind `tree`), 6: hidden Markov model (batched forward–backward VMP, hmm_kernels.hpp)
+    int kind = 0;  // 0: LGSSM, 1: GMM, 2: HGF, 3: noise-free drift chain, 4: probit chain (batched EP, probit_kernels.hpp), 5: the level-scheduled node-array executor (tree_engine.hip; everything lives behind `tree`), 6: hidden Markov model (batched forward–backward VMP, hmm_kernels.hpp), 7: latent autoregressive model (batched banded structured VMP, lar_kernels.hpp)
     rxhip::tree::Engine* tree = nullptr;
     struct Drift { double m0 = 0, v0 = 1, c = 0, obs_var = 1; } dr;
     struct Hgf {
@@ -123,6 +123,11 @@ struct rxhip_engine : rxhip_engine_life {
         double *d_par = nullptr, *d_alpha = nullptr, *d_gamma = nullptr, *d_fe_series = nullptr;
         int fe_cap = 0;
     } hm;
+    struct Lar {      // kind == 7: constants, parameter block (initial q | G per set | KL | statistics | their sum), parameter history, row records, m and the Σ band, free energies
+        int P = 0, shared = 0;
+        double *d_cst = nullptr, *d_par = nullptr, *d_hist = nullptr, *d_rec = nullptr, *d_out = nullptr, *d_fe_series = nullptr;
+        int fe_cap = 0, hist_cap = 0;
+    } la;
     struct Gmm {
         long long N = 0;
         int K = 0, KT = 0, materialize = 0, nblocks = 0, it = 0, iterations = 0, hist_cap = 0;
@@ -280,6 +285,8 @@ rxhip_status probit_run_async(rxhip_engine* e, int32_t iterations, int32_t want_
 rxhip_status probit_check_data(rxhip_engine* e);   // … and its check of freshly ingested observations: 0, 1 or NaN
 rxhip_status hmm_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe);      // the hidden Markov model's run (vmp_engines.hip)
 rxhip_status hmm_check_data(rxhip_engine* e);   // … and its check of freshly ingested observations: an integer code 0 … M−1 or NaN
+rxhip_status lar_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe);      // the latent autoregressive model's run (vmp_engines.hip)
+rxhip_status lar_check_data(rxhip_engine* e);   // … and its check of freshly ingested observations: finite or NaN (missing)
 bool host_chol_inv(int n, const double* A, double* out, double* logdet);   // host Cholesky inverse + log-determinant of an SPD matrix (rxhip.hip host::chol_inv)
 }  // namespace rxhip
 

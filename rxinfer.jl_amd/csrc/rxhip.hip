@@ -1462,6 +1462,8 @@ static void free_all(rxhip_engine* e) {
         if (*b) { (void)hipFree(*b); *b = nullptr; }
     for (double** b : {&e->hm.d_par, &e->hm.d_alpha, &e->hm.d_gamma, &e->hm.d_fe_series})
         if (*b) { (void)hipFree(*b); *b = nullptr; }
+    for (double** b : {&e->la.d_cst, &e->la.d_par, &e->la.d_hist, &e->la.d_rec, &e->la.d_out, &e->la.d_fe_series})
+        if (*b) { (void)hipFree(*b); *b = nullptr; }
     for (double** b : {&e->d_scanm, &e->d_fstart_m, &e->d_beta_xi, &e->d_vend, &e->d_qtab, &e->d_loc, &e->d_aggpart, &e->d_bnd})
         if (*b) { if (!e->in_arena(*b)) (void)hipFree(*b); *b = nullptr; }
     if (e->d_coll) { (void)hipFree(e->d_coll); e->d_coll = nullptr; }
@@ -2540,6 +2542,7 @@ rxhip_status rxhip_set_data(rxhip_engine* e, int32_t var_id, const double* host,
     if (var_id != RXHIP_VAR_Y) return fail(e, RXHIP_ERR_BADARG, "set_data: variable %d is not a data variable", var_id);
     const rxhip_status st = ingest(e, host, n, layout, false);
     if (st == RXHIP_OK && e->kind == 6) return rxhip::hmm_check_data(e);
+    if (st == RXHIP_OK && e->kind == 7) return rxhip::lar_check_data(e);
     return st == RXHIP_OK && e->kind == 4 ? rxhip::probit_check_data(e) : st;
 }
 rxhip_status rxhip_set_data_device(rxhip_engine* e, int32_t var_id, const double* dev, size_t n, int32_t layout) {
@@ -2548,6 +2551,7 @@ rxhip_status rxhip_set_data_device(rxhip_engine* e, int32_t var_id, const double
     if (var_id != RXHIP_VAR_Y) return fail(e, RXHIP_ERR_BADARG, "set_data: variable %d is not a data variable", var_id);
     const rxhip_status st = ingest(e, dev, n, layout, true);
     if (st == RXHIP_OK && e->kind == 6) return rxhip::hmm_check_data(e);
+    if (st == RXHIP_OK && e->kind == 7) return rxhip::lar_check_data(e);
     return st == RXHIP_OK && e->kind == 4 ? rxhip::probit_check_data(e) : st;
 }
 
@@ -2968,6 +2972,10 @@ static rxhip_status run_impl(rxhip_engine* e, int32_t iterations, int32_t want_f
     if (e->kind == 6) {
         if (filter) return fail(e, RXHIP_ERR_BADARG, "run_filter: not a state-space engine with a streaming twin");
         return rxhip::hmm_run_async(e, iterations, want_fe);
+    }
+    if (e->kind == 7) {
+        if (filter) return fail(e, RXHIP_ERR_BADARG, "run_filter: not a state-space engine with a streaming twin");
+        return rxhip::lar_run_async(e, iterations, want_fe);
     }
     if (e->kind == 3) {
         if (filter) return fail(e, RXHIP_ERR_BADARG, "run_filter: not a state-space engine with a streaming twin");

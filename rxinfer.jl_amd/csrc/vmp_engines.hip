@@ -1,6 +1,6 @@
 // vmp_engines.hip — the mean-field engines of the pattern-matched families behind the C ABI: the uni- and multivariate Gaussian-mixture engines
 // (csrc/gmm_kernels.hpp, mvgmm_kernels.hpp; SURVEY §8 a9/a10: rxhip_gmm_* / rxhip_mvgmm_create) and the hierarchical Gaussian filter
-// (csrc/hgf_kernels.hpp; a11: rxhip_hgf_create, its run), and the probit chain's batched EP (csrc/probit_kernels.hpp: rxhip_probit_create, its run) and the hidden Markov model's forward–backward VMP (csrc/hmm_kernels.hpp: rxhip_hmm_create, its run).  The runtime they share with the state-space engines — streams, profiling events,
+// (csrc/hgf_kernels.hpp; a11: rxhip_hgf_create, its run), and the probit chain's batched EP (csrc/probit_kernels.hpp: rxhip_probit_create, its run) and the hidden Markov model's forward–backward VMP (csrc/hmm_kernels.hpp: rxhip_hmm_create, its run) and the latent autoregressive model's banded structured VMP (csrc/lar_kernels.hpp: rxhip_lar_create, its run).  The runtime they share with the state-space engines — streams, profiling events,
 // the engine handle — is rxhip.hip's (engine.hpp).  No kernels of the state-space path live here.
 #include "../../include/rxhip.h"
 
@@ -20,6 +20,7 @@
 #include "mvgmm_dense_kernels.hpp"
 #include "probit_kernels.hpp"
 #include "hmm_kernels.hpp"
+#include "lar_kernels.hpp"
 #include "engine.hpp"
 
 using namespace rxhip;
@@ -643,6 +644,280 @@ rxhip_status rxhip_hmm_get_parameters(rxhip_engine* e, double* A_counts, double*
 }
 
 }  // extern "C"
+
+// the latent autoregressive model's parameter block (doubles): initial q | G, mγ per set | KL per set | statistics [ns][series] | their sum
+static LarParams lar_params(const rxhip_engine* e) {
+    const size_t C = (size_t)e->n_chains, G = e->la.shared ? 1 : C;
+    const int P = e->la.P;
+    LarParams p;
+    p.T = e->T; p.n_series = e->n_chains; p.P = P; p.shared = e->la.shared; p.want_fe = 0;
+    p.y = e->d_y;
+    p.cst = e->la.d_cst;
+    double* q = e->la.d_par;
+    p.init = q; q += lar::nq(P);
+    p.gm = q; q += G * (size_t)lar::ng(P);
+    p.kl = q; q += G;
+    p.stat = q; q += C * (size_t)lar::ns(P);
+    p.stat_sum = q;
+    p.hist = e->la.d_hist; p.rec = e->la.d_rec; p.zmean = e->la.d_out; p.band = e->la.d_out + ((size_t)e->T + P) * C;
+    p.fe_series = e->la.d_fe_series; p.status = e->d_status;
+    return p;
+}
+
+// a symmetric positive definite p×p matrix (symmetric within 1e-12 of its largest entry, Cholesky succeeds): its symmetrised copy, inverse and ln det
+static bool lar_spd(int p, const double* a, std::vector<double>& sym, std::vector<double>& inv, double* logdet) {
+    double big = 0.0;
+    for (int i = 0; i < p * p; ++i) {
+        if (!std::isfinite(a[i])) return false;
+        big = std::max(big, std::fabs(a[i]));
+    }
+    sym.assign((size_t)p * p, 0.0);
+    inv.assign((size_t)p * p, 0.0);
+    for (int i = 0; i < p; ++i)
+        for (int j = 0; j < p; ++j) {
+            if (std::fabs(a[i * p + j] - a[j * p + i]) > 1e-12 * big) return false;
+            sym[(size_t)(i * p + j)] = 0.5 * (a[i * p + j] + a[j * p + i]);
+        }
+    return rxhip::host_chol_inv(p, sym.data(), inv.data(), logdet);
+}
+
+extern "C" {
+
+rxhip_status rxhip_lar_create(const rxhip_lar_desc* ds, rxhip_engine** out) {
+    if (!out) return RXHIP_ERR_BADARG;
+    *out = nullptr;
+    if (!ds) return RXHIP_ERR_BADARG;
+    rxhip_engine* e = new rxhip_engine();   // from here on every refusal carries a text (rxhip_last_error; the caller destroys the handle)
+    *out = e;
+    e->kind = 7;
+    e->device = -1;
+    if (ds->order < 1 || ds->order > lar::kMaxP) return fail(e, RXHIP_ERR_BADARG, "lar: order must be 1 … %d (got %d)", lar::kMaxP, ds->order);
+    if (ds->T < 1) return fail(e, RXHIP_ERR_BADARG, "lar: T must be at least 1 (got %lld)", (long long)ds->T);
+    if (ds->n_series < 1) return fail(e, RXHIP_ERR_BADARG, "lar: n_series must be at least 1 (got %lld)", (long long)ds->n_series);
+    auto positive = [](double v) { return v > 0.0 && std::isfinite(v); };
+    if (!positive(ds->tau)) return fail(e, RXHIP_ERR_BADARG, "lar: tau must be positive and finite (got %g)", ds->tau);
+    if (!positive(ds->prior_gamma_shape) || !positive(ds->prior_gamma_rate))
+        return fail(e, RXHIP_ERR_BADARG, "lar: prior_gamma shape and rate must be positive and finite (got %g, %g)", ds->prior_gamma_shape, ds->prior_gamma_rate);
+    const double ia = ds->init_gamma_shape ? *ds->init_gamma_shape : ds->prior_gamma_shape, ib = ds->init_gamma_rate ? *ds->init_gamma_rate : ds->prior_gamma_rate;
+    if (!positive(ia) || !positive(ib)) return fail(e, RXHIP_ERR_BADARG, "lar: init_gamma shape and rate must be positive and finite (got %g, %g)", ia, ib);
+    if (!ds->prior_theta_mean || !ds->prior_theta_precision || !ds->prior_x0_mean || !ds->prior_x0_precision)
+        return fail(e, RXHIP_ERR_BADARG, "lar: prior_theta_mean, prior_theta_precision, prior_x0_mean and prior_x0_precision are required");
+    const int P = ds->order;
+    const size_t C = (size_t)ds->n_series, G = ds->share_parameters ? 1 : C, n = (size_t)ds->T + (size_t)P;
+    auto finite = [](const double* v, int cnt) {
+        for (int i = 0; i < cnt; ++i)
+            if (!std::isfinite(v[i])) return false;
+        return true;
+    };
+    if (!finite(ds->prior_theta_mean, P)) return fail(e, RXHIP_ERR_BADARG, "lar: prior_theta_mean must be finite");
+    if (!finite(ds->prior_x0_mean, P)) return fail(e, RXHIP_ERR_BADARG, "lar: prior_x0_mean must be finite");
+    if (ds->init_theta_mean && !finite(ds->init_theta_mean, P)) return fail(e, RXHIP_ERR_BADARG, "lar: init_theta_mean must be finite");
+    std::vector<double> wth0, vth0, w0, v0, vinit, winit;
+    double ld_wth0 = 0.0, ld_w0 = 0.0, ld = 0.0;
+    if (!lar_spd(P, ds->prior_theta_precision, wth0, vth0, &ld_wth0))
+        return fail(e, RXHIP_ERR_BADARG, "lar: prior_theta_precision is not symmetric positive definite");
+    if (!lar_spd(P, ds->prior_x0_precision, w0, v0, &ld_w0)) return fail(e, RXHIP_ERR_BADARG, "lar: prior_x0_precision is not symmetric positive definite");
+    if (ds->init_theta_cov) {
+        if (!lar_spd(P, ds->init_theta_cov, vinit, winit, &ld)) return fail(e, RXHIP_ERR_BADARG, "lar: init_theta_cov is not symmetric positive definite");
+    } else
+        vinit = vth0;   // the prior's own covariance
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(e, RXHIP_ERR_NO_DEVICE, "no HIP device visible");
+    e->la.P = P; e->la.shared = ds->share_parameters ? 1 : 0;
+    e->T = ds->T;
+    e->n_chains = ds->n_series;
+    e->d = e->dy = e->dpad = 1;
+    if (ds->device >= 0) {
+        if (ds->device >= ndev) return fail(e, RXHIP_ERR_BADARG, "device %d out of range (%d visible)", ds->device, ndev);
+        e->device = ds->device;
+    } else
+        HIPCHK(e, hipGetDevice(&e->device));
+    SET_DEVICE(e);
+    if (ds->stream) e->stream = (hipStream_t)ds->stream;
+    else {
+        HIPCHK(e, stream_acquire(e->device, &e->stream));
+        e->own_stream = true;
+    }
+    // host images: the constants (lar::consts) and the initial q
+    std::vector<double> cst((size_t)lar::nconst(P), 0.0), init((size_t)lar::nq(P), 0.0);
+    {
+        double* c = cst.data();
+        double *cw0 = c, *cm0 = c + P * P, *ch0 = cm0 + P, *cwth0 = ch0 + P, *cmth0 = cwth0 + P * P, *cwm0 = cmth0 + P, *sc = cwm0 + P;
+        for (int i = 0; i < P; ++i) {
+            cm0[i] = ds->prior_x0_mean[i];
+            cmth0[i] = ds->prior_theta_mean[i];
+            for (int j = 0; j < P; ++j) {
+                cw0[i * P + j] = w0[(size_t)(i * P + j)];
+                cwth0[i * P + j] = wth0[(size_t)(i * P + j)];
+            }
+        }
+        for (int i = 0; i < P; ++i) {
+            double s0 = 0.0, s1 = 0.0;
+            for (int j = 0; j < P; ++j) { s0 += cw0[i * P + j] * cm0[j]; s1 += cwth0[i * P + j] * cmth0[j]; }
+            ch0[i] = s0;
+            cwm0[i] = s1;
+        }
+        sc[0] = ds->prior_gamma_shape; sc[1] = ds->prior_gamma_rate; sc[2] = ld_w0; sc[3] = ld_wth0; sc[4] = ds->tau;
+        sc[5] = std::lgamma(ds->prior_gamma_shape); sc[6] = std::log(ds->prior_gamma_rate); sc[7] = std::log(ds->tau);
+        for (int i = 0; i < P; ++i) init[(size_t)i] = ds->init_theta_mean ? ds->init_theta_mean[i] : ds->prior_theta_mean[i];
+        for (int i = 0; i < P * P; ++i) init[(size_t)(P + i)] = vinit[(size_t)i];
+        init[(size_t)(P + P * P)] = ia;
+        init[(size_t)(P + P * P + 1)] = ib;
+    }
+    const size_t par = (size_t)lar::nq(P) + G * (size_t)lar::ng(P) + G + (C + 1) * (size_t)lar::ns(P);
+    HIPCHK(e, hipMalloc(&e->la.d_cst, sizeof(double) * cst.size()));
+    HIPCHK(e, hipMemcpy(e->la.d_cst, cst.data(), sizeof(double) * cst.size(), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMalloc(&e->la.d_par, sizeof(double) * par));
+    HIPCHK(e, hipMemcpy(e->la.d_par, init.data(), sizeof(double) * init.size(), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMalloc(&e->la.d_rec, sizeof(double) * n * (size_t)(P + 2) * C));
+    HIPCHK(e, hipMalloc(&e->la.d_out, sizeof(double) * n * (size_t)(P + 2) * C));   // m [n][series] | band [n][P + 1][series]
+    HIPCHK(e, hipMalloc(&e->d_fe_chain, sizeof(double) * C));
+    e->fe_total_cap = 32;
+    HIPCHK(e, hipMalloc(&e->d_fe_total, sizeof(double) * e->fe_total_cap));
+    HIPCHK(e, hipMalloc(&e->d_status, sizeof(int)));
+    HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
+    return RXHIP_OK;
+}
+
+rxhip_status rxhip_lar_get_states(rxhip_engine* e, double* mean, double* cov, int32_t layout) {
+    if (!e || e->kind != 7) return RXHIP_ERR_BADARG;
+    if (layout != RXHIP_LAYOUT_TIME_CHAIN && layout != RXHIP_LAYOUT_CHAIN_TIME) return fail(e, RXHIP_ERR_BADARG, "lar_get_states: unknown layout %d", layout);
+    if (!e->ran) return fail(e, RXHIP_ERR_STATE, "lar_get_states: no run yet");
+    SET_DEVICE(e);
+    const size_t C = (size_t)e->n_chains, T = (size_t)e->T, P = (size_t)e->la.P, n = T + P;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    std::vector<double> tmp(n * (P + 2) * C);
+    HIPCHK(e, hipMemcpy(tmp.data(), e->la.d_out, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost));
+    const double *zm = tmp.data(), *band = zm + n * C;
+    // x[t] = (z_t … z_{t-P+1}): component a is the scalar of index t + P − 1 − a; Σ(i, j) with i ≤ j sits at band[i][j − i]
+    for (size_t t = 1; t <= T; ++t)
+        for (size_t s = 0; s < C; ++s) {
+            const size_t o = layout == RXHIP_LAYOUT_TIME_CHAIN ? (t - 1) * C + s : s * T + (t - 1);
+            for (size_t a = 0; a < P; ++a) {
+                const size_t ia = t + P - 1 - a;
+                if (mean) mean[o * P + a] = zm[ia * C + s];
+                if (cov)
+                    for (size_t b = 0; b < P; ++b) {
+                        const size_t ib = t + P - 1 - b, lo = std::min(ia, ib), lag = std::max(ia, ib) - lo;
+                        cov[(o * P + a) * P + b] = band[(lo * (P + 1) + lag) * C + s];
+                    }
+            }
+        }
+    return RXHIP_OK;
+}
+
+rxhip_status rxhip_lar_get_parameters(rxhip_engine* e, double* theta_mean, double* theta_cov, double* gamma_shape, double* gamma_rate) {
+    if (!e || e->kind != 7) return RXHIP_ERR_BADARG;
+    if (!e->ran) return fail(e, RXHIP_ERR_STATE, "lar_get_parameters: no run yet");
+    SET_DEVICE(e);
+    const size_t C = (size_t)e->n_chains, P = (size_t)e->la.P, G = e->la.shared ? 1 : C, NQ = (size_t)lar::nq((int)P), rows = (size_t)e->last_iterations * G;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    std::vector<double> tmp(rows * NQ);
+    HIPCHK(e, hipMemcpy(tmp.data(), e->la.d_hist, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < rows; ++r) {
+        const double* q = &tmp[r * NQ];
+        if (theta_mean) std::memcpy(theta_mean + r * P, q, sizeof(double) * P);
+        if (theta_cov) std::memcpy(theta_cov + r * P * P, q + P, sizeof(double) * P * P);
+        if (gamma_shape) gamma_shape[r] = q[P + P * P];
+        if (gamma_rate) gamma_rate[r] = q[P + P * P + 1];
+    }
+    return RXHIP_OK;
+}
+
+}  // extern "C"
+
+// every observation of a latent autoregressive engine is finite or NaN: checked on the device copy, whichever way it arrived
+rxhip_status rxhip::lar_check_data(rxhip_engine* e) {
+    SET_DEVICE(e);
+    const long long n = e->T * e->n_chains;
+    const unsigned nb = (unsigned)std::min<long long>((n + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_lar_check_y, dim3(nb), dim3(256), 0, e->stream, (const double*)e->d_y, n, e->d_status);
+    HIPCHK(e, hipGetLastError());
+    int st = 0;
+    HIPCHK(e, hipMemcpyAsync(&st, e->d_status, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (st & ST_LAR_BAD_Y) {
+        HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
+        e->have_data = false;
+        return fail(e, RXHIP_ERR_BADARG, "set_data: an observation is infinite (finite values and NaN = missing are accepted)");
+    }
+    return RXHIP_OK;
+}
+
+template <int P>
+static void lar_launch_sweep(const LarParams& p, bool out, hipStream_t stream) {
+    const unsigned grid = (unsigned)((p.n_series + 63) / 64);
+    if (out) hipLaunchKernelGGL((k_lar_sweep<P, true>), dim3(grid), dim3(64), 0, stream, p);
+    else hipLaunchKernelGGL((k_lar_sweep<P, false>), dim3(grid), dim3(64), 0, stream, p);
+}
+
+rxhip_status rxhip::lar_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
+    if (iterations <= 0) return fail(e, RXHIP_ERR_BADARG, "run: iterations must be positive");
+    if (!e->have_data) return fail(e, RXHIP_ERR_STATE, "run: no observations (call rxhip_set_data first)");
+    SET_DEVICE(e);
+    const size_t C = (size_t)e->n_chains, G = e->la.shared ? 1 : C;
+    if (iterations > e->fe_total_cap) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        HIPCHK(e, hipFree(e->d_fe_total));
+        e->d_fe_total = nullptr;
+        e->fe_total_cap = iterations;
+        HIPCHK(e, hipMalloc(&e->d_fe_total, sizeof(double) * e->fe_total_cap));
+    }
+    if (want_fe && iterations > e->la.fe_cap) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        if (e->la.d_fe_series) HIPCHK(e, hipFree(e->la.d_fe_series));
+        e->la.d_fe_series = nullptr;
+        e->la.fe_cap = 0;
+        HIPCHK(e, hipMalloc(&e->la.d_fe_series, sizeof(double) * (size_t)iterations * C));
+        e->la.fe_cap = iterations;
+    }
+    if (iterations > e->la.hist_cap) {   // the parameter history: every iteration of the run
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        if (e->la.d_hist) HIPCHK(e, hipFree(e->la.d_hist));
+        e->la.d_hist = nullptr;
+        e->la.hist_cap = 0;
+        HIPCHK(e, hipMalloc(&e->la.d_hist, sizeof(double) * (size_t)iterations * G * (size_t)lar::nq(e->la.P)));
+        e->la.hist_cap = iterations;
+    }
+    LarParams p = lar_params(e);
+    p.want_fe = want_fe ? 1 : 0;
+    const unsigned ggrid = (unsigned)((G + 255) / 256), sgrid = (unsigned)((C + 255) / 256);
+    // every run starts from the initial q
+    hipLaunchKernelGGL(k_lar_init, dim3(ggrid), dim3(256), 0, e->stream, p);
+    for (int i = 0; i < iterations; ++i) {
+        const bool last = i == iterations - 1;
+        switch (p.P) {
+            case 1: lar_launch_sweep<1>(p, last, e->stream); break;
+            case 2: lar_launch_sweep<2>(p, last, e->stream); break;
+            case 3: lar_launch_sweep<3>(p, last, e->stream); break;
+            case 4: lar_launch_sweep<4>(p, last, e->stream); break;
+            case 5: lar_launch_sweep<5>(p, last, e->stream); break;
+            case 6: lar_launch_sweep<6>(p, last, e->stream); break;
+            case 7: lar_launch_sweep<7>(p, last, e->stream); break;
+            default: lar_launch_sweep<8>(p, last, e->stream); break;
+        }
+        if (p.shared) hipLaunchKernelGGL(k_lar_reduce, dim3(1), dim3(256), 0, e->stream, p);
+        hipLaunchKernelGGL(k_lar_update, dim3(ggrid), dim3(256), 0, e->stream, p, i);
+        if (want_fe) {
+            hipLaunchKernelGGL(k_lar_fe, dim3(sgrid), dim3(256), 0, e->stream, p, i);
+            hipLaunchKernelGGL(k_lar_fe_total, dim3(1), dim3(256), 0, e->stream, p, i, e->d_fe_total);
+        }
+    }
+    if (want_fe)
+        HIPCHK(e, hipMemcpyAsync(e->d_fe_chain, e->la.d_fe_series + (size_t)(iterations - 1) * C, sizeof(double) * C, hipMemcpyDeviceToDevice, e->stream));
+    HIPCHK(e, hipGetLastError());
+    e->last_iterations = iterations;
+    e->last_want_fe = want_fe != 0;
+    e->ran = true;
+    e->last_filter = false;
+    // reference-equivalent events per series and iteration: per step the AR node's messages toward x[t], x[t-1], θ and γ and the observation
+    // message; products and marginals at the T + 1 states and the two parameters
+    const uint64_t Cs = (uint64_t)C, T = (uint64_t)e->T, I = (uint64_t)iterations;
+    e->rule_calls = I * Cs * (5 * T + 1);
+    e->products = I * Cs * (4 * T + 2);
+    e->marginals = I * Cs * (T + 3);
+    return RXHIP_OK;
+}
 
 // every observation of a hidden Markov model engine is an integer code 0 … M−1 or NaN: checked on the device copy, whichever way it arrived
 rxhip_status rxhip::hmm_check_data(rxhip_engine* e) {

@@ -119,6 +119,14 @@ class HmmDesc(ctypes.Structure):   # rxhip_hmm_desc
         ("share_parameters", ctypes.c_int32), ("per_series", ctypes.c_int32), ("device", ctypes.c_int32), ("stream", ctypes.c_void_p)]
 
 
+class LarDesc(ctypes.Structure):   # rxhip_lar_desc
+    _fields_ = [("T", ctypes.c_int64), ("n_series", ctypes.c_int64), ("order", ctypes.c_int32), ("tau", ctypes.c_double),
+                ("prior_theta_mean", c_double_p), ("prior_theta_precision", c_double_p), ("prior_gamma_shape", ctypes.c_double),
+                ("prior_gamma_rate", ctypes.c_double)] + [
+        (n, c_double_p) for n in ("prior_x0_mean", "prior_x0_precision", "init_theta_mean", "init_theta_cov", "init_gamma_shape", "init_gamma_rate")] + [
+        ("share_parameters", ctypes.c_int32), ("device", ctypes.c_int32), ("stream", ctypes.c_void_p)]
+
+
 class NoisePrior(ctypes.Structure):   # rxhip_noise_prior
     _fields_ = [("nu0", ctypes.c_double), ("S0", c_double_p), ("init_nu", ctypes.c_double), ("init_V", c_double_p)]
 
@@ -223,6 +231,9 @@ SYMBOLS = [
     ("rxhip_hmm_create", ctypes.c_int32, [ctypes.POINTER(HmmDesc), ctypes.POINTER(_H)]),
     ("rxhip_hmm_get_states", ctypes.c_int32, [_H, c_double_p, ctypes.c_int32]),
     ("rxhip_hmm_get_parameters", ctypes.c_int32, [_H, c_double_p, c_double_p]),
+    ("rxhip_lar_create", ctypes.c_int32, [ctypes.POINTER(LarDesc), ctypes.POINTER(_H)]),
+    ("rxhip_lar_get_states", ctypes.c_int32, [_H, c_double_p, c_double_p, ctypes.c_int32]),
+    ("rxhip_lar_get_parameters", ctypes.c_int32, [_H, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("rxhip_hgf_get_history", ctypes.c_int32, [_H, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_int32]),
     ("rxhip_set_profiling", ctypes.c_int32, [_H, ctypes.c_int32]),
     ("rxhip_get_kernel_times", ctypes.c_int32, [_H, c_double_p, c_u64_p]),

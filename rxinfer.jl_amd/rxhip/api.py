@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RxHipError
-from .engine import DriftChainEngine, GMMEngine, HGFEngine, LGSSMEngine, MvGMMEngine, ProbitEngine, HMMEngine
+from .engine import DriftChainEngine, GMMEngine, HGFEngine, LGSSMEngine, MvGMMEngine, ProbitEngine, HMMEngine, LAREngine
 
 
 @dataclass
@@ -327,6 +327,62 @@ def _infer_hmm(model, data, iterations, free_energy, options, catch_exception):
 
 
 @dataclass
+class LatentAutoregressive:
+    """`γ ~ Gamma(a0, b0); θ ~ MvNormal(mθ0, Wθ0⁻¹); x0 ~ MvNormal(m0, W0⁻¹); x[t] ~ AR(x[t-1], θ, γ); y[t] ~ Normal(dot(c, x[t]), τ⁻¹)` with
+    c = e₁ and `q(x, x0, θ, γ) = q(x, x0)q(θ)q(γ)` (test/models/autoregressive/lar_tests.jl:51-76); order 1 is the Univariate spelling."""
+    order: int
+    tau: float
+    prior_theta: Optional[tuple] = None
+    prior_gamma: tuple = (1.0, 1.0)
+    prior_x0: Optional[tuple] = None
+    init_theta: Optional[tuple] = None
+    init_gamma: Optional[tuple] = None
+    share_parameters: bool = False
+
+
+def latent_autoregressive(order, tau, prior_theta=None, prior_gamma=(1, 1), prior_x0=None, init_theta=None, init_gamma=None, share_parameters=False):
+    """prior_theta, prior_x0: (mean [p], precision [p][p]) or None = zero mean and identity precision; prior_gamma: (shape, rate);
+    init_theta: (mean [p], covariance [p][p]), init_gamma: (shape, rate), None = the prior's own values (the reference's initialisation)."""
+    f = lambda v: None if v is None else (np.asarray(v[0], dtype=np.float64), np.asarray(v[1], dtype=np.float64))
+    g = lambda v: None if v is None else (float(v[0]), float(v[1]))
+    return LatentAutoregressive(int(order), float(tau), f(prior_theta), g(prior_gamma), f(prior_x0), f(init_theta), g(init_gamma), bool(share_parameters))
+
+
+def _infer_lar(model, data, iterations, free_energy, options, catch_exception):
+    """y: [T] or [T][series], NaN = missing.  posteriors["x"]: (mean [T][p], cov [T][p][p]) of the last iteration (a series axis after T for a
+    batch); posteriors["theta"]: (mean [iterations][p], cov [iterations][p][p]) and posteriors["gamma"]: (shape [iterations], rate [iterations])
+    per iteration (a series axis after the iterations for an unshared batch); free_energy: one value per iteration (summed over the series)."""
+    options = _check_options(options)
+    y = np.asarray(data["y"], dtype=np.float64)
+    single = y.ndim == 1
+    if single:
+        y = y[:, None]
+    T, C = y.shape
+    iters = 1 if iterations is None else int(iterations)
+    eng = None
+    try:
+        eng = LAREngine(T, model.order, model.tau, model.prior_theta, model.prior_gamma, model.prior_x0, model.init_theta, model.init_gamma,
+                        n_series=C, share_parameters=model.share_parameters, device=int(options.get("device", -1)))
+        eng.set_data(y, layout="time_chain")
+        eng.run(iterations=iters, free_energy=free_energy)
+        xm, xc = eng.states(layout="time_chain")
+        tm, tc, ga, gb = eng.parameters()
+        fe = eng.free_energy() if free_energy else None
+        if single:
+            xm, xc = xm[:, 0], xc[:, 0]
+        if single or model.share_parameters:
+            tm, tc, ga, gb = tm[:, 0], tc[:, 0], ga[:, 0], gb[:, 0]
+        return InferenceResult({"x": (xm, xc), "theta": (tm, tc), "gamma": (ga, gb)}, None, fe, model, None)
+    except Exception as err:
+        if not catch_exception:
+            raise
+        return InferenceResult({}, None, None, model, err)
+    finally:
+        if eng is not None:
+            eng.close()
+
+
+@dataclass
 class InferenceResult:
     """src/inference/batch.jl:18-24"""
     posteriors: dict
@@ -594,6 +650,8 @@ def infer(*, model, data, iterations=None, free_energy=False, options=None, retu
         return _infer_probit(model, data, iterations, free_energy, options, catch_exception)
     if isinstance(model, HiddenMarkovModel):
         return _infer_hmm(model, data, iterations, free_energy, options, catch_exception)
+    if isinstance(model, LatentAutoregressive):
+        return _infer_lar(model, data, iterations, free_energy, options, catch_exception)
     if not isinstance(model, LinearGaussianSSM):
         raise TypeError("infer: no device schedule for this model type")
     if model.noise_precision_prior is not None:

@@ -736,6 +736,87 @@ class HMMEngine:
         return a, b
 
 
+class LAREngine:
+    """Latent autoregressive model of order p = 1 … 8 with unknown coefficients θ and driving-noise precision γ
+    (test/models/autoregressive/lar_tests.jl:51-76) for n_series independent series: batched banded structured VMP (include/rxhip.h
+    rxhip_lar_desc).  prior_theta / prior_x0: (mean [p], precision [p][p]) or None = zero mean and identity precision; prior_gamma: (shape, rate);
+    init_theta: (mean [p], covariance [p][p]) and init_gamma: (shape, rate), None = the prior's own values.
+    `run(iterations)`: that many iterations from the initial q; `states()`: q(x[1 … T]) of the last one; `parameters()`: q(θ), q(γ) after every one."""
+
+    def __init__(self, T, order, tau, prior_theta=None, prior_gamma=(1.0, 1.0), prior_x0=None, init_theta=None, init_gamma=None, n_series=1,
+                 share_parameters=False, device=-1, stream=None):
+        L = _lib.lib()
+        p = int(order)
+        shape_p = max(p, 0)
+
+        def pair(v, name):
+            if v is None:
+                return _c(np.zeros(shape_p)), _c(np.eye(shape_p))
+            m, w = _c(v[0]), _c(v[1])
+            if m.shape != (shape_p,) or w.shape != (shape_p, shape_p):
+                raise ValueError(f"{name} must be (mean [p], matrix [p][p]) with p = {p}")
+            return m, w
+
+        pt, px = pair(prior_theta, "prior_theta"), pair(prior_x0, "prior_x0")
+        it = None if init_theta is None else pair(init_theta, "init_theta")
+        desc = _lib.LarDesc()
+        desc.T, desc.n_series, desc.order, desc.tau = int(T), int(n_series), p, float(tau)
+        desc.prior_theta_mean, desc.prior_theta_precision = _p(pt[0]), _p(pt[1])
+        desc.prior_gamma_shape, desc.prior_gamma_rate = float(prior_gamma[0]), float(prior_gamma[1])
+        desc.prior_x0_mean, desc.prior_x0_precision = _p(px[0]), _p(px[1])
+        if it is not None:
+            desc.init_theta_mean, desc.init_theta_cov = _p(it[0]), _p(it[1])
+        ig = None if init_gamma is None else _c([float(init_gamma[0]), float(init_gamma[1])])
+        if ig is not None:
+            desc.init_gamma_shape = _p(ig[0:1])
+            desc.init_gamma_rate = _p(ig[1:2])
+        desc.share_parameters, desc.device = int(bool(share_parameters)), int(device)
+        desc.stream = ctypes.c_void_p(stream) if stream else None
+        self.T, self.n_series, self.n_chains, self.order = int(T), int(n_series), int(n_series), p
+        self.share_parameters = bool(share_parameters)
+        self._h = ctypes.c_void_p()
+        st = L.rxhip_lar_create(ctypes.byref(desc), ctypes.byref(self._h))
+        if st != _lib.OK:
+            msg = L.rxhip_last_error(self._h).decode() if self._h else L.rxhip_status_string(st).decode()
+            if self._h:
+                L.rxhip_destroy(self._h)
+                self._h = None
+            raise RxHipError(st, msg or L.rxhip_status_string(st).decode())
+        self._iters = 0
+        self._data_ref = None
+
+    _chk = LGSSMEngine._chk
+    close = LGSSMEngine.close
+    __del__ = LGSSMEngine.__del__
+    __enter__ = LGSSMEngine.__enter__
+    __exit__ = LGSSMEngine.__exit__
+    sync = LGSSMEngine.sync
+    run = LGSSMEngine.run
+    run_async = LGSSMEngine.run_async
+    set_data = HGFEngine.set_data
+    set_data_device = HGFEngine.set_data_device
+    free_energy = LGSSMEngine.free_energy
+    free_energy_per_chain = LGSSMEngine.free_energy_per_chain
+    counters = LGSSMEngine.counters
+    stream = LGSSMEngine.stream
+
+    def states(self, layout="time_chain"):
+        """q(x[t]), t = 1 … T, x[t] = (z_t … z_{t-p+1}): (mean [T][series][p], cov [T][series][p][p]) ('time_chain') or [series][T][…] ('chain_time')."""
+        lay = _lib.LAYOUT_TIME_CHAIN if layout == "time_chain" else _lib.LAYOUT_CHAIN_TIME
+        lead = (self.T, self.n_series) if layout == "time_chain" else (self.n_series, self.T)
+        mean, cov = np.empty(lead + (self.order,)), np.empty(lead + (self.order, self.order))
+        self._chk(_lib.lib().rxhip_lar_get_states(self._h, _p(mean), _p(cov), lay))
+        return mean, cov
+
+    def parameters(self):
+        """q(θ), q(γ) after every iteration of the last run: (θ mean [iterations][G][p], θ covariance [iterations][G][p][p], γ shape
+        [iterations][G], γ rate [iterations][G]); G = n_series, or 1 with shared parameters."""
+        G, n, p = (1 if self.share_parameters else self.n_series), max(int(self._iters), 0), self.order
+        tm, tc, ga, gb = np.empty((n, G, p)), np.empty((n, G, p, p)), np.empty((n, G)), np.empty((n, G))
+        self._chk(_lib.lib().rxhip_lar_get_parameters(self._h, _p(tm), _p(tc), _p(ga), _p(gb)))
+        return tm, tc, ga, gb
+
+
 class Communicator:
     """RCCL communicator made through the C ABI (rxhip_comm_*): rank 0 calls `Communicator.unique_id()`, the 128 bytes
     travel to the other ranks by any host-side means, every rank constructs `Communicator(nranks, id, rank)`."""
