@@ -122,8 +122,10 @@ enum {
 enum {
     RXHIP_VAR_Y = 0, /* data variable y[t]   (src/inference/batch.jl:405-407 new_observation!) */
     RXHIP_VAR_X = 1, /* random variable x[t] (posteriors[:x], src/inference/batch.jl:325-332) */
-    RXHIP_VAR_U = 2  /* data variable u[t] of `A * x[t-1] + B_u * u[t]`: engines built by rxhip_create from a graph with such
+    RXHIP_VAR_U = 2, /* data variable u[t] of `A * x[t-1] + B_u * u[t]`: engines built by rxhip_create from a graph with such
                         inputs take them through rxhip_set_data, (T·n_chains·du doubles, same layouts as y) */
+    RXHIP_VAR_REGRESSORS = 3, /* binomial regression engine: the regressors X, [problem][N][d] */
+    RXHIP_VAR_TRIALS = 4      /* binomial regression engine: the numbers of trials n_trials, [problem][N] */
 };
 
 /* ------------------------------------------------------------------------------------------
@@ -966,6 +968,49 @@ rxhip_status rxhip_lar_get_states(rxhip_engine* e, double* mean, double* cov, in
 /* q(θ), q(γ) after EVERY iteration of the last run (the reference keeps KeepEach() for γ and θ): theta_mean [iterations][G][p], theta_cov
  * [iterations][G][p][p], gamma_shape, gamma_rate [iterations][G], G = n_series (1 with shared parameters); any pointer may be NULL */
 rxhip_status rxhip_lar_get_parameters(rxhip_engine* e, double* theta_mean, double* theta_cov, double* gamma_shape, double* gamma_rate);
+
+/* ------------------------------------------------------------------------------------------
+ * Bayesian binomial (logistic) regression under Pólya-Gamma augmentation (reference model test/models/regression/binomialreg_tests.jl; the
+ * workload the reference benchmarks as "binomialreg"), for each of n_problems independent regressions with N points and d features (1 … 32):
+ *     β ~ MvNormalWeightedMeanPrecision(ξ0, W0);   y[i] ~ BinomialPolya(X[i], n_trials[i], β):  y_i | β ~ Binomial(n_i, σ(x_iᵀβ))      i = 1 … N
+ *     q(β, ω) = q(β) Π_i q(ω_i)       (Polson–Scott–Windle augmentation ω_i; coordinate-ascent VMP as in Durante–Rigon)
+ * A NaN y_i is missing and contributes no factor (a batch with ragged N is padded with NaN).  κ_i = y_i − n_i/2.  Once per data set:
+ *     ξ = ξ0 + Σ_obs κ_i x_i,      lc = Σ_obs ln C(n_i, y_i) (through lgamma).
+ * Every run starts from init q(β) = N(init_mean, init_cov); NULL means the prior's W0⁻¹ξ0, W0⁻¹ (what the reference's
+ * RequireMessageFunctionalDependencies(β = prior) amounts to).
+ * One ITERATION (rxhip_run's argument) is a defined semantic of this engine (csrc/binreg_kernels.hpp), from the current q(β) = N(m, V):
+ *   1. S = V + m mᵀ,  c_i² = x_iᵀ S x_i,  q(ω_i) = PG(n_i, c_i),  ω̄_i = n_i·tanh(c_i/2)/(2 c_i) (→ n_i/4 as c_i → 0),
+ *      G = Σ_obs ω̄_i x_i x_iᵀ,    P = Σ_obs (−n_i ln(2 cosh(c_i/2)) + ½ c_i² ω̄_i);
+ *   2. W = W0 + G,  V = W⁻¹,  m = V ξ.
+ * The posterior of iteration i is q(β) after step 2; its free energy is the exact variational free energy at that point,
+ *     F = −[lc + mᵀ(ξ − ξ0) − ½ tr((V + m mᵀ) G) + P] + KL(N(m, V) ‖ N(W0⁻¹ξ0, W0⁻¹)),
+ * exact for q(ω) of step 1 and the new q(β).  Both steps are exact coordinate minimisers, so F does not rise from one iteration to the next.
+ * With n_i = 1 it equals minus the Jaakkola–Jordan bound (Bishop 10.164).  The values per iteration belong to this engine (ReactiveMP's own
+ * BinomialPolya rules were not at hand; the reference's test asserts decrease of F and coverage of the true β, not values).
+ * Handle protocol: rxhip_set_data with RXHIP_VAR_REGRESSORS (X, [problem][N][d]), RXHIP_VAR_Y (y, [problem][N]) and RXHIP_VAR_TRIALS (n_trials,
+ * [problem][N]) in any order, host arrays only (the layout argument is not read; rxhip_set_data_device: RXHIP_ERR_BADARG), rxhip_run(e, iterations,
+ * want_free_energy), rxhip_binreg_get_parameters, rxhip_get_free_energy (per iteration, summed over the problems), rxhip_get_free_energy_per_chain
+ * (per problem, last iteration), rxhip_counters, rxhip_destroy.  Results are bit-identical from run to run, with and without the free energy,
+ * and for a problem alone or inside a batch.
+ * Checked on the host before any launch, RXHIP_ERR_BADARG with a text: d outside 1 … 32, N < 1, n_problems < 1 (or above 65535); a precision or
+ * covariance that is not symmetric (within 1e-12 of its largest entry) positive definite; ±Inf anywhere; NaN anywhere but in y; n_i < 0; an
+ * observed y_i outside 0 … n_i.  A refused array counts as not set, and a run without all three arrays is RXHIP_ERR_STATE.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    int64_t N, n_problems;
+    int32_t d;                                        /* features, 1 … 32 */
+    const double *prior_xi, *prior_precision;         /* ξ0 [d], W0 [d][d] */
+    const double *init_mean, *init_cov;               /* [d], [d][d] (a covariance) or NULL = the prior's W0⁻¹ξ0, W0⁻¹ */
+    int32_t device;
+    void* stream;
+} rxhip_binreg_desc;
+rxhip_status rxhip_binreg_create(const rxhip_binreg_desc* desc, rxhip_engine** out);
+/* q(β) after EVERY iteration of the last run: mean [iterations][problems][d], cov [iterations][problems][d][d], and F per iteration and problem
+ * [iterations][problems] (RXHIP_ERR_STATE if the run was without the free energy); any pointer may be NULL */
+rxhip_status rxhip_binreg_get_parameters(rxhip_engine* e, double* mean, double* cov, double* free_energy);
+/* the pass's schedule for N points of d features: points per tile and workgroups (chunks) per problem — a function of N and d only, so a problem's
+ * bits do not depend on the batch; a workgroup takes ceil(tiles / chunks) tiles at most.  Zeros for arguments outside the engine's range. */
+void rxhip_binreg_schedule(int64_t N, int32_t d, int32_t* tile_points, int32_t* chunks);
 
 /* ------------------------------------------------------------------------------------------
  * Several GPUs (one process per GPU; chains / series / points shard).  The path's only exchange is the sum

@@ -105,7 +105,7 @@ struct rxhip_engine : rxhip_engine_life {
     int* d_status = nullptr;
     double* d_fe_blocks = nullptr;
     // Gaussian-mixture VMP engine (kind == 1)
-    int kind = 0;  // 0: LGSSM, 1: GMM, 2: HGF, 3: noise-free drift chain, 4: probit chain (batched EP, probit_kernels.hpp), 5: the level-scheduled node-array executor (tree_engine.hip; everything lives behind `tree`), 6: hidden Markov model (batched forward–backward VMP, hmm_kernels.hpp), 7: latent autoregressive model (batched banded structured VMP, lar_kernels.hpp)
+    int kind = 0;  // 0: LGSSM, 1: GMM, 2: HGF, 3: noise-free drift chain, 4: probit chain (batched EP, probit_kernels.hpp), 5: the level-scheduled node-array executor (tree_engine.hip; everything lives behind `tree`), 6: hidden Markov model (batched forward–backward VMP, hmm_kernels.hpp), 7: latent autoregressive model (batched banded structured VMP, lar_kernels.hpp), 8: binomial regression (batched Pólya-Gamma VMP, binreg_kernels.hpp)
     rxhip::tree::Engine* tree = nullptr;
     struct Drift { double m0 = 0, v0 = 1, c = 0, obs_var = 1; } dr;
     struct Hgf {
@@ -128,6 +128,13 @@ struct rxhip_engine : rxhip_engine_life {
         double *d_cst = nullptr, *d_par = nullptr, *d_hist = nullptr, *d_rec = nullptr, *d_out = nullptr, *d_fe_series = nullptr;
         int fe_cap = 0, hist_cap = 0;
     } la;
+    struct Breg {     // kind == 8: X, n_eff, κ, constants, ξ, lc, S, the pass's partials, ξ partials, parameter history, free energies; y and n_trials stay on the host for the checks
+        int d = 0, nchunk = 0, nchunk_xi = 0, hist_cap = 0;
+        double *d_X = nullptr, *d_neff = nullptr, *d_kappa = nullptr, *d_cst = nullptr, *d_xi = nullptr, *d_lc = nullptr, *d_S = nullptr, *d_part = nullptr,
+               *d_xi_part = nullptr, *d_hist = nullptr, *d_fe_prob = nullptr;
+        bool have_X = false, have_y = false, have_n = false, ready = false;
+        std::vector<double> h_y, h_n;
+    } br;
     struct Gmm {
         long long N = 0;
         int K = 0, KT = 0, materialize = 0, nblocks = 0, it = 0, iterations = 0, hist_cap = 0;
@@ -287,6 +294,8 @@ rxhip_status hmm_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe)
 rxhip_status hmm_check_data(rxhip_engine* e);   // … and its check of freshly ingested observations: an integer code 0 … M−1 or NaN
 rxhip_status lar_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe);      // the latent autoregressive model's run (vmp_engines.hip)
 rxhip_status lar_check_data(rxhip_engine* e);   // … and its check of freshly ingested observations: finite or NaN (missing)
+rxhip_status binreg_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe);   // the binomial regression's run (vmp_engines.hip)
+rxhip_status binreg_set_data(rxhip_engine* e, int32_t var_id, const double* host, size_t n);   // … and its three data arrays, checked on the host
 bool host_chol_inv(int n, const double* A, double* out, double* logdet);   // host Cholesky inverse + log-determinant of an SPD matrix (rxhip.hip host::chol_inv)
 }  // namespace rxhip
 

@@ -1464,6 +1464,8 @@ static void free_all(rxhip_engine* e) {
         if (*b) { (void)hipFree(*b); *b = nullptr; }
     for (double** b : {&e->la.d_cst, &e->la.d_par, &e->la.d_hist, &e->la.d_rec, &e->la.d_out, &e->la.d_fe_series})
         if (*b) { (void)hipFree(*b); *b = nullptr; }
+    for (double** b : {&e->br.d_X, &e->br.d_neff, &e->br.d_kappa, &e->br.d_cst, &e->br.d_xi, &e->br.d_lc, &e->br.d_S, &e->br.d_part, &e->br.d_xi_part, &e->br.d_hist, &e->br.d_fe_prob})
+        if (*b) { (void)hipFree(*b); *b = nullptr; }
     for (double** b : {&e->d_scanm, &e->d_fstart_m, &e->d_beta_xi, &e->d_vend, &e->d_qtab, &e->d_loc, &e->d_aggpart, &e->d_bnd})
         if (*b) { if (!e->in_arena(*b)) (void)hipFree(*b); *b = nullptr; }
     if (e->d_coll) { (void)hipFree(e->d_coll); e->d_coll = nullptr; }
@@ -2538,6 +2540,7 @@ static rxhip_status ingest_inputs(rxhip_engine* e, const double* u, size_t n, in
 rxhip_status rxhip_set_data(rxhip_engine* e, int32_t var_id, const double* host, size_t n, int32_t layout) {
     TREE_GUARD(e);
     if (!e) return RXHIP_ERR_BADARG;
+    if (e->kind == 8) return rxhip::binreg_set_data(e, var_id, host, n);
     if (var_id == RXHIP_VAR_U) return ingest_inputs(e, host, n, layout);
     if (var_id != RXHIP_VAR_Y) return fail(e, RXHIP_ERR_BADARG, "set_data: variable %d is not a data variable", var_id);
     const rxhip_status st = ingest(e, host, n, layout, false);
@@ -2548,6 +2551,7 @@ rxhip_status rxhip_set_data(rxhip_engine* e, int32_t var_id, const double* host,
 rxhip_status rxhip_set_data_device(rxhip_engine* e, int32_t var_id, const double* dev, size_t n, int32_t layout) {
     TREE_GUARD(e);
     if (!e) return RXHIP_ERR_BADARG;
+    if (e->kind == 8) return fail(e, RXHIP_ERR_BADARG, "set_data_device: the binomial regression engine checks its data on the host (rxhip_set_data)");
     if (var_id != RXHIP_VAR_Y) return fail(e, RXHIP_ERR_BADARG, "set_data: variable %d is not a data variable", var_id);
     const rxhip_status st = ingest(e, dev, n, layout, true);
     if (st == RXHIP_OK && e->kind == 6) return rxhip::hmm_check_data(e);
@@ -2976,6 +2980,10 @@ static rxhip_status run_impl(rxhip_engine* e, int32_t iterations, int32_t want_f
     if (e->kind == 7) {
         if (filter) return fail(e, RXHIP_ERR_BADARG, "run_filter: not a state-space engine with a streaming twin");
         return rxhip::lar_run_async(e, iterations, want_fe);
+    }
+    if (e->kind == 8) {
+        if (filter) return fail(e, RXHIP_ERR_BADARG, "run_filter: not a state-space engine with a streaming twin");
+        return rxhip::binreg_run_async(e, iterations, want_fe);
     }
     if (e->kind == 3) {
         if (filter) return fail(e, RXHIP_ERR_BADARG, "run_filter: not a state-space engine with a streaming twin");

@@ -1,6 +1,6 @@
 // vmp_engines.hip — the mean-field engines of the pattern-matched families behind the C ABI: the uni- and multivariate Gaussian-mixture engines
 // (csrc/gmm_kernels.hpp, mvgmm_kernels.hpp; SURVEY §8 a9/a10: rxhip_gmm_* / rxhip_mvgmm_create) and the hierarchical Gaussian filter
-// (csrc/hgf_kernels.hpp; a11: rxhip_hgf_create, its run), and the probit chain's batched EP (csrc/probit_kernels.hpp: rxhip_probit_create, its run) and the hidden Markov model's forward–backward VMP (csrc/hmm_kernels.hpp: rxhip_hmm_create, its run) and the latent autoregressive model's banded structured VMP (csrc/lar_kernels.hpp: rxhip_lar_create, its run).  The runtime they share with the state-space engines — streams, profiling events,
+// (csrc/hgf_kernels.hpp; a11: rxhip_hgf_create, its run), and the probit chain's batched EP (csrc/probit_kernels.hpp: rxhip_probit_create, its run) and the hidden Markov model's forward–backward VMP (csrc/hmm_kernels.hpp: rxhip_hmm_create, its run) and the latent autoregressive model's banded structured VMP (csrc/lar_kernels.hpp: rxhip_lar_create, its run) and the binomial regression's Pólya-Gamma VMP (csrc/binreg_kernels.hpp: rxhip_binreg_create, its run).  The runtime they share with the state-space engines — streams, profiling events,
 // the engine handle — is rxhip.hip's (engine.hpp).  No kernels of the state-space path live here.
 #include "../../include/rxhip.h"
 
@@ -21,6 +21,7 @@
 #include "probit_kernels.hpp"
 #include "hmm_kernels.hpp"
 #include "lar_kernels.hpp"
+#include "binreg_kernels.hpp"
 #include "engine.hpp"
 
 using namespace rxhip;
@@ -916,6 +917,248 @@ rxhip_status rxhip::lar_run_async(rxhip_engine* e, int32_t iterations, int32_t w
     e->rule_calls = I * Cs * (5 * T + 1);
     e->products = I * Cs * (4 * T + 2);
     e->marginals = I * Cs * (T + 3);
+    return RXHIP_OK;
+}
+
+// the binomial regression's kernel arguments
+static BregParams breg_params(const rxhip_engine* e) {
+    const int d = e->br.d;
+    BregParams p;
+    p.N = e->T; p.C = e->n_chains; p.d = d; p.nchunk = e->br.nchunk; p.nchunk_xi = e->br.nchunk_xi; p.want_fe = 0;
+    p.X = e->br.d_X; p.neff = e->br.d_neff; p.kappa = e->br.d_kappa; p.cst = e->br.d_cst; p.xi = e->br.d_xi; p.lc = e->br.d_lc;
+    p.S = e->br.d_S; p.part = e->br.d_part; p.xi_part = e->br.d_xi_part;
+    p.hist_m = e->br.d_hist; p.hist_v = e->br.d_hist + (size_t)e->br.hist_cap * (size_t)e->n_chains * (size_t)d;
+    p.fe_prob = e->br.d_fe_prob; p.status = e->d_status;
+    return p;
+}
+
+extern "C" {
+
+void rxhip_binreg_schedule(int64_t N, int32_t d, int32_t* tile_points, int32_t* chunks) {
+    const bool ok = N >= 1 && d >= 1 && d <= breg::kMaxD;
+    if (tile_points) *tile_points = ok ? breg::tile_points(d) : 0;
+    if (chunks) *chunks = ok ? breg::chunks(N, d) : 0;
+}
+
+rxhip_status rxhip_binreg_create(const rxhip_binreg_desc* ds, rxhip_engine** out) {
+    if (!out) return RXHIP_ERR_BADARG;
+    *out = nullptr;
+    if (!ds) return RXHIP_ERR_BADARG;
+    rxhip_engine* e = new rxhip_engine();   // from here on every refusal carries a text (rxhip_last_error; the caller destroys the handle)
+    *out = e;
+    e->kind = 8;
+    e->device = -1;
+    if (ds->d < 1 || ds->d > breg::kMaxD) return fail(e, RXHIP_ERR_BADARG, "binreg: d must be 1 … %d (got %d)", breg::kMaxD, ds->d);
+    if (ds->N < 1) return fail(e, RXHIP_ERR_BADARG, "binreg: N must be at least 1 (got %lld)", (long long)ds->N);
+    if (ds->n_problems < 1) return fail(e, RXHIP_ERR_BADARG, "binreg: n_problems must be at least 1 (got %lld)", (long long)ds->n_problems);
+    if (!ds->prior_xi || !ds->prior_precision) return fail(e, RXHIP_ERR_BADARG, "binreg: prior_xi and prior_precision are required");
+    const int d = ds->d;
+    for (int i = 0; i < d; ++i) {
+        if (!std::isfinite(ds->prior_xi[i])) return fail(e, RXHIP_ERR_BADARG, "binreg: prior_xi must be finite");
+        if (ds->init_mean && !std::isfinite(ds->init_mean[i])) return fail(e, RXHIP_ERR_BADARG, "binreg: init_mean must be finite");
+    }
+    std::vector<double> w0, v0, vinit, winit;
+    double ld_w0 = 0.0, ld = 0.0;
+    if (!lar_spd(d, ds->prior_precision, w0, v0, &ld_w0)) return fail(e, RXHIP_ERR_BADARG, "binreg: prior_precision is not symmetric positive definite");
+    if (ds->init_cov) {
+        if (!lar_spd(d, ds->init_cov, vinit, winit, &ld)) return fail(e, RXHIP_ERR_BADARG, "binreg: init_cov is not symmetric positive definite");
+    } else
+        vinit = v0;   // the prior's own covariance
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(e, RXHIP_ERR_NO_DEVICE, "no HIP device visible");
+    e->br.d = d;
+    e->T = ds->N;
+    e->n_chains = ds->n_problems;
+    e->d = e->dy = e->dpad = 1;
+    if (ds->device >= 0) {
+        if (ds->device >= ndev) return fail(e, RXHIP_ERR_BADARG, "device %d out of range (%d visible)", ds->device, ndev);
+        e->device = ds->device;
+    } else
+        HIPCHK(e, hipGetDevice(&e->device));
+    SET_DEVICE(e);
+    if (ds->stream) e->stream = (hipStream_t)ds->stream;
+    else {
+        HIPCHK(e, stream_acquire(e->device, &e->stream));
+        e->own_stream = true;
+    }
+    // constants: ξ0 | W0 | m0 = W0⁻¹ξ0 | ln det W0 | initial m | initial V
+    std::vector<double> cst((size_t)breg::nconst(d), 0.0);
+    {
+        double *xi0 = cst.data(), *W0 = xi0 + d, *m0 = W0 + d * d, *im = m0 + d + 1, *iv = im + d;
+        for (int i = 0; i < d; ++i) xi0[i] = ds->prior_xi[i];
+        for (int i = 0; i < d * d; ++i) { W0[i] = w0[(size_t)i]; iv[i] = vinit[(size_t)i]; }
+        for (int i = 0; i < d; ++i) {
+            double s = 0.0;
+            for (int j = 0; j < d; ++j) s += v0[(size_t)(i * d + j)] * xi0[j];
+            m0[i] = s;
+        }
+        m0[d] = ld_w0;
+        for (int i = 0; i < d; ++i) im[i] = ds->init_mean ? ds->init_mean[i] : m0[i];
+    }
+    const size_t C = (size_t)ds->n_problems, N = (size_t)ds->N, DP = (size_t)breg::dpad(d);
+    e->br.nchunk = breg::chunks(ds->N, d);
+    e->br.nchunk_xi = (int)std::min<long long>((ds->N + BREG_XI_ROWS - 1) / BREG_XI_ROWS, 256);
+    HIPCHK(e, hipMalloc(&e->br.d_cst, sizeof(double) * cst.size()));
+    HIPCHK(e, hipMemcpy(e->br.d_cst, cst.data(), sizeof(double) * cst.size(), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMalloc(&e->br.d_X, sizeof(double) * C * N * (size_t)d));
+    HIPCHK(e, hipMalloc(&e->br.d_neff, sizeof(double) * C * N));
+    HIPCHK(e, hipMalloc(&e->br.d_kappa, sizeof(double) * C * N));
+    HIPCHK(e, hipMalloc(&e->br.d_xi, sizeof(double) * C * (size_t)d));
+    HIPCHK(e, hipMalloc(&e->br.d_lc, sizeof(double) * C));
+    HIPCHK(e, hipMalloc(&e->br.d_S, sizeof(double) * C * DP * DP));
+    HIPCHK(e, hipMalloc(&e->br.d_part, sizeof(double) * C * (size_t)e->br.nchunk * (size_t)breg::npart(d)));
+    HIPCHK(e, hipMalloc(&e->br.d_xi_part, sizeof(double) * C * (size_t)e->br.nchunk_xi * 32));
+    HIPCHK(e, hipMalloc(&e->d_fe_chain, sizeof(double) * C));
+    e->fe_total_cap = 32;
+    HIPCHK(e, hipMalloc(&e->d_fe_total, sizeof(double) * e->fe_total_cap));
+    HIPCHK(e, hipMalloc(&e->d_status, sizeof(int)));
+    HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
+    return RXHIP_OK;
+}
+
+rxhip_status rxhip_binreg_get_parameters(rxhip_engine* e, double* mean, double* cov, double* free_energy) {
+    if (!e || e->kind != 8) return RXHIP_ERR_BADARG;
+    if (!e->ran) return fail(e, RXHIP_ERR_STATE, "binreg_get_parameters: no run yet");
+    if (free_energy && !e->last_want_fe) return fail(e, RXHIP_ERR_STATE, "binreg_get_parameters: free energy was not requested in the last run");
+    SET_DEVICE(e);
+    const size_t C = (size_t)e->n_chains, d = (size_t)e->br.d, rows = (size_t)e->last_iterations * C;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    const BregParams p = breg_params(e);
+    if (mean) HIPCHK(e, hipMemcpy(mean, p.hist_m, sizeof(double) * rows * d, hipMemcpyDeviceToHost));
+    if (cov) HIPCHK(e, hipMemcpy(cov, p.hist_v, sizeof(double) * rows * d * d, hipMemcpyDeviceToHost));
+    if (free_energy) HIPCHK(e, hipMemcpy(free_energy, p.fe_prob, sizeof(double) * rows, hipMemcpyDeviceToHost));
+    return RXHIP_OK;
+}
+
+}  // extern "C"
+
+// X, y and n_trials of a binomial regression engine, checked on the host before anything reaches the device: ±Inf anywhere (NaN too, except in y,
+// where it means missing), n_i < 0, an observed y_i outside 0 … n_i.  A refused array counts as not set.
+rxhip_status rxhip::binreg_set_data(rxhip_engine* e, int32_t var_id, const double* host, size_t n) {
+    const size_t C = (size_t)e->n_chains, N = (size_t)e->T, d = (size_t)e->br.d;
+    auto& b = e->br;
+    if (var_id != RXHIP_VAR_Y && var_id != RXHIP_VAR_REGRESSORS && var_id != RXHIP_VAR_TRIALS)
+        return fail(e, RXHIP_ERR_BADARG, "set_data: variable %d is not a data variable of the binomial regression engine", var_id);
+    const size_t need = var_id == RXHIP_VAR_REGRESSORS ? C * N * d : C * N;
+    if (!host || n != need) return fail(e, RXHIP_ERR_BADARG, "set_data: expected %zu doubles, got %zu", need, n);
+    b.ready = false;
+    if (var_id == RXHIP_VAR_REGRESSORS) {
+        b.have_X = false;
+        for (size_t i = 0; i < need; ++i)
+            if (!std::isfinite(host[i])) return fail(e, RXHIP_ERR_BADARG, "set_data: regressor %zu is not finite (%g)", i, host[i]);
+        SET_DEVICE(e);
+        HIPCHK(e, hipMemcpyAsync(b.d_X, host, sizeof(double) * need, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        b.have_X = true;
+        return RXHIP_OK;
+    }
+    bool& have = var_id == RXHIP_VAR_Y ? b.have_y : b.have_n;
+    std::vector<double>& keep = var_id == RXHIP_VAR_Y ? b.h_y : b.h_n;
+    have = false;
+    for (size_t i = 0; i < need; ++i) {
+        const double v = host[i];
+        if (var_id == RXHIP_VAR_Y ? std::isinf(v) : !std::isfinite(v)) return fail(e, RXHIP_ERR_BADARG, "set_data: %s %zu is not finite (%g)", var_id == RXHIP_VAR_Y ? "observation" : "n_trials", i, v);
+        if (var_id == RXHIP_VAR_TRIALS && v < 0.0) return fail(e, RXHIP_ERR_BADARG, "set_data: n_trials %zu is negative (%g)", i, v);
+    }
+    keep.assign(host, host + need);
+    have = true;
+    if (b.have_y && b.have_n)
+        for (size_t i = 0; i < need; ++i) {
+            const double y = b.h_y[i];
+            if (y == y && !(y >= 0.0 && y <= b.h_n[i])) {
+                have = false;
+                return fail(e, RXHIP_ERR_BADARG, "set_data: observation %zu = %g lies outside 0 … n_trials = %g", i, y, b.h_n[i]);
+            }
+        }
+    return RXHIP_OK;
+}
+
+// once per data set: n_eff, κ, lc from the host copies of y and n_trials; ξ on the device
+static rxhip_status breg_prepare(rxhip_engine* e) {
+    const size_t C = (size_t)e->n_chains, N = (size_t)e->T;
+    auto& b = e->br;
+    std::vector<double> neff(C * N), kappa(C * N), lc(C);
+    for (size_t c = 0; c < C; ++c) {
+        double s = 0.0;
+        for (size_t i = 0; i < N; ++i) {
+            const double y = b.h_y[c * N + i], n = b.h_n[c * N + i];
+            const bool seen = y == y;
+            neff[c * N + i] = seen ? n : 0.0;
+            kappa[c * N + i] = seen ? y - 0.5 * n : 0.0;
+            if (seen) s += std::lgamma(n + 1.0) - std::lgamma(y + 1.0) - std::lgamma(n - y + 1.0);
+        }
+        lc[c] = s;
+    }
+    HIPCHK(e, hipMemcpyAsync(b.d_neff, neff.data(), sizeof(double) * C * N, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(b.d_kappa, kappa.data(), sizeof(double) * C * N, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(b.d_lc, lc.data(), sizeof(double) * C, hipMemcpyHostToDevice, e->stream));
+    const BregParams p = breg_params(e);
+    hipLaunchKernelGGL(k_breg_xi, dim3((unsigned)p.nchunk_xi, (unsigned)C), dim3(256), 0, e->stream, p);
+    hipLaunchKernelGGL(k_breg_xi_total, dim3((unsigned)((C * (size_t)p.d + 255) / 256)), dim3(256), 0, e->stream, p);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipStreamSynchronize(e->stream));   // the host images go out of scope
+    b.ready = true;
+    return RXHIP_OK;
+}
+
+rxhip_status rxhip::binreg_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
+    if (iterations <= 0) return fail(e, RXHIP_ERR_BADARG, "run: iterations must be positive");
+    auto& b = e->br;
+    if (!b.have_X || !b.have_y || !b.have_n)
+        return fail(e, RXHIP_ERR_STATE, "run: the binomial regression engine needs RXHIP_VAR_REGRESSORS, RXHIP_VAR_Y and RXHIP_VAR_TRIALS (missing:%s%s%s)",
+                    b.have_X ? "" : " regressors", b.have_y ? "" : " y", b.have_n ? "" : " n_trials");
+    SET_DEVICE(e);
+    const size_t C = (size_t)e->n_chains, d = (size_t)b.d;
+    if (C > 65535) return fail(e, RXHIP_ERR_BADARG, "binreg: at most 65535 problems per engine (got %zu)", C);
+    if (!b.ready)
+        if (rxhip_status st = breg_prepare(e)) return st;
+    if (iterations > e->fe_total_cap) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        HIPCHK(e, hipFree(e->d_fe_total));
+        e->d_fe_total = nullptr;
+        e->fe_total_cap = iterations;
+        HIPCHK(e, hipMalloc(&e->d_fe_total, sizeof(double) * e->fe_total_cap));
+    }
+    if (iterations > b.hist_cap) {   // the parameter history and the per-problem free energies: every iteration of the run
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        if (b.d_hist) HIPCHK(e, hipFree(b.d_hist));
+        if (b.d_fe_prob) HIPCHK(e, hipFree(b.d_fe_prob));
+        b.d_hist = b.d_fe_prob = nullptr;
+        b.hist_cap = 0;
+        HIPCHK(e, hipMalloc(&b.d_hist, sizeof(double) * (size_t)iterations * C * (d + d * d)));
+        HIPCHK(e, hipMalloc(&b.d_fe_prob, sizeof(double) * (size_t)iterations * C));
+        b.hist_cap = iterations;
+    }
+    BregParams p = breg_params(e);
+    p.want_fe = want_fe ? 1 : 0;
+    const dim3 pgrid((unsigned)p.nchunk, (unsigned)C);
+    hipLaunchKernelGGL(k_breg_init, dim3((unsigned)C), dim3(64), 0, e->stream, p);   // every run starts from the initial q(β)
+    for (int i = 0; i < iterations; ++i) {
+        switch (p.d) {
+            case 1: hipLaunchKernelGGL(k_breg_pass_small<1>, pgrid, dim3(256), 0, e->stream, p); break;
+            case 2: hipLaunchKernelGGL(k_breg_pass_small<2>, pgrid, dim3(256), 0, e->stream, p); break;
+            case 3: hipLaunchKernelGGL(k_breg_pass_small<3>, pgrid, dim3(256), 0, e->stream, p); break;
+            case 4: hipLaunchKernelGGL(k_breg_pass_small<4>, pgrid, dim3(256), 0, e->stream, p); break;
+            default:
+                if (p.d <= 16) hipLaunchKernelGGL(k_breg_pass<1>, pgrid, dim3(256), 0, e->stream, p);
+                else hipLaunchKernelGGL(k_breg_pass<2>, pgrid, dim3(256), 0, e->stream, p);
+        }
+        hipLaunchKernelGGL(k_breg_update, dim3((unsigned)C), dim3(64), 0, e->stream, p, i);
+        if (want_fe) hipLaunchKernelGGL(k_breg_fe_total, dim3(1), dim3(256), 0, e->stream, p, i, e->d_fe_total);
+    }
+    if (want_fe)
+        HIPCHK(e, hipMemcpyAsync(e->d_fe_chain, b.d_fe_prob + (size_t)(iterations - 1) * C, sizeof(double) * C, hipMemcpyDeviceToDevice, e->stream));
+    HIPCHK(e, hipGetLastError());
+    e->last_iterations = iterations;
+    e->last_want_fe = want_fe != 0;
+    e->ran = true;
+    e->last_filter = false;
+    // reference-equivalent events per problem and iteration: per point the BinomialPolya node's message toward β and its ω marginal; the prior's
+    // message; products of the N + 1 messages at β
+    const uint64_t Cs = (uint64_t)C, N = (uint64_t)e->T, I = (uint64_t)iterations;
+    e->rule_calls = I * Cs * (N + 1);
+    e->products = I * Cs * N;
+    e->marginals = I * Cs * (N + 1);
     return RXHIP_OK;
 }
 

@@ -19,6 +19,8 @@ const RXHIP_LAYOUT_CHAIN_TIME = Int32(1)
 const RXHIP_VAR_Y = Int32(0)
 const RXHIP_VAR_X = Int32(1)
 const RXHIP_VAR_U = Int32(2)
+const RXHIP_VAR_REGRESSORS = Int32(3)
+const RXHIP_VAR_TRIALS = Int32(4)
 
 struct RxHipError <: Exception
     status::Int32
@@ -980,6 +982,67 @@ function DriftChainEngine(; T::Integer, m0, v0, c, obs_var, n_chains::Integer = 
     st == RXHIP_OK || throw(RxHipError(st, unsafe_string(ccall((:rxhip_status_string, librxhip), Cstring, (Int32,), st))))
     finalizer(destroy!, e)
     return e
+end
+
+# mirrors rxhip_binreg_desc (include/rxhip.h); field order and types must match the C struct
+struct BinregDesc
+    N::Int64
+    n_problems::Int64
+    d::Int32
+    prior_xi::Ptr{Float64}
+    prior_precision::Ptr{Float64}
+    init_mean::Ptr{Float64}
+    init_cov::Ptr{Float64}
+    device::Int32
+    stream::Ptr{Cvoid}
+end
+"""
+    BinomialRegressionEngine(prior_xi, prior_precision; N, n_problems = 1, init = nothing, device = -1)
+
+`β ~ MvNormalWeightedMeanPrecision(prior_xi, prior_precision); y[i] ~ BinomialPolya(X[i], n_trials[i], β)` of
+test/models/regression/binomialreg_tests.jl:32-43 for `n_problems` independent regressions (batched Pólya-Gamma VMP, rxhip_binreg_desc).
+`init = (mean, cov)` is the initial q(β); `nothing` means the prior's own, as the reference's `RequireMessageFunctionalDependencies(β = prior)`.
+Then `binreg_set_data!(e, X, y, n_trials)`, `run!`, `binreg_parameters(e)`.
+"""
+function BinomialRegressionEngine(prior_xi::AbstractVector, prior_precision::AbstractMatrix; N::Integer, n_problems::Integer = 1, init = nothing,
+                                  device::Integer = -1, stream = nothing)
+    d = length(prior_xi)
+    xi, w0 = rowmajor(prior_xi), rowmajor(prior_precision)
+    im = init === nothing ? Float64[] : rowmajor(init[1])
+    iv = init === nothing ? Float64[] : rowmajor(init[2])
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    st = GC.@preserve xi w0 im iv begin
+        desc = BinregDesc(N, n_problems, d, pointer(xi), pointer(w0), isempty(im) ? Ptr{Float64}(C_NULL) : pointer(im),
+                          isempty(iv) ? Ptr{Float64}(C_NULL) : pointer(iv), device, stream_handle(stream))
+        ccall((:rxhip_binreg_create, librxhip), Int32, (Ref{BinregDesc}, Ref{Ptr{Cvoid}}), desc, h)
+    end
+    e = Engine(h[], d, 1, N, n_problems, 0)
+    if st != RXHIP_OK
+        h[] != C_NULL && (try check(e, st) finally ccall((:rxhip_destroy, librxhip), Int32, (Ptr{Cvoid},), h[]) end)
+        throw(RxHipError(st, unsafe_string(ccall((:rxhip_status_string, librxhip), Cstring, (Int32,), st))))
+    end
+    finalizer(destroy!, e)
+    return e
+end
+"""X: one `N × d` matrix per problem (or one matrix), y and n_trials: one vector per problem (or one vector); `NaN` in y = missing."""
+function binreg_set_data!(e::Engine, X, y, n_trials)
+    xs = X isa AbstractMatrix ? [X] : X
+    x = reduce(vcat, rowmajor.(xs))
+    flat(v) = v isa AbstractVector{<:Real} ? Vector{Float64}(v) : reduce(vcat, Vector{Float64}.(v))
+    for (id, a) in ((RXHIP_VAR_REGRESSORS, x), (RXHIP_VAR_TRIALS, flat(n_trials)), (RXHIP_VAR_Y, flat(y)))
+        check(e, ccall((:rxhip_set_data, librxhip), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Csize_t, Int32), e.handle, id, a, length(a), Int32(0)))
+    end
+    return e
+end
+"""q(β) after every one of the `iterations` of the last run: (means d × problems × iterations, covariances d × d × problems × iterations,
+free energies problems × iterations or `nothing`) — the C arrays `[iterations][problems][…]` seen column-major (covariances are symmetric)."""
+function binreg_parameters(e::Engine, iterations::Integer; free_energy::Bool = true)
+    mean = Array{Float64}(undef, e.d, e.n_chains, iterations)
+    cov = Array{Float64}(undef, e.d, e.d, e.n_chains, iterations)
+    fe = free_energy ? Array{Float64}(undef, e.n_chains, iterations) : nothing
+    check(e, ccall((:rxhip_binreg_get_parameters, librxhip), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), e.handle, mean, cov,
+                   free_energy ? fe : Ptr{Float64}(C_NULL)))
+    return mean, cov, fe
 end
 
 # ---- several GPUs: the free-energy / statistics exchange over RCCL (no torch, no MPI dependency in this file) ----------

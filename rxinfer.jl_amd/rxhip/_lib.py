@@ -13,7 +13,7 @@ c_u64_p = ctypes.POINTER(ctypes.c_uint64)
 
 OK, ERR_BADARG, ERR_UNSUPPORTED, ERR_NOT_POSDEF, ERR_NONFINITE_FE, ERR_HIP, ERR_NO_DEVICE, ERR_STATE, ERR_RCCL = range(9)
 LAYOUT_TIME_CHAIN, LAYOUT_CHAIN_TIME = 0, 1
-VAR_Y, VAR_X, VAR_U = 0, 1, 2
+VAR_Y, VAR_X, VAR_U, VAR_REGRESSORS, VAR_TRIALS = 0, 1, 2, 3, 4
 (K_SEG_AGGREGATE, K_BOUNDARY_SCAN, K_FORWARD, K_BACKWARD, K_FE_REDUCE, K_GMM_PASS, K_GMM_REDUCE, K_GMM_UPDATE, K_HGF_FILTER,
  K_DRIFT_CHAIN, K_PROBIT_SWEEP, K_COUNT) = range(12)
 KERNEL_NAMES = ["k_seg_aggregate", "k_boundary_scan", "k_forward", "k_backward", "k_fe_reduce", "k_gmm_pass", "k_gmm_reduce",
@@ -127,6 +127,11 @@ class LarDesc(ctypes.Structure):   # rxhip_lar_desc
         ("share_parameters", ctypes.c_int32), ("device", ctypes.c_int32), ("stream", ctypes.c_void_p)]
 
 
+class BinregDesc(ctypes.Structure):   # rxhip_binreg_desc
+    _fields_ = [("N", ctypes.c_int64), ("n_problems", ctypes.c_int64), ("d", ctypes.c_int32)] + [
+        (n, c_double_p) for n in ("prior_xi", "prior_precision", "init_mean", "init_cov")] + [("device", ctypes.c_int32), ("stream", ctypes.c_void_p)]
+
+
 class NoisePrior(ctypes.Structure):   # rxhip_noise_prior
     _fields_ = [("nu0", ctypes.c_double), ("S0", c_double_p), ("init_nu", ctypes.c_double), ("init_V", c_double_p)]
 
@@ -234,6 +239,9 @@ SYMBOLS = [
     ("rxhip_lar_create", ctypes.c_int32, [ctypes.POINTER(LarDesc), ctypes.POINTER(_H)]),
     ("rxhip_lar_get_states", ctypes.c_int32, [_H, c_double_p, c_double_p, ctypes.c_int32]),
     ("rxhip_lar_get_parameters", ctypes.c_int32, [_H, c_double_p, c_double_p, c_double_p, c_double_p]),
+    ("rxhip_binreg_create", ctypes.c_int32, [ctypes.POINTER(BinregDesc), ctypes.POINTER(_H)]),
+    ("rxhip_binreg_get_parameters", ctypes.c_int32, [_H, c_double_p, c_double_p, c_double_p]),
+    ("rxhip_binreg_schedule", None, [ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     ("rxhip_hgf_get_history", ctypes.c_int32, [_H, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_int32]),
     ("rxhip_set_profiling", ctypes.c_int32, [_H, ctypes.c_int32]),
     ("rxhip_get_kernel_times", ctypes.c_int32, [_H, c_double_p, c_u64_p]),

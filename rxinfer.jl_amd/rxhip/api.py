@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RxHipError
-from .engine import DriftChainEngine, GMMEngine, HGFEngine, LGSSMEngine, MvGMMEngine, ProbitEngine, HMMEngine, LAREngine
+from .engine import DriftChainEngine, GMMEngine, HGFEngine, LGSSMEngine, MvGMMEngine, ProbitEngine, HMMEngine, LAREngine, BinomialRegressionEngine
 
 
 @dataclass
@@ -383,6 +383,53 @@ def _infer_lar(model, data, iterations, free_energy, options, catch_exception):
 
 
 @dataclass
+class BinomialRegression:
+    """`β ~ MvNormalWeightedMeanPrecision(ξ0, W0); y[i] ~ BinomialPolya(X[i], n_trials[i], β)` with `q(β, ω) = q(β)Πq(ω_i)`
+    (test/models/regression/binomialreg_tests.jl)."""
+    prior_xi: np.ndarray
+    prior_precision: np.ndarray
+    init: Optional[tuple] = None
+
+
+def binomial_regression(prior_xi, prior_precision, init=None):
+    """prior_xi [d], prior_precision [d][d]: the weighted mean ξ0 and precision W0 of β's prior; init: (mean [d], covariance [d][d]) of the
+    initial q(β), None = the prior's own W0⁻¹ξ0, W0⁻¹ (the reference's `RequireMessageFunctionalDependencies(β = prior)`)."""
+    f = lambda v: None if v is None else (np.asarray(v[0], dtype=np.float64), np.asarray(v[1], dtype=np.float64))
+    return BinomialRegression(np.asarray(prior_xi, dtype=np.float64), np.asarray(prior_precision, dtype=np.float64), f(init))
+
+
+def _infer_binreg(model, data, iterations, free_energy, options, catch_exception):
+    """X: [N][d] or [problems][N][d]; y, n_trials: [N] or [problems][N], a NaN y = missing.  posteriors["β"]: (mean [iterations][d], cov
+    [iterations][d][d]) after every iteration (a problem axis after the iterations for a batch); free_energy: one value per iteration, per
+    problem ([iterations][problems]) for a batch."""
+    options = _check_options(options)
+    X = np.asarray(data["X"], dtype=np.float64)
+    single = X.ndim == 2
+    if single:
+        X = X[None]
+    y = np.asarray(data["y"], dtype=np.float64).reshape(X.shape[:2])
+    n = np.asarray(data["n_trials"], dtype=np.float64).reshape(X.shape[:2])
+    C, N, d = X.shape
+    iters = 1 if iterations is None else int(iterations)
+    eng = None
+    try:
+        eng = BinomialRegressionEngine(N, d, model.prior_xi, model.prior_precision, model.init, n_problems=C, device=int(options.get("device", -1)))
+        eng.set_data(X, y, n)
+        eng.run(iterations=iters, free_energy=free_energy)
+        mean, cov, fe = eng.parameters()
+        if single:
+            mean, cov, fe = mean[:, 0], cov[:, 0], (fe[:, 0] if fe is not None else None)
+        return InferenceResult({"β": (mean, cov)}, None, fe, model, None)
+    except Exception as err:
+        if not catch_exception:
+            raise
+        return InferenceResult({}, None, None, model, err)
+    finally:
+        if eng is not None:
+            eng.close()
+
+
+@dataclass
 class InferenceResult:
     """src/inference/batch.jl:18-24"""
     posteriors: dict
@@ -652,6 +699,8 @@ def infer(*, model, data, iterations=None, free_energy=False, options=None, retu
         return _infer_hmm(model, data, iterations, free_energy, options, catch_exception)
     if isinstance(model, LatentAutoregressive):
         return _infer_lar(model, data, iterations, free_energy, options, catch_exception)
+    if isinstance(model, BinomialRegression):
+        return _infer_binreg(model, data, iterations, free_energy, options, catch_exception)
     if not isinstance(model, LinearGaussianSSM):
         raise TypeError("infer: no device schedule for this model type")
     if model.noise_precision_prior is not None:

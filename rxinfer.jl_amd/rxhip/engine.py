@@ -817,6 +817,97 @@ class LAREngine:
         return tm, tc, ga, gb
 
 
+class BinomialRegressionEngine:
+    """Bayesian binomial (logistic) regression `β ~ MvNormalWeightedMeanPrecision(ξ0, W0); y[i] ~ BinomialPolya(X[i], n_trials[i], β)`
+    (test/models/regression/binomialreg_tests.jl) for n_problems independent regressions of N points and d = 1 … 32 features: batched
+    Pólya-Gamma VMP (include/rxhip.h rxhip_binreg_desc).  init: (mean [d], covariance [d][d]) or None = the prior's W0⁻¹ξ0, W0⁻¹.
+    `set_data(X, y, n_trials)`; `run(iterations)`: that many iterations from the initial q(β); `parameters()`: q(β) after every one."""
+
+    def __init__(self, N, d, prior_xi, prior_precision, init=None, n_problems=1, device=-1, stream=None):
+        L = _lib.lib()
+        d = int(d)
+        xi, w0 = _c(prior_xi), _c(prior_precision)
+        if xi.shape != (max(d, 0),) or w0.shape != (max(d, 0), max(d, 0)):
+            raise ValueError(f"prior_xi must be [d] and prior_precision [d][d] with d = {d}")
+        desc = _lib.BinregDesc()
+        desc.N, desc.n_problems, desc.d = int(N), int(n_problems), d
+        desc.prior_xi, desc.prior_precision = _p(xi), _p(w0)
+        if init is not None:
+            im, iv = _c(init[0]), _c(init[1])
+            if im.shape != xi.shape or iv.shape != w0.shape:
+                raise ValueError(f"init must be (mean [d], covariance [d][d]) with d = {d}")
+            desc.init_mean, desc.init_cov = _p(im), _p(iv)
+        desc.device = int(device)
+        desc.stream = ctypes.c_void_p(stream) if stream else None
+        self.N, self.d, self.n_problems, self.n_chains = int(N), d, int(n_problems), int(n_problems)
+        self._h = ctypes.c_void_p()
+        st = L.rxhip_binreg_create(ctypes.byref(desc), ctypes.byref(self._h))
+        if st != _lib.OK:
+            msg = L.rxhip_last_error(self._h).decode() if self._h else L.rxhip_status_string(st).decode()
+            if self._h:
+                L.rxhip_destroy(self._h)
+                self._h = None
+            raise RxHipError(st, msg or L.rxhip_status_string(st).decode())
+        self._iters = 0
+        self._fe = False
+
+    _chk = LGSSMEngine._chk
+    close = LGSSMEngine.close
+    __del__ = LGSSMEngine.__del__
+    __enter__ = LGSSMEngine.__enter__
+    __exit__ = LGSSMEngine.__exit__
+    sync = LGSSMEngine.sync
+    free_energy = LGSSMEngine.free_energy
+    free_energy_per_chain = LGSSMEngine.free_energy_per_chain
+    counters = LGSSMEngine.counters
+    stream = LGSSMEngine.stream
+
+    @staticmethod
+    def schedule(N, d):
+        """(points per tile, workgroups per problem) of the pass for N points of d features: a function of N and d only."""
+        tp, ch = ctypes.c_int32(), ctypes.c_int32()
+        _lib.lib().rxhip_binreg_schedule(int(N), int(d), ctypes.byref(tp), ctypes.byref(ch))
+        return tp.value, ch.value
+
+    def _set(self, var, a, shape, name):
+        a = _c(a)
+        if a.shape != shape and not (self.n_problems == 1 and a.shape == shape[1:]):
+            raise ValueError(f"{name} must be {list(shape)} (the problem axis may be left out for one problem), got {list(a.shape)}")
+        self._chk(_lib.lib().rxhip_set_data(self._h, var, _p(a), a.size, _lib.LAYOUT_TIME_CHAIN))
+
+    def set_regressors(self, X):
+        self._set(_lib.VAR_REGRESSORS, X, (self.n_problems, self.N, self.d), "X")
+
+    def set_observations(self, y):
+        """y [problems][N]; NaN = missing."""
+        self._set(_lib.VAR_Y, y, (self.n_problems, self.N), "y")
+
+    def set_trials(self, n_trials):
+        self._set(_lib.VAR_TRIALS, n_trials, (self.n_problems, self.N), "n_trials")
+
+    def set_data(self, X, y, n_trials):
+        self.set_regressors(X)
+        self.set_trials(n_trials)
+        self.set_observations(y)
+
+    def run(self, iterations=1, free_energy=True):
+        self._chk(_lib.lib().rxhip_run(self._h, int(iterations), int(bool(free_energy))))
+        self._iters, self._fe = int(iterations), bool(free_energy)
+
+    def run_async(self, iterations=1, free_energy=True):
+        self._chk(_lib.lib().rxhip_run_async(self._h, int(iterations), int(bool(free_energy))))
+        self._iters, self._fe = int(iterations), bool(free_energy)
+
+    def parameters(self):
+        """q(β) after every iteration of the last run: (mean [iterations][problems][d], covariance [iterations][problems][d][d], free energy
+        [iterations][problems] or None when the run was without it)."""
+        n, C, d = max(int(self._iters), 0), self.n_problems, self.d
+        mean, cov = np.empty((n, C, d)), np.empty((n, C, d, d))
+        fe = np.empty((n, C)) if self._fe else None
+        self._chk(_lib.lib().rxhip_binreg_get_parameters(self._h, _p(mean), _p(cov), _p(fe) if self._fe else None))
+        return mean, cov, fe
+
+
 class Communicator:
     """RCCL communicator made through the C ABI (rxhip_comm_*): rank 0 calls `Communicator.unique_id()`, the 128 bytes
     travel to the other ranks by any host-side means, every rank constructs `Communicator(nranks, id, rank)`."""
