@@ -8,6 +8,8 @@ import pytest
 import rxhip
 import rxoracle
 
+import mvgmm_ref
+
 pytestmark = pytest.mark.gpu
 
 
@@ -28,6 +30,9 @@ def run_both(y, priors, init, iters, materialize=False):
 
 
 def assert_parity(hist, fe, ohist, ofe):
+    """element-wise over [iteration][mean m, var m, shape p, rate p, alpha s][component]; prints the largest error per key"""
+    e = np.max(np.abs(hist - ohist) / np.maximum(np.abs(ohist), 1e-300), axis=(0, 2))
+    print("univariate " + " ".join(f"{k} {v:.2e}" for k, v in zip(("mean", "var", "shape", "rate", "alpha"), e)), f"fe {np.max(np.abs(fe - ofe) / np.abs(ofe)):.2e}")
     assert np.max(np.abs(hist - ohist) / np.maximum(np.abs(ohist), 1e-300)) < 1e-6
     assert np.max(np.abs(fe - ofe) / np.abs(ofe)) < 1e-8
 
@@ -54,6 +59,62 @@ def test_gmm_k_components(K, n, seed):
     hist, fe, _, cnt, ohist, ofe, _, ocnt = run_both(y, priors, init, 8)
     assert_parity(hist, fe, ohist, ofe)
     assert np.all(np.abs(hist[-1, 0] - mus) < 1.0)  # component means recovered
+
+
+# k_gmm_pass runs workgroups of WG lanes, a point per lane, in a grid-stride loop over at most GRID_CAP workgroups (rxhip_gmm_create:
+# nb = (N + 255) / 256, capped at 1024).  KT = 16 keeps the constants of the responsibility rule in LDS (CST_LDS), smaller tiles in registers.
+WG, GRID_CAP = 256, 1024
+
+
+@pytest.mark.parametrize("K", [2, 11])
+def test_grid_stride(K):
+    """N = GRID_CAP·WG + WG + 37: the grid-stride loop of k_gmm_pass<2> and of k_gmm_pass<16> (K = 11: the LDS-constants path with five padding
+    components) runs a second time, in full in workgroup 0 and ragged in workgroup 1.  The oracle sums sequentially; its order sensitivity on
+    these inputs is asserted by tests/test_mvgmm_ref_cpu.py (4.5e-11 element-wise)."""
+    n = GRID_CAP * WG + WG + 37
+    assert n == mvgmm_ref.STRIDE_N
+    y, priors, init = mvgmm_ref.uv_case(K, n, 20 + K)
+    hist, fe, resp, _, ohist, ofe, oresp, _ = run_both(y, priors, init, 3, materialize=True)
+    assert_parity(hist, fe, ohist, ofe)
+    print(f"univariate K={K} N={n} resp {np.max(np.abs(resp - oresp)):.2e}")
+    assert resp.shape == (n, K) and np.max(np.abs(resp - oresp)) < 1e-9
+
+
+def test_lds_constants_with_padding_components():
+    """K = 11 in the tile of 16 (CST_LDS) with the responsibilities materialised: rows of K entries beside statistics for KT components"""
+    y, priors, init = mvgmm_ref.uv_case(11, 700, 31)
+    hist, fe, resp, _, ohist, ofe, oresp, _ = run_both(y, priors, init, 6, materialize=True)
+    assert_parity(hist, fe, ohist, ofe)
+    print(f"univariate K=11 N=700 resp {np.max(np.abs(resp - oresp)):.2e}")
+    assert resp.shape == (700, 11) and np.max(np.abs(resp - oresp)) < 1e-9
+    assert np.max(np.abs(resp.sum(axis=1) - 1.0)) < 1e-12
+
+
+@pytest.mark.parametrize("n", [1, 255, 257])
+def test_sizes_around_a_workgroup(n):
+    """K = 3 (KT = 4, one padding component) at one point, one lane short of a workgroup, and one point into the second workgroup"""
+    y, priors, init = mvgmm_ref.uv_case(3, n, 40 + n)
+    hist, fe, resp, _, ohist, ofe, oresp, _ = run_both(y, priors, init, 4, materialize=True)
+    assert_parity(hist, fe, ohist, ofe)
+    print(f"univariate K=3 N={n} resp {np.max(np.abs(resp - oresp)):.2e}")
+    assert np.max(np.abs(resp - oresp)) < 1e-9
+
+
+def test_run_to_run_bit_equality():
+    """two runs of one engine and a fresh engine at K = 11 (CST_LDS): the same bits in history, free energy and responsibilities"""
+    y, priors, init = mvgmm_ref.uv_case(11, 5000, 32)
+    runs = []
+    with rxhip.GMMEngine(y.size, *priors, *init, materialize_responsibilities=True) as eng:
+        eng.set_data(y)
+        for _ in range(2):
+            eng.run(5, True)
+            runs.append((eng.history().copy(), eng.free_energy().copy(), eng.responsibilities().copy()))
+    with rxhip.GMMEngine(y.size, *priors, *init, materialize_responsibilities=True) as eng:
+        eng.set_data(y)
+        eng.run(5, True)
+        runs.append((eng.history(), eng.free_energy(), eng.responsibilities()))
+    for other in runs[1:]:
+        assert all(np.array_equal(a, b) for a, b in zip(runs[0], other))
 
 
 def test_iid_gaussian_unknown_mean_and_precision():
