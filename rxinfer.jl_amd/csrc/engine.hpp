@@ -1,5 +1,7 @@
-// engine.hpp — what every translation unit behind the C ABI shares: the engine object, the error path, the device guards.
-//   rxhip.hip       runtime (pools, arenas), the state-space / mixture / HGF engines and the entry points common to all engines
+// engine.hpp — what every translation unit behind the C ABI shares: the engine object, its family table, the error path, the device guards and the
+// helpers every creator and run uses.
+//   rxhip.hip       runtime (pools, arenas), the state-space and drift-chain engines, the entry points common to all engines, the shared helpers
+//   vmp_engines.hip the mixture, HGF, probit, HMM, latent-AR and binomial-regression engines and their family rows
 //   graph_abi.hip   the graph entry points: host-only lowering (graph_lowering.hpp), rxhip_create, the node-array executor's rxhip_tree_* wrappers
 //   rccl_abi.hip    the RCCL exchange entry points (rxhip_comm_*, rxhip_allreduce_free_energy, rxhip_gmm_allreduce_statistics)
 //   tree_engine.hip the node-array executor itself (behind tree_engine.hpp)
@@ -9,6 +11,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -71,6 +74,18 @@ struct rxhip_engine_life {
     double k_ms[RXHIP_K_COUNT] = {};
     uint64_t k_n[RXHIP_K_COUNT] = {};
 };
+// The family of an engine: one row of the family table each (EngineFamily below).
+enum class EngineKind : int {
+    Lgssm = 0,    // linear Gaussian state-space model: every schedule of rxhip.hip's run_impl
+    Mixture = 1,  // uni- and multivariate Gaussian mixture (gmm_kernels.hpp, mvgmm_kernels.hpp, mvgmm_dense_kernels.hpp)
+    Hgf = 2,      // hierarchical Gaussian filter (hgf_kernels.hpp)
+    Drift = 3,    // noise-free drift chain (drift_kernels.hpp)
+    Probit = 4,   // probit chain, batched EP (probit_kernels.hpp)
+    Tree = 5,     // the level-scheduled node-array executor (tree_engine.hip; everything lives behind `tree`)
+    Hmm = 6,      // hidden Markov model, batched forward–backward VMP (hmm_kernels.hpp)
+    Lar = 7,      // latent autoregressive model, batched banded structured VMP (lar_kernels.hpp)
+    Binreg = 8,   // binomial regression, batched Pólya-Gamma VMP (binreg_kernels.hpp)
+};
 struct rxhip_engine : rxhip_engine_life {
     // one device allocation holds every buffer of a state-space engine (creation / destruction cost two driver calls
     // instead of ≈40: 2.9 ms -> see DESIGN §6c); pointers inside it are never freed individually
@@ -104,31 +119,31 @@ struct rxhip_engine : rxhip_engine_life {
     int* d_chain_model = nullptr;
     int* d_status = nullptr;
     double* d_fe_blocks = nullptr;
-    // Gaussian-mixture VMP engine (kind == 1)
-    int kind = 0;  // 0: LGSSM, 1: GMM, 2: HGF, 3: noise-free drift chain, 4: probit chain (batched EP, probit_kernels.hpp), 5: the level-scheduled node-array executor (tree_engine.hip; everything lives behind `tree`), 6: hidden Markov model (batched forward–backward VMP, hmm_kernels.hpp), 7: latent autoregressive model (batched banded structured VMP, lar_kernels.hpp), 8: binomial regression (batched Pólya-Gamma VMP, binreg_kernels.hpp)
+    EngineKind kind = EngineKind::Lgssm;
     rxhip::tree::Engine* tree = nullptr;
+    // one sub-object per family with state of its own (the state-space engine's lives in the fields around them)
     struct Drift { double m0 = 0, v0 = 1, c = 0, obs_var = 1; } dr;
     struct Hgf {
         rxhip_hgf_desc ds;
         double *d_out = nullptr, *d_fe_series = nullptr, *d_gh = nullptr, *d_fe_total = nullptr;
         int fe_cap = 0;
     } h;
-    struct Probit {   // kind == 4: one block (sites | forward messages | free-energy scratch) next to d_mean / d_cov / d_fe_chain / d_fe_total
+    struct Probit {   // one block (sites | forward messages | free-energy scratch) next to d_mean / d_cov / d_fe_chain / d_fe_total
         rxhip_probit_desc ds;
         double *d_block = nullptr, *d_gh = nullptr, *d_fe_series = nullptr;
         int fe_cap = 0;
     } pb;
-    struct Hmm {      // kind == 6: parameter block (π | prior | init | counts | log tables ×2 | Ã B̃ | KL | statistics | their sum | log Z̃), α̂ and γ, free energies
+    struct Hmm {      // parameter block (π | prior | init | counts | log tables ×2 | Ã B̃ | KL | statistics | their sum | log Z̃), α̂ and γ, free energies
         int K = 0, M = 0, shared = 0;
         double *d_par = nullptr, *d_alpha = nullptr, *d_gamma = nullptr, *d_fe_series = nullptr;
         int fe_cap = 0;
     } hm;
-    struct Lar {      // kind == 7: constants, parameter block (initial q | G per set | KL | statistics | their sum), parameter history, row records, m and the Σ band, free energies
+    struct Lar {      // constants, parameter block (initial q | G per set | KL | statistics | their sum), parameter history, row records, m and the Σ band, free energies
         int P = 0, shared = 0;
         double *d_cst = nullptr, *d_par = nullptr, *d_hist = nullptr, *d_rec = nullptr, *d_out = nullptr, *d_fe_series = nullptr;
         int fe_cap = 0, hist_cap = 0;
     } la;
-    struct Breg {     // kind == 8: X, n_eff, κ, constants, ξ, lc, S, the pass's partials, ξ partials, parameter history, free energies; y and n_trials stay on the host for the checks
+    struct Breg {     // X, n_eff, κ, constants, ξ, lc, S, the pass's partials, ξ partials, parameter history, free energies; y and n_trials stay on the host for the checks
         int d = 0, nchunk = 0, nchunk_xi = 0, hist_cap = 0;
         double *d_X = nullptr, *d_neff = nullptr, *d_kappa = nullptr, *d_cst = nullptr, *d_xi = nullptr, *d_lc = nullptr, *d_S = nullptr, *d_part = nullptr,
                *d_xi_part = nullptr, *d_hist = nullptr, *d_fe_prob = nullptr;
@@ -281,21 +296,60 @@ struct DevGuard {
 };
 #define SET_DEVICE(e) DevGuard _dev_guard; HIPCHK((e), _dev_guard.set((e)->device))
 
-// what the translation units of the engines share with the runtime in rxhip.hip: an idle stream of the device (pooled: creating one costs milliseconds on this
-// runtime), the HIP-event pair around a kernel of an engine that is being profiled, the HGF engine's run (vmp_engines.hip) as rxhip_run dispatches to it
+// One row per EngineKind: what the entry points common to all engines (rxhip_run, rxhip_set_data(_device), the free-energy and marginal getters,
+// rxhip_destroy) need to know about a family.  Plain function pointers and flags, like the launch tables (launch_tables.hpp).  The rows of the
+// families in vmp_engines.hip are defined there (vmp_family), the state-space and drift rows in rxhip.hip (family_of); the node-array executor's
+// row is empty (every entry point hands an engine with `tree` to tree_engine.hip before it looks at the row).  The rows are function-local
+// statics: a namespace-scope constant would also be emitted for the device, where the host functions it points to do not exist.
+struct EngineFamily {
+    rxhip_status (*run)(rxhip_engine* e, int32_t iterations, int32_t want_fe);   // rxhip_run_async
+    bool filter_twin;                                      // rxhip_run_filter is meaningful: a state-space engine with a streaming twin
+    rxhip_status (*check_data)(rxhip_engine* e);           // after a successful ingest of observations, host or device (null: any double is data)
+    rxhip_status (*set_data)(rxhip_engine* e, int32_t var_id, const double* host, size_t n);   // replaces rxhip_set_data (null: the common ingest)
+    const char* no_device_data;                            // text of rxhip_set_data_device's refusal (null: accepted)
+    double* (*fe_total)(const rxhip_engine* e);            // the per-iteration free-energy buffer (null: d_fe_total)
+    bool has_x;                                            // RXHIP_VAR_X marginals exist (d_mean / d_cov)
+    void (*release)(rxhip_engine* e);                      // frees the family's sub-object (null: nothing beyond the common buffers)
+};
+
+// destruction: device buffers of an engine that are freed unless they are part of its arena (free_all and the families' release hooks)
+inline void free_buffers(rxhip_engine* e, std::initializer_list<double**> bufs) {
+    for (double** b : bufs)
+        if (*b) { if (!e->in_arena(*b)) (void)hipFree(*b); *b = nullptr; }
+}
+
+// what the translation units of the engines share with the runtime in rxhip.hip
 namespace rxhip {
+const EngineFamily& family_of(const rxhip_engine* e);   // the row of the engine's kind
+const EngineFamily* vmp_family(EngineKind kind);        // … of a family of vmp_engines.hip (null: not one of them)
+inline double* fe_total_of(const rxhip_engine* e) { const auto f = family_of(e).fe_total; return f ? f(e) : e->d_fe_total; }
+// an idle stream of the device (pooled: creating one costs milliseconds on this runtime)
 hipError_t stream_acquire(int device, hipStream_t* out);
+// the HIP-event pair around a kernel of an engine that is being profiled
 rxhip_status prof_begin(rxhip_engine* e, int k);
 rxhip_status prof_end(rxhip_engine* e);
-rxhip_status hgf_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe);
-rxhip_status probit_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe);   // the probit chain's run (vmp_engines.hip)
-rxhip_status probit_check_data(rxhip_engine* e);   // … and its check of freshly ingested observations: 0, 1 or NaN
-rxhip_status hmm_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe);      // the hidden Markov model's run (vmp_engines.hip)
-rxhip_status hmm_check_data(rxhip_engine* e);   // … and its check of freshly ingested observations: an integer code 0 … M−1 or NaN
-rxhip_status lar_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe);      // the latent autoregressive model's run (vmp_engines.hip)
-rxhip_status lar_check_data(rxhip_engine* e);   // … and its check of freshly ingested observations: finite or NaN (missing)
-rxhip_status binreg_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe);   // the binomial regression's run (vmp_engines.hip)
-rxhip_status binreg_set_data(rxhip_engine* e, int32_t var_id, const double* host, size_t n);   // … and its three data arrays, checked on the host
-bool host_chol_inv(int n, const double* A, double* out, double* logdet);   // host Cholesky inverse + log-determinant of an SPD matrix (rxhip.hip host::chol_inv)
-}  // namespace rxhip
+bool host_chol_inv(int n, const double* A, double* out, double* logdet);   // host Cholesky inverse + log-determinant of an SPD matrix
 
+// ---- creators -------------------------------------------------------------------------------------------------------------------
+// The device and stream of a new engine: desc.device (≥ 0: checked against the `ndev` visible ones; else the caller's current device) becomes e->device and
+// is SELECTED through the creator's own guard — declared before the call, so that it covers the rest of the creator and hands the caller its device
+// back on every way out — then desc.stream is adopted or a pooled one acquired.
+rxhip_status open_device(rxhip_engine* e, DevGuard& guard, int device, void* stream, int ndev);
+// ---- runs -----------------------------------------------------------------------------------------------------------------------
+// "iterations must be positive", "no observations": the refusals every run starts with (need_data false: the family has a data check of its own)
+rxhip_status run_preamble(rxhip_engine* e, int32_t iterations, bool need_data = true);
+// Per-iteration device buffers that share one capacity: grown (never shrunk) to `iterations` entries of `per_iteration` doubles each.  Growing waits for
+// the stream, frees what is not part of the arena and leaves the capacity at 0 if an allocation fails.
+struct IterBuf { double** p; size_t per_iteration; };
+rxhip_status reserve(rxhip_engine* e, int* cap, int iterations, std::initializer_list<IterBuf> bufs);
+// the result bookkeeping of a finished run
+inline void finish_run(rxhip_engine* e, int iterations, bool want_fe, bool filter = false) {
+    e->last_iterations = iterations;
+    e->last_want_fe = want_fe;
+    e->ran = true;
+    e->last_filter = filter;
+}
+// A family's check of freshly ingested observations, on the device copy, whichever way it arrived: `launch` enqueues the kernel that raises `bit` of
+// d_status over the n = T · chains values (nb blocks of 256); a refused array counts as not set.
+rxhip_status check_observations(rxhip_engine* e, void (*launch)(rxhip_engine* e, long long n, unsigned nb), int bit, const char* message);
+}  // namespace rxhip

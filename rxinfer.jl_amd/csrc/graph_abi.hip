@@ -103,7 +103,7 @@ rxhip_status rxhip_tree_create(const rxhip_graph_desc* g, int32_t device, void* 
     const rxhip_status st = rxhip::tree::create(g, device, stream, &t, err);
     if (st) { rxhip_lower::last_error() = err; return st; }
     rxhip_engine* e = new rxhip_engine();
-    e->kind = 5;
+    e->kind = EngineKind::Tree;
     e->tree = t;
     e->device = rxhip::tree::device_of(t);
     e->stream = (hipStream_t)rxhip::tree::stream_of(t);   // (owned by the executor; the cross-GPU free-energy sum is enqueued on it)

@@ -156,13 +156,13 @@ rxhip_status rxhip_allreduce_free_energy(rxhip_engine* e, void* rccl_comm) {
         return ordered_allreduce(e, rccl_comm, fe, its, "allreduce_free_energy");
     }
     if (!e->ran || !e->last_want_fe) return fail(e, RXHIP_ERR_STATE, "free energy was not requested in the last run");
-    double* fe = e->kind == 1 ? e->g.d_fe : e->kind == 2 ? e->h.d_fe_total : e->d_fe_total;
+    double* fe = fe_total_of(e);
     return ordered_allreduce(e, rccl_comm, fe, e->last_iterations, "allreduce_free_energy");
 }
 
 rxhip_status rxhip_gmm_allreduce_statistics(rxhip_engine* e, void* rccl_comm) {
     TREE_GUARD(e);
-    if (!e || e->kind != 1) return RXHIP_ERR_BADARG;
+    if (!e || e->kind != EngineKind::Mixture) return RXHIP_ERR_BADARG;
     return ordered_allreduce(e, rccl_comm, e->g.d_totals, e->g.nq, "gmm_allreduce_statistics");
 }
 

@@ -138,6 +138,53 @@ hipError_t rxhip::stream_acquire(int device, hipStream_t* out) {
     }
     return hipStreamCreateWithFlags(out, hipStreamNonBlocking);
 }
+// ---- what every creator and every run shares (engine.hpp) ----
+rxhip_status rxhip::open_device(rxhip_engine* e, DevGuard& guard, int device, void* stream, int ndev) {
+    if (device >= 0) {
+        if (device >= ndev) return fail(e, RXHIP_ERR_BADARG, "device %d out of range (%d visible)", device, ndev);
+        e->device = device;
+    } else
+        HIPCHK(e, hipGetDevice(&e->device));
+    HIPCHK(e, guard.set(e->device));
+    if (stream) e->stream = (hipStream_t)stream;
+    else {
+        HIPCHK(e, stream_acquire(e->device, &e->stream));
+        e->own_stream = true;
+    }
+    return RXHIP_OK;
+}
+rxhip_status rxhip::run_preamble(rxhip_engine* e, int32_t iterations, bool need_data) {
+    if (iterations <= 0) return fail(e, RXHIP_ERR_BADARG, "run: iterations must be positive");
+    if (need_data && !e->have_data) return fail(e, RXHIP_ERR_STATE, "run: no observations (call rxhip_set_data first)");
+    return RXHIP_OK;
+}
+rxhip_status rxhip::reserve(rxhip_engine* e, int* cap, int iterations, std::initializer_list<IterBuf> bufs) {
+    if (iterations <= *cap) return RXHIP_OK;
+    if (e->stream) HIPCHK(e, hipStreamSynchronize(e->stream));
+    *cap = 0;
+    for (const IterBuf& b : bufs) {
+        if (*b.p && !e->in_arena(*b.p)) HIPCHK(e, hipFree(*b.p));
+        *b.p = nullptr;
+    }
+    for (const IterBuf& b : bufs) HIPCHK(e, hipMalloc(b.p, sizeof(double) * (size_t)iterations * b.per_iteration));
+    *cap = iterations;
+    return RXHIP_OK;
+}
+rxhip_status rxhip::check_observations(rxhip_engine* e, void (*launch)(rxhip_engine* e, long long n, unsigned nb), int bit, const char* message) {
+    SET_DEVICE(e);
+    const long long n = e->T * e->n_chains;
+    launch(e, n, (unsigned)std::min<long long>((n + 255) / 256, 1024));
+    HIPCHK(e, hipGetLastError());
+    int st = 0;
+    HIPCHK(e, hipMemcpyAsync(&st, e->d_status, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (st & bit) {
+        HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
+        e->have_data = false;
+        return fail(e, RXHIP_ERR_BADARG, "%s", message);
+    }
+    return RXHIP_OK;
+}
 // Arenas up to 2 GB are parked the same way — hipFree of a multi-megabyte block costs ≈120–170 µs (more than a whole sweep of
 // the reference's own benchmark sizes), hipMalloc + hipFree of the 1 GB of a d = 64, T = 10⁴ engine ≈40 ms.  At most 4 blocks /
 // 4 GB are kept; rxhip_release_cached_memory() frees them.
@@ -1444,30 +1491,15 @@ static void free_all(rxhip_engine* e) {
     }
     e->d_models = nullptr;  // lives in the arena
     if (e->mseg_block) e->d_filt = e->d_vend = e->d_fstart_m = e->d_beta_xi = nullptr;  // carved from mseg_block (freed below)
-    double** bufs[] = {&e->d_vtab, &e->d_scan, &e->d_filt, &e->d_mean, &e->d_cov, &e->d_cst, &e->d_tab, &e->d_agg, &e->d_elem,
-                       &e->d_fstart, &e->d_beta, &e->d_fe_part, &e->d_fe_chain, &e->d_fe_total};
-    for (auto b : bufs)
-        if (*b) { if (!e->in_arena(*b)) (void)hipFree(*b); *b = nullptr; }
+    free_buffers(e, {&e->d_vtab, &e->d_scan, &e->d_filt, &e->d_mean, &e->d_cov, &e->d_cst, &e->d_tab, &e->d_agg, &e->d_elem,
+                     &e->d_fstart, &e->d_beta, &e->d_fe_part, &e->d_fe_chain, &e->d_fe_total});
     if (e->own_y && e->d_y && !e->in_arena(e->d_y)) (void)hipFree(e->d_y);
     e->d_y = nullptr;
     if (e->d_chain_model && !e->in_arena(e->d_chain_model)) (void)hipFree(e->d_chain_model);
     if (e->d_status && !e->in_arena(e->d_status)) (void)hipFree(e->d_status);
     if (e->d_fe_blocks && !e->in_arena(e->d_fe_blocks)) (void)hipFree(e->d_fe_blocks);
-    for (double** b : {&e->g.d_resp, &e->g.d_par, &e->g.d_drv, &e->g.d_prior, &e->g.d_init, &e->g.d_partial, &e->g.d_totals,
-                       &e->g.d_hist, &e->g.d_fe})
-        if (*b) { (void)hipFree(*b); *b = nullptr; }
-    for (double** b : {&e->h.d_out, &e->h.d_fe_series, &e->h.d_gh, &e->h.d_fe_total})
-        if (*b) { (void)hipFree(*b); *b = nullptr; }
-    for (double** b : {&e->pb.d_block, &e->pb.d_gh, &e->pb.d_fe_series})
-        if (*b) { (void)hipFree(*b); *b = nullptr; }
-    for (double** b : {&e->hm.d_par, &e->hm.d_alpha, &e->hm.d_gamma, &e->hm.d_fe_series})
-        if (*b) { (void)hipFree(*b); *b = nullptr; }
-    for (double** b : {&e->la.d_cst, &e->la.d_par, &e->la.d_hist, &e->la.d_rec, &e->la.d_out, &e->la.d_fe_series})
-        if (*b) { (void)hipFree(*b); *b = nullptr; }
-    for (double** b : {&e->br.d_X, &e->br.d_neff, &e->br.d_kappa, &e->br.d_cst, &e->br.d_xi, &e->br.d_lc, &e->br.d_S, &e->br.d_part, &e->br.d_xi_part, &e->br.d_hist, &e->br.d_fe_prob})
-        if (*b) { (void)hipFree(*b); *b = nullptr; }
-    for (double** b : {&e->d_scanm, &e->d_fstart_m, &e->d_beta_xi, &e->d_vend, &e->d_qtab, &e->d_loc, &e->d_aggpart, &e->d_bnd})
-        if (*b) { if (!e->in_arena(*b)) (void)hipFree(*b); *b = nullptr; }
+    if (family_of(e).release) family_of(e).release(e);   // the family's own sub-object
+    free_buffers(e, {&e->d_scanm, &e->d_fstart_m, &e->d_beta_xi, &e->d_vend, &e->d_qtab, &e->d_loc, &e->d_aggpart, &e->d_bnd});
     if (e->d_coll) { (void)hipFree(e->d_coll); e->d_coll = nullptr; }
     if (e->mseg_block) { (void)hipFree(e->mseg_block); e->mseg_block = nullptr; }
     if (e->noise_block) { (void)hipFree(e->noise_block); e->noise_block = nullptr; }
@@ -1528,7 +1560,6 @@ static bool engine_pool_key(const rxhip_lgssm_desc* ds, const ScheduleHooks& hoo
     hooks.append_key(key);   // every schedule hook: an engine of another schedule is another engine
     return true;
 }
-static void free_all(rxhip_engine* e);
 static void engine_pool_flush() {
     std::vector<rxhip_engine*> old;
     {
@@ -1627,7 +1658,7 @@ static void offsets_to_shifts(rxhip_engine* e, const double* cx, const double* c
 
 rxhip_status rxhip_lgssm_set_offsets(rxhip_engine* e, const double* state_offset, const double* obs_offset) {
     TREE_GUARD(e);
-    if (!e || e->kind != 0) return RXHIP_ERR_BADARG;
+    if (!e || e->kind != EngineKind::Lgssm) return RXHIP_ERR_BADARG;
     if (!e->d_mu) return fail(e, RXHIP_ERR_STATE, "set_offsets: the engine was created without offsets (pass zero arrays at creation to reserve them)");
     if (e->off_chain) return fail(e, RXHIP_ERR_STATE, "set_offsets: this engine carries per-chain inputs (rxhip_lgssm_set_chain_offsets)");
     SET_DEVICE(e);
@@ -1648,7 +1679,7 @@ rxhip_status rxhip_lgssm_set_offsets(rxhip_engine* e, const double* state_offset
 // the covariance table of the model does not see them.
 rxhip_status rxhip_lgssm_set_chain_offsets(rxhip_engine* e, const double* state_offset, const double* obs_offset, int32_t layout) {
     TREE_GUARD(e);
-    if (!e || e->kind != 0) return RXHIP_ERR_BADARG;
+    if (!e || e->kind != EngineKind::Lgssm) return RXHIP_ERR_BADARG;
     if (layout != RXHIP_LAYOUT_TIME_CHAIN && layout != RXHIP_LAYOUT_CHAIN_TIME) return fail(e, RXHIP_ERR_BADARG, "set_chain_offsets: unknown layout %d", layout);
     if (!e->d_mu) return fail(e, RXHIP_ERR_STATE, "set_chain_offsets: the engine was created without offsets (pass zero arrays at creation to reserve them)");
     SET_DEVICE(e);
@@ -2260,18 +2291,8 @@ rxhip_status rxhip_lgssm_create(const rxhip_lgssm_desc* ds, rxhip_engine** out) 
     e->pool_key = pkey;
     e->hooks = hooks;
     if (rxhip_status st = create_describe(e, ds, vt, dense)) return st;
-    if (ds->device >= 0) {
-        if (ds->device >= ndev) return fail(e, RXHIP_ERR_BADARG, "device %d out of range (%d visible)", ds->device, ndev);
-        e->device = ds->device;
-    } else
-        HIPCHK(e, hipGetDevice(&e->device));
-    SET_DEVICE(e);
-    if (ds->stream) {
-        e->stream = (hipStream_t)ds->stream;
-    } else {
-        HIPCHK(e, stream_acquire(e->device, &e->stream));
-        e->own_stream = true;
-    }
+    DevGuard guard;
+    if (rxhip_status st = open_device(e, guard, ds->device, ds->stream, ndev)) return st;
     if (e->gseq) return create_gseq(e, ds);
     if (dense) return create_dense(e, ds);
     return create_lanes(e, ds);
@@ -2387,21 +2408,12 @@ rxhip_status rxhip_drift_chain_create(const rxhip_drift_chain_desc* ds, rxhip_en
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return RXHIP_ERR_NO_DEVICE;
     rxhip_engine* e = new rxhip_engine();
     *out = e;
-    e->kind = 3;
+    e->kind = EngineKind::Drift;
     e->T = ds->T; e->n_chains = ds->n_chains; e->d = 1; e->dy = 1; e->dpad = 1;
     e->ptt = ds->prior_through_transition ? 1 : 0;
     e->dr.m0 = ds->m0; e->dr.v0 = ds->v0; e->dr.c = ds->c; e->dr.obs_var = ds->obs_var;
-    if (ds->device >= 0) {
-        if (ds->device >= ndev) return fail(e, RXHIP_ERR_BADARG, "device %d out of range (%d visible)", ds->device, ndev);
-        e->device = ds->device;
-    } else
-        HIPCHK(e, hipGetDevice(&e->device));
-    SET_DEVICE(e);
-    if (ds->stream) e->stream = (hipStream_t)ds->stream;
-    else {
-        HIPCHK(e, stream_acquire(e->device, &e->stream));
-        e->own_stream = true;
-    }
+    DevGuard guard;
+    if (rxhip_status st = open_device(e, guard, ds->device, ds->stream, ndev)) return st;
     const size_t C = (size_t)e->n_chains, T = (size_t)e->T;
     ArenaPlan ap;
     ap.zeroed(&e->d_status, sizeof(int));
@@ -2418,16 +2430,9 @@ rxhip_status rxhip_drift_chain_create(const rxhip_drift_chain_desc* ds, rxhip_en
 }
 
 static rxhip_status drift_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
-    if (iterations <= 0) return fail(e, RXHIP_ERR_BADARG, "run: iterations must be positive");
-    if (!e->have_data) return fail(e, RXHIP_ERR_STATE, "run: no observations (call rxhip_set_data first)");
+    if (rxhip_status st = run_preamble(e, iterations)) return st;
     SET_DEVICE(e);
-    if (iterations > e->fe_total_cap) {
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        if (!e->in_arena(e->d_fe_total)) HIPCHK(e, hipFree(e->d_fe_total));
-        e->d_fe_total = nullptr;
-        e->fe_total_cap = iterations;
-        HIPCHK(e, hipMalloc(&e->d_fe_total, sizeof(double) * e->fe_total_cap));
-    }
+    if (rxhip_status st = reserve(e, &e->fe_total_cap, iterations, {{&e->d_fe_total, 1}})) return st;
     DriftParams p;
     p.T = e->T; p.n_chains = e->n_chains; p.y = e->d_y; p.mean = e->d_mean; p.var = e->d_cov; p.fe_chain = e->d_fe_chain;
     p.m0 = e->dr.m0; p.v0 = e->dr.v0; p.c = e->dr.c; p.obs_var = e->dr.obs_var; p.ptt = e->ptt; p.status = e->d_status;
@@ -2440,10 +2445,7 @@ static rxhip_status drift_run_async(rxhip_engine* e, int32_t iterations, int32_t
         if (want_fe) hipLaunchKernelGGL(k_sum_fixed, dim3(1), dim3(256), 0, e->stream, (const double*)e->d_fe_chain, e->n_chains, e->d_fe_total + it);
     }
     HIPCHK(e, hipGetLastError());
-    e->last_iterations = iterations;
-    e->last_want_fe = want_fe != 0;
-    e->ran = true;
-    e->last_filter = false;
+    finish_run(e, iterations, want_fe != 0);
     // reference-equivalent events per chain and iteration: `+`(:out), Normal(:μ), `+`(:in1) per step + the prior's message;
     // products: forward (fwd ⊗ obs) and backward (obs ⊗ bwd) at every interior state, the marginals (2 / 1 pairwise), q(x_prior)
     const uint64_t C = (uint64_t)e->n_chains, T = (uint64_t)e->T, I = (uint64_t)iterations;
@@ -2452,9 +2454,6 @@ static rxhip_status drift_run_async(rxhip_engine* e, int32_t iterations, int32_t
     e->marginals = I * C * (T + (e->ptt ? 1 : 0));
     return RXHIP_OK;
 }
-
-rxhip_status rxhip_hgf_get_history(rxhip_engine* e, double* z_mean, double* z_var, double* x_mean, double* x_var,
-                                   int32_t layout);
 
 static rxhip_status ingest(rxhip_engine* e, const double* src, size_t n, int32_t layout, bool src_on_device) {
     if (!e) return RXHIP_ERR_BADARG;
@@ -2507,7 +2506,7 @@ static rxhip_status ingest(rxhip_engine* e, const double* src, size_t n, int32_t
 
 // u[t] of every chain -> c[t] = B_u u[t] (+ the constant part of the same step) -> per-chain offsets
 static rxhip_status ingest_inputs(rxhip_engine* e, const double* u, size_t n, int32_t layout) {
-    if (e->kind != 0 || e->du <= 0) return fail(e, RXHIP_ERR_BADARG, "set_data: this engine has no data inputs u[t]");
+    if (e->kind != EngineKind::Lgssm || e->du <= 0) return fail(e, RXHIP_ERR_BADARG, "set_data: this engine has no data inputs u[t]");
     const size_t C = (size_t)e->n_chains, T = (size_t)e->T, To = (size_t)e->Tout(), d = (size_t)e->d, du = (size_t)e->du;
     if (!u || n != T * C * du) return fail(e, RXHIP_ERR_BADARG, "set_data(u): expected %zu doubles, got %zu", T * C * du, n);
     if (layout != RXHIP_LAYOUT_TIME_CHAIN && layout != RXHIP_LAYOUT_CHAIN_TIME) return fail(e, RXHIP_ERR_BADARG, "set_data: unknown layout %d", layout);
@@ -2540,23 +2539,21 @@ static rxhip_status ingest_inputs(rxhip_engine* e, const double* u, size_t n, in
 rxhip_status rxhip_set_data(rxhip_engine* e, int32_t var_id, const double* host, size_t n, int32_t layout) {
     TREE_GUARD(e);
     if (!e) return RXHIP_ERR_BADARG;
-    if (e->kind == 8) return rxhip::binreg_set_data(e, var_id, host, n);
+    const EngineFamily& f = family_of(e);
+    if (f.set_data) return f.set_data(e, var_id, host, n);
     if (var_id == RXHIP_VAR_U) return ingest_inputs(e, host, n, layout);
     if (var_id != RXHIP_VAR_Y) return fail(e, RXHIP_ERR_BADARG, "set_data: variable %d is not a data variable", var_id);
     const rxhip_status st = ingest(e, host, n, layout, false);
-    if (st == RXHIP_OK && e->kind == 6) return rxhip::hmm_check_data(e);
-    if (st == RXHIP_OK && e->kind == 7) return rxhip::lar_check_data(e);
-    return st == RXHIP_OK && e->kind == 4 ? rxhip::probit_check_data(e) : st;
+    return st == RXHIP_OK && f.check_data ? f.check_data(e) : st;
 }
 rxhip_status rxhip_set_data_device(rxhip_engine* e, int32_t var_id, const double* dev, size_t n, int32_t layout) {
     TREE_GUARD(e);
     if (!e) return RXHIP_ERR_BADARG;
-    if (e->kind == 8) return fail(e, RXHIP_ERR_BADARG, "set_data_device: the binomial regression engine checks its data on the host (rxhip_set_data)");
+    const EngineFamily& f = family_of(e);
+    if (f.no_device_data) return fail(e, RXHIP_ERR_BADARG, "%s", f.no_device_data);
     if (var_id != RXHIP_VAR_Y) return fail(e, RXHIP_ERR_BADARG, "set_data: variable %d is not a data variable", var_id);
     const rxhip_status st = ingest(e, dev, n, layout, true);
-    if (st == RXHIP_OK && e->kind == 6) return rxhip::hmm_check_data(e);
-    if (st == RXHIP_OK && e->kind == 7) return rxhip::lar_check_data(e);
-    return st == RXHIP_OK && e->kind == 4 ? rxhip::probit_check_data(e) : st;
+    return st == RXHIP_OK && f.check_data ? f.check_data(e) : st;
 }
 
 // fold finished (kernel start, kernel end) event pairs into the per-kernel sums; with `wait` the stream has been drained and
@@ -2604,24 +2601,25 @@ extern "C++" rxhip_status rxhip::prof_end(rxhip_engine* e) {
 static rxhip_status run_impl(rxhip_engine* e, int32_t iterations, int32_t want_fe, bool filter);
 rxhip_status rxhip_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
     if (e && e->tree) return rxhip_run(e, iterations, want_fe);
-    return run_impl(e, iterations, want_fe, false);
+    if (!e) return RXHIP_ERR_BADARG;
+    return family_of(e).run(e, iterations, want_fe);
 }
 rxhip_status rxhip_run_filter_async(rxhip_engine* e, int32_t want_fe) {
     TREE_GUARD(e);
     if (!e) return RXHIP_ERR_BADARG;
-    if (e->kind != 0) return fail(e, RXHIP_ERR_BADARG, "run_filter: not a state-space engine with a streaming twin (the HGF engine is a filter already)");
+    if (!family_of(e).filter_twin) return fail(e, RXHIP_ERR_BADARG, "run_filter: not a state-space engine with a streaming twin (the HGF engine is a filter already)");
     return run_impl(e, 1, want_fe, true);
 }
 rxhip_status rxhip_filter_reset(rxhip_engine* e) {
     TREE_GUARD(e);
-    if (!e || e->kind != 0) return RXHIP_ERR_BADARG;
+    if (!e || e->kind != EngineKind::Lgssm) return RXHIP_ERR_BADARG;
     e->stream_k = 0;
     return RXHIP_OK;
 }
 rxhip_status rxhip_filter_step(rxhip_engine* e, const double* y, double* mean, double* cov, double* free_energy) {
     TREE_GUARD(e);
     if (!e || !y) return RXHIP_ERR_BADARG;
-    if (e->kind != 0) return fail(e, RXHIP_ERR_BADARG, "filter_step: not a state-space engine");
+    if (e->kind != EngineKind::Lgssm) return fail(e, RXHIP_ERR_BADARG, "filter_step: not a state-space engine");
     if (!e->dense && !e->vt) return fail(e, RXHIP_ERR_UNSUPPORTED, "filter_step: no device schedule for this shape");
     e->cov_current = false; e->cov_pending = false; e->records_hold_gains = false;   // the step-wise filter writes the posterior arrays itself
     if ((e->d_step_model || e->d_cx) && e->stream_k >= e->Tout())
@@ -2966,39 +2964,9 @@ static rxhip_status run_tail(rxhip_engine* e, const RunPlan& pl, const Params& p
     return RXHIP_OK;
 }
 
+// The run of a state-space engine: smoothing (the family row's run) or, with `filter`, its streaming twin (rxhip_run_filter, rxhip_lgssm_infer).
 static rxhip_status run_impl(rxhip_engine* e, int32_t iterations, int32_t want_fe, bool filter) {
-    if (!e) return RXHIP_ERR_BADARG;
-    if (e->kind == 2) return rxhip::hgf_run_async(e, iterations, want_fe);
-    if (e->kind == 4) {
-        if (filter) return fail(e, RXHIP_ERR_BADARG, "run_filter: not a state-space engine with a streaming twin");
-        return rxhip::probit_run_async(e, iterations, want_fe);
-    }
-    if (e->kind == 6) {
-        if (filter) return fail(e, RXHIP_ERR_BADARG, "run_filter: not a state-space engine with a streaming twin");
-        return rxhip::hmm_run_async(e, iterations, want_fe);
-    }
-    if (e->kind == 7) {
-        if (filter) return fail(e, RXHIP_ERR_BADARG, "run_filter: not a state-space engine with a streaming twin");
-        return rxhip::lar_run_async(e, iterations, want_fe);
-    }
-    if (e->kind == 8) {
-        if (filter) return fail(e, RXHIP_ERR_BADARG, "run_filter: not a state-space engine with a streaming twin");
-        return rxhip::binreg_run_async(e, iterations, want_fe);
-    }
-    if (e->kind == 3) {
-        if (filter) return fail(e, RXHIP_ERR_BADARG, "run_filter: not a state-space engine with a streaming twin");
-        return drift_run_async(e, iterations, want_fe);
-    }
-    if (e->kind == 1) {
-        rxhip_status st = rxhip_gmm_begin_run(e, iterations);
-        for (int it = 0; !st && it < iterations; ++it) {
-            st = rxhip_gmm_accumulate(e);
-            if (!st) st = rxhip_gmm_update(e, want_fe);
-        }
-        return st;
-    }
-    if (iterations <= 0) return fail(e, RXHIP_ERR_BADARG, "run: iterations must be positive");
-    if (!e->have_data) return fail(e, RXHIP_ERR_STATE, "run: no observations (call rxhip_set_data first)");
+    if (rxhip_status st = run_preamble(e, iterations)) return st;
     const bool was_cov_current = e->cov_current && !filter;
     e->cov_current = false;   // any run may rewrite the posterior arrays; the shared-model smoothing schedules say otherwise below
     e->cov_pending = false;
@@ -3006,13 +2974,7 @@ static rxhip_status run_impl(rxhip_engine* e, int32_t iterations, int32_t want_f
     // the reference refuses to run while a datavar has no value (batch.jl:387-407): so does an engine whose graph has data inputs
     if (e->du > 0 && !e->have_inputs) return fail(e, RXHIP_ERR_STATE, "run: this model has data inputs u[t]: call rxhip_set_data(RXHIP_VAR_U) first");
     SET_DEVICE(e);
-    if (iterations > e->fe_total_cap) {
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        if (!e->in_arena(e->d_fe_total)) HIPCHK(e, hipFree(e->d_fe_total));
-        e->d_fe_total = nullptr;
-        e->fe_total_cap = iterations;
-        HIPCHK(e, hipMalloc(&e->d_fe_total, sizeof(double) * e->fe_total_cap));
-    }
+    if (rxhip_status st = reserve(e, &e->fe_total_cap, iterations, {{&e->d_fe_total, 1}})) return st;
     const bool fe = want_fe != 0;
     const RunPlan pl = resolve_run(e, filter, fe);
     Params p = fill_params(e, pl);
@@ -3047,13 +3009,10 @@ static rxhip_status run_impl(rxhip_engine* e, int32_t iterations, int32_t want_f
     }
     HIPCHK(e, hipGetLastError());
     if (cov_once) e->cov_current = true;   // rows 0 … T−1 hold what the next smoothing sweep would store
-    e->last_iterations = iterations;
-    e->last_want_fe = fe;
-    e->ran = true;
+    finish_run(e, iterations, fe, filter);
     e->records_tinv = p.tinv_records != 0 && iterations > 0;
     // reference-equivalent operation counts (6 rule calls, 4 products per step)
     const uint64_t C = (uint64_t)e->n_chains, T = (uint64_t)e->T, I = (uint64_t)iterations;
-    e->last_filter = filter;
     if (filter) {
         // one-step graph per observation: prior MvN(:out), `*`_A(:out), MvN_x(:out), MvN_y(:μ), `*`_B(:in) -> 5 rule
         // calls, 1 product for q(x_t) (without the transition at t = 1 when the prior sits on x[1]: 3 rule calls)
@@ -3066,6 +3025,20 @@ static rxhip_status run_impl(rxhip_engine* e, int32_t iterations, int32_t want_f
     e->products = I * C * (e->ptt ? 4 * T - 2 : (T == 1 ? 1 : 4 * T - 4));
     e->marginals = I * C * (e->ptt ? T + 1 : T);
     return RXHIP_OK;
+}
+static rxhip_status lgssm_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) { return run_impl(e, iterations, want_fe, false); }
+
+// The family table (engine.hpp): the rows of the two families of this unit, the node-array executor's empty row, and the lookup.
+extern "C++" const EngineFamily& rxhip::family_of(const rxhip_engine* e) {
+    //                                 run              filter  check    set_data  no_device_data  fe_total  has_x  release
+    static const EngineFamily lgssm = {lgssm_run_async, true,   nullptr, nullptr,  nullptr,        nullptr,  true,  nullptr},
+                              drift = {drift_run_async, false,  nullptr, nullptr,  nullptr,        nullptr,  true,  nullptr}, tree = {};
+    switch (e->kind) {
+        case EngineKind::Lgssm: return lgssm;
+        case EngineKind::Drift: return drift;
+        case EngineKind::Tree: return tree;
+        default: return *vmp_family(e->kind);
+    }
 }
 
 // rxhip_set_covariance_mode(1): the per-chain covariance array of a shared-model batch is written when somebody needs it
@@ -3094,7 +3067,7 @@ rxhip_status rxhip_set_covariance_mode(rxhip_engine* e, int32_t mode) {
 rxhip_status rxhip_get_covariance_writes(rxhip_engine* e, uint64_t* n) {
     TREE_GUARD(e);
     if (!e || !n) return RXHIP_ERR_BADARG;
-    if (e->kind != 0) return fail(e, RXHIP_ERR_UNSUPPORTED, "get_covariance_writes: not a state-space engine");
+    if (e->kind != EngineKind::Lgssm) return fail(e, RXHIP_ERR_UNSUPPORTED, "get_covariance_writes: not a state-space engine");
     *n = e->cov_writes;
     return RXHIP_OK;
 }
@@ -3138,7 +3111,7 @@ rxhip_status rxhip_lgssm_infer(rxhip_engine* e, const double* y, size_t n, int32
     TREE_GUARD(e);
     TREE_GUARD(e);
     if (!e || !y) return RXHIP_ERR_BADARG;
-    if (e->kind != 0) return fail(e, RXHIP_ERR_BADARG, "infer: not a state-space engine");
+    if (e->kind != EngineKind::Lgssm) return fail(e, RXHIP_ERR_BADARG, "infer: not a state-space engine");
     const size_t C = (size_t)e->n_chains, ny = (size_t)e->T * C * e->dy, nm = (size_t)e->Tout() * C * e->d, nc = nm * e->d;
     if (n != ny) return fail(e, RXHIP_ERR_BADARG, "infer: expected %zu doubles, got %zu", ny, n);
     // one staging block: y | the span of the results as it lies in the arena (status word | mean | cov | fe per chain, each 256-byte aligned:
@@ -3209,7 +3182,7 @@ rxhip_status rxhip_get_marginals_device(rxhip_engine* e, int32_t var_id, const d
     TREE_GUARD(e);
     TREE_GUARD(e);
     if (!e) return RXHIP_ERR_BADARG;
-    if (var_id != RXHIP_VAR_X || (e->kind != 0 && e->kind != 3 && e->kind != 4)) return fail(e, RXHIP_ERR_BADARG, "get_marginals: variable %d is not random", var_id);
+    if (var_id != RXHIP_VAR_X || !family_of(e).has_x) return fail(e, RXHIP_ERR_BADARG, "get_marginals: variable %d is not random", var_id);
     if (!e->ran) return fail(e, RXHIP_ERR_STATE, "get_marginals: no run yet");
     if (rxhip_status stc = ensure_cov(e)) return stc;   // covariance mode 1: the per-chain array is written now
     if (mean_dev) *mean_dev = e->d_mean;
@@ -3239,7 +3212,7 @@ rxhip_status rxhip_hgf_get_history(rxhip_engine* e, double* z_mean, double* z_va
                                    int32_t layout) {
     TREE_GUARD(e);
     TREE_GUARD(e);
-    if (!e || e->kind != 2) return RXHIP_ERR_BADARG;
+    if (!e || e->kind != EngineKind::Hgf) return RXHIP_ERR_BADARG;
     if (!e->ran) return fail(e, RXHIP_ERR_STATE, "get_history: no run yet");
     if (layout != RXHIP_LAYOUT_TIME_CHAIN && layout != RXHIP_LAYOUT_CHAIN_TIME)
         return fail(e, RXHIP_ERR_BADARG, "get_history: unknown layout %d", layout);
@@ -3257,7 +3230,7 @@ rxhip_status rxhip_hgf_get_history(rxhip_engine* e, double* z_mean, double* z_va
 rxhip_status rxhip_get_marginals(rxhip_engine* e, int32_t var_id, double* mean, double* cov, int32_t layout) {
     TREE_GUARD(e);
     if (!e) return RXHIP_ERR_BADARG;
-    if (var_id != RXHIP_VAR_X || (e->kind != 0 && e->kind != 3 && e->kind != 4)) return fail(e, RXHIP_ERR_BADARG, "get_marginals: variable %d is not random", var_id);
+    if (var_id != RXHIP_VAR_X || !family_of(e).has_x) return fail(e, RXHIP_ERR_BADARG, "get_marginals: variable %d is not random", var_id);
     if (!e->ran) return fail(e, RXHIP_ERR_STATE, "get_marginals: no run yet");
     if (layout != RXHIP_LAYOUT_TIME_CHAIN && layout != RXHIP_LAYOUT_CHAIN_TIME)
         return fail(e, RXHIP_ERR_BADARG, "get_marginals: unknown layout %d", layout);
@@ -3286,7 +3259,7 @@ rxhip_status rxhip_get_marginals(rxhip_engine* e, int32_t var_id, double* mean, 
 rxhip_status rxhip_get_predictions(rxhip_engine* e, int32_t var_id, double* mean, double* cov, int32_t layout) {
     TREE_GUARD(e);
     if (!e) return RXHIP_ERR_BADARG;
-    if (var_id != RXHIP_VAR_Y || e->kind != 0) return fail(e, RXHIP_ERR_BADARG, "get_predictions: variable %d is not a data variable of a state-space engine", var_id);
+    if (var_id != RXHIP_VAR_Y || e->kind != EngineKind::Lgssm) return fail(e, RXHIP_ERR_BADARG, "get_predictions: variable %d is not a data variable of a state-space engine", var_id);
     if (!e->ran || e->last_filter) return fail(e, RXHIP_ERR_STATE, "get_predictions: needs a smoothing run (rxhip_run) first");
     if (layout != RXHIP_LAYOUT_TIME_CHAIN && layout != RXHIP_LAYOUT_CHAIN_TIME) return fail(e, RXHIP_ERR_BADARG, "get_predictions: unknown layout %d", layout);
     SET_DEVICE(e);
@@ -3334,7 +3307,7 @@ rxhip_status rxhip_get_predictions(rxhip_engine* e, int32_t var_id, double* mean
 rxhip_status rxhip_get_node_marginals(rxhip_engine* e, int32_t node_type, double* mean, double* cov, int32_t layout) {
     TREE_GUARD(e);
     if (!e) return RXHIP_ERR_BADARG;
-    if (node_type != RXHIP_NODE_MVNORMAL_MEAN_COV || e->kind != 0)
+    if (node_type != RXHIP_NODE_MVNORMAL_MEAN_COV || e->kind != EngineKind::Lgssm)
         return fail(e, RXHIP_ERR_BADARG, "get_node_marginals: node-local joints exist for the transition nodes of a state-space engine");
     if (!e->ran || e->last_filter) return fail(e, RXHIP_ERR_STATE, "get_node_marginals: needs a smoothing run (rxhip_run) first");
     if (!e->dense && !e->vt) return fail(e, RXHIP_ERR_UNSUPPORTED, "node-local joints: no device schedule for this shape");
@@ -3414,14 +3387,14 @@ rxhip_status rxhip_get_free_energy(rxhip_engine* e, double* per_iteration) {
     if (!e->ran || !e->last_want_fe) return fail(e, RXHIP_ERR_STATE, "free energy was not requested in the last run");
     SET_DEVICE(e);
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    HIPCHK(e, hipMemcpy(per_iteration, e->kind == 1 ? e->g.d_fe : e->kind == 2 ? e->h.d_fe_total : e->d_fe_total, sizeof(double) * e->last_iterations,
+    HIPCHK(e, hipMemcpy(per_iteration, fe_total_of(e), sizeof(double) * e->last_iterations,
                         hipMemcpyDeviceToHost));
     return RXHIP_OK;
 }
 rxhip_status rxhip_get_free_energy_per_chain(rxhip_engine* e, double* per_chain) {
     if (!e || !per_chain) return RXHIP_ERR_BADARG;
     if (e->tree) return rxhip::tree::get_free_energy_per_replica(e->tree, per_chain, e->err);
-    if (e->kind == 1) return fail(e, RXHIP_ERR_BADARG, "per-chain free energy is not defined for the mixture engine");
+    if (e->kind == EngineKind::Mixture) return fail(e, RXHIP_ERR_BADARG, "per-chain free energy is not defined for the mixture engine");
     if (!e->ran || !e->last_want_fe) return fail(e, RXHIP_ERR_STATE, "free energy was not requested in the last run");
     SET_DEVICE(e);
     HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -3432,7 +3405,7 @@ rxhip_status rxhip_get_free_energy_device(rxhip_engine* e, double** fe_dev) {
     TREE_GUARD(e);
     if (!e || !fe_dev) return RXHIP_ERR_BADARG;
     if (!e->ran || !e->last_want_fe) return fail(e, RXHIP_ERR_STATE, "free energy was not requested in the last run");
-    *fe_dev = (e->kind == 1 ? e->g.d_fe : e->kind == 2 ? e->h.d_fe_total : e->d_fe_total) + (e->last_iterations - 1);
+    *fe_dev = fe_total_of(e) + (e->last_iterations - 1);
     return RXHIP_OK;
 }
 
@@ -3441,7 +3414,7 @@ rxhip_status rxhip_copy_free_energy_to_device(rxhip_engine* e, double* dst_dev) 
     if (!e || !dst_dev) return RXHIP_ERR_BADARG;
     if (!e->ran || !e->last_want_fe) return fail(e, RXHIP_ERR_STATE, "free energy was not requested in the last run");
     SET_DEVICE(e);
-    HIPCHK(e, hipMemcpyAsync(dst_dev, (e->kind == 1 ? e->g.d_fe : e->kind == 2 ? e->h.d_fe_total : e->d_fe_total) + (e->last_iterations - 1), sizeof(double),
+    HIPCHK(e, hipMemcpyAsync(dst_dev, fe_total_of(e) + (e->last_iterations - 1), sizeof(double),
                              hipMemcpyDeviceToDevice, e->stream));
     return RXHIP_OK;
 }
@@ -3520,7 +3493,7 @@ rxhip_status rxhip_get_stream(rxhip_engine* e, void** stream) {
 rxhip_status rxhip_get_schedule(rxhip_engine* e, int32_t* segments, int64_t* segment_len) {
     TREE_GUARD(e);
     if (!e) return RXHIP_ERR_BADARG;
-    if (e->kind == 1) {
+    if (e->kind == EngineKind::Mixture) {
         if (segments) *segments = e->g.nblocks;
         if (segment_len) *segment_len = 256;
         return RXHIP_OK;
@@ -3536,7 +3509,7 @@ rxhip_status rxhip_get_marginals_chains(rxhip_engine* e, int32_t var_id, const i
     TREE_GUARD(e);
     TREE_GUARD(e);
     if (!e) return RXHIP_ERR_BADARG;
-    if (var_id != RXHIP_VAR_X || (e->kind != 0 && e->kind != 3 && e->kind != 4)) return fail(e, RXHIP_ERR_BADARG, "get_marginals_chains: variable %d is not random", var_id);
+    if (var_id != RXHIP_VAR_X || !family_of(e).has_x) return fail(e, RXHIP_ERR_BADARG, "get_marginals_chains: variable %d is not random", var_id);
     if (!e->ran) return fail(e, RXHIP_ERR_STATE, "get_marginals_chains: no run yet");
     if (!chains || n <= 0) return fail(e, RXHIP_ERR_BADARG, "get_marginals_chains: empty chain list");
     for (int64_t i = 0; i < n; ++i)

@@ -1,7 +1,13 @@
-// vmp_engines.hip — the mean-field engines of the pattern-matched families behind the C ABI: the uni- and multivariate Gaussian-mixture engines
-// (csrc/gmm_kernels.hpp, mvgmm_kernels.hpp; SURVEY §8 a9/a10: rxhip_gmm_* / rxhip_mvgmm_create) and the hierarchical Gaussian filter
-// (csrc/hgf_kernels.hpp; a11: rxhip_hgf_create, its run), and the probit chain's batched EP (csrc/probit_kernels.hpp: rxhip_probit_create, its run) and the hidden Markov model's forward–backward VMP (csrc/hmm_kernels.hpp: rxhip_hmm_create, its run) and the latent autoregressive model's banded structured VMP (csrc/lar_kernels.hpp: rxhip_lar_create, its run) and the binomial regression's Pólya-Gamma VMP (csrc/binreg_kernels.hpp: rxhip_binreg_create, its run).  The runtime they share with the state-space engines — streams, profiling events,
-// the engine handle — is rxhip.hip's (engine.hpp).  No kernels of the state-space path live here.
+// vmp_engines.hip — the engines of the pattern-matched families other than the state-space ones, behind the C ABI.  Per family: its creator, its
+// getters, its run and its row of the family table (engine.hpp EngineFamily), through which the entry points common to all engines reach it.
+//   mixture   uni- and multivariate Gaussian mixture (gmm_kernels.hpp, mvgmm_kernels.hpp, mvgmm_dense_kernels.hpp)
+//   HGF       hierarchical Gaussian filter (hgf_kernels.hpp; a11)
+//   probit    probit chain, batched EP (probit_kernels.hpp)
+//   HMM       hidden Markov model, forward–backward VMP (hmm_kernels.hpp)
+//   LAR       latent autoregressive model, banded structured VMP (lar_kernels.hpp)
+//   binreg    binomial regression, Pólya-Gamma VMP (binreg_kernels.hpp)
+// The runtime they share with the state-space engines — streams, profiling events, the engine handle, the creation and run helpers — is rxhip.hip's
+// (engine.hpp).  No kernels of the state-space path live here.
 #include "../../include/rxhip.h"
 
 #include <hip/hip_runtime.h>
@@ -25,10 +31,6 @@
 #include "engine.hpp"
 
 using namespace rxhip;
-
-namespace host {
-static bool chol_inv(int n, const double* A, double* out, double* logdet) { return rxhip::host_chol_inv(n, A, out, logdet); }
-}  // namespace host
 
 // ------------------------------------------------------------------------------------------
 // Gaussian-mixture VMP engine
@@ -116,6 +118,39 @@ struct GmmLaunch {
         default: GmmLaunch<16>::CALL; break;     \
     }
 
+// One stage of an iteration on the kernels of the engine's shape: the matrix-core ones (d > 4), the lane ones (d ≤ 4) or the univariate ones.
+// `flag`: the pass also writes the responsibilities / the update also evaluates the free energy.
+enum class GmmStage { Init, Pass, Reduce, Update };
+static void gmm_launch(rxhip_engine* e, GmmStage stage, bool flag = false) {
+    const int d = e->g.mvd, kt = e->g.KT;
+    hipStream_t s = e->stream;
+    if (d > 4) {
+        const MvgParams p = mvg_params(e);
+        switch (stage) {
+            case GmmStage::Init: MvdLaunch::init(p, d, s); break;
+            case GmmStage::Pass: MvdLaunch::pass(p, d, flag, s); break;
+            case GmmStage::Reduce: MvdLaunch::reduce(p, e->g.nq, s); break;
+            case GmmStage::Update: MvdLaunch::update(p, d, flag, s); break;
+        }
+    } else if (d) {
+        const MvgParams p = mvg_params(e);
+        switch (stage) {
+            case GmmStage::Init: MVG_DISPATCH(d, kt, init(p, s)); break;
+            case GmmStage::Pass: MVG_DISPATCH(d, kt, pass(p, flag, s)); break;
+            case GmmStage::Reduce: MVG_DISPATCH(d, kt, reduce(p, s)); break;
+            case GmmStage::Update: MVG_DISPATCH(d, kt, update(p, flag, s)); break;
+        }
+    } else {
+        const GmmParams p = gmm_params(e);
+        switch (stage) {
+            case GmmStage::Init: GMM_DISPATCH(kt, init(p, s)); break;
+            case GmmStage::Pass: GMM_DISPATCH(kt, pass(p, flag, s)); break;
+            case GmmStage::Reduce: GMM_DISPATCH(kt, reduce(p, s)); break;
+            case GmmStage::Update: GMM_DISPATCH(kt, update(p, flag, s)); break;
+        }
+    }
+}
+
 
 extern "C" {
 
@@ -134,7 +169,7 @@ rxhip_status rxhip_gmm_create(const rxhip_gmm_desc* ds, rxhip_engine** out) {
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return RXHIP_ERR_NO_DEVICE;
     rxhip_engine* e = new rxhip_engine();
     *out = e;
-    e->kind = 1;
+    e->kind = EngineKind::Mixture;
     e->g.N = ds->N;
     e->g.K = ds->K;
     e->g.KT = gmm_kt(ds->K);
@@ -142,17 +177,8 @@ rxhip_status rxhip_gmm_create(const rxhip_gmm_desc* ds, rxhip_engine** out) {
     e->n_chains = 1;
     e->T = ds->N;
     e->dy = 1;
-    if (ds->device >= 0) {
-        if (ds->device >= ndev) return fail(e, RXHIP_ERR_BADARG, "device %d out of range (%d visible)", ds->device, ndev);
-        e->device = ds->device;
-    } else
-        HIPCHK(e, hipGetDevice(&e->device));
-    SET_DEVICE(e);
-    if (ds->stream) e->stream = (hipStream_t)ds->stream;
-    else {
-        HIPCHK(e, stream_acquire(e->device, &e->stream));
-        e->own_stream = true;
-    }
+    DevGuard guard;
+    if (rxhip_status st = open_device(e, guard, ds->device, ds->stream, ndev)) return st;
     const int KT = e->g.KT, K = e->g.K;
     e->g.nq = 3 * KT + 1;
     e->g.hist_stride = 5 * K;
@@ -198,23 +224,14 @@ rxhip_status rxhip_mvgmm_create(const rxhip_mvgmm_desc* ds, rxhip_engine** out) 
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return RXHIP_ERR_NO_DEVICE;
     rxhip_engine* e = new rxhip_engine();
     *out = e;
-    e->kind = 1;
+    e->kind = EngineKind::Mixture;
     e->g.mvd = d;
     e->g.N = ds->N; e->g.K = K; e->g.KT = KT;
     e->g.materialize = ds->materialize_responsibilities ? 1 : 0;
     e->g.nq = KT * STAT + 1; e->g.hist_stride = K * SZ; e->g.state_size = K * SZ;
     e->n_chains = 1; e->T = ds->N; e->dy = d; e->d = d;
-    if (ds->device >= 0) {
-        if (ds->device >= ndev) return fail(e, RXHIP_ERR_BADARG, "device %d out of range (%d visible)", ds->device, ndev);
-        e->device = ds->device;
-    } else
-        HIPCHK(e, hipGetDevice(&e->device));
-    SET_DEVICE(e);
-    if (ds->stream) e->stream = (hipStream_t)ds->stream;
-    else {
-        HIPCHK(e, stream_acquire(e->device, &e->stream));
-        e->own_stream = true;
-    }
+    DevGuard guard;
+    if (rxhip_status st = open_device(e, guard, ds->device, ds->stream, ndev)) return st;
     long long nb = dense ? (e->g.N + MVD_TP - 1) / MVD_TP : (e->g.N + 255) / 256;
     const long long nb_cap = dense ? MVD_GRID_CAP : 1024;
     if (nb > nb_cap) nb = nb_cap;
@@ -225,9 +242,9 @@ rxhip_status rxhip_mvgmm_create(const rxhip_mvgmm_desc* ds, rxhip_engine** out) 
         double* pr = prior.data() + (size_t)k * PRI;
         double ldS = 0, ldV = 0;
         for (int a = 0; a < d; ++a) pr[a] = ds->mu0[k * d + a];
-        if (!host::chol_inv(d, ds->S0 + (size_t)k * dd, pr + d, &ldS)) return fail(e, RXHIP_ERR_NOT_POSDEF, "prior covariance of m[%d] is not positive definite", k);
+        if (!host_chol_inv(d, ds->S0 + (size_t)k * dd, pr + d, &ldS)) return fail(e, RXHIP_ERR_NOT_POSDEF, "prior covariance of m[%d] is not positive definite", k);
         pr[d + dd] = ds->nu0[k];
-        if (!host::chol_inv(d, ds->V0 + (size_t)k * dd, pr + d + dd + 1, &ldV)) return fail(e, RXHIP_ERR_NOT_POSDEF, "Wishart scale of w[%d] is not positive definite", k);
+        if (!host_chol_inv(d, ds->V0 + (size_t)k * dd, pr + d + dd + 1, &ldV)) return fail(e, RXHIP_ERR_NOT_POSDEF, "Wishart scale of w[%d] is not positive definite", k);
         pr[d + 2 * dd + 1] = ds->alpha0[k];
         pr[d + 2 * dd + 2] = ldS;
         pr[d + 2 * dd + 3] = ldV;
@@ -237,7 +254,7 @@ rxhip_status rxhip_mvgmm_create(const rxhip_mvgmm_desc* ds, rxhip_engine** out) 
         in[d + dd] = ds->init_w_nu[k];
         for (int q = 0; q < dd; ++q) in[d + dd + 1 + q] = ds->init_w_V[(size_t)k * dd + q];
         in[SZ - 1] = ds->init_s_alpha[k];
-        if (!host::chol_inv(d, in + d, tmp.data(), nullptr) || !host::chol_inv(d, in + d + dd + 1, tmp.data(), nullptr))
+        if (!host_chol_inv(d, in + d, tmp.data(), nullptr) || !host_chol_inv(d, in + d + dd + 1, tmp.data(), nullptr))
             return fail(e, RXHIP_ERR_NOT_POSDEF, "initial marginal of component %d is not positive definite", k);
     }
     HIPCHK(e, hipMalloc(&e->g.d_prior, sizeof(double) * prior.size()));
@@ -256,97 +273,54 @@ rxhip_status rxhip_mvgmm_create(const rxhip_mvgmm_desc* ds, rxhip_engine** out) 
 
 rxhip_status rxhip_gmm_begin_run(rxhip_engine* e, int32_t iterations) {
     TREE_GUARD(e);
-    if (!e || e->kind != 1) return RXHIP_ERR_BADARG;
-    if (iterations <= 0) return fail(e, RXHIP_ERR_BADARG, "run: iterations must be positive");
-    if (!e->have_data) return fail(e, RXHIP_ERR_STATE, "run: no observations (call rxhip_set_data first)");
+    if (!e || e->kind != EngineKind::Mixture) return RXHIP_ERR_BADARG;
+    if (rxhip_status st = run_preamble(e, iterations)) return st;
     SET_DEVICE(e);
-    if (iterations > e->g.hist_cap) {
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        if (e->g.d_hist) HIPCHK(e, hipFree(e->g.d_hist));
-        if (e->g.d_fe) HIPCHK(e, hipFree(e->g.d_fe));
-        e->g.d_hist = e->g.d_fe = nullptr;
-        HIPCHK(e, hipMalloc(&e->g.d_hist, sizeof(double) * (size_t)iterations * e->g.hist_stride));
-        HIPCHK(e, hipMalloc(&e->g.d_fe, sizeof(double) * iterations));
-        e->g.hist_cap = iterations;
-    }
+    if (rxhip_status st = reserve(e, &e->g.hist_cap, iterations, {{&e->g.d_hist, (size_t)e->g.hist_stride}, {&e->g.d_fe, 1}})) return st;
     HIPCHK(e, hipMemsetAsync(e->g.d_fe, 0, sizeof(double) * iterations, e->stream));
     HIPCHK(e, hipMemcpyAsync(e->g.d_par, e->g.d_init, sizeof(double) * e->g.state_size, hipMemcpyDeviceToDevice, e->stream));
     e->g.it = 0;
     e->g.iterations = iterations;
-    if (e->g.mvd > 4) {
-        MvdLaunch::init(mvg_params(e), e->g.mvd, e->stream);
-    } else if (e->g.mvd) {
-        MvgParams p = mvg_params(e);
-        MVG_DISPATCH(e->g.mvd, e->g.KT, init(p, e->stream));
-    } else {
-        GmmParams p = gmm_params(e);
-        GMM_DISPATCH(e->g.KT, init(p, e->stream));
-    }
+    gmm_launch(e, GmmStage::Init);
     HIPCHK(e, hipGetLastError());
     e->rule_calls = e->products = e->marginals = 0;
     return RXHIP_OK;
 }
 rxhip_status rxhip_gmm_accumulate(rxhip_engine* e) {
     TREE_GUARD(e);
-    if (!e || e->kind != 1) return RXHIP_ERR_BADARG;
+    if (!e || e->kind != EngineKind::Mixture) return RXHIP_ERR_BADARG;
     if (e->g.it >= e->g.iterations) return fail(e, RXHIP_ERR_STATE, "accumulate: no iteration left (call rxhip_gmm_begin_run)");
     SET_DEVICE(e);
     const bool resp = e->g.materialize && e->g.it == e->g.iterations - 1;
     rxhip_status st;
     if ((st = prof_begin(e, RXHIP_K_GMM_PASS))) return st;
-    if (e->g.mvd > 4) {
-        MvdLaunch::pass(mvg_params(e), e->g.mvd, resp, e->stream);
-    } else if (e->g.mvd) {
-        MvgParams p = mvg_params(e);
-        MVG_DISPATCH(e->g.mvd, e->g.KT, pass(p, resp, e->stream));
-    } else {
-        GmmParams p = gmm_params(e);
-        GMM_DISPATCH(e->g.KT, pass(p, resp, e->stream));
-    }
+    gmm_launch(e, GmmStage::Pass, resp);
     if ((st = prof_end(e))) return st;
     if ((st = prof_begin(e, RXHIP_K_GMM_REDUCE))) return st;
-    if (e->g.mvd > 4) {
-        MvdLaunch::reduce(mvg_params(e), e->g.nq, e->stream);
-    } else if (e->g.mvd) {
-        MvgParams p = mvg_params(e);
-        MVG_DISPATCH(e->g.mvd, e->g.KT, reduce(p, e->stream));
-    } else {
-        GmmParams p = gmm_params(e);
-        GMM_DISPATCH(e->g.KT, reduce(p, e->stream));
-    }
+    gmm_launch(e, GmmStage::Reduce);
     if ((st = prof_end(e))) return st;
     HIPCHK(e, hipGetLastError());
     return RXHIP_OK;
 }
 rxhip_status rxhip_gmm_statistics_device(rxhip_engine* e, double** stats_dev, int32_t* n) {
     TREE_GUARD(e);
-    if (!e || e->kind != 1) return RXHIP_ERR_BADARG;
+    if (!e || e->kind != EngineKind::Mixture) return RXHIP_ERR_BADARG;
     if (stats_dev) *stats_dev = e->g.d_totals;
     if (n) *n = e->g.nq;
     return RXHIP_OK;
 }
 rxhip_status rxhip_gmm_update(rxhip_engine* e, int32_t want_fe) {
     TREE_GUARD(e);
-    if (!e || e->kind != 1) return RXHIP_ERR_BADARG;
+    if (!e || e->kind != EngineKind::Mixture) return RXHIP_ERR_BADARG;
     if (e->g.it >= e->g.iterations) return fail(e, RXHIP_ERR_STATE, "update: no iteration left");
     SET_DEVICE(e);
     rxhip_status st;
     if ((st = prof_begin(e, RXHIP_K_GMM_UPDATE))) return st;
-    if (e->g.mvd > 4) {
-        MvdLaunch::update(mvg_params(e), e->g.mvd, want_fe != 0, e->stream);
-    } else if (e->g.mvd) {
-        MvgParams p = mvg_params(e);
-        MVG_DISPATCH(e->g.mvd, e->g.KT, update(p, want_fe != 0, e->stream));
-    } else {
-        GmmParams p = gmm_params(e);
-        GMM_DISPATCH(e->g.KT, update(p, want_fe != 0, e->stream));
-    }
+    gmm_launch(e, GmmStage::Update, want_fe != 0);
     if ((st = prof_end(e))) return st;
     HIPCHK(e, hipGetLastError());
     e->g.it++;
-    e->last_iterations = e->g.it;
-    e->last_want_fe = want_fe != 0;
-    e->ran = true;
+    finish_run(e, e->g.it, want_fe != 0);
     // reference-equivalent event counts per iteration (the oracle counts its own invocations the same way)
     const uint64_t N = (uint64_t)e->g.N, K = (uint64_t)e->g.K;
     e->rule_calls += N * (2 + 3 * K);
@@ -356,7 +330,7 @@ rxhip_status rxhip_gmm_update(rxhip_engine* e, int32_t want_fe) {
 }
 rxhip_status rxhip_gmm_get_history(rxhip_engine* e, double* hist) {
     TREE_GUARD(e);
-    if (!e || e->kind != 1 || !hist) return RXHIP_ERR_BADARG;
+    if (!e || e->kind != EngineKind::Mixture || !hist) return RXHIP_ERR_BADARG;
     if (!e->ran) return fail(e, RXHIP_ERR_STATE, "get_history: no run yet");
     SET_DEVICE(e);
     HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -365,7 +339,7 @@ rxhip_status rxhip_gmm_get_history(rxhip_engine* e, double* hist) {
 }
 rxhip_status rxhip_gmm_get_responsibilities(rxhip_engine* e, double* resp) {
     TREE_GUARD(e);
-    if (!e || e->kind != 1 || !resp) return RXHIP_ERR_BADARG;
+    if (!e || e->kind != EngineKind::Mixture || !resp) return RXHIP_ERR_BADARG;
     if (!e->g.materialize) return fail(e, RXHIP_ERR_STATE, "responsibilities were not materialised (desc.materialize_responsibilities)");
     if (!e->ran || e->g.it < e->g.iterations) return fail(e, RXHIP_ERR_STATE, "get_responsibilities: run not finished");
     SET_DEVICE(e);
@@ -404,6 +378,18 @@ static void gauss_hermite_host(int n, double* x, double* w) {
         w[n - 1 - i] = w[i];
     }
 }
+// … and their device table as the HGF and probit kernels read it: nodes [32] | weights / √π [32]
+static rxhip_status gauss_hermite_upload(rxhip_engine* e, int n_gh, double** d_gh) {
+    double gh[64] = {0}, gx[32], gw[32];
+    gauss_hermite_host(n_gh, gx, gw);
+    for (int i = 0; i < n_gh; ++i) {
+        gh[i] = gx[i];
+        gh[32 + i] = gw[i] / 1.7724538509055160273;
+    }
+    HIPCHK(e, hipMalloc(d_gh, sizeof(gh)));
+    HIPCHK(e, hipMemcpy(*d_gh, gh, sizeof(gh), hipMemcpyHostToDevice));
+    return RXHIP_OK;
+}
 
 // steps per partial sum of k_probit_energy: PROBIT_ECHUNK unless that would be more chunks than a grid dimension holds
 static long long probit_echunk(long long T) { return std::max<long long>(PROBIT_ECHUNK, (T + 32767) / 32768); }
@@ -421,7 +407,7 @@ rxhip_status rxhip_hgf_create(const rxhip_hgf_desc* ds, rxhip_engine** out) {
     if (nonfinite) {   // (a handle that carries the text, nothing else: the caller destroys it)
         rxhip_engine* e = new rxhip_engine();
         *out = e;
-        e->kind = 2;
+        e->kind = EngineKind::Hgf;
         e->device = -1;
         return fail(e, RXHIP_ERR_BADARG, "hgf: %s must be finite", nonfinite);
     }
@@ -429,31 +415,15 @@ rxhip_status rxhip_hgf_create(const rxhip_hgf_desc* ds, rxhip_engine** out) {
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return RXHIP_ERR_NO_DEVICE;
     rxhip_engine* e = new rxhip_engine();
     *out = e;
-    e->kind = 2;
+    e->kind = EngineKind::Hgf;
     e->h.ds = *ds;
     e->T = ds->T;
     e->n_chains = ds->n_series;
     e->dy = 1;
     e->d = 1;
-    if (ds->device >= 0) {
-        if (ds->device >= ndev) return fail(e, RXHIP_ERR_BADARG, "device %d out of range (%d visible)", ds->device, ndev);
-        e->device = ds->device;
-    } else
-        HIPCHK(e, hipGetDevice(&e->device));
-    SET_DEVICE(e);
-    if (ds->stream) e->stream = (hipStream_t)ds->stream;
-    else {
-        HIPCHK(e, stream_acquire(e->device, &e->stream));
-        e->own_stream = true;
-    }
-    double gh[64] = {0}, gx[32], gw[32];
-    gauss_hermite_host(ds->n_gh, gx, gw);
-    for (int i = 0; i < ds->n_gh; ++i) {
-        gh[i] = gx[i];
-        gh[32 + i] = gw[i] / 1.7724538509055160273;
-    }
-    HIPCHK(e, hipMalloc(&e->h.d_gh, sizeof(gh)));
-    HIPCHK(e, hipMemcpy(e->h.d_gh, gh, sizeof(gh), hipMemcpyHostToDevice));
+    DevGuard guard;
+    if (rxhip_status st = open_device(e, guard, ds->device, ds->stream, ndev)) return st;
+    if (rxhip_status st = gauss_hermite_upload(e, ds->n_gh, &e->h.d_gh)) return st;
     HIPCHK(e, hipMalloc(&e->h.d_out, sizeof(double) * 4 * (size_t)ds->T * ds->n_series));
     HIPCHK(e, hipMalloc(&e->d_fe_chain, sizeof(double) * (size_t)ds->n_series));
     HIPCHK(e, hipMalloc(&e->d_status, sizeof(int)));
@@ -467,7 +437,7 @@ rxhip_status rxhip_probit_create(const rxhip_probit_desc* ds, rxhip_engine** out
     if (!ds || ds->T <= 0 || ds->n_series <= 0) return RXHIP_ERR_BADARG;
     rxhip_engine* e = new rxhip_engine();   // from here on every refusal carries a text (rxhip_last_error; the caller destroys the handle)
     *out = e;
-    e->kind = 4;
+    e->kind = EngineKind::Probit;
     e->device = -1;
     if (!(ds->q > 0) || !std::isfinite(ds->q)) return fail(e, RXHIP_ERR_BADARG, "probit: the transition variance q must be positive and finite (got %g)", ds->q);
     if (!(ds->v0 > 0) || !std::isfinite(ds->v0)) return fail(e, RXHIP_ERR_BADARG, "probit: the prior variance v0 must be positive and finite (got %g)", ds->v0);
@@ -480,34 +450,17 @@ rxhip_status rxhip_probit_create(const rxhip_probit_desc* ds, rxhip_engine** out
     e->H = 1;   // x has T + 1 entries: the posterior arrays carry one row beyond the observations
     e->n_chains = ds->n_series;
     e->d = e->dy = e->dpad = 1;
-    if (ds->device >= 0) {
-        if (ds->device >= ndev) return fail(e, RXHIP_ERR_BADARG, "device %d out of range (%d visible)", ds->device, ndev);
-        e->device = ds->device;
-    } else
-        HIPCHK(e, hipGetDevice(&e->device));
-    SET_DEVICE(e);
-    if (ds->stream) e->stream = (hipStream_t)ds->stream;
-    else {
-        HIPCHK(e, stream_acquire(e->device, &e->stream));
-        e->own_stream = true;
-    }
-    double gh[64] = {0}, gx[32], gw[32];
-    gauss_hermite_host(ds->n_gh, gx, gw);
-    for (int i = 0; i < ds->n_gh; ++i) {
-        gh[i] = gx[i];
-        gh[32 + i] = gw[i] / 1.7724538509055160273;
-    }
+    DevGuard guard;
+    if (rxhip_status st = open_device(e, guard, ds->device, ds->stream, ndev)) return st;
     const size_t C = (size_t)ds->n_series, R = (size_t)ds->T + 1;
     const size_t chunks = (size_t)((ds->T + probit_echunk(ds->T) - 1) / probit_echunk(ds->T));
-    HIPCHK(e, hipMalloc(&e->pb.d_gh, sizeof(gh)));
-    HIPCHK(e, hipMemcpy(e->pb.d_gh, gh, sizeof(gh), hipMemcpyHostToDevice));
+    if (rxhip_status st = gauss_hermite_upload(e, ds->n_gh, &e->pb.d_gh)) return st;
     // sites ξ | w, forward messages pm | pv ([T+1][series] each), Gaussian free-energy part [series], Probit energies [chunks][series]
     HIPCHK(e, hipMalloc(&e->pb.d_block, sizeof(double) * (4 * R * C + C + chunks * C)));
     HIPCHK(e, hipMalloc(&e->d_mean, sizeof(double) * R * C));
     HIPCHK(e, hipMalloc(&e->d_cov, sizeof(double) * R * C));
     HIPCHK(e, hipMalloc(&e->d_fe_chain, sizeof(double) * C));
-    e->fe_total_cap = 16;
-    HIPCHK(e, hipMalloc(&e->d_fe_total, sizeof(double) * e->fe_total_cap));
+    if (rxhip_status st = reserve(e, &e->fe_total_cap, 16, {{&e->d_fe_total, 1}})) return st;
     HIPCHK(e, hipMalloc(&e->d_status, sizeof(int)));
     HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
     return RXHIP_OK;
@@ -544,7 +497,7 @@ rxhip_status rxhip_hmm_create(const rxhip_hmm_desc* ds, rxhip_engine** out) {
     if (!ds) return RXHIP_ERR_BADARG;
     rxhip_engine* e = new rxhip_engine();   // from here on every refusal carries a text (rxhip_last_error; the caller destroys the handle)
     *out = e;
-    e->kind = 6;
+    e->kind = EngineKind::Hmm;
     e->device = -1;
     if (ds->T < 1) return fail(e, RXHIP_ERR_BADARG, "hmm: T must be at least 1 (got %lld)", (long long)ds->T);
     if (ds->n_series < 1) return fail(e, RXHIP_ERR_BADARG, "hmm: n_series must be at least 1 (got %lld)", (long long)ds->n_series);
@@ -574,17 +527,8 @@ rxhip_status rxhip_hmm_create(const rxhip_hmm_desc* ds, rxhip_engine** out) {
     e->H = 1;   // s has T + 1 entries
     e->n_chains = ds->n_series;
     e->d = e->dy = e->dpad = 1;
-    if (ds->device >= 0) {
-        if (ds->device >= ndev) return fail(e, RXHIP_ERR_BADARG, "device %d out of range (%d visible)", ds->device, ndev);
-        e->device = ds->device;
-    } else
-        HIPCHK(e, hipGetDevice(&e->device));
-    SET_DEVICE(e);
-    if (ds->stream) e->stream = (hipStream_t)ds->stream;
-    else {
-        HIPCHK(e, stream_acquire(e->device, &e->stream));
-        e->own_stream = true;
-    }
+    DevGuard guard;
+    if (rxhip_status st = open_device(e, guard, ds->device, ds->stream, ndev)) return st;
     // host image of π | prior | init: one set per parameter set g, the K×K block of A and then the M×K block of B
     std::vector<double> host(16 + 2 * G * KM, 0.0);
     for (size_t i = 0; i < K; ++i) host[i] = ds->prior_s0[i];
@@ -603,15 +547,14 @@ rxhip_status rxhip_hmm_create(const rxhip_hmm_desc* ds, rxhip_engine** out) {
     HIPCHK(e, hipMalloc(&e->hm.d_alpha, sizeof(double) * R * C * K));
     HIPCHK(e, hipMalloc(&e->hm.d_gamma, sizeof(double) * R * C * K));
     HIPCHK(e, hipMalloc(&e->d_fe_chain, sizeof(double) * C));
-    e->fe_total_cap = 32;
-    HIPCHK(e, hipMalloc(&e->d_fe_total, sizeof(double) * e->fe_total_cap));
+    if (rxhip_status st = reserve(e, &e->fe_total_cap, 32, {{&e->d_fe_total, 1}})) return st;
     HIPCHK(e, hipMalloc(&e->d_status, sizeof(int)));
     HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
     return RXHIP_OK;
 }
 
 rxhip_status rxhip_hmm_get_states(rxhip_engine* e, double* probs, int32_t layout) {
-    if (!e || e->kind != 6) return RXHIP_ERR_BADARG;
+    if (!e || e->kind != EngineKind::Hmm) return RXHIP_ERR_BADARG;
     if (!probs) return fail(e, RXHIP_ERR_BADARG, "hmm_get_states: no output array");
     if (layout != RXHIP_LAYOUT_TIME_CHAIN && layout != RXHIP_LAYOUT_CHAIN_TIME) return fail(e, RXHIP_ERR_BADARG, "hmm_get_states: unknown layout %d", layout);
     if (!e->ran) return fail(e, RXHIP_ERR_STATE, "hmm_get_states: no run yet");
@@ -630,7 +573,7 @@ rxhip_status rxhip_hmm_get_states(rxhip_engine* e, double* probs, int32_t layout
 }
 
 rxhip_status rxhip_hmm_get_parameters(rxhip_engine* e, double* A_counts, double* B_counts) {
-    if (!e || e->kind != 6) return RXHIP_ERR_BADARG;
+    if (!e || e->kind != EngineKind::Hmm) return RXHIP_ERR_BADARG;
     if (!e->ran) return fail(e, RXHIP_ERR_STATE, "hmm_get_parameters: no run yet");
     SET_DEVICE(e);
     const size_t C = (size_t)e->n_chains, K = (size_t)e->hm.K, M = (size_t)e->hm.M, KM = (K + M) * K, G = e->hm.shared ? 1 : C;
@@ -666,7 +609,7 @@ static LarParams lar_params(const rxhip_engine* e) {
 }
 
 // a symmetric positive definite p×p matrix (symmetric within 1e-12 of its largest entry, Cholesky succeeds): its symmetrised copy, inverse and ln det
-static bool lar_spd(int p, const double* a, std::vector<double>& sym, std::vector<double>& inv, double* logdet) {
+static bool spd_inverse(int p, const double* a, std::vector<double>& sym, std::vector<double>& inv, double* logdet) {
     double big = 0.0;
     for (int i = 0; i < p * p; ++i) {
         if (!std::isfinite(a[i])) return false;
@@ -679,7 +622,7 @@ static bool lar_spd(int p, const double* a, std::vector<double>& sym, std::vecto
             if (std::fabs(a[i * p + j] - a[j * p + i]) > 1e-12 * big) return false;
             sym[(size_t)(i * p + j)] = 0.5 * (a[i * p + j] + a[j * p + i]);
         }
-    return rxhip::host_chol_inv(p, sym.data(), inv.data(), logdet);
+    return host_chol_inv(p, sym.data(), inv.data(), logdet);
 }
 
 extern "C" {
@@ -690,7 +633,7 @@ rxhip_status rxhip_lar_create(const rxhip_lar_desc* ds, rxhip_engine** out) {
     if (!ds) return RXHIP_ERR_BADARG;
     rxhip_engine* e = new rxhip_engine();   // from here on every refusal carries a text (rxhip_last_error; the caller destroys the handle)
     *out = e;
-    e->kind = 7;
+    e->kind = EngineKind::Lar;
     e->device = -1;
     if (ds->order < 1 || ds->order > lar::kMaxP) return fail(e, RXHIP_ERR_BADARG, "lar: order must be 1 … %d (got %d)", lar::kMaxP, ds->order);
     if (ds->T < 1) return fail(e, RXHIP_ERR_BADARG, "lar: T must be at least 1 (got %lld)", (long long)ds->T);
@@ -715,11 +658,11 @@ rxhip_status rxhip_lar_create(const rxhip_lar_desc* ds, rxhip_engine** out) {
     if (ds->init_theta_mean && !finite(ds->init_theta_mean, P)) return fail(e, RXHIP_ERR_BADARG, "lar: init_theta_mean must be finite");
     std::vector<double> wth0, vth0, w0, v0, vinit, winit;
     double ld_wth0 = 0.0, ld_w0 = 0.0, ld = 0.0;
-    if (!lar_spd(P, ds->prior_theta_precision, wth0, vth0, &ld_wth0))
+    if (!spd_inverse(P, ds->prior_theta_precision, wth0, vth0, &ld_wth0))
         return fail(e, RXHIP_ERR_BADARG, "lar: prior_theta_precision is not symmetric positive definite");
-    if (!lar_spd(P, ds->prior_x0_precision, w0, v0, &ld_w0)) return fail(e, RXHIP_ERR_BADARG, "lar: prior_x0_precision is not symmetric positive definite");
+    if (!spd_inverse(P, ds->prior_x0_precision, w0, v0, &ld_w0)) return fail(e, RXHIP_ERR_BADARG, "lar: prior_x0_precision is not symmetric positive definite");
     if (ds->init_theta_cov) {
-        if (!lar_spd(P, ds->init_theta_cov, vinit, winit, &ld)) return fail(e, RXHIP_ERR_BADARG, "lar: init_theta_cov is not symmetric positive definite");
+        if (!spd_inverse(P, ds->init_theta_cov, vinit, winit, &ld)) return fail(e, RXHIP_ERR_BADARG, "lar: init_theta_cov is not symmetric positive definite");
     } else
         vinit = vth0;   // the prior's own covariance
     int ndev = 0;
@@ -728,17 +671,8 @@ rxhip_status rxhip_lar_create(const rxhip_lar_desc* ds, rxhip_engine** out) {
     e->T = ds->T;
     e->n_chains = ds->n_series;
     e->d = e->dy = e->dpad = 1;
-    if (ds->device >= 0) {
-        if (ds->device >= ndev) return fail(e, RXHIP_ERR_BADARG, "device %d out of range (%d visible)", ds->device, ndev);
-        e->device = ds->device;
-    } else
-        HIPCHK(e, hipGetDevice(&e->device));
-    SET_DEVICE(e);
-    if (ds->stream) e->stream = (hipStream_t)ds->stream;
-    else {
-        HIPCHK(e, stream_acquire(e->device, &e->stream));
-        e->own_stream = true;
-    }
+    DevGuard guard;
+    if (rxhip_status st = open_device(e, guard, ds->device, ds->stream, ndev)) return st;
     // host images: the constants (lar::consts) and the initial q
     std::vector<double> cst((size_t)lar::nconst(P), 0.0), init((size_t)lar::nq(P), 0.0);
     {
@@ -773,15 +707,14 @@ rxhip_status rxhip_lar_create(const rxhip_lar_desc* ds, rxhip_engine** out) {
     HIPCHK(e, hipMalloc(&e->la.d_rec, sizeof(double) * n * (size_t)(P + 2) * C));
     HIPCHK(e, hipMalloc(&e->la.d_out, sizeof(double) * n * (size_t)(P + 2) * C));   // m [n][series] | band [n][P + 1][series]
     HIPCHK(e, hipMalloc(&e->d_fe_chain, sizeof(double) * C));
-    e->fe_total_cap = 32;
-    HIPCHK(e, hipMalloc(&e->d_fe_total, sizeof(double) * e->fe_total_cap));
+    if (rxhip_status st = reserve(e, &e->fe_total_cap, 32, {{&e->d_fe_total, 1}})) return st;
     HIPCHK(e, hipMalloc(&e->d_status, sizeof(int)));
     HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
     return RXHIP_OK;
 }
 
 rxhip_status rxhip_lar_get_states(rxhip_engine* e, double* mean, double* cov, int32_t layout) {
-    if (!e || e->kind != 7) return RXHIP_ERR_BADARG;
+    if (!e || e->kind != EngineKind::Lar) return RXHIP_ERR_BADARG;
     if (layout != RXHIP_LAYOUT_TIME_CHAIN && layout != RXHIP_LAYOUT_CHAIN_TIME) return fail(e, RXHIP_ERR_BADARG, "lar_get_states: unknown layout %d", layout);
     if (!e->ran) return fail(e, RXHIP_ERR_STATE, "lar_get_states: no run yet");
     SET_DEVICE(e);
@@ -808,7 +741,7 @@ rxhip_status rxhip_lar_get_states(rxhip_engine* e, double* mean, double* cov, in
 }
 
 rxhip_status rxhip_lar_get_parameters(rxhip_engine* e, double* theta_mean, double* theta_cov, double* gamma_shape, double* gamma_rate) {
-    if (!e || e->kind != 7) return RXHIP_ERR_BADARG;
+    if (!e || e->kind != EngineKind::Lar) return RXHIP_ERR_BADARG;
     if (!e->ran) return fail(e, RXHIP_ERR_STATE, "lar_get_parameters: no run yet");
     SET_DEVICE(e);
     const size_t C = (size_t)e->n_chains, P = (size_t)e->la.P, G = e->la.shared ? 1 : C, NQ = (size_t)lar::nq((int)P), rows = (size_t)e->last_iterations * G;
@@ -827,22 +760,11 @@ rxhip_status rxhip_lar_get_parameters(rxhip_engine* e, double* theta_mean, doubl
 
 }  // extern "C"
 
-// every observation of a latent autoregressive engine is finite or NaN: checked on the device copy, whichever way it arrived
-rxhip_status rxhip::lar_check_data(rxhip_engine* e) {
-    SET_DEVICE(e);
-    const long long n = e->T * e->n_chains;
-    const unsigned nb = (unsigned)std::min<long long>((n + 255) / 256, 1024);
-    hipLaunchKernelGGL(k_lar_check_y, dim3(nb), dim3(256), 0, e->stream, (const double*)e->d_y, n, e->d_status);
-    HIPCHK(e, hipGetLastError());
-    int st = 0;
-    HIPCHK(e, hipMemcpyAsync(&st, e->d_status, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (st & ST_LAR_BAD_Y) {
-        HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
-        e->have_data = false;
-        return fail(e, RXHIP_ERR_BADARG, "set_data: an observation is infinite (finite values and NaN = missing are accepted)");
-    }
-    return RXHIP_OK;
+// every observation of a latent autoregressive engine is finite or NaN
+static rxhip_status lar_check_data(rxhip_engine* e) {
+    return check_observations(e, [](rxhip_engine* e, long long n, unsigned nb) {
+        hipLaunchKernelGGL(k_lar_check_y, dim3(nb), dim3(256), 0, e->stream, (const double*)e->d_y, n, e->d_status);
+    }, ST_LAR_BAD_Y, "set_data: an observation is infinite (finite values and NaN = missing are accepted)");
 }
 
 template <int P>
@@ -852,34 +774,14 @@ static void lar_launch_sweep(const LarParams& p, bool out, hipStream_t stream) {
     else hipLaunchKernelGGL((k_lar_sweep<P, false>), dim3(grid), dim3(64), 0, stream, p);
 }
 
-rxhip_status rxhip::lar_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
-    if (iterations <= 0) return fail(e, RXHIP_ERR_BADARG, "run: iterations must be positive");
-    if (!e->have_data) return fail(e, RXHIP_ERR_STATE, "run: no observations (call rxhip_set_data first)");
+static rxhip_status lar_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
+    if (rxhip_status st = run_preamble(e, iterations)) return st;
     SET_DEVICE(e);
     const size_t C = (size_t)e->n_chains, G = e->la.shared ? 1 : C;
-    if (iterations > e->fe_total_cap) {
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        HIPCHK(e, hipFree(e->d_fe_total));
-        e->d_fe_total = nullptr;
-        e->fe_total_cap = iterations;
-        HIPCHK(e, hipMalloc(&e->d_fe_total, sizeof(double) * e->fe_total_cap));
-    }
-    if (want_fe && iterations > e->la.fe_cap) {
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        if (e->la.d_fe_series) HIPCHK(e, hipFree(e->la.d_fe_series));
-        e->la.d_fe_series = nullptr;
-        e->la.fe_cap = 0;
-        HIPCHK(e, hipMalloc(&e->la.d_fe_series, sizeof(double) * (size_t)iterations * C));
-        e->la.fe_cap = iterations;
-    }
-    if (iterations > e->la.hist_cap) {   // the parameter history: every iteration of the run
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        if (e->la.d_hist) HIPCHK(e, hipFree(e->la.d_hist));
-        e->la.d_hist = nullptr;
-        e->la.hist_cap = 0;
-        HIPCHK(e, hipMalloc(&e->la.d_hist, sizeof(double) * (size_t)iterations * G * (size_t)lar::nq(e->la.P)));
-        e->la.hist_cap = iterations;
-    }
+    rxhip_status rs = reserve(e, &e->fe_total_cap, iterations, {{&e->d_fe_total, 1}});
+    if (!rs && want_fe) rs = reserve(e, &e->la.fe_cap, iterations, {{&e->la.d_fe_series, C}});
+    if (!rs) rs = reserve(e, &e->la.hist_cap, iterations, {{&e->la.d_hist, G * (size_t)lar::nq(e->la.P)}});   // the parameter history: every iteration of the run
+    if (rs) return rs;
     LarParams p = lar_params(e);
     p.want_fe = want_fe ? 1 : 0;
     const unsigned ggrid = (unsigned)((G + 255) / 256), sgrid = (unsigned)((C + 255) / 256);
@@ -907,10 +809,7 @@ rxhip_status rxhip::lar_run_async(rxhip_engine* e, int32_t iterations, int32_t w
     if (want_fe)
         HIPCHK(e, hipMemcpyAsync(e->d_fe_chain, e->la.d_fe_series + (size_t)(iterations - 1) * C, sizeof(double) * C, hipMemcpyDeviceToDevice, e->stream));
     HIPCHK(e, hipGetLastError());
-    e->last_iterations = iterations;
-    e->last_want_fe = want_fe != 0;
-    e->ran = true;
-    e->last_filter = false;
+    finish_run(e, iterations, want_fe != 0);
     // reference-equivalent events per series and iteration: per step the AR node's messages toward x[t], x[t-1], θ and γ and the observation
     // message; products and marginals at the T + 1 states and the two parameters
     const uint64_t Cs = (uint64_t)C, T = (uint64_t)e->T, I = (uint64_t)iterations;
@@ -946,7 +845,7 @@ rxhip_status rxhip_binreg_create(const rxhip_binreg_desc* ds, rxhip_engine** out
     if (!ds) return RXHIP_ERR_BADARG;
     rxhip_engine* e = new rxhip_engine();   // from here on every refusal carries a text (rxhip_last_error; the caller destroys the handle)
     *out = e;
-    e->kind = 8;
+    e->kind = EngineKind::Binreg;
     e->device = -1;
     if (ds->d < 1 || ds->d > breg::kMaxD) return fail(e, RXHIP_ERR_BADARG, "binreg: d must be 1 … %d (got %d)", breg::kMaxD, ds->d);
     if (ds->N < 1) return fail(e, RXHIP_ERR_BADARG, "binreg: N must be at least 1 (got %lld)", (long long)ds->N);
@@ -959,9 +858,9 @@ rxhip_status rxhip_binreg_create(const rxhip_binreg_desc* ds, rxhip_engine** out
     }
     std::vector<double> w0, v0, vinit, winit;
     double ld_w0 = 0.0, ld = 0.0;
-    if (!lar_spd(d, ds->prior_precision, w0, v0, &ld_w0)) return fail(e, RXHIP_ERR_BADARG, "binreg: prior_precision is not symmetric positive definite");
+    if (!spd_inverse(d, ds->prior_precision, w0, v0, &ld_w0)) return fail(e, RXHIP_ERR_BADARG, "binreg: prior_precision is not symmetric positive definite");
     if (ds->init_cov) {
-        if (!lar_spd(d, ds->init_cov, vinit, winit, &ld)) return fail(e, RXHIP_ERR_BADARG, "binreg: init_cov is not symmetric positive definite");
+        if (!spd_inverse(d, ds->init_cov, vinit, winit, &ld)) return fail(e, RXHIP_ERR_BADARG, "binreg: init_cov is not symmetric positive definite");
     } else
         vinit = v0;   // the prior's own covariance
     int ndev = 0;
@@ -970,17 +869,8 @@ rxhip_status rxhip_binreg_create(const rxhip_binreg_desc* ds, rxhip_engine** out
     e->T = ds->N;
     e->n_chains = ds->n_problems;
     e->d = e->dy = e->dpad = 1;
-    if (ds->device >= 0) {
-        if (ds->device >= ndev) return fail(e, RXHIP_ERR_BADARG, "device %d out of range (%d visible)", ds->device, ndev);
-        e->device = ds->device;
-    } else
-        HIPCHK(e, hipGetDevice(&e->device));
-    SET_DEVICE(e);
-    if (ds->stream) e->stream = (hipStream_t)ds->stream;
-    else {
-        HIPCHK(e, stream_acquire(e->device, &e->stream));
-        e->own_stream = true;
-    }
+    DevGuard guard;
+    if (rxhip_status st = open_device(e, guard, ds->device, ds->stream, ndev)) return st;
     // constants: ξ0 | W0 | m0 = W0⁻¹ξ0 | ln det W0 | initial m | initial V
     std::vector<double> cst((size_t)breg::nconst(d), 0.0);
     {
@@ -1009,15 +899,14 @@ rxhip_status rxhip_binreg_create(const rxhip_binreg_desc* ds, rxhip_engine** out
     HIPCHK(e, hipMalloc(&e->br.d_part, sizeof(double) * C * (size_t)e->br.nchunk * (size_t)breg::npart(d)));
     HIPCHK(e, hipMalloc(&e->br.d_xi_part, sizeof(double) * C * (size_t)e->br.nchunk_xi * 32));
     HIPCHK(e, hipMalloc(&e->d_fe_chain, sizeof(double) * C));
-    e->fe_total_cap = 32;
-    HIPCHK(e, hipMalloc(&e->d_fe_total, sizeof(double) * e->fe_total_cap));
+    if (rxhip_status st = reserve(e, &e->fe_total_cap, 32, {{&e->d_fe_total, 1}})) return st;
     HIPCHK(e, hipMalloc(&e->d_status, sizeof(int)));
     HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
     return RXHIP_OK;
 }
 
 rxhip_status rxhip_binreg_get_parameters(rxhip_engine* e, double* mean, double* cov, double* free_energy) {
-    if (!e || e->kind != 8) return RXHIP_ERR_BADARG;
+    if (!e || e->kind != EngineKind::Binreg) return RXHIP_ERR_BADARG;
     if (!e->ran) return fail(e, RXHIP_ERR_STATE, "binreg_get_parameters: no run yet");
     if (free_energy && !e->last_want_fe) return fail(e, RXHIP_ERR_STATE, "binreg_get_parameters: free energy was not requested in the last run");
     SET_DEVICE(e);
@@ -1034,7 +923,7 @@ rxhip_status rxhip_binreg_get_parameters(rxhip_engine* e, double* mean, double* 
 
 // X, y and n_trials of a binomial regression engine, checked on the host before anything reaches the device: ±Inf anywhere (NaN too, except in y,
 // where it means missing), n_i < 0, an observed y_i outside 0 … n_i.  A refused array counts as not set.
-rxhip_status rxhip::binreg_set_data(rxhip_engine* e, int32_t var_id, const double* host, size_t n) {
+static rxhip_status binreg_set_data(rxhip_engine* e, int32_t var_id, const double* host, size_t n) {
     const size_t C = (size_t)e->n_chains, N = (size_t)e->T, d = (size_t)e->br.d;
     auto& b = e->br;
     if (var_id != RXHIP_VAR_Y && var_id != RXHIP_VAR_REGRESSORS && var_id != RXHIP_VAR_TRIALS)
@@ -1101,8 +990,8 @@ static rxhip_status breg_prepare(rxhip_engine* e) {
     return RXHIP_OK;
 }
 
-rxhip_status rxhip::binreg_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
-    if (iterations <= 0) return fail(e, RXHIP_ERR_BADARG, "run: iterations must be positive");
+static rxhip_status binreg_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
+    if (rxhip_status st = run_preamble(e, iterations, false)) return st;   // (its three arrays, not have_data: below)
     auto& b = e->br;
     if (!b.have_X || !b.have_y || !b.have_n)
         return fail(e, RXHIP_ERR_STATE, "run: the binomial regression engine needs RXHIP_VAR_REGRESSORS, RXHIP_VAR_Y and RXHIP_VAR_TRIALS (missing:%s%s%s)",
@@ -1112,23 +1001,10 @@ rxhip_status rxhip::binreg_run_async(rxhip_engine* e, int32_t iterations, int32_
     if (C > 65535) return fail(e, RXHIP_ERR_BADARG, "binreg: at most 65535 problems per engine (got %zu)", C);
     if (!b.ready)
         if (rxhip_status st = breg_prepare(e)) return st;
-    if (iterations > e->fe_total_cap) {
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        HIPCHK(e, hipFree(e->d_fe_total));
-        e->d_fe_total = nullptr;
-        e->fe_total_cap = iterations;
-        HIPCHK(e, hipMalloc(&e->d_fe_total, sizeof(double) * e->fe_total_cap));
-    }
-    if (iterations > b.hist_cap) {   // the parameter history and the per-problem free energies: every iteration of the run
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        if (b.d_hist) HIPCHK(e, hipFree(b.d_hist));
-        if (b.d_fe_prob) HIPCHK(e, hipFree(b.d_fe_prob));
-        b.d_hist = b.d_fe_prob = nullptr;
-        b.hist_cap = 0;
-        HIPCHK(e, hipMalloc(&b.d_hist, sizeof(double) * (size_t)iterations * C * (d + d * d)));
-        HIPCHK(e, hipMalloc(&b.d_fe_prob, sizeof(double) * (size_t)iterations * C));
-        b.hist_cap = iterations;
-    }
+    rxhip_status rs = reserve(e, &e->fe_total_cap, iterations, {{&e->d_fe_total, 1}});
+    // the parameter history and the per-problem free energies: every iteration of the run
+    if (!rs) rs = reserve(e, &b.hist_cap, iterations, {{&b.d_hist, C * (d + d * d)}, {&b.d_fe_prob, C}});
+    if (rs) return rs;
     BregParams p = breg_params(e);
     p.want_fe = want_fe ? 1 : 0;
     const dim3 pgrid((unsigned)p.nchunk, (unsigned)C);
@@ -1149,10 +1025,7 @@ rxhip_status rxhip::binreg_run_async(rxhip_engine* e, int32_t iterations, int32_
     if (want_fe)
         HIPCHK(e, hipMemcpyAsync(e->d_fe_chain, b.d_fe_prob + (size_t)(iterations - 1) * C, sizeof(double) * C, hipMemcpyDeviceToDevice, e->stream));
     HIPCHK(e, hipGetLastError());
-    e->last_iterations = iterations;
-    e->last_want_fe = want_fe != 0;
-    e->ran = true;
-    e->last_filter = false;
+    finish_run(e, iterations, want_fe != 0);
     // reference-equivalent events per problem and iteration: per point the BinomialPolya node's message toward β and its ω marginal; the prior's
     // message; products of the N + 1 messages at β
     const uint64_t Cs = (uint64_t)C, N = (uint64_t)e->T, I = (uint64_t)iterations;
@@ -1162,22 +1035,13 @@ rxhip_status rxhip::binreg_run_async(rxhip_engine* e, int32_t iterations, int32_
     return RXHIP_OK;
 }
 
-// every observation of a hidden Markov model engine is an integer code 0 … M−1 or NaN: checked on the device copy, whichever way it arrived
-rxhip_status rxhip::hmm_check_data(rxhip_engine* e) {
-    SET_DEVICE(e);
-    const long long n = e->T * e->n_chains;
-    const unsigned nb = (unsigned)std::min<long long>((n + 255) / 256, 1024);
-    hipLaunchKernelGGL(k_hmm_check_x, dim3(nb), dim3(256), 0, e->stream, (const double*)e->d_y, n, e->hm.M, e->d_status);
-    HIPCHK(e, hipGetLastError());
-    int st = 0;
-    HIPCHK(e, hipMemcpyAsync(&st, e->d_status, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (st & ST_HMM_BAD_X) {
-        HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
-        e->have_data = false;
-        return fail(e, RXHIP_ERR_BADARG, "set_data: an observation is neither an integer symbol code 0 … %d nor NaN (missing)", e->hm.M - 1);
-    }
-    return RXHIP_OK;
+// every observation of a hidden Markov model engine is an integer code 0 … M−1 or NaN
+static rxhip_status hmm_check_data(rxhip_engine* e) {
+    char msg[128];
+    snprintf(msg, sizeof msg, "set_data: an observation is neither an integer symbol code 0 … %d nor NaN (missing)", e->hm.M - 1);
+    return check_observations(e, [](rxhip_engine* e, long long n, unsigned nb) {
+        hipLaunchKernelGGL(k_hmm_check_x, dim3(nb), dim3(256), 0, e->stream, (const double*)e->d_y, n, e->hm.M, e->d_status);
+    }, ST_HMM_BAD_X, msg);
 }
 
 template <int R>
@@ -1188,26 +1052,13 @@ static void hmm_launch_sweep(const HmmParams& p, bool out, hipStream_t stream) {
     else hipLaunchKernelGGL((k_hmm_sweep<R, false>), dim3(grid), dim3(64), lds, stream, p);
 }
 
-rxhip_status rxhip::hmm_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
-    if (iterations <= 0) return fail(e, RXHIP_ERR_BADARG, "run: iterations must be positive");
-    if (!e->have_data) return fail(e, RXHIP_ERR_STATE, "run: no observations (call rxhip_set_data first)");
+static rxhip_status hmm_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
+    if (rxhip_status st = run_preamble(e, iterations)) return st;
     SET_DEVICE(e);
     const size_t C = (size_t)e->n_chains;
-    if (iterations > e->fe_total_cap) {
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        HIPCHK(e, hipFree(e->d_fe_total));
-        e->d_fe_total = nullptr;
-        e->fe_total_cap = iterations;
-        HIPCHK(e, hipMalloc(&e->d_fe_total, sizeof(double) * e->fe_total_cap));
-    }
-    if (want_fe && iterations > e->hm.fe_cap) {
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        if (e->hm.d_fe_series) HIPCHK(e, hipFree(e->hm.d_fe_series));
-        e->hm.d_fe_series = nullptr;
-        e->hm.fe_cap = 0;
-        HIPCHK(e, hipMalloc(&e->hm.d_fe_series, sizeof(double) * (size_t)iterations * C));
-        e->hm.fe_cap = iterations;
-    }
+    rxhip_status rs = reserve(e, &e->fe_total_cap, iterations, {{&e->d_fe_total, 1}});
+    if (!rs && want_fe) rs = reserve(e, &e->hm.fe_cap, iterations, {{&e->hm.d_fe_series, C}});
+    if (rs) return rs;
     const HmmParams p = hmm_params(e);
     const int K = p.K, KM = (K + p.M) * K;
     const long long G = p.shared ? 1 : p.n_series;
@@ -1231,10 +1082,7 @@ rxhip_status rxhip::hmm_run_async(rxhip_engine* e, int32_t iterations, int32_t w
     if (want_fe)
         HIPCHK(e, hipMemcpyAsync(e->d_fe_chain, e->hm.d_fe_series + (size_t)(iterations - 1) * C, sizeof(double) * C, hipMemcpyDeviceToDevice, e->stream));
     HIPCHK(e, hipGetLastError());
-    e->last_iterations = iterations;
-    e->last_want_fe = want_fe != 0;
-    e->ran = true;
-    e->last_filter = false;
+    finish_run(e, iterations, want_fe != 0);
     // reference-equivalent events per series and iteration: a forward and a backward transition message and an observation message per step, the
     // messages toward A and B; products and marginals at the T + 1 states and the two matrices
     const uint64_t Cs = (uint64_t)C, T = (uint64_t)e->T, I = (uint64_t)iterations;
@@ -1244,44 +1092,20 @@ rxhip_status rxhip::hmm_run_async(rxhip_engine* e, int32_t iterations, int32_t w
     return RXHIP_OK;
 }
 
-// every observation of a probit engine is 0, 1 or NaN: checked on the device copy, whichever way it arrived
-rxhip_status rxhip::probit_check_data(rxhip_engine* e) {
-    SET_DEVICE(e);
-    const long long n = e->T * e->n_chains;
-    const unsigned nb = (unsigned)std::min<long long>((n + 255) / 256, 1024);
-    hipLaunchKernelGGL(k_probit_check_y, dim3(nb), dim3(256), 0, e->stream, (const double*)e->d_y, n, e->d_status);
-    HIPCHK(e, hipGetLastError());
-    int st = 0;
-    HIPCHK(e, hipMemcpyAsync(&st, e->d_status, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (st & ST_PROBIT_BAD_Y) {
-        HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
-        e->have_data = false;
-        return fail(e, RXHIP_ERR_BADARG, "set_data: a Probit observation is neither 0, 1 nor NaN (missing)");
-    }
-    return RXHIP_OK;
+// every observation of a probit engine is 0, 1 or NaN
+static rxhip_status probit_check_data(rxhip_engine* e) {
+    return check_observations(e, [](rxhip_engine* e, long long n, unsigned nb) {
+        hipLaunchKernelGGL(k_probit_check_y, dim3(nb), dim3(256), 0, e->stream, (const double*)e->d_y, n, e->d_status);
+    }, ST_PROBIT_BAD_Y, "set_data: a Probit observation is neither 0, 1 nor NaN (missing)");
 }
 
-rxhip_status rxhip::probit_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
-    if (iterations <= 0) return fail(e, RXHIP_ERR_BADARG, "run: iterations must be positive");
-    if (!e->have_data) return fail(e, RXHIP_ERR_STATE, "run: no observations (call rxhip_set_data first)");
+static rxhip_status probit_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
+    if (rxhip_status st = run_preamble(e, iterations)) return st;
     SET_DEVICE(e);
     const size_t C = (size_t)e->n_chains, R = (size_t)e->T + 1;
-    if (iterations > e->fe_total_cap) {
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        HIPCHK(e, hipFree(e->d_fe_total));
-        e->d_fe_total = nullptr;
-        e->fe_total_cap = iterations;
-        HIPCHK(e, hipMalloc(&e->d_fe_total, sizeof(double) * e->fe_total_cap));
-    }
-    if (want_fe && iterations > e->pb.fe_cap) {
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        if (e->pb.d_fe_series) HIPCHK(e, hipFree(e->pb.d_fe_series));
-        e->pb.d_fe_series = nullptr;
-        e->pb.fe_cap = 0;
-        HIPCHK(e, hipMalloc(&e->pb.d_fe_series, sizeof(double) * (size_t)iterations * C));
-        e->pb.fe_cap = iterations;
-    }
+    rxhip_status rs = reserve(e, &e->fe_total_cap, iterations, {{&e->d_fe_total, 1}});
+    if (!rs && want_fe) rs = reserve(e, &e->pb.fe_cap, iterations, {{&e->pb.d_fe_series, C}});
+    if (rs) return rs;
     const rxhip_probit_desc& d = e->pb.ds;
     ProbitParams p;
     p.T = e->T; p.n_series = e->n_chains; p.y = e->d_y;
@@ -1296,7 +1120,7 @@ rxhip_status rxhip::probit_run_async(rxhip_engine* e, int32_t iterations, int32_
     rxhip_status st;
     // sweep i = 0 … iterations − 1 performs update i + 1 and (i ≥ 1) sees the marginals of iteration i; the last sweep only reads
     for (int i = 0; i <= iterations; ++i) {
-        const bool update = i < iterations, last = i == iterations, fe = want_fe && i >= 1;
+        const bool update = i < iterations, fe = want_fe && i >= 1;
         if ((st = prof_begin(e, RXHIP_K_PROBIT_SWEEP))) return st;
         if (update && !fe) hipLaunchKernelGGL((k_probit_sweep<true, false, false>), grid, dim3(64), 0, e->stream, p);
         else if (update) hipLaunchKernelGGL((k_probit_sweep<true, true, true>), grid, dim3(64), 0, e->stream, p);
@@ -1307,15 +1131,11 @@ rxhip_status rxhip::probit_run_async(rxhip_engine* e, int32_t iterations, int32_
             hipLaunchKernelGGL(k_probit_energy, egrid, dim3(256), 0, e->stream, p);
             hipLaunchKernelGGL(k_probit_fe, dim3(1), dim3(256), 0, e->stream, p, i - 1, chunks, e->d_fe_total);
         }
-        (void)last;
     }
     if (want_fe)
         HIPCHK(e, hipMemcpyAsync(e->d_fe_chain, e->pb.d_fe_series + (size_t)(iterations - 1) * C, sizeof(double) * C, hipMemcpyDeviceToDevice, e->stream));
     HIPCHK(e, hipGetLastError());
-    e->last_iterations = iterations;
-    e->last_want_fe = want_fe != 0;
-    e->ran = true;
-    e->last_filter = false;
+    finish_run(e, iterations, want_fe != 0);
     // reference-equivalent events per series and iteration: a forward and a backward transition message per step, a Probit(:in) message per
     // observed step (counted as every step: the mask lives on the device); products and marginals at the T + 1 states
     const uint64_t Cs = (uint64_t)C, T = (uint64_t)e->T, I = (uint64_t)iterations;
@@ -1325,20 +1145,11 @@ rxhip_status rxhip::probit_run_async(rxhip_engine* e, int32_t iterations, int32_
     return RXHIP_OK;
 }
 
-rxhip_status rxhip::hgf_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
-    if (iterations <= 0) return fail(e, RXHIP_ERR_BADARG, "run: iterations must be positive");
-    if (!e->have_data) return fail(e, RXHIP_ERR_STATE, "run: no observations (call rxhip_set_data first)");
+static rxhip_status hgf_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
+    if (rxhip_status st = run_preamble(e, iterations)) return st;
     SET_DEVICE(e);
     const size_t C = (size_t)e->n_chains, T = (size_t)e->T;
-    if (iterations > e->h.fe_cap) {
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        if (e->h.d_fe_series) HIPCHK(e, hipFree(e->h.d_fe_series));
-        if (e->h.d_fe_total) HIPCHK(e, hipFree(e->h.d_fe_total));
-        e->h.d_fe_series = e->h.d_fe_total = nullptr;
-        HIPCHK(e, hipMalloc(&e->h.d_fe_series, sizeof(double) * (size_t)iterations * C));
-        HIPCHK(e, hipMalloc(&e->h.d_fe_total, sizeof(double) * iterations));
-        e->h.fe_cap = iterations;
-    }
+    if (rxhip_status st = reserve(e, &e->h.fe_cap, iterations, {{&e->h.d_fe_series, C}, {&e->h.d_fe_total, 1}})) return st;
     HIPCHK(e, hipMemsetAsync(e->h.d_fe_series, 0, sizeof(double) * (size_t)iterations * C, e->stream));
     HgfParams p;
     p.T = e->T; p.n_series = e->n_chains; p.y = e->d_y;
@@ -1360,12 +1171,54 @@ rxhip_status rxhip::hgf_run_async(rxhip_engine* e, int32_t iterations, int32_t w
                                  hipMemcpyDeviceToDevice, e->stream));
     }
     HIPCHK(e, hipGetLastError());
-    e->last_iterations = iterations;
-    e->last_want_fe = want_fe != 0;
-    e->ran = true;
+    finish_run(e, iterations, want_fe != 0);
     e->rule_calls = (uint64_t)C * T * (4 + 2 * (uint64_t)iterations);
     e->products = (uint64_t)C * T * 2 * (uint64_t)iterations;
     e->marginals = (uint64_t)C * T * 3 * (uint64_t)iterations;
     return RXHIP_OK;
 }
 
+// the mixture engines' run: the split-phase entry points (several GPUs all-reduce the statistics between accumulate and update) back to back
+static rxhip_status mixture_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
+    rxhip_status st = rxhip_gmm_begin_run(e, iterations);
+    for (int it = 0; !st && it < iterations; ++it) {
+        st = rxhip_gmm_accumulate(e);
+        if (!st) st = rxhip_gmm_update(e, want_fe);
+    }
+    return st;
+}
+
+// The rows of the family table (engine.hpp EngineFamily; rxhip.hip's family_of looks here for the kinds it does not own).
+const EngineFamily* rxhip::vmp_family(EngineKind kind) {
+    using E = rxhip_engine;
+    const char* const host_only = "set_data_device: the binomial regression engine checks its data on the host (rxhip_set_data)";
+    //                            run                filter check              set_data         no_device_data  fe_total, has_x, release
+    static const EngineFamily mixture = {mixture_run_async, false, nullptr, nullptr, nullptr, [](const E* e) { return e->g.d_fe; }, false, [](E* e) {
+        free_buffers(e, {&e->g.d_resp, &e->g.d_par, &e->g.d_drv, &e->g.d_prior, &e->g.d_init, &e->g.d_partial, &e->g.d_totals, &e->g.d_hist, &e->g.d_fe});
+    }};
+    static const EngineFamily hgf = {hgf_run_async, false, nullptr, nullptr, nullptr, [](const E* e) { return e->h.d_fe_total; }, false, [](E* e) {
+        free_buffers(e, {&e->h.d_out, &e->h.d_fe_series, &e->h.d_gh, &e->h.d_fe_total});
+    }};
+    static const EngineFamily probit = {probit_run_async, false, probit_check_data, nullptr, nullptr, nullptr, true, [](E* e) {
+        free_buffers(e, {&e->pb.d_block, &e->pb.d_gh, &e->pb.d_fe_series});
+    }};
+    static const EngineFamily hmm = {hmm_run_async, false, hmm_check_data, nullptr, nullptr, nullptr, false, [](E* e) {
+        free_buffers(e, {&e->hm.d_par, &e->hm.d_alpha, &e->hm.d_gamma, &e->hm.d_fe_series});
+    }};
+    static const EngineFamily lar = {lar_run_async, false, lar_check_data, nullptr, nullptr, nullptr, false, [](E* e) {
+        free_buffers(e, {&e->la.d_cst, &e->la.d_par, &e->la.d_hist, &e->la.d_rec, &e->la.d_out, &e->la.d_fe_series});
+    }};
+    static const EngineFamily binreg = {binreg_run_async, false, nullptr, binreg_set_data, host_only, nullptr, false, [](E* e) {
+        free_buffers(e, {&e->br.d_X, &e->br.d_neff, &e->br.d_kappa, &e->br.d_cst, &e->br.d_xi, &e->br.d_lc, &e->br.d_S, &e->br.d_part, &e->br.d_xi_part,
+                         &e->br.d_hist, &e->br.d_fe_prob});
+    }};
+    switch (kind) {
+        case EngineKind::Mixture: return &mixture;
+        case EngineKind::Hgf: return &hgf;
+        case EngineKind::Probit: return &probit;
+        case EngineKind::Hmm: return &hmm;
+        case EngineKind::Lar: return &lar;
+        case EngineKind::Binreg: return &binreg;
+        default: return nullptr;
+    }
+}
