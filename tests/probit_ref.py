@@ -6,8 +6,13 @@ test/models/statespace/probit_tests.jl:11-18), numpy + scipy, one series at a ti
 Two forms of the same parallel-EP iteration.  `run_messages` is written with forward / backward messages, the way the kernels are
 (but with the site update in the literal textbook form, not the kernels' rearranged one).  `run_dense` builds the tridiagonal precision
 of the chain plus diag(w), inverts it, and reads every marginal, pair marginal and cavity from the inverse: nothing is shared between
-the two but the tilted moments and the Gauss–Hermite rule.  tests/test_probit_ref_cpu.py holds the first to the second and both to the
-reference's golden free energy."""
+the two but the tilted moments, the Gauss–Hermite rule and the closed form of a transition's free-energy term (_bethe), which each feeds
+from its own pair precision.  tests/test_probit_ref_cpu.py holds the first to the second and both to the reference's golden free energy.
+
+Pinned range.  tests/test_probit_contract_cpu.py holds `run_messages` — means, variances and the free energy of every iteration — to the
+60-digit restatement tests/probit_mp.py at every point of probit_mp.GRID (a ∈ {0, −0.9, 0.5, 1, 1.05}, q from 1e-8 to 1e3, v0 from 1e-4 to 1e6,
+m0 from −8 to +40), at 100× inside the engine's contract.  Outside that range it is not pinned.  `run_dense` is the independent second form
+at ordinary parameters only (its Schur complements subtract numbers of size 1/q): it is not held at small q."""
 import numpy as np
 from scipy.special import erfcx, log_ndtr, ndtr
 
@@ -67,16 +72,23 @@ def entropy(var):
     return 0.5 * (LOG2PI + 1.0 + np.log(var))
 
 
-def _bethe(mean, var, pair_cov, y, a, c, q, m0, v0, gh):
-    """Bethe free energy of a Gaussian q: mean / var of x[0 … T], pair_cov[k] = cov(x[k], x[k+1])."""
+def _bethe(mean, var, pairs, y, a, c, q, m0, v0, gh):
+    """Bethe free energy of a Gaussian q: mean / var of x[0 … T] and, per transition (k-1, k), pairs[k-1] = (fp, fξ, lξ, lw): the pair marginal
+    of (x[k-1], x[k]) has precision [[fp + a²/q, −a/q], [−a/q, 1/q + lw]] and weighted mean (fξ − a c/q, lξ + c/q) — (fp, fξ) is what x[k-1] hears
+    from everything but this transition, (lξ, lw) what x[k] does.  The residual x[k] − a x[k-1] − c and the pair entropy are read from that
+    precision: with D = q·det = fp (1 + q lw) + a² lw the vector (−a, 1) times the inverse precision is (−a lw, fp) / det, so
+        E[res] = q (fp (lξ − c lw) − a lw fξ) / D,   var[res] = q (fp + a² lw) / D,   H = log 2πe − ½ log(D / q),
+    sums of products of one sign in the variance and the determinant.  (From covariances — var[k-1] var[k] − cov² and var[k] − 2a cov +
+    a² var[k-1] — both cancel when the pair is nearly singular: NaN at q = 1e-8, v0 = 100.)"""
     T = len(y)
     obs = ~np.isnan(y)
     fe = 0.5 * (LOG2PI + np.log(v0)) + 0.5 * ((mean[0] - m0) ** 2 + var[0]) / v0 - entropy(var[0])      # prior node
     for k in range(1, T + 1):                                                                           # transitions
-        res = mean[k] - a * mean[k - 1] - c
-        e2 = res * res + var[k] - 2.0 * a * pair_cov[k - 1] + a * a * var[k - 1]
-        det = var[k - 1] * var[k] - pair_cov[k - 1] ** 2
-        fe += 0.5 * (LOG2PI + np.log(q)) + 0.5 * e2 / q - (LOG2PI + 1.0 + 0.5 * np.log(det))
+        fp, fxi, lxi, lw = pairs[k - 1]
+        D = fp * (1.0 + q * lw) + a * a * lw
+        res = q * (fp * (lxi - c * lw) - a * lw * fxi) / D
+        e2 = res * res + q * (fp + a * a * lw) / D
+        fe += 0.5 * (LOG2PI + np.log(q)) + 0.5 * e2 / q - (LOG2PI + 1.0 - 0.5 * (np.log(D) - np.log(q)))
     for k in range(1, T + 1):                                                                           # probit nodes
         if obs[k - 1]:
             fe += probit_energy(mean[k], var[k], y[k - 1], gh) - entropy(var[k])
@@ -101,7 +113,7 @@ def run_messages(y, a, c, q, m0, v0, iterations, n_gh=32):
             fp = 1.0 / pv[k - 1] + w[k - 1]
             fm = (pm[k - 1] / pv[k - 1] + xi[k - 1]) / fp
             pm[k], pv[k] = a * fm + c, a * a / fp + q
-        mean, var, pc = np.zeros(T + 1), np.zeros(T + 1), np.zeros(T)
+        mean, var, pairs = np.zeros(T + 1), np.zeros(T + 1), [None] * T
         bxi, bw = 0.0, 0.0                          # backward message at x[k]
         nxi, nw = xi.copy(), w.copy()
         for k in range(T, -1, -1):
@@ -113,12 +125,10 @@ def run_messages(y, a, c, q, m0, v0, iterations, n_gh=32):
                 nxi[k], nw[k] = site_update(cm, 1.0 / cp, y[k - 1])
             if k >= 1:
                 lxi, lw = bxi + xi[k], bw + w[k]    # everything x[k] hears from its observation and the future: the OLD site
-                fp = 1.0 / pv[k - 1] + w[k - 1]     # filtered belief of x[k-1]
-                # pair marginal of (x[k-1], x[k]): precision [[fp + a²/q, −a/q], [−a/q, 1/q + lw]]
-                det = (fp + a * a / q) * (1.0 / q + lw) - (a / q) ** 2
-                pc[k - 1] = (a / q) / det
+                # filtered belief of x[k-1] (precision, weighted mean) and what x[k] hears: the pair marginal of (x[k-1], x[k]), see _bethe
+                pairs[k - 1] = (1.0 / pv[k - 1] + w[k - 1], pm[k - 1] / pv[k - 1] + xi[k - 1], lxi, lw)
                 bxi, bw = a * (lxi - c * lw) / (1.0 + q * lw), a * a * lw / (1.0 + q * lw)
-        return mean, var, pc, nxi, nw
+        return mean, var, pairs, nxi, nw
 
     for it in range(iterations):
         mean, var, pc, nxi, nw = sweep(True)
@@ -128,6 +138,27 @@ def run_messages(y, a, c, q, m0, v0, iterations, n_gh=32):
     mean, var, pc, _, _ = sweep(False)
     fes.append(_bethe(mean, var, pc, y, a, c, q, m0, v0, gh))
     return mean, var, np.array(fes)
+
+
+def _dense_pairs(L, h, xi, w, a, c, q, m0, v0):
+    """_bethe's pair input from the dense precision L and weighted mean h: the states before x[k-1] and after x[k] are integrated out by
+    Schur complements (dense inverses of the two blocks), and the transition's own entries are never added, so nothing of size a²/q is
+    subtracted back out."""
+    n = len(h)
+    pairs = []
+    for k in range(1, n):
+        fp, fxi = (1.0 / v0, m0 / v0) if k == 1 else (1.0 / q + w[k - 1], c / q + xi[k - 1])
+        if k >= 2:      # the past x[0 … k-2], coupled to x[k-1] by −a/q
+            P = np.linalg.inv(L[:k - 1, :k - 1])
+            fp -= (a / q) ** 2 * P[-1, -1]
+            fxi += (a / q) * (P @ h[:k - 1])[-1]
+        lxi, lw = xi[k], w[k]
+        if k < n - 1:   # the future x[k+1 … T], coupled to x[k] by −a/q; the outgoing transition puts a²/q, −a c/q on x[k]
+            F = np.linalg.inv(L[k + 1:, k + 1:])
+            lw += (a * a / q) * (1.0 - F[0, 0] / q)
+            lxi += -a * c / q + (a / q) * (F @ h[k + 1:])[0]
+        pairs.append((fp, fxi, lxi, lw))
+    return pairs
 
 
 def run_dense(y, a, c, q, m0, v0, iterations, n_gh=32):
@@ -154,7 +185,7 @@ def run_dense(y, a, c, q, m0, v0, iterations, n_gh=32):
         mu = S @ (h0 + xi)
         var = np.diag(S).copy()
         if it > 0:
-            fes.append(_bethe(mu, var, np.diag(S, 1).copy(), y, a, c, q, m0, v0, gh))
+            fes.append(_bethe(mu, var, _dense_pairs(L0 + np.diag(w), h0 + xi, xi, w, a, c, q, m0, v0), y, a, c, q, m0, v0, gh))
         if it == iterations:
             return mu, var, np.array(fes)
         nxi, nw = xi.copy(), w.copy()
@@ -175,3 +206,18 @@ def run_batch(y, a, c, q, m0, v0, iterations, n_gh=32, run=run_messages):
     for s in range(C):
         mean[:, s], var[:, s], fe[:, s] = run(y[:, s], a, c, q, m0, v0, iterations, n_gh)
     return mean, var, fe
+
+
+def contract_series(T, seed=7):
+    """The six series of the contract grid, y [T][6]: all 1; all 0; alternating; random with 15 % missing and the first and last steps
+    missing; a single observed step; nothing observed (its free energy is exactly 0)."""
+    rng = np.random.default_rng(seed)
+    y = np.full((T, 6), np.nan)
+    y[:, 0] = 1.0
+    y[:, 1] = 0.0
+    y[:, 2] = np.arange(T) % 2
+    y[:, 3] = np.where(rng.random(T) < 0.15, np.nan, (rng.random(T) < 0.5).astype(np.float64))
+    y[0, 3] = y[-1, 3] = np.nan
+    y[T // 3, 4] = 1.0
+    y.setflags(write=False)
+    return y
