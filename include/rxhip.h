@@ -1016,6 +1016,66 @@ rxhip_status rxhip_binreg_get_parameters(rxhip_engine* e, double* mean, double* 
 void rxhip_binreg_schedule(int64_t N, int32_t d, int32_t* tile_points, int32_t* chunks);
 
 /* ------------------------------------------------------------------------------------------
+ * Bayesian linear regression with unknown coefficients and noise precision, and the autoregression with observed regressors that it is when the
+ * regressors are the lags of the series itself (reference model test/models/autoregressive/ar_tests.jl:17-46; the workload the reference
+ * benchmarks as "models" "ar", :72), for each of n_series independent problems with d = 1 … 32 regressors:
+ *     γ ~ Gamma(shape = a0, rate = b0);   θ ~ MvNormal(mean = m0, precision = Λ0);   y[i] ~ Normal(mean = dot(x[i], θ), precision = γ)
+ *     q(γ, θ) = q(γ) q(θ)          (MeanField is the same factorisation: there are only two variables)
+ * The data enter only through the statistics G = Σ x xᵀ, h = Σ y x, s = Σ y² and n, computed ONCE per data set by one streaming pass and kept: a
+ * second rxhip_run on the same data launches only the iterations.  Two data modes, fixed at creation by `lagged`:
+ *   lagged = 0 (regressors): rxhip_set_data with RXHIP_VAR_REGRESSORS (X, [series][N][d]) and RXHIP_VAR_Y (y, [series][N]) in either order, host
+ *     arrays (the layout argument is not read; rxhip_set_data_device: RXHIP_ERR_BADARG).  A NaN y_i drops the row; NaN or ±Inf in X and ±Inf in y
+ *     are refused.
+ *   lagged = 1: only RXHIP_VAR_Y, the raw series z of T values per series ([T][series] or [series][T] by layout), from the host or through
+ *     rxhip_set_data_device; d is the order p.  Row t, t = p … T−1, has y = z_t and x = (z_{t−1}, …, z_{t−p}), most recent first (ar_ssm_data,
+ *     ar_tests.jl:7-15); no regressor matrix is formed on the host or on the device.  A NaN z_t drops every row it appears in, as output or as
+ *     regressor; ±Inf is refused (RXHIP_ERR_BADARG).  T ≤ p, or every row dropped, is legal: n = 0, the posterior is the prior and F = 0.
+ * A refused array counts as not set, and a run without its data is RXHIP_ERR_STATE.
+ * Every run starts from q(γ) = Gamma(init_gamma_shape, init_gamma_rate), NULL = the prior's values; ḡ = a/b.
+ * One ITERATION (rxhip_run's argument) is a defined semantic of this engine (csrc/arreg_kernels.hpp):
+ *   1. q(θ):  Λ = Λ0 + ḡ G,  V = Λ⁻¹,  m = V(Λ0 m0 + ḡ h);
+ *   2. q(γ):  a = a0 + n/2,  b = b0 + R/2,  R = s − 2 mᵀh + tr((V + m mᵀ) G), with the new θ;  ḡ = a/b.
+ * The posterior of iteration i is q(θ), q(γ) after step 2; its free energy is the exact variational free energy there,
+ *     F = −[n/2 (ψ(a) − ln b − ln 2π) − ½ (a/b) R] + KL(N(m, V) ‖ N(m0, Λ0⁻¹)) + KL(Gamma(a, b) ‖ Gamma(a0, b0)).
+ * Both steps are exact coordinate minimisers, so F does not rise.  The values per iteration belong to this engine; the reference asserts lengths
+ * and decrease only (ar_tests.jl:61-65).
+ * share_parameters = 1: the statistics are added over the series in ascending order and there is one q(θ), q(γ) (G = 1 below).
+ * Numerical envelope: R is formed from s, h and G, so its relative error is about ε·s/R: data whose residual is below 1e-8 of their energy (a
+ * large common offset on y with tiny noise) are outside the contract.
+ * Handle protocol: the data as above, rxhip_run(e, iterations, want_free_energy) — the whole run is ONE launch after the pass —,
+ * rxhip_arreg_get_parameters, rxhip_arreg_get_statistics, rxhip_get_free_energy (per iteration, summed over the groups),
+ * rxhip_get_free_energy_per_chain (last iteration per series; with shared parameters entry 0 holds F and the others 0), rxhip_counters,
+ * rxhip_destroy; rxhip_run_filter and RXHIP_VAR_X marginals are refused.  Results are bit-identical from run to run, with and without the free
+ * energy, and for a series alone or inside a batch (no floating-point atomics, fixed summation order).
+ * RXHIP_ERR_BADARG with a text, before any device call: d outside 1 … 32, N < 1, n_series < 1, a shape or rate that is not positive and finite, a
+ * prior mean that is not finite, a precision that is not symmetric (within 1e-12 of its largest entry) positive definite (host Cholesky).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    int64_t N;                                                    /* rows per series (regressors) or T, the length of a series (lagged) */
+    int64_t n_series;
+    int32_t d;                                                    /* regressors, or the order p: 1 … 32 */
+    int32_t lagged;                                               /* 0: X and y; 1: the raw series only */
+    const double *prior_theta_mean, *prior_theta_precision;       /* m0 [d], Λ0 [d][d] */
+    double prior_gamma_shape, prior_gamma_rate;
+    const double *init_gamma_shape, *init_gamma_rate;             /* one double each or NULL = the prior's */
+    int32_t share_parameters;
+    int32_t device;
+    void* stream;
+} rxhip_arreg_desc;
+rxhip_status rxhip_arreg_create(const rxhip_arreg_desc* desc, rxhip_engine** out);
+/* q(θ), q(γ) and F after EVERY iteration of the last run: theta_mean [iterations][G][d], theta_cov [iterations][G][d][d], gamma_shape, gamma_rate,
+ * free_energy [iterations][G], G = n_series (1 with shared parameters); any pointer may be NULL (free_energy: RXHIP_ERR_STATE if the run was
+ * without it) */
+rxhip_status rxhip_arreg_get_parameters(rxhip_engine* e, double* theta_mean, double* theta_cov, double* gamma_shape, double* gamma_rate, double* free_energy);
+/* the statistics of the data in place, per series (the pass alone; it is run if it has not been): G [series][d][d], h [series][d], s and n [series];
+ * any pointer may be NULL; RXHIP_ERR_STATE without data */
+rxhip_status rxhip_arreg_get_statistics(rxhip_engine* e, double* G, double* h, double* s, double* n);
+/* the pass's schedule for n_rows rows (N in regressor mode, max(T − p, 0) in lagged mode) of d regressors: rows per tile and workgroups (chunks)
+ * per series — a function of n_rows and d only; a workgroup strides over ceil(tiles / chunks) tiles at most.  Zeros for arguments outside the
+ * engine's range. */
+void rxhip_arreg_schedule(int64_t n_rows, int32_t d, int32_t* tile_rows, int32_t* chunks);
+
+/* ------------------------------------------------------------------------------------------
  * Several GPUs (one process per GPU; chains / series / points shard).  The path's only exchange is the sum
  * over shards of the Bethe free energy (reference: the single `sumreduce` of src/model/plugins/reactivemp_free_energy.jl:99-123
  * over ALL nodes and variables of the model) and, for the mixture, of the responsibility-weighted statistics that

@@ -85,6 +85,10 @@ enum class EngineKind : int {
     Hmm = 6,      // hidden Markov model, batched forward–backward VMP (hmm_kernels.hpp)
     Lar = 7,      // latent autoregressive model, batched banded structured VMP (lar_kernels.hpp)
     Binreg = 8,   // binomial regression, batched Pólya-Gamma VMP (binreg_kernels.hpp)
+    Arreg = 9,    // regression / autoregression with unknown coefficients and noise precision, batched Normal-Gamma VMP from the statistics
+                  // (arreg_kernels.hpp), regressor mode: X and y through the family's own set_data, host arrays only
+    ArregLagged = 10,   // … lagged mode: the raw series through the common ingest, host or device (the same run, release and getters; the two rows
+                        // differ in how the data arrive, which is what a row of the family table says)
 };
 struct rxhip_engine : rxhip_engine_life {
     // one device allocation holds every buffer of a state-space engine (creation / destruction cost two driver calls
@@ -150,6 +154,12 @@ struct rxhip_engine : rxhip_engine_life {
         bool have_X = false, have_y = false, have_n = false, ready = false;
         std::vector<double> h_y, h_n;
     } br;
+    struct Arreg {    // kinds 9 and 10: X and y (regressor mode; lagged mode reads d_y), constants, the pass's partials (kept: the statistics of the data in place), history, free energies
+        int d = 0, lagged = 0, shared = 0, nchunk = 0, hist_cap = 0;
+        long long rows = 0;   // rows per series as the pass counts them
+        double *d_X = nullptr, *d_yreg = nullptr, *d_cst = nullptr, *d_part = nullptr, *d_hist = nullptr, *d_fe = nullptr;
+        bool have_X = false, have_y = false, stats_ready = false;
+    } ar;
     struct Gmm {
         long long N = 0;
         int K = 0, KT = 0, materialize = 0, nblocks = 0, it = 0, iterations = 0, hist_cap = 0;

@@ -6,6 +6,8 @@
 //   HMM       hidden Markov model, forward–backward VMP (hmm_kernels.hpp)
 //   LAR       latent autoregressive model, banded structured VMP (lar_kernels.hpp)
 //   binreg    binomial regression, Pólya-Gamma VMP (binreg_kernels.hpp)
+//   arreg     regression / autoregression with unknown coefficients and noise precision, Normal-Gamma VMP from the statistics (arreg_kernels.hpp): two
+//             rows, X and y from the host or the raw series through the common ingest
 // The runtime they share with the state-space engines — streams, profiling events, the engine handle, the creation and run helpers — is rxhip.hip's
 // (engine.hpp).  No kernels of the state-space path live here.
 #include "../../include/rxhip.h"
@@ -28,6 +30,7 @@
 #include "hmm_kernels.hpp"
 #include "lar_kernels.hpp"
 #include "binreg_kernels.hpp"
+#include "arreg_kernels.hpp"
 #include "engine.hpp"
 
 using namespace rxhip;
@@ -1035,6 +1038,236 @@ static rxhip_status binreg_run_async(rxhip_engine* e, int32_t iterations, int32_
     return RXHIP_OK;
 }
 
+// ---- regression / autoregression with unknown coefficients and noise precision (arreg_kernels.hpp) ----
+static bool is_arreg(const rxhip_engine* e) { return e->kind == EngineKind::Arreg || e->kind == EngineKind::ArregLagged; }
+
+static ArregParams arreg_params(const rxhip_engine* e) {
+    const auto& a = e->ar;
+    ArregParams p;
+    p.N = a.rows; p.T = e->T; p.C = e->n_chains;
+    p.d = a.d; p.nchunk = a.nchunk; p.shared = a.shared; p.want_fe = 0; p.iterations = 0;
+    p.X = a.d_X; p.y = a.lagged ? e->d_y : a.d_yreg;
+    p.cst = a.d_cst; p.part = a.d_part; p.hist = a.d_hist; p.fe = a.d_fe; p.fe_total = e->d_fe_total; p.fe_chain = e->d_fe_chain;
+    p.status = e->d_status;
+    return p;
+}
+
+extern "C" {
+
+void rxhip_arreg_schedule(int64_t n_rows, int32_t d, int32_t* tile_rows, int32_t* chunks) {
+    const bool ok = n_rows >= 0 && d >= 1 && d <= arreg::kMaxD;
+    if (tile_rows) *tile_rows = ok ? arreg::tile_rows(d) : 0;
+    if (chunks) *chunks = ok ? arreg::chunks(n_rows, d) : 0;
+}
+
+rxhip_status rxhip_arreg_create(const rxhip_arreg_desc* ds, rxhip_engine** out) {
+    if (!out) return RXHIP_ERR_BADARG;
+    *out = nullptr;
+    if (!ds) return RXHIP_ERR_BADARG;
+    rxhip_engine* e = new rxhip_engine();   // from here on every refusal carries a text (rxhip_last_error; the caller destroys the handle)
+    *out = e;
+    e->kind = ds->lagged ? EngineKind::ArregLagged : EngineKind::Arreg;
+    e->device = -1;
+    if (ds->d < 1 || ds->d > arreg::kMaxD) return fail(e, RXHIP_ERR_BADARG, "arreg: d must be 1 … %d (got %d)", arreg::kMaxD, ds->d);
+    if (ds->N < 1) return fail(e, RXHIP_ERR_BADARG, "arreg: N must be at least 1 (got %lld)", (long long)ds->N);
+    if (ds->n_series < 1) return fail(e, RXHIP_ERR_BADARG, "arreg: n_series must be at least 1 (got %lld)", (long long)ds->n_series);
+    if (ds->n_series > 65535) return fail(e, RXHIP_ERR_BADARG, "arreg: at most 65535 series per engine (got %lld)", (long long)ds->n_series);
+    auto positive = [](double v) { return v > 0.0 && std::isfinite(v); };
+    if (!positive(ds->prior_gamma_shape) || !positive(ds->prior_gamma_rate))
+        return fail(e, RXHIP_ERR_BADARG, "arreg: prior_gamma shape and rate must be positive and finite (got %g, %g)", ds->prior_gamma_shape, ds->prior_gamma_rate);
+    const double ia = ds->init_gamma_shape ? *ds->init_gamma_shape : ds->prior_gamma_shape, ib = ds->init_gamma_rate ? *ds->init_gamma_rate : ds->prior_gamma_rate;
+    if (!positive(ia) || !positive(ib)) return fail(e, RXHIP_ERR_BADARG, "arreg: init_gamma shape and rate must be positive and finite (got %g, %g)", ia, ib);
+    if (!ds->prior_theta_mean || !ds->prior_theta_precision) return fail(e, RXHIP_ERR_BADARG, "arreg: prior_theta_mean and prior_theta_precision are required");
+    const int d = ds->d;
+    for (int i = 0; i < d; ++i)
+        if (!std::isfinite(ds->prior_theta_mean[i])) return fail(e, RXHIP_ERR_BADARG, "arreg: prior_theta_mean must be finite");
+    std::vector<double> l0, v0;
+    double ld_l0 = 0.0;
+    if (!spd_inverse(d, ds->prior_theta_precision, l0, v0, &ld_l0)) return fail(e, RXHIP_ERR_BADARG, "arreg: prior_theta_precision is not symmetric positive definite");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(e, RXHIP_ERR_NO_DEVICE, "no HIP device visible");
+    auto& a = e->ar;
+    a.d = d; a.lagged = ds->lagged ? 1 : 0; a.shared = ds->share_parameters ? 1 : 0;
+    a.rows = a.lagged ? arreg::lag_rows(ds->N, d) : ds->N;
+    a.nchunk = arreg::chunks(a.rows, d);
+    e->T = ds->N;
+    e->n_chains = ds->n_series;
+    e->d = e->dy = e->dpad = 1;
+    DevGuard guard;
+    if (rxhip_status st = open_device(e, guard, ds->device, ds->stream, ndev)) return st;
+    // constants: Λ0 | m0 | Λ0 m0 | a0, b0, initial a, initial b, ln det Λ0, lnΓ(a0), ln b0
+    std::vector<double> cst((size_t)arreg::nconst(d), 0.0);
+    {
+        double *L0 = cst.data(), *m0 = L0 + d * d, *wm0 = m0 + d, *sc = wm0 + d;
+        for (int i = 0; i < d * d; ++i) L0[i] = l0[(size_t)i];
+        for (int i = 0; i < d; ++i) m0[i] = ds->prior_theta_mean[i];
+        for (int i = 0; i < d; ++i) {
+            double s = 0.0;
+            for (int j = 0; j < d; ++j) s += L0[i * d + j] * m0[j];
+            wm0[i] = s;
+        }
+        sc[0] = ds->prior_gamma_shape; sc[1] = ds->prior_gamma_rate; sc[2] = ia; sc[3] = ib; sc[4] = ld_l0;
+        sc[5] = std::lgamma(ds->prior_gamma_shape); sc[6] = std::log(ds->prior_gamma_rate);
+    }
+    const size_t C = (size_t)ds->n_series, N = (size_t)ds->N;
+    HIPCHK(e, hipMalloc(&a.d_cst, sizeof(double) * cst.size()));
+    HIPCHK(e, hipMemcpy(a.d_cst, cst.data(), sizeof(double) * cst.size(), hipMemcpyHostToDevice));
+    if (!a.lagged) {
+        HIPCHK(e, hipMalloc(&a.d_X, sizeof(double) * C * N * (size_t)d));
+        HIPCHK(e, hipMalloc(&a.d_yreg, sizeof(double) * C * N));
+    }
+    HIPCHK(e, hipMalloc(&a.d_part, sizeof(double) * C * (size_t)a.nchunk * (size_t)arreg::nstat(d)));
+    HIPCHK(e, hipMalloc(&e->d_fe_chain, sizeof(double) * C));
+    HIPCHK(e, hipMemset(e->d_fe_chain, 0, sizeof(double) * C));
+    if (rxhip_status st = reserve(e, &e->fe_total_cap, 32, {{&e->d_fe_total, 1}})) return st;
+    HIPCHK(e, hipMalloc(&e->d_status, sizeof(int)));
+    HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
+    return RXHIP_OK;
+}
+
+}  // extern "C"
+
+// regressor mode: X and y, checked on the host before anything reaches the device (NaN or ±Inf in X, ±Inf in y); a refused array counts as not set
+static rxhip_status arreg_set_data(rxhip_engine* e, int32_t var_id, const double* host, size_t n) {
+    const size_t C = (size_t)e->n_chains, N = (size_t)e->T, d = (size_t)e->ar.d;
+    auto& a = e->ar;
+    if (var_id != RXHIP_VAR_Y && var_id != RXHIP_VAR_REGRESSORS)
+        return fail(e, RXHIP_ERR_BADARG, "set_data: variable %d is not a data variable of the regression engine", var_id);
+    const bool isX = var_id == RXHIP_VAR_REGRESSORS;
+    const size_t need = isX ? C * N * d : C * N;
+    if (!host || n != need) return fail(e, RXHIP_ERR_BADARG, "set_data: expected %zu doubles, got %zu", need, n);
+    a.stats_ready = false;
+    bool& have = isX ? a.have_X : a.have_y;
+    have = false;
+    for (size_t i = 0; i < need; ++i) {
+        const double v = host[i];
+        if (isX ? !std::isfinite(v) : std::isinf(v))
+            return fail(e, RXHIP_ERR_BADARG, isX ? "set_data: regressor %zu is not finite (%g)" : "set_data: observation %zu is infinite (%g; finite values and NaN = a dropped row are accepted)", i, v);
+    }
+    SET_DEVICE(e);
+    HIPCHK(e, hipMemcpyAsync(isX ? a.d_X : a.d_yreg, host, sizeof(double) * need, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    have = true;
+    return RXHIP_OK;
+}
+
+// lagged mode: the series arrived through the common ingest (host or device): finite or NaN, checked on the device copy; new data, new statistics
+static rxhip_status arreg_check_data(rxhip_engine* e) {
+    e->ar.stats_ready = false;
+    return check_observations(e, [](rxhip_engine* e, long long n, unsigned nb) {
+        hipLaunchKernelGGL(k_lar_check_y, dim3(nb), dim3(256), 0, e->stream, (const double*)e->d_y, n, e->d_status);
+    }, ST_LAR_BAD_Y, "set_data: an observation is infinite (finite values and NaN = missing are accepted)");
+}
+
+template <bool LAG>
+static void arreg_launch_pass(const ArregParams& p, hipStream_t stream) {
+    const dim3 grid((unsigned)p.nchunk, (unsigned)p.C);
+    switch (p.d) {
+        case 1: hipLaunchKernelGGL((k_arreg_pass_small<1, LAG>), grid, dim3(256), 0, stream, p); break;
+        case 2: hipLaunchKernelGGL((k_arreg_pass_small<2, LAG>), grid, dim3(256), 0, stream, p); break;
+        case 3: hipLaunchKernelGGL((k_arreg_pass_small<3, LAG>), grid, dim3(256), 0, stream, p); break;
+        case 4: hipLaunchKernelGGL((k_arreg_pass_small<4, LAG>), grid, dim3(256), 0, stream, p); break;
+        default:
+            if (p.d <= 16) hipLaunchKernelGGL((k_arreg_pass<1, LAG>), grid, dim3(256), 0, stream, p);
+            else hipLaunchKernelGGL((k_arreg_pass<2, LAG>), grid, dim3(256), 0, stream, p);
+    }
+}
+
+// "run: …" refusals of an engine without its data; then the statistics pass, once per data set
+static rxhip_status arreg_statistics(rxhip_engine* e, const char* who) {
+    auto& a = e->ar;
+    if (a.lagged ? !e->have_data : !(a.have_X && a.have_y)) {
+        if (a.lagged) return fail(e, RXHIP_ERR_STATE, "%s: no observations (call rxhip_set_data first)", who);
+        return fail(e, RXHIP_ERR_STATE, "%s: the regression engine needs RXHIP_VAR_REGRESSORS and RXHIP_VAR_Y (missing:%s%s)", who, a.have_X ? "" : " regressors",
+                    a.have_y ? "" : " y");
+    }
+    if (a.stats_ready) return RXHIP_OK;
+    const ArregParams p = arreg_params(e);
+    if (a.lagged) arreg_launch_pass<true>(p, e->stream);
+    else arreg_launch_pass<false>(p, e->stream);
+    HIPCHK(e, hipGetLastError());
+    a.stats_ready = true;
+    return RXHIP_OK;
+}
+
+static rxhip_status arreg_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
+    if (rxhip_status st = run_preamble(e, iterations, false)) return st;   // (its own data flags: arreg_statistics)
+    SET_DEVICE(e);
+    auto& a = e->ar;
+    if (rxhip_status st = arreg_statistics(e, "run")) return st;
+    const size_t C = (size_t)e->n_chains, G = a.shared ? 1 : C;
+    rxhip_status rs = reserve(e, &e->fe_total_cap, iterations, {{&e->d_fe_total, 1}});
+    // the parameter history and the per-group free energies: every iteration of the run
+    if (!rs) rs = reserve(e, &a.hist_cap, iterations, {{&a.d_hist, G * (size_t)arreg::nhist(a.d)}, {&a.d_fe, G}});
+    if (rs) return rs;
+    ArregParams p = arreg_params(e);
+    p.want_fe = want_fe ? 1 : 0;
+    p.iterations = iterations;
+    hipLaunchKernelGGL(k_arreg_iterate, dim3((unsigned)G), dim3(64), 0, e->stream, p);   // every run starts from the initial q(γ); ONE launch for all iterations
+    if (want_fe && G > 1) hipLaunchKernelGGL(k_arreg_fe_total, dim3((unsigned)iterations), dim3(256), 0, e->stream, p);
+    HIPCHK(e, hipGetLastError());
+    finish_run(e, iterations, want_fe != 0);
+    // reference-equivalent events per series and iteration: per row the Normal node's messages toward θ and γ; the two priors' messages; products of
+    // the N + 1 messages at θ and at γ; the two marginals
+    const uint64_t Cs = (uint64_t)C, N = (uint64_t)a.rows, I = (uint64_t)iterations;
+    e->rule_calls = I * Cs * (2 * N + 2);
+    e->products = I * Cs * 2 * N;
+    e->marginals = I * Cs * 2;
+    return RXHIP_OK;
+}
+
+extern "C" {
+
+rxhip_status rxhip_arreg_get_parameters(rxhip_engine* e, double* theta_mean, double* theta_cov, double* gamma_shape, double* gamma_rate, double* free_energy) {
+    if (!e || !is_arreg(e)) return RXHIP_ERR_BADARG;
+    if (!e->ran) return fail(e, RXHIP_ERR_STATE, "arreg_get_parameters: no run yet");
+    if (free_energy && !e->last_want_fe) return fail(e, RXHIP_ERR_STATE, "arreg_get_parameters: free energy was not requested in the last run");
+    SET_DEVICE(e);
+    const size_t C = (size_t)e->n_chains, d = (size_t)e->ar.d, G = e->ar.shared ? 1 : C, NH = (size_t)arreg::nhist((int)d), rows = (size_t)e->last_iterations * G;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    std::vector<double> tmp(rows * NH);
+    HIPCHK(e, hipMemcpy(tmp.data(), e->ar.d_hist, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < rows; ++r) {
+        const double* q = &tmp[r * NH];
+        if (theta_mean) std::memcpy(theta_mean + r * d, q, sizeof(double) * d);
+        if (theta_cov) std::memcpy(theta_cov + r * d * d, q + d, sizeof(double) * d * d);
+        if (gamma_shape) gamma_shape[r] = q[d + d * d];
+        if (gamma_rate) gamma_rate[r] = q[d + d * d + 1];
+    }
+    if (free_energy) HIPCHK(e, hipMemcpy(free_energy, e->ar.d_fe, sizeof(double) * rows, hipMemcpyDeviceToHost));
+    return RXHIP_OK;
+}
+
+rxhip_status rxhip_arreg_get_statistics(rxhip_engine* e, double* Gout, double* hout, double* sout, double* nout) {
+    if (!e || !is_arreg(e)) return RXHIP_ERR_BADARG;
+    SET_DEVICE(e);
+    if (rxhip_status st = arreg_statistics(e, "arreg_get_statistics")) return st;
+    const size_t C = (size_t)e->n_chains, d = (size_t)e->ar.d, NS = (size_t)arreg::nstat((int)d), NG = (size_t)arreg::ngram((int)d), nchunk = (size_t)e->ar.nchunk;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    std::vector<double> part(C * nchunk * NS), tot(NS);
+    HIPCHK(e, hipMemcpy(part.data(), e->ar.d_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost));
+    for (size_t s = 0; s < C; ++s) {
+        for (size_t q = 0; q < NS; ++q) {   // ascending chunk order, as k_arreg_iterate adds them
+            double acc = part[s * nchunk * NS + q];
+            for (size_t c = 1; c < nchunk; ++c) acc += part[(s * nchunk + c) * NS + q];
+            tot[q] = acc;
+        }
+        for (size_t i = 0; i < d; ++i) {
+            if (Gout)
+                for (size_t j = 0; j < d; ++j) {
+                    const size_t lo = std::max(i, j), hi = std::min(i, j);
+                    Gout[(s * d + i) * d + j] = tot[lo * (lo + 1) / 2 + hi];
+                }
+            if (hout) hout[s * d + i] = tot[NG + i];
+        }
+        if (sout) sout[s] = tot[NG + d];
+        if (nout) nout[s] = tot[NG + d + 1];
+    }
+    return RXHIP_OK;
+}
+
+}  // extern "C"
+
 // every observation of a hidden Markov model engine is an integer code 0 … M−1 or NaN
 static rxhip_status hmm_check_data(rxhip_engine* e) {
     char msg[128];
@@ -1212,7 +1445,15 @@ const EngineFamily* rxhip::vmp_family(EngineKind kind) {
         free_buffers(e, {&e->br.d_X, &e->br.d_neff, &e->br.d_kappa, &e->br.d_cst, &e->br.d_xi, &e->br.d_lc, &e->br.d_S, &e->br.d_part, &e->br.d_xi_part,
                          &e->br.d_hist, &e->br.d_fe_prob});
     }};
+    // regression / autoregression: two rows that differ in how the data arrive — X and y through the family's own host-side set_data, or the raw
+    // series through the common ingest (host or device) with the check of the latent autoregressive engine
+    const char* const arreg_host_only = "set_data_device: the regression engine checks X and y on the host (rxhip_set_data); the lagged mode takes device data";
+    const auto arreg_release = [](E* e) { free_buffers(e, {&e->ar.d_X, &e->ar.d_yreg, &e->ar.d_cst, &e->ar.d_part, &e->ar.d_hist, &e->ar.d_fe}); };
+    static const EngineFamily arreg = {arreg_run_async, false, nullptr, arreg_set_data, arreg_host_only, nullptr, false, arreg_release};
+    static const EngineFamily arreg_lagged = {arreg_run_async, false, arreg_check_data, nullptr, nullptr, nullptr, false, arreg_release};
     switch (kind) {
+        case EngineKind::Arreg: return &arreg;
+        case EngineKind::ArregLagged: return &arreg_lagged;
         case EngineKind::Mixture: return &mixture;
         case EngineKind::Hgf: return &hgf;
         case EngineKind::Probit: return &probit;

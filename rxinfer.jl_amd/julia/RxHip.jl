@@ -1045,6 +1045,92 @@ function binreg_parameters(e::Engine, iterations::Integer; free_energy::Bool = t
     return mean, cov, fe
 end
 
+# mirrors rxhip_arreg_desc (include/rxhip.h); field order and types must match the C struct
+struct ArregDesc
+    N::Int64
+    n_series::Int64
+    d::Int32
+    lagged::Int32
+    prior_theta_mean::Ptr{Float64}
+    prior_theta_precision::Ptr{Float64}
+    prior_gamma_shape::Float64
+    prior_gamma_rate::Float64
+    init_gamma_shape::Ptr{Float64}
+    init_gamma_rate::Ptr{Float64}
+    share_parameters::Int32
+    device::Int32
+    stream::Ptr{Cvoid}
+end
+"""
+    ARRegressionEngine(prior_mean, prior_precision; N, n_series = 1, lagged = false, prior_gamma = (1.0, 1.0), init_gamma = nothing,
+                       share_parameters = false, device = -1)
+
+`γ ~ Gamma(a0, b0); θ ~ MvNormal(mean = m0, precision = Λ0); y[i] ~ Normal(mean = dot(x[i], θ), precision = γ)` with `q(γ, θ) = q(γ)q(θ)` of
+test/models/autoregressive/ar_tests.jl:17-46 for `n_series` independent problems (batched Normal-Gamma VMP from the statistics, rxhip_arreg_desc).
+`lagged = true`: `N` is the length of a series, `length(prior_mean)` the order, and `arreg_set_series!(e, z)` takes the raw series; otherwise
+`arreg_set_data!(e, X, y)`.  Then `run!`, `arreg_parameters(e, iterations)`.
+"""
+function ARRegressionEngine(prior_mean::AbstractVector, prior_precision::AbstractMatrix; N::Integer, n_series::Integer = 1, lagged::Bool = false,
+                            prior_gamma = (1.0, 1.0), init_gamma = nothing, share_parameters::Bool = false, device::Integer = -1, stream = nothing)
+    d = length(prior_mean)
+    m0, l0 = rowmajor(prior_mean), rowmajor(prior_precision)
+    ig = init_gamma === nothing ? Float64[] : Float64[init_gamma[1], init_gamma[2]]
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    st = GC.@preserve m0 l0 ig begin
+        desc = ArregDesc(N, n_series, d, lagged ? 1 : 0, pointer(m0), pointer(l0), Float64(prior_gamma[1]), Float64(prior_gamma[2]),
+                         isempty(ig) ? Ptr{Float64}(C_NULL) : pointer(ig), isempty(ig) ? Ptr{Float64}(C_NULL) : pointer(ig) + 8,
+                         share_parameters ? 1 : 0, device, stream_handle(stream))
+        ccall((:rxhip_arreg_create, librxhip), Int32, (Ref{ArregDesc}, Ref{Ptr{Cvoid}}), desc, h)
+    end
+    e = Engine(h[], d, 1, N, n_series, 0)
+    if st != RXHIP_OK
+        h[] != C_NULL && (try check(e, st) finally ccall((:rxhip_destroy, librxhip), Int32, (Ptr{Cvoid},), h[]) end)
+        throw(RxHipError(st, unsafe_string(ccall((:rxhip_status_string, librxhip), Cstring, (Int32,), st))))
+    end
+    finalizer(destroy!, e)
+    return e
+end
+"""regressor mode — X: one `N × d` matrix per series (or one matrix), y: one vector per series (or one vector); `NaN` in y drops the row."""
+function arreg_set_data!(e::Engine, X, y)
+    xs = X isa AbstractMatrix ? [X] : X
+    x = reduce(vcat, rowmajor.(xs))
+    yy = y isa AbstractVector{<:Real} ? Vector{Float64}(y) : reduce(vcat, Vector{Float64}.(y))
+    for (id, a) in ((RXHIP_VAR_REGRESSORS, x), (RXHIP_VAR_Y, yy))
+        check(e, ccall((:rxhip_set_data, librxhip), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Csize_t, Int32), e.handle, id, a, length(a), Int32(0)))
+    end
+    return e
+end
+"""lagged mode — z: `T × n_series` (a vector for one series); column-major Julia storage is the C layout [series][T]; `NaN` = missing."""
+function arreg_set_series!(e::Engine, z::AbstractVecOrMat)
+    a = Array{Float64}(z)
+    check(e, ccall((:rxhip_set_data, librxhip), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Csize_t, Int32), e.handle, RXHIP_VAR_Y, a, length(a),
+                   RXHIP_LAYOUT_CHAIN_TIME))
+    return e
+end
+"""q(θ), q(γ) and F after every one of the `iterations` of the last run: (θ means d × G × iterations, θ covariances d × d × G × iterations, γ shapes
+and rates G × iterations, free energies G × iterations or `nothing`), G = n_series or 1 with shared parameters — the C arrays
+`[iterations][G][…]` seen column-major (covariances are symmetric)."""
+function arreg_parameters(e::Engine, iterations::Integer; shared::Bool = false, free_energy::Bool = true)
+    G = shared ? 1 : e.n_chains
+    mean = Array{Float64}(undef, e.d, G, iterations)
+    cov = Array{Float64}(undef, e.d, e.d, G, iterations)
+    ga = Array{Float64}(undef, G, iterations)
+    gb = Array{Float64}(undef, G, iterations)
+    fe = free_energy ? Array{Float64}(undef, G, iterations) : nothing
+    check(e, ccall((:rxhip_arreg_get_parameters, librxhip), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                   e.handle, mean, cov, ga, gb, free_energy ? fe : Ptr{Float64}(C_NULL)))
+    return mean, cov, ga, gb, fe
+end
+"""the statistics of the data in place, per series: (G d × d × series, h d × series, s, n)"""
+function arreg_statistics(e::Engine)
+    G = Array{Float64}(undef, e.d, e.d, e.n_chains)
+    h = Array{Float64}(undef, e.d, e.n_chains)
+    s = Vector{Float64}(undef, e.n_chains)
+    n = Vector{Float64}(undef, e.n_chains)
+    check(e, ccall((:rxhip_arreg_get_statistics, librxhip), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), e.handle, G, h, s, n))
+    return G, h, s, n
+end
+
 # ---- several GPUs: the free-energy / statistics exchange over RCCL (no torch, no MPI dependency in this file) ----------
 """128-byte RCCL id, created by rank 0 and moved to the other ranks by the host (file, socket, MPI.jl, Distributed)."""
 function comm_unique_id()

@@ -132,6 +132,13 @@ class BinregDesc(ctypes.Structure):   # rxhip_binreg_desc
         (n, c_double_p) for n in ("prior_xi", "prior_precision", "init_mean", "init_cov")] + [("device", ctypes.c_int32), ("stream", ctypes.c_void_p)]
 
 
+class ArregDesc(ctypes.Structure):   # rxhip_arreg_desc
+    _fields_ = [("N", ctypes.c_int64), ("n_series", ctypes.c_int64), ("d", ctypes.c_int32), ("lagged", ctypes.c_int32),
+                ("prior_theta_mean", c_double_p), ("prior_theta_precision", c_double_p), ("prior_gamma_shape", ctypes.c_double),
+                ("prior_gamma_rate", ctypes.c_double), ("init_gamma_shape", c_double_p), ("init_gamma_rate", c_double_p),
+                ("share_parameters", ctypes.c_int32), ("device", ctypes.c_int32), ("stream", ctypes.c_void_p)]
+
+
 class NoisePrior(ctypes.Structure):   # rxhip_noise_prior
     _fields_ = [("nu0", ctypes.c_double), ("S0", c_double_p), ("init_nu", ctypes.c_double), ("init_V", c_double_p)]
 
@@ -242,6 +249,10 @@ SYMBOLS = [
     ("rxhip_binreg_create", ctypes.c_int32, [ctypes.POINTER(BinregDesc), ctypes.POINTER(_H)]),
     ("rxhip_binreg_get_parameters", ctypes.c_int32, [_H, c_double_p, c_double_p, c_double_p]),
     ("rxhip_binreg_schedule", None, [ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    ("rxhip_arreg_create", ctypes.c_int32, [ctypes.POINTER(ArregDesc), ctypes.POINTER(_H)]),
+    ("rxhip_arreg_get_parameters", ctypes.c_int32, [_H, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    ("rxhip_arreg_get_statistics", ctypes.c_int32, [_H, c_double_p, c_double_p, c_double_p, c_double_p]),
+    ("rxhip_arreg_schedule", None, [ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     ("rxhip_hgf_get_history", ctypes.c_int32, [_H, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_int32]),
     ("rxhip_set_profiling", ctypes.c_int32, [_H, ctypes.c_int32]),
     ("rxhip_get_kernel_times", ctypes.c_int32, [_H, c_double_p, c_u64_p]),

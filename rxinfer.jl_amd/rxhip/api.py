@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RxHipError
-from .engine import DriftChainEngine, GMMEngine, HGFEngine, LGSSMEngine, MvGMMEngine, ProbitEngine, HMMEngine, LAREngine, BinomialRegressionEngine
+from .engine import DriftChainEngine, GMMEngine, HGFEngine, LGSSMEngine, MvGMMEngine, ProbitEngine, HMMEngine, LAREngine, BinomialRegressionEngine, ARRegressionEngine
 
 
 @dataclass
@@ -430,6 +430,77 @@ def _infer_binreg(model, data, iterations, free_energy, options, catch_exception
 
 
 @dataclass
+class GaussianRegression:
+    """`γ ~ Gamma(a0, b0); θ ~ MvNormal(m0, Λ0⁻¹); y[i] ~ Normal(dot(x[i], θ), γ⁻¹)` with `q(γ, θ) = q(γ)q(θ)` (test/models/autoregressive/
+    ar_tests.jl:17-46).  order is not None: the regressors are the `order` previous values of the series itself, most recent first (ar_ssm_data)."""
+    order: Optional[int]
+    prior_theta: Optional[tuple] = None
+    prior_gamma: tuple = (1.0, 1.0)
+    init_gamma: Optional[tuple] = None
+    share_parameters: bool = False
+
+
+def autoregression(order, prior_theta=None, prior_gamma=(1, 1), init_gamma=None, share_parameters=False):
+    """AR(order) with observed regressors: `data={"y": series}`, [T] or [T][series]; row t has y = z_t and x = (z_{t−1} … z_{t−order}).
+    prior_theta: (mean [p], precision [p][p]) or None = zero mean and identity precision; prior_gamma, init_gamma: (shape, rate), init None = the
+    prior's (the reference initialises q(γ) = GammaShapeRate(1, 1), its prior)."""
+    f = lambda v: None if v is None else (np.asarray(v[0], dtype=np.float64), np.asarray(v[1], dtype=np.float64))
+    g = lambda v: None if v is None else (float(v[0]), float(v[1]))
+    return GaussianRegression(int(order), f(prior_theta), g(prior_gamma), g(init_gamma), bool(share_parameters))
+
+
+def gaussian_regression(prior_mean, prior_precision, prior_gamma=(1, 1), init_gamma=None, share_parameters=False):
+    """Linear regression with unknown coefficients and noise precision: `data={"x": X, "y": y}`, X [N][d] or [series][N][d], y [N] or [series][N]
+    (a NaN y drops the row)."""
+    g = lambda v: None if v is None else (float(v[0]), float(v[1]))
+    return GaussianRegression(None, (np.asarray(prior_mean, dtype=np.float64), np.asarray(prior_precision, dtype=np.float64)), g(prior_gamma), g(init_gamma),
+                              bool(share_parameters))
+
+
+def _infer_arreg(model, data, iterations, free_energy, options, catch_exception):
+    """posteriors["θ"]: (mean [iterations][d], cov [iterations][d][d]) and posteriors["γ"]: (shape [iterations], rate [iterations]) after every
+    iteration (KeepEach; a series axis after the iterations for an unshared batch); free_energy: one value per iteration (summed over the series)."""
+    options = _check_options(options)
+    dev = int(options.get("device", -1))
+    iters = 1 if iterations is None else int(iterations)
+    eng = None
+    try:
+        if model.order is not None:
+            y = np.asarray(data["y"], dtype=np.float64)
+            single = y.ndim == 1
+            if single:
+                y = y[:, None]
+            T, C = y.shape
+            eng = ARRegressionEngine(T, model.order, model.prior_theta, model.prior_gamma, model.init_gamma, n_series=C, lagged=True,
+                                     share_parameters=model.share_parameters, device=dev)
+            eng.set_data(y, layout="time_chain")
+        else:
+            X = np.asarray(data["x"], dtype=np.float64)
+            single = X.ndim == 2
+            if single:
+                X = X[None]
+            C, N, d = X.shape
+            y = np.asarray(data["y"], dtype=np.float64).reshape(C, N)
+            eng = ARRegressionEngine(N, d, model.prior_theta, model.prior_gamma, model.init_gamma, n_series=C, share_parameters=model.share_parameters,
+                                     device=dev)
+            eng.set_regressors(X)
+            eng.set_observations(y)
+        eng.run(iterations=iters, free_energy=free_energy)
+        tm, tc, ga, gb, _ = eng.parameters()
+        fe = eng.free_energy() if free_energy else None
+        if single or model.share_parameters:
+            tm, tc, ga, gb = tm[:, 0], tc[:, 0], ga[:, 0], gb[:, 0]
+        return InferenceResult({"θ": (tm, tc), "γ": (ga, gb)}, None, fe, model, None)
+    except Exception as err:
+        if not catch_exception:
+            raise
+        return InferenceResult({}, None, None, model, err)
+    finally:
+        if eng is not None:
+            eng.close()
+
+
+@dataclass
 class InferenceResult:
     """src/inference/batch.jl:18-24"""
     posteriors: dict
@@ -701,6 +772,8 @@ def infer(*, model, data, iterations=None, free_energy=False, options=None, retu
         return _infer_lar(model, data, iterations, free_energy, options, catch_exception)
     if isinstance(model, BinomialRegression):
         return _infer_binreg(model, data, iterations, free_energy, options, catch_exception)
+    if isinstance(model, GaussianRegression):
+        return _infer_arreg(model, data, iterations, free_energy, options, catch_exception)
     if not isinstance(model, LinearGaussianSSM):
         raise TypeError("infer: no device schedule for this model type")
     if model.noise_precision_prior is not None:

@@ -908,6 +908,104 @@ class BinomialRegressionEngine:
         return mean, cov, fe
 
 
+class ARRegressionEngine:
+    """Bayesian linear regression with unknown coefficients θ and noise precision γ, `γ ~ Gamma(a0, b0); θ ~ MvNormal(m0, Λ0⁻¹); y[i] ~
+    Normal(dot(x[i], θ), γ⁻¹)` with `q(γ, θ) = q(γ)q(θ)` (test/models/autoregressive/ar_tests.jl:17-46) for n_series independent problems or one
+    θ, γ for all of them, d = 1 … 32: batched Normal-Gamma VMP from the statistics G, h, s, n (include/rxhip.h rxhip_arreg_desc).
+    lagged=False: `set_regressors(X [series][N][d])`, `set_observations(y [series][N])`, a NaN y drops the row.  lagged=True: N is the length T of
+    a series and d the order p; `set_data(z, layout)` takes the raw series ([T][series] or [series][T]) and row t has y = z_t, x = (z_{t−1} … z_{t−p});
+    no regressor matrix is formed.  prior_theta: (mean [d], precision [d][d]) or None = zero mean and identity precision; prior_gamma, init_gamma:
+    (shape, rate), init None = the prior's.  `run(iterations)`: that many iterations from the initial q(γ), ONE launch after the pass over the data;
+    `parameters()`: q(θ), q(γ), F after every one; `statistics()`: G, h, s, n per series."""
+
+    def __init__(self, N, d, prior_theta=None, prior_gamma=(1.0, 1.0), init_gamma=None, n_series=1, lagged=False, share_parameters=False, device=-1,
+                 stream=None):
+        L = _lib.lib()
+        d = int(d)
+        sd = max(d, 0)
+        if prior_theta is None:
+            m0, l0 = _c(np.zeros(sd)), _c(np.eye(sd))
+        else:
+            m0, l0 = _c(prior_theta[0]), _c(prior_theta[1])
+            if m0.shape != (sd,) or l0.shape != (sd, sd):
+                raise ValueError(f"prior_theta must be (mean [d], precision [d][d]) with d = {d}")
+        desc = _lib.ArregDesc()
+        desc.N, desc.n_series, desc.d, desc.lagged = int(N), int(n_series), d, int(bool(lagged))
+        desc.prior_theta_mean, desc.prior_theta_precision = _p(m0), _p(l0)
+        desc.prior_gamma_shape, desc.prior_gamma_rate = float(prior_gamma[0]), float(prior_gamma[1])
+        ig = None if init_gamma is None else _c([float(init_gamma[0]), float(init_gamma[1])])
+        if ig is not None:
+            desc.init_gamma_shape = _p(ig[0:1])
+            desc.init_gamma_rate = _p(ig[1:2])
+        desc.share_parameters, desc.device = int(bool(share_parameters)), int(device)
+        desc.stream = ctypes.c_void_p(stream) if stream else None
+        self.N, self.T, self.d, self.n_series, self.n_chains = int(N), int(N), d, int(n_series), int(n_series)
+        self.lagged, self.share_parameters = bool(lagged), bool(share_parameters)
+        self._h = ctypes.c_void_p()
+        st = L.rxhip_arreg_create(ctypes.byref(desc), ctypes.byref(self._h))
+        if st != _lib.OK:
+            msg = L.rxhip_last_error(self._h).decode() if self._h else L.rxhip_status_string(st).decode()
+            if self._h:
+                L.rxhip_destroy(self._h)
+                self._h = None
+            raise RxHipError(st, msg or L.rxhip_status_string(st).decode())
+        self._iters = 0
+        self._fe = False
+        self._data_ref = None
+
+    _chk = LGSSMEngine._chk
+    close = LGSSMEngine.close
+    __del__ = LGSSMEngine.__del__
+    __enter__ = LGSSMEngine.__enter__
+    __exit__ = LGSSMEngine.__exit__
+    sync = LGSSMEngine.sync
+    set_data = HGFEngine.set_data                  # lagged mode: the raw series, [T][series] ('time_chain') or [series][T] ('chain_time')
+    set_data_device = HGFEngine.set_data_device
+    free_energy = LGSSMEngine.free_energy
+    free_energy_per_chain = LGSSMEngine.free_energy_per_chain
+    counters = LGSSMEngine.counters
+    stream = LGSSMEngine.stream
+    run = BinomialRegressionEngine.run
+    run_async = BinomialRegressionEngine.run_async
+
+    @staticmethod
+    def schedule(n_rows, d):
+        """(rows per tile, workgroups per series) of the pass for n_rows rows (N, or max(T − p, 0) in lagged mode) of d regressors."""
+        tp, ch = ctypes.c_int32(), ctypes.c_int32()
+        _lib.lib().rxhip_arreg_schedule(int(n_rows), int(d), ctypes.byref(tp), ctypes.byref(ch))
+        return tp.value, ch.value
+
+    def _set(self, var, a, shape, name):
+        a = _c(a)
+        if a.shape != shape and not (self.n_series == 1 and a.shape == shape[1:]):
+            raise ValueError(f"{name} must be {list(shape)} (the series axis may be left out for one series), got {list(a.shape)}")
+        self._chk(_lib.lib().rxhip_set_data(self._h, var, _p(a), a.size, _lib.LAYOUT_TIME_CHAIN))
+
+    def set_regressors(self, X):
+        """regressor mode: X [series][N][d]."""
+        self._set(_lib.VAR_REGRESSORS, X, (self.n_series, self.N, self.d), "X")
+
+    def set_observations(self, y):
+        """regressor mode: y [series][N]; NaN drops the row."""
+        self._set(_lib.VAR_Y, y, (self.n_series, self.N), "y")
+
+    def parameters(self):
+        """after every iteration of the last run: (θ mean [iterations][G][d], θ covariance [iterations][G][d][d], γ shape [iterations][G], γ rate
+        [iterations][G], free energy [iterations][G] or None when the run was without it); G = n_series, or 1 with shared parameters."""
+        G, n, d = (1 if self.share_parameters else self.n_series), max(int(self._iters), 0), self.d
+        tm, tc, ga, gb = np.empty((n, G, d)), np.empty((n, G, d, d)), np.empty((n, G)), np.empty((n, G))
+        fe = np.empty((n, G)) if self._fe else None
+        self._chk(_lib.lib().rxhip_arreg_get_parameters(self._h, _p(tm), _p(tc), _p(ga), _p(gb), _p(fe) if self._fe else None))
+        return tm, tc, ga, gb, fe
+
+    def statistics(self):
+        """the pass alone: (G [series][d][d], h [series][d], s [series], n [series]) of the data in place."""
+        C, d = self.n_series, self.d
+        G, h, s, n = np.empty((C, d, d)), np.empty((C, d)), np.empty(C), np.empty(C)
+        self._chk(_lib.lib().rxhip_arreg_get_statistics(self._h, _p(G), _p(h), _p(s), _p(n)))
+        return G, h, s, n
+
+
 class Communicator:
     """RCCL communicator made through the C ABI (rxhip_comm_*): rank 0 calls `Communicator.unique_id()`, the 128 bytes
     travel to the other ranks by any host-side means, every rank constructs `Communicator(nranks, id, rank)`."""
