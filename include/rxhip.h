@@ -901,6 +901,15 @@ rxhip_status rxhip_probit_create(const rxhip_probit_desc* desc, rxhip_engine** o
  * per-series parts, whose sum lacks the KL terms that rxhip_get_free_energy adds once), rxhip_counters, rxhip_destroy.
  * RXHIP_ERR_BADARG with a text: K or M out of range, T < 1, a count that is not positive and finite, prior_s0 not positive or not summing to
  * 1 within 1e-12, per_series together with share_parameters.
+ * Range.  Every positive finite count is accepted; the contract (γ within 1e-9 absolute, counts within 1e-9 relative, free energy within
+ * 1e-8·max(1, |F|), against a 50-digit restatement, per series and iteration) is held on this grid (tests/hmm_mp.py GRID): prior counts of scale
+ * 1e-3 … 1e9 (scale·U(0.5, 3)), initial counts all ones or of the prior's scale from 1e-2 up, magnitudes mixed by 1e-3 inside one table, symbols
+ * that never occur, a single symbol, nothing observed, K = 2 … 16, M = 2 … 64, T = 1 … 4096, shared parameters.  At large counts the KL terms are
+ * formed from the statistics N, Mstat themselves (lnΓ(p + n) − lnΓ(p) by Stirling's series from p = 64 on), not from differences of log-gammas.
+ * Below that range — initial counts of a few 1e-3, where Ã = exp(ψ(c) − ψ(Σc)) ≈ exp(−1/c) nears the smallest double — a run is REFUSED, not
+ * answered: if a normaliser c_t or d_t of a sweep is at or below 1e-200 (or not finite), rxhip_run / rxhip_sync return RXHIP_ERR_NONFINITE_FE
+ * with a text that says that a normaliser underflowed and that the counts are too small for this sweep; no result of that run is valid, the
+ * engine stays usable (other data on the same handle may well be answered).  Sparse PRIORS are not the issue: 1e-3 with initial counts of 1 is on the grid.
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
     int64_t T, n_series;

@@ -330,6 +330,9 @@ inline void free_buffers(rxhip_engine* e, std::initializer_list<double**> bufs) 
 
 // what the translation units of the engines share with the runtime in rxhip.hip
 namespace rxhip {
+// status bit of k_hmm_sweep (hmm_kernels.hpp; next to ST_NOT_POSDEF = 1, ST_NONFINITE = 2, ST_PROBIT_BAD_Y = 4, ST_HMM_BAD_X = 8, ST_LAR_BAD_Y = 16): a normaliser of
+// the forward–backward sweep underflowed.  rxhip_sync reports it as RXHIP_ERR_NONFINITE_FE with a text of its own.
+constexpr int ST_HMM_UNDERFLOW = 32;
 const EngineFamily& family_of(const rxhip_engine* e);   // the row of the engine's kind
 const EngineFamily* vmp_family(EngineKind kind);        // … of a family of vmp_engines.hip (null: not one of them)
 inline double* fe_total_of(const rxhip_engine* e) { const auto f = family_of(e).fe_total; return f ? f(e) : e->d_fe_total; }

@@ -31,6 +31,9 @@
 // one owner that adds in time order: results are bit-identical run to run and do not depend on which other series are in the batch.  γ goes
 // to global memory only on the sweep whose posteriors are read (the last).  The observation and its B̃ row are loaded one and two steps ahead.
 // k_hmm_tables / k_hmm_update give a thread one Dirichlet column (its digammas, log-gammas, exp); k_hmm_fe a thread per series.
+// Range: the sweep is in the linear domain with one normaliser per step, so it refuses (status bit, RXHIP_ERR_NONFINITE_FE) a run in which a
+// normaliser falls to hmm::kMinNormaliser or below, where entries of Ã, B̃ have underflowed; the update forms the KL terms from the statistics
+// themselves (hmm::lgamma_diff), so the free energy keeps its digits at counts of 1e9 (tests/test_hmm_contract_*.py).
 // Bytes per (series, step, iteration): x read twice (16), α̂ written and read (16·K); γ (8·K) on the last sweep only.
 //
 // The per-column and per-state arithmetic is `__host__ __device__` and self-contained (only digamma.hpp), floating-point contraction off: the
@@ -54,20 +57,50 @@ namespace hmm {
 
 constexpr int kMaxK = 16, kMaxM = 64;
 
-// One Dirichlet column (n counts, `stride` doubles apart): expected logs l[i] = ψ(c_i) − ψ(Σc) and their exponentials t[i]; returns
-// KL(Dir(c) ‖ Dir(p)) = lnΓ(Σc) − lnΓ(Σp) − Σ(lnΓ(c_i) − lnΓ(p_i)) + Σ(c_i − p_i)·l[i]
-HMM_HD double column_table(const double* cnt, const double* pri, int n, int stride, double* l, double* t) {
+// A sweep whose normaliser c_t or d_t is at or below this is refused (k_hmm_sweep).  Ã = exp(ψ(c) − ψ(Σc)) is about exp(−1/c) at small counts and
+// reaches the denormal range when 1/c nears 700: a denormal entry has lost digits but is still positive, and the sums it enters come out finite
+// and wrong.  The smallest normal double is 2.2e-308, so with a normaliser above 1e-200 a term lost to underflow is below 1e-108 of the sum it
+// belongs to.  Measured: every silently wrong run found had a normaliser of 2.8e-234 or less.
+constexpr double kMinNormaliser = 1e-200;
+
+// lnΓ(p + n) − lnΓ(p), n ≥ 0, without forming either: from p = 64 on by Stirling's series,
+//     (p − ½)·log1p(n/p) + n·(ln(p + n) − 1) + S(p + n) − S(p),   S(x) = 1/(12x) − 1/(360x³) + 1/(1260x⁵) − 1/(1680x⁷)
+// (the next term of S is below 1/(1188·64⁹) = 5e-20); below 64 the two log-gammas are O(100) and their plain difference keeps its digits.
+constexpr double kLgammaDiffFrom = 64.0;
+HMM_HD double stirling_tail(double x) {
     HMM_NO_CONTRACT
-    double sc = 0.0, sp = 0.0;
-    for (int i = 0; i < n; ++i) { sc += cnt[i * stride]; sp += pri[i * stride]; }
+    const double r = 1.0 / x, r2 = r * r;
+    return r * (1.0 / 12.0 - r2 * (1.0 / 360.0 - r2 * (1.0 / 1260.0 - r2 * (1.0 / 1680.0))));
+}
+HMM_HD double lgamma_diff(double p, double n) {
+    HMM_NO_CONTRACT
+    const double c = p + n;
+    if (p < kLgammaDiffFrom) return lgamma(c) - lgamma(p);
+    return (p - 0.5) * log1p(n / p) + n * (log(c) - 1.0) + (stirling_tail(c) - stirling_tail(p));
+}
+
+// One Dirichlet column (n counts, `stride` doubles apart): expected logs l[i] = ψ(c_i) − ψ(Σc) and their exponentials t[i]; returns
+// KL(Dir(c) ‖ Dir(p)) = lnΓ(Σc) − lnΓ(Σp) − Σ(lnΓ(c_i) − lnΓ(p_i)) + Σ(c_i − p_i)·l[i].
+// `st`: the statistics the counts were updated with (c_i = p_i + st_i bit for bit), or nullptr (the initial counts of a run, whose KL enters no
+// free energy).  With them the KL term takes c_i − p_i and the log-gamma differences from st_i itself: at counts of 1e12, c_i − p_i has lost
+// the digits of a statistic of 10, and lnΓ(c_i) − lnΓ(p_i) is a difference of numbers near 1e13 whose sum over the column is O(1).
+HMM_HD double column_table(const double* cnt, const double* pri, const double* st, int n, int stride, double* l, double* t) {
+    HMM_NO_CONTRACT
+    double sc = 0.0, sp = 0.0, ss = 0.0;
+    for (int i = 0; i < n; ++i) {
+        sc += cnt[i * stride];
+        sp += pri[i * stride];
+        if (st) ss += st[i * stride];
+    }
     const double dsum = digamma_dev(sc);
-    double kl = lgamma(sc) - lgamma(sp);
+    double kl = st ? lgamma_diff(sp, ss) : lgamma(sc) - lgamma(sp);
     for (int i = 0; i < n; ++i) {
         const double c = cnt[i * stride], p = pri[i * stride];
         const double li = digamma_dev(c) - dsum;
         l[i * stride] = li;
         t[i * stride] = exp(li);
-        kl += (c - p) * li - (lgamma(c) - lgamma(p));
+        if (st) kl += st[i * stride] * li - lgamma_diff(p, st[i * stride]);
+        else kl += (c - p) * li - (lgamma(c) - lgamma(p));
     }
     return kl;
 }
@@ -155,13 +188,13 @@ __device__ __forceinline__ void hmm_column_thread(const HmmParams& p, int cur) {
     const int n = isB ? M : K;
     const long long in_set = (isB ? K * K : 0) + (isB ? c - K : c), off = g * KM + in_set;
     double* cnt = p.counts + off;
+    const double* st = FROM_STATS ? (p.shared ? p.stat_sum : p.stat + g * KM) + in_set : nullptr;
     if (FROM_STATS) {
-        const double* st = (p.shared ? p.stat_sum : p.stat + g * KM) + in_set;
         for (int i = 0; i < n; ++i) cnt[i * K] = p.prior[off + i * K] + st[i * K];
     } else {
         for (int i = 0; i < n; ++i) cnt[i * K] = p.init[off + i * K];
     }
-    const double kl = hmm::column_table(cnt, p.prior + off, n, K, p.ltab + (long long)cur * G * KM + off, p.ttab + off);
+    const double kl = hmm::column_table(cnt, p.prior + off, st, n, K, p.ltab + (long long)cur * G * KM + off, p.ttab + off);
     p.kl[idx] = kl;
     if (!(kl - kl == 0.0)) atomicOr(p.status, 2);   // ST_NONFINITE
 }
@@ -227,7 +260,7 @@ __global__ void __launch_bounds__(64) k_hmm_sweep(HmmParams p) {
         for (int j = 0; j < R; ++j) al[j] = __shfl(a, j, R);
         const double v = hmm::forward_state<R>(arow, al, f);
         const double c = hmm_row_sum<R>(v);
-        bad = bad || !(c > 0.0) || !(c - c == 0.0);
+        bad = bad || !(c > hmm::kMinNormaliser) || !(c - c == 0.0);
         a = v / c;
         logz += log(c);
         if (mine) al_s[t * CK] = a;
@@ -256,7 +289,7 @@ __global__ void __launch_bounds__(64) k_hmm_sweep(HmmParams p) {
         for (int j = 0; j < R; ++j) { wl[j] = __shfl(w, j, R); al[j] = __shfl(am, j, R); }
         const double bt = hmm::backward_state<R>(acol, wl);
         const double d = hmm_row_sum<R>(am * bt);
-        bad = bad || !(d > 0.0) || !(d - d == 0.0);
+        bad = bad || !(d > hmm::kMinNormaliser) || !(d - d == 0.0);
         hmm::accumulate_xi<R>(nrow, arow, al, w / d);
         b = bt / d;
         a = am; f = fp; xt = xp; ap = app; xp = xpp;
@@ -269,7 +302,7 @@ __global__ void __launch_bounds__(64) k_hmm_sweep(HmmParams p) {
             if (j < K) st[i * K + j] = nrow[j];
         for (int m = 0; m < M; ++m) st[K * K + m * K + i] = ms[m * R];
         if (i == 0) p.logz[s] = logz;
-        if (bad) atomicOr(p.status, 2);   // ST_NONFINITE
+        if (bad) atomicOr(p.status, 32);   // ST_HMM_UNDERFLOW (engine.hpp): a normaliser at or below hmm::kMinNormaliser, or not finite
     }
 }
 

@@ -3091,6 +3091,9 @@ rxhip_status rxhip_sync(rxhip_engine* e) {
         HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
         if (st & ST_NOT_POSDEF)
             return fail(e, RXHIP_ERR_NOT_POSDEF, "a covariance / precision block lost positive definiteness on device");
+        if (st & ST_HMM_UNDERFLOW)
+            return fail(e, RXHIP_ERR_NONFINITE_FE, "hmm: a normaliser of the forward–backward sweep underflowed (at or below 1e-200, or not finite): the counts are too "
+                                                   "small for this sweep, no result of this run is valid (device flags 0x%x)", st);
         return fail(e, RXHIP_ERR_NONFINITE_FE, "free energy is NaN or Inf (device flags 0x%x)", st);
     }
     return RXHIP_OK;

@@ -7,8 +7,11 @@
 // output with tests/hmm_ref.py.
 //
 // stdin:  n_cases, then per case   T K M iterations | π [K] | prior_A [K][K] | prior_B [M][K] | init_A | init_B | x [T] (nan = missing)
-// stdout: per case four lines      γ [T+1][K] | A counts [K][K] | B counts [M][K] | free energy [iterations]
+// stdout: first line                hmm::kMinNormaliser
+//         per case five lines       γ [T+1][K] | A counts [K][K] | B counts [M][K] | free energy [iterations] | refused (0 / 1), smallest normaliser
 //         then, for the rest of stdin, one line ψ(v) per value v
+// `refused` is the guard of k_hmm_sweep restated: 1 if a normaliser c_t or d_t of any sweep was at or below hmm::kMinNormaliser or not finite (the
+// device then raises its status bit and rxhip_run returns RXHIP_ERR_NONFINITE_FE); the other four lines are printed as computed either way.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -29,13 +32,13 @@ struct Case {
 };
 
 // all columns of a parameter set: what k_hmm_tables / k_hmm_update do with a thread per column
-static double tables(const Case& c, const std::vector<double>& counts, std::vector<double>& l, std::vector<double>& t) {
+static double tables(const Case& c, const std::vector<double>& counts, const std::vector<double>* stat, std::vector<double>& l, std::vector<double>& t) {
     const int K = c.K, M = c.M;
     double kl = 0.0;
     for (int col = 0; col < 2 * K; ++col) {
         const bool isB = col >= K;
         const int off = (isB ? K * K : 0) + (isB ? col - K : col);
-        kl += hmm::column_table(&counts[(size_t)off], &c.prior[(size_t)off], isB ? M : K, K, &l[(size_t)off], &t[(size_t)off]);
+        kl += hmm::column_table(&counts[(size_t)off], &c.prior[(size_t)off], stat ? &(*stat)[(size_t)off] : nullptr, isB ? M : K, K, &l[(size_t)off], &t[(size_t)off]);
     }
     return kl;
 }
@@ -45,7 +48,13 @@ static void run_case(const Case& c) {
     const int T = c.T, K = c.K, M = c.M, KM = (K + M) * K;
     std::vector<double> counts = c.init, l_old((size_t)KM), l_new((size_t)KM), tt((size_t)KM), stat((size_t)KM), fe;
     std::vector<double> alpha((size_t)(T + 1) * R, 0.0), gamma((size_t)(T + 1) * R, 0.0);
-    tables(c, counts, l_old, tt);
+    tables(c, counts, nullptr, l_old, tt);
+    bool bad = false;
+    double smallest = INFINITY;
+    auto guard = [&](double v) {   // k_hmm_sweep's check of c_t and d_t
+        bad = bad || !(v > hmm::kMinNormaliser) || !(v - v == 0.0);
+        if (!(v >= smallest)) smallest = v;   // (keeps a NaN)
+    };
     for (int it = 0; it < c.iterations; ++it) {
         const double *At = tt.data(), *Bt = At + K * K;
         double arow[R][R], acol[R][R], nrow[R][R];
@@ -66,6 +75,7 @@ static void run_case(const Case& c) {
             double v[R], cs = 0.0;
             for (int i = 0; i < R; ++i) v[i] = hmm::forward_state<R>(arow[i], al, factor(c.x[(size_t)t - 1], i));
             for (int i = 0; i < R; ++i) cs += v[i];
+            guard(cs);
             for (int i = 0; i < R; ++i) alpha[(size_t)t * R + i] = v[i] / cs;
             logz += log(cs);
         }
@@ -84,6 +94,7 @@ static void run_case(const Case& c) {
             }
             for (int i = 0; i < R; ++i) bt[i] = hmm::backward_state<R>(acol[i], w);
             for (int i = 0; i < R; ++i) d += am[i] * bt[i];
+            guard(d);
             for (int i = 0; i < R; ++i) {
                 hmm::accumulate_xi<R>(nrow[i], arow[i], am, w[i] / d);
                 b[i] = bt[i] / d;
@@ -94,7 +105,7 @@ static void run_case(const Case& c) {
             for (int j = 0; j < K; ++j) stat[(size_t)(i * K + j)] = nrow[i][j];
         // update, tables of the new counts, free energy (k_hmm_update, k_hmm_fe)
         for (int e = 0; e < KM; ++e) counts[(size_t)e] = c.prior[(size_t)e] + stat[(size_t)e];
-        const double kl = tables(c, counts, l_new, tt);
+        const double kl = tables(c, counts, &stat, l_new, tt);
         double f = -logz;
         for (int e = 0; e < KM; ++e) f += stat[(size_t)e] * (l_old[(size_t)e] - l_new[(size_t)e]);
         fe.push_back(f + kl);
@@ -109,10 +120,12 @@ static void run_case(const Case& c) {
     std::printf("\n");
     for (double f : fe) std::printf("%.17g ", f);
     std::printf("\n");
+    std::printf("%d %.17g\n", bad ? 1 : 0, smallest);
 }
 
 int main() {
     const int n_cases = (int)read_double();
+    std::printf("%.17g\n", hmm::kMinNormaliser);
     for (int cs = 0; cs < n_cases; ++cs) {
         Case c;
         c.T = (int)read_double(); c.K = (int)read_double(); c.M = (int)read_double(); c.iterations = (int)read_double();

@@ -46,10 +46,14 @@ def test_host_build_of_the_helpers_equals_the_restatement(exe):
     cases = _cases()
     text = f"{len(cases)}\n" + "\n".join(_case_text(*c) for c in cases) + "\n"
     lines = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.splitlines()
-    assert len(lines) == 4 * len(cases)
+    assert float(lines[0]) == R.K_MIN_NORMALISER      # the first line: hmm::kMinNormaliser
+    lines = lines[1:]
+    assert len(lines) == 5 * len(cases)
     for n, (x, m, iters) in enumerate(cases):
         gamma, a, b, fe = R.run(x, **m, iterations=iters)
-        gg, ga, gb, gf = (np.array(lines[4 * n + j].split(), dtype=np.float64) for j in range(4))
+        gg, ga, gb, gf, flag = (np.array(lines[5 * n + j].split(), dtype=np.float64) for j in range(5))
+        small = R.min_normaliser(x, **m, iterations=iters)
+        assert flag[0] == 0.0 and small > 1e-30 and abs(flag[1] - small) < 1e-9 * small, (n, flag, small)   # not refused: ordinary counts
         assert np.all(np.isfinite(gg)) and np.all(np.isfinite(gf))
         assert np.max(np.abs(gg - gamma.ravel())) < 1e-9
         assert np.max(np.abs(ga - a.ravel()) / a.ravel()) < 1e-9 and np.max(np.abs(gb - b.ravel()) / b.ravel()) < 1e-9
@@ -64,5 +68,5 @@ def test_digamma_of_the_header(exe):
     six roundings of O(1) terms (1e-15).  3e-13 absolute (relative to |ψ| where that is above 1) covers both."""
     pts = [1e-3, 0.5, 1.0, 2.5, 5.999, 6.0, 6.001, 17.0, 1e3, 1e8]
     lines = subprocess.run([exe], input="0\n" + "\n".join(repr(p) for p in pts) + "\n", capture_output=True, text=True, check=True).stdout.split()
-    got = np.array(lines, dtype=np.float64)
+    got = np.array(lines[1:], dtype=np.float64)      # (after the constant of the first line)
     assert np.max(np.abs(got - digamma(pts)) / np.maximum(1.0, np.abs(digamma(pts)))) < 3e-13
