@@ -1085,6 +1085,72 @@ rxhip_status rxhip_arreg_get_statistics(rxhip_engine* e, double* G, double* h, d
 void rxhip_arreg_schedule(int64_t n_rows, int32_t d, int32_t* tile_rows, int32_t* chunks);
 
 /* ------------------------------------------------------------------------------------------
+ * Bayesian multinomial regression under stick-breaking Pólya-Gamma augmentation (reference model test/models/regression/multinomialreg_tests.jl), for
+ * each of n_problems independent problems with N count vectors of K = 2 … 65 categories, d = K − 1:
+ *     ψ ~ MvNormalWeightedMeanPrecision(ξ0, W0);   y[i] ~ MultinomialPolya(N_i, ψ):  p(y_i | ψ) = Π_{k<K} Binomial(y_ik | N_ik, σ(ψ_k))
+ *     N_i = Σ_k y_ik,   N_ik = Σ_{j≥k} y_ij (the stick remainders),   κ_ik = y_ik − N_ik/2,   q(ψ, ω) = q(ψ) Π q(ω_ik)
+ * Counts arrive as doubles; a row with any NaN is missing (ragged batches are padded with such rows).
+ * STATISTICS, once per data set and problem over the observed rows, by one streaming pass whose partials are kept (a second rxhip_run on the same
+ * data launches only the iterations):
+ *     Y_k = Σ_i y_ik (k = 1 … K),  S_k = Σ_i N_ik = Σ_{j≥k} Y_j,  n = observed rows,  lc = Σ_i [lnΓ(N_i + 1) − Σ_{k≤K} lnΓ(y_ik + 1)],
+ *     κ_k = Y_k − S_k/2,  ξ = ξ0 + κ.
+ * Y, S, κ and n are sums of integers below 2⁵³: exact in fp64 in any order.  Only lc depends on the order of summation, which is fixed.
+ * Every offline run starts from init q(ψ) = N(init_mean, init_cov); NULL means the prior's W0⁻¹ξ0, W0⁻¹.
+ * One ITERATION (rxhip_run's argument) is a defined semantic of this engine (csrc/mnreg_kernels.hpp), from the current q(ψ) = N(m, V):
+ *   1. c_k² = m_k² + V_kk,  ω̄_k = S_k·tanh(c_k/2)/(2 c_k) (→ S_k/4 as c_k → 0; exact: the PG mean is linear in its first parameter and every
+ *      observation shares c_k),    P = Σ_k (−S_k ln(2 cosh(c_k/2)) + ½ c_k² ω̄_k);
+ *   2. W = W0 + diag(ω̄),  V = W⁻¹,  m = V ξ.
+ * The posterior of iteration i is q(ψ) after step 2; its free energy is the exact variational free energy at that point,
+ *     F = −[lc + mᵀκ − ½ Σ_k (V_kk + m_k²) ω̄_k + P] + KL(N(m, V) ‖ N(W0⁻¹ξ0, W0⁻¹)).
+ * Both steps are exact coordinate minimisers, so F does not rise.  This is the binomial engine's iteration on the expanded problem (rows x = e_k,
+ * n = N_ik, y = y_ik).  The values per iteration belong to this engine (ReactiveMP's own MultinomialPolya rules were not at hand; the reference's
+ * test asserts an MSE and the decrease of F, not values).
+ * mode = RXHIP_MNREG_ONLINE (the reference's `@autoupdates ξ_ψ, W_ψ = weightedmean_precision(q(ψ))`, iterations = 1, keephistory = T): N is the
+ * number T of rows per series, n_problems the number of series, processed in order.  Before step 1 (ξ, W) = (ξ0, W0).  Step t: its prior is the
+ * current (ξ, W); its starting q(ψ) is N(W⁻¹ξ, W⁻¹) (init_mean / init_cov are not read); it runs `iterations` offline iterations on the single row
+ * t; then ξ += κ_t, W += diag(ω̄_t) with the ω̄ of the last iteration: the step's posterior in weighted-mean / precision form.  F_t is the one-row
+ * free energy of the last iteration against the step's prior.  A missing row leaves (ξ, W) unchanged, repeats the history entry and gives F_t = 0.
+ * rxhip_get_free_energy then holds, per iteration index i, Σ_series Σ_t of the step's F after i + 1 iterations; rxhip_get_free_energy_per_chain
+ * Σ_t F_t per series.
+ * Handle protocol: rxhip_set_data with RXHIP_VAR_Y (the counts, [problem][N][K] row-major; host arrays only, the layout argument is not read;
+ * rxhip_set_data_device: RXHIP_ERR_BADARG), rxhip_run(e, iterations, want_free_energy) — offline ONE resident launch after the pass, online ONE launch
+ * for all T steps, `iterations` per step —, rxhip_mnreg_get_parameters, rxhip_mnreg_get_history, rxhip_mnreg_get_statistics, rxhip_get_free_energy,
+ * rxhip_get_free_energy_per_chain, rxhip_counters, rxhip_destroy; rxhip_run_filter and RXHIP_VAR_X marginals are refused.  With rxhip_set_profiling
+ * the statistics pass is counted under RXHIP_K_GMM_PASS and the resident kernel under RXHIP_K_GMM_UPDATE.  Results are bit-identical from run to
+ * run, with and without the free energy, and for a problem alone or inside a batch (no floating-point atomics, fixed summation order).
+ * RXHIP_ERR_BADARG with a text that names mnreg, before any device call: K outside 2 … 65, N < 1, n_problems outside 1 … 65535, a precision or
+ * covariance that is not symmetric (within 1e-12 of its largest entry) positive definite, NaN or ±Inf in the priors; in the data ±Inf, a negative
+ * or non-integer count, a row sum above 2³¹, and, where n_trials > 0, an observed row whose sum differs from it.  A refused array counts as not
+ * set, and a run without data is RXHIP_ERR_STATE.
+ * ------------------------------------------------------------------------------------------ */
+enum { RXHIP_MNREG_BATCH = 0, RXHIP_MNREG_ONLINE = 1 };
+typedef struct {
+    int64_t N, n_problems;                            /* rows per problem (T online), problems (series online) */
+    int32_t K;                                        /* categories, 2 … 65 */
+    int32_t mode;                                     /* RXHIP_MNREG_BATCH or RXHIP_MNREG_ONLINE */
+    int64_t n_trials;                                 /* > 0: every observed row must sum to it; 0: not checked */
+    const double *prior_xi, *prior_precision;         /* ξ0 [d], W0 [d][d] */
+    const double *init_mean, *init_cov;               /* offline: [d], [d][d] (a covariance) or NULL = the prior's W0⁻¹ξ0, W0⁻¹ */
+    int32_t keep_cov_history;                         /* online: keep the covariance of every step, T·d² doubles per series */
+    int32_t device;
+    void* stream;
+} rxhip_mnreg_desc;
+rxhip_status rxhip_mnreg_create(const rxhip_mnreg_desc* desc, rxhip_engine** out);
+/* offline: q(ψ) after EVERY iteration of the last run: mean [iterations][problems][d], cov [iterations][problems][d][d], F [iterations][problems];
+ * online: the last step's mean [series][d], cov [series][d][d], F_T [series].  Any pointer may be NULL (free_energy: RXHIP_ERR_STATE if the run
+ * was without it) */
+rxhip_status rxhip_mnreg_get_parameters(rxhip_engine* e, double* mean, double* cov, double* free_energy);
+/* online: q(ψ) after every step: mean [T][series][d], var [T][series][d] (the diagonal of the covariance), cov [T][series][d][d] (RXHIP_ERR_STATE
+ * without keep_cov_history), free_energy F_t [T][series]; any pointer may be NULL */
+rxhip_status rxhip_mnreg_get_history(rxhip_engine* e, double* mean, double* var, double* cov, double* free_energy);
+/* offline: the statistics of the data in place, per problem (the pass alone; it is run if it has not been): Y [problems][K], S [problems][K]
+ * (S_K = Y_K), lc and n [problems]; any pointer may be NULL; RXHIP_ERR_STATE without data */
+rxhip_status rxhip_mnreg_get_statistics(rxhip_engine* e, double* Y, double* S, double* lc, double* n);
+/* the pass's schedule for N rows of K categories: rows per tile and workgroups (chunks) per problem — a function of N and K only; a workgroup
+ * strides over ceil(tiles / chunks) tiles at most.  Zeros for arguments outside the engine's range. */
+void rxhip_mnreg_schedule(int64_t N, int32_t K, int32_t* tile_rows, int32_t* chunks);
+
+/* ------------------------------------------------------------------------------------------
  * Several GPUs (one process per GPU; chains / series / points shard).  The path's only exchange is the sum
  * over shards of the Bethe free energy (reference: the single `sumreduce` of src/model/plugins/reactivemp_free_energy.jl:99-123
  * over ALL nodes and variables of the model) and, for the mixture, of the responsibility-weighted statistics that

@@ -1,7 +1,7 @@
 // engine.hpp — what every translation unit behind the C ABI shares: the engine object, its family table, the error path, the device guards and the
 // helpers every creator and run uses.
 //   rxhip.hip       runtime (pools, arenas), the state-space and drift-chain engines, the entry points common to all engines, the shared helpers
-//   vmp_engines.hip the mixture, HGF, probit, HMM, latent-AR and binomial-regression engines and their family rows
+//   vmp_engines.hip the mixture, HGF, probit, HMM, latent-AR, binomial-, linear- and multinomial-regression engines and their family rows
 //   graph_abi.hip   the graph entry points: host-only lowering (graph_lowering.hpp), rxhip_create, the node-array executor's rxhip_tree_* wrappers
 //   rccl_abi.hip    the RCCL exchange entry points (rxhip_comm_*, rxhip_allreduce_free_energy, rxhip_gmm_allreduce_statistics)
 //   tree_engine.hip the node-array executor itself (behind tree_engine.hpp)
@@ -89,6 +89,9 @@ enum class EngineKind : int {
                   // (arreg_kernels.hpp), regressor mode: X and y through the family's own set_data, host arrays only
     ArregLagged = 10,   // … lagged mode: the raw series through the common ingest, host or device (the same run, release and getters; the two rows
                         // differ in how the data arrive, which is what a row of the family table says)
+    Mnreg = 11,         // multinomial regression, batched stick-breaking Pólya-Gamma VMP from the column sums (mnreg_kernels.hpp), offline: every
+                        // iteration of a run in one resident launch
+    MnregOnline = 12,   // … streamed one row at a time with the posterior fed back as the next prior (the same plumbing, release and getters)
 };
 struct rxhip_engine : rxhip_engine_life {
     // one device allocation holds every buffer of a state-space engine (creation / destruction cost two driver calls
@@ -160,6 +163,14 @@ struct rxhip_engine : rxhip_engine_life {
         double *d_X = nullptr, *d_yreg = nullptr, *d_cst = nullptr, *d_part = nullptr, *d_hist = nullptr, *d_fe = nullptr;
         bool have_X = false, have_y = false, stats_ready = false;
     } ar;
+    struct Mnreg {    // kinds 11 and 12: the counts, constants, the pass's partials (kept: the statistics of the data in place), offline history and free energies;
+                      // online: mean | variance history, F_t, per-iteration sums, the last step's mean | covariance, the covariance history on request
+        int K = 0, d = 0, online = 0, keep_cov = 0, nchunk = 0, hist_cap = 0;
+        long long n_trials = 0;
+        double *d_data = nullptr, *d_cst = nullptr, *d_part = nullptr, *d_hist = nullptr, *d_fe = nullptr, *d_on = nullptr, *d_oncov = nullptr, *d_feit = nullptr;
+        bool have = false, stats_ready = false;
+        uint64_t stats_launches = 0;
+    } mn;
     struct Gmm {
         long long N = 0;
         int K = 0, KT = 0, materialize = 0, nblocks = 0, it = 0, iterations = 0, hist_cap = 0;

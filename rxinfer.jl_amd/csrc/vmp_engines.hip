@@ -8,6 +8,7 @@
 //   binreg    binomial regression, Pólya-Gamma VMP (binreg_kernels.hpp)
 //   arreg     regression / autoregression with unknown coefficients and noise precision, Normal-Gamma VMP from the statistics (arreg_kernels.hpp): two
 //             rows, X and y from the host or the raw series through the common ingest
+//   mnreg     multinomial regression, stick-breaking Pólya-Gamma VMP from the column sums (mnreg_kernels.hpp): two rows, offline and online
 // The runtime they share with the state-space engines — streams, profiling events, the engine handle, the creation and run helpers — is rxhip.hip's
 // (engine.hpp).  No kernels of the state-space path live here.
 #include "../../include/rxhip.h"
@@ -31,6 +32,7 @@
 #include "lar_kernels.hpp"
 #include "binreg_kernels.hpp"
 #include "arreg_kernels.hpp"
+#include "mnreg_kernels.hpp"
 #include "engine.hpp"
 
 using namespace rxhip;
@@ -1268,6 +1270,259 @@ rxhip_status rxhip_arreg_get_statistics(rxhip_engine* e, double* Gout, double* h
 
 }  // extern "C"
 
+// ---- multinomial regression, stick-breaking Pólya-Gamma VMP from the column sums (mnreg_kernels.hpp): two rows, offline and online ----
+static bool is_mnreg(const rxhip_engine* e) { return e->kind == EngineKind::Mnreg || e->kind == EngineKind::MnregOnline; }
+
+static MnregParams mnreg_params(const rxhip_engine* e) {
+    const auto& m = e->mn;
+    const size_t C = (size_t)e->n_chains, T = (size_t)e->T, d = (size_t)m.d;
+    MnregParams p;
+    p.N = e->T; p.C = e->n_chains; p.K = m.K; p.d = m.d; p.nchunk = m.nchunk; p.want_fe = 0; p.iterations = 0; p.keep_cov = m.keep_cov;
+    p.data = m.d_data; p.cst = m.d_cst; p.part = m.d_part;
+    if (m.online) {
+        p.hist_m = m.d_on; p.hist_v = m.d_on + T * C * d; p.fe = m.d_on + 2 * T * C * d; p.last = m.d_on + 2 * T * C * d + T * C;
+    } else {
+        p.hist_m = m.d_hist; p.hist_v = m.d_hist + (size_t)m.hist_cap * C * d; p.fe = m.d_fe; p.last = nullptr;
+    }
+    p.hist_cov = m.d_oncov; p.fe_it = m.d_feit;
+    p.fe_total = e->d_fe_total; p.fe_chain = e->d_fe_chain; p.status = e->d_status;
+    return p;
+}
+
+extern "C" {
+
+void rxhip_mnreg_schedule(int64_t N, int32_t K, int32_t* tile_rows, int32_t* chunks) {
+    const bool ok = N >= 1 && K >= mnreg::kMinK && K <= mnreg::kMaxK;
+    if (tile_rows) *tile_rows = ok ? mnreg::tile_rows(K) : 0;
+    if (chunks) *chunks = ok ? mnreg::chunks(N, K) : 0;
+}
+
+rxhip_status rxhip_mnreg_create(const rxhip_mnreg_desc* ds, rxhip_engine** out) {
+    if (!out) return RXHIP_ERR_BADARG;
+    *out = nullptr;
+    if (!ds) return RXHIP_ERR_BADARG;
+    rxhip_engine* e = new rxhip_engine();   // from here on every refusal carries a text (rxhip_last_error; the caller destroys the handle)
+    *out = e;
+    e->kind = ds->mode == RXHIP_MNREG_ONLINE ? EngineKind::MnregOnline : EngineKind::Mnreg;
+    e->device = -1;
+    if (ds->mode != RXHIP_MNREG_BATCH && ds->mode != RXHIP_MNREG_ONLINE) return fail(e, RXHIP_ERR_BADARG, "mnreg: mode must be RXHIP_MNREG_BATCH or RXHIP_MNREG_ONLINE (got %d)", ds->mode);
+    if (ds->K < mnreg::kMinK || ds->K > mnreg::kMaxK) return fail(e, RXHIP_ERR_BADARG, "mnreg: K must be %d … %d (got %d)", mnreg::kMinK, mnreg::kMaxK, ds->K);
+    if (ds->N < 1) return fail(e, RXHIP_ERR_BADARG, "mnreg: N must be at least 1 (got %lld)", (long long)ds->N);
+    if (ds->n_problems < 1 || ds->n_problems > 65535) return fail(e, RXHIP_ERR_BADARG, "mnreg: n_problems must be 1 … 65535 (got %lld)", (long long)ds->n_problems);
+    if (ds->n_trials < 0 || ds->n_trials > (1LL << 31)) return fail(e, RXHIP_ERR_BADARG, "mnreg: n_trials must be 0 (not checked) … 2^31 (got %lld)", (long long)ds->n_trials);
+    if (!ds->prior_xi || !ds->prior_precision) return fail(e, RXHIP_ERR_BADARG, "mnreg: prior_xi and prior_precision are required");
+    const int K = ds->K, d = K - 1;
+    for (int i = 0; i < d; ++i) {
+        if (!std::isfinite(ds->prior_xi[i])) return fail(e, RXHIP_ERR_BADARG, "mnreg: prior_xi must be finite");
+        if (ds->init_mean && !std::isfinite(ds->init_mean[i])) return fail(e, RXHIP_ERR_BADARG, "mnreg: init_mean must be finite");
+    }
+    std::vector<double> w0, v0, vinit, winit;
+    double ld_w0 = 0.0, ld = 0.0;
+    if (!spd_inverse(d, ds->prior_precision, w0, v0, &ld_w0)) return fail(e, RXHIP_ERR_BADARG, "mnreg: prior_precision is not symmetric positive definite");
+    if (ds->init_cov) {
+        if (!spd_inverse(d, ds->init_cov, vinit, winit, &ld)) return fail(e, RXHIP_ERR_BADARG, "mnreg: init_cov is not symmetric positive definite");
+    } else
+        vinit = v0;   // the prior's own covariance
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(e, RXHIP_ERR_NO_DEVICE, "no HIP device visible");
+    auto& m = e->mn;
+    m.K = K; m.d = d; m.online = ds->mode == RXHIP_MNREG_ONLINE; m.keep_cov = m.online && ds->keep_cov_history ? 1 : 0; m.n_trials = ds->n_trials;
+    m.nchunk = mnreg::chunks(ds->N, K);
+    e->T = ds->N;
+    e->n_chains = ds->n_problems;
+    e->d = e->dy = e->dpad = 1;
+    DevGuard guard;
+    if (rxhip_status st = open_device(e, guard, ds->device, ds->stream, ndev)) return st;
+    // constants: ξ0 | W0 | m0 = W0⁻¹ξ0 | ln det W0 | initial m | initial V
+    std::vector<double> cst((size_t)mnreg::nconst(d), 0.0);
+    {
+        double *xi0 = cst.data(), *W0 = xi0 + d, *m0 = W0 + d * d, *im = m0 + d + 1, *iv = im + d;
+        for (int i = 0; i < d; ++i) xi0[i] = ds->prior_xi[i];
+        for (int i = 0; i < d * d; ++i) { W0[i] = w0[(size_t)i]; iv[i] = vinit[(size_t)i]; }
+        for (int i = 0; i < d; ++i) {
+            double s = 0.0;
+            for (int j = 0; j < d; ++j) s += v0[(size_t)(i * d + j)] * xi0[j];
+            m0[i] = s;
+        }
+        m0[d] = ld_w0;
+        for (int i = 0; i < d; ++i) im[i] = ds->init_mean ? ds->init_mean[i] : m0[i];
+    }
+    const size_t C = (size_t)ds->n_problems, N = (size_t)ds->N, D = (size_t)d;
+    HIPCHK(e, hipMalloc(&m.d_cst, sizeof(double) * cst.size()));
+    HIPCHK(e, hipMemcpy(m.d_cst, cst.data(), sizeof(double) * cst.size(), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMalloc(&m.d_data, sizeof(double) * C * N * (size_t)K));
+    if (m.online) {
+        HIPCHK(e, hipMalloc(&m.d_on, sizeof(double) * (2 * N * C * D + N * C + C * (D + D * D))));
+        if (m.keep_cov) HIPCHK(e, hipMalloc(&m.d_oncov, sizeof(double) * N * C * D * D));
+    } else
+        HIPCHK(e, hipMalloc(&m.d_part, sizeof(double) * C * (size_t)m.nchunk * (size_t)mnreg::npart(K)));
+    HIPCHK(e, hipMalloc(&e->d_fe_chain, sizeof(double) * C));
+    HIPCHK(e, hipMemset(e->d_fe_chain, 0, sizeof(double) * C));
+    if (rxhip_status st = reserve(e, &e->fe_total_cap, 32, {{&e->d_fe_total, 1}})) return st;
+    HIPCHK(e, hipMalloc(&e->d_status, sizeof(int)));
+    HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
+    return RXHIP_OK;
+}
+
+}  // extern "C"
+
+// the counts, checked on the host before anything reaches the device: ±Inf, a negative or non-integer count, a row sum above 2³¹ or different from the
+// descriptor's n_trials; a row with any NaN is missing.  A refused array counts as not set.
+static rxhip_status mnreg_set_data(rxhip_engine* e, int32_t var_id, const double* host, size_t n) {
+    auto& m = e->mn;
+    const size_t C = (size_t)e->n_chains, N = (size_t)e->T, K = (size_t)m.K, need = C * N * K;
+    if (var_id != RXHIP_VAR_Y) return fail(e, RXHIP_ERR_BADARG, "set_data: variable %d is not a data variable of the multinomial regression engine (mnreg)", var_id);
+    if (!host || n != need) return fail(e, RXHIP_ERR_BADARG, "set_data: mnreg expected %zu doubles, got %zu", need, n);
+    m.have = false;
+    m.stats_ready = false;
+    for (size_t r = 0; r < C * N; ++r) {
+        const double* y = host + r * K;
+        bool missing = false;
+        double sum = 0.0;
+        for (size_t k = 0; k < K; ++k) {
+            const double v = y[k];
+            if (v != v) { missing = true; continue; }
+            if (std::isinf(v)) return fail(e, RXHIP_ERR_BADARG, "set_data: mnreg count %zu of row %zu is infinite", k, r);
+            if (v < 0.0 || v != std::floor(v)) return fail(e, RXHIP_ERR_BADARG, "set_data: mnreg count %zu of row %zu is not a non-negative integer (%g)", k, r, v);
+            sum += v;
+        }
+        if (missing) continue;
+        if (sum > 2147483648.0) return fail(e, RXHIP_ERR_BADARG, "set_data: mnreg row %zu sums to %g, above 2^31", r, sum);
+        if (m.n_trials > 0 && sum != (double)m.n_trials)
+            return fail(e, RXHIP_ERR_BADARG, "set_data: mnreg row %zu sums to %g, the descriptor's n_trials is %lld", r, sum, (long long)m.n_trials);
+    }
+    SET_DEVICE(e);
+    HIPCHK(e, hipMemcpyAsync(m.d_data, host, sizeof(double) * need, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    m.have = true;
+    return RXHIP_OK;
+}
+
+// the refusal of an engine without its data; then (offline) the statistics pass, once per data set
+static rxhip_status mnreg_statistics(rxhip_engine* e, const char* who) {
+    auto& m = e->mn;
+    if (!m.have) return fail(e, RXHIP_ERR_STATE, "%s: no observations (the multinomial regression engine, mnreg, takes its counts through rxhip_set_data with RXHIP_VAR_Y)", who);
+    if (m.online || m.stats_ready) return RXHIP_OK;
+    const MnregParams p = mnreg_params(e);
+    rxhip_status st;
+    if ((st = prof_begin(e, RXHIP_K_GMM_PASS))) return st;
+    hipLaunchKernelGGL(k_mnreg_stats, dim3((unsigned)p.nchunk, (unsigned)p.C), dim3(256), 0, e->stream, p);
+    if ((st = prof_end(e))) return st;
+    HIPCHK(e, hipGetLastError());
+    m.stats_ready = true;
+    ++m.stats_launches;
+    return RXHIP_OK;
+}
+
+static rxhip_status mnreg_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
+    if (rxhip_status st = run_preamble(e, iterations, false)) return st;   // (its own data flag: mnreg_statistics)
+    SET_DEVICE(e);
+    auto& m = e->mn;
+    if (rxhip_status st = mnreg_statistics(e, "run")) return st;
+    const size_t C = (size_t)e->n_chains, d = (size_t)m.d;
+    rxhip_status rs = reserve(e, &e->fe_total_cap, iterations, {{&e->d_fe_total, 1}});
+    if (!rs) {
+        if (m.online) rs = reserve(e, &m.hist_cap, iterations, {{&m.d_feit, C}});
+        else rs = reserve(e, &m.hist_cap, iterations, {{&m.d_hist, C * (d + d * d)}, {&m.d_fe, C}});
+    }
+    if (rs) return rs;
+    MnregParams p = mnreg_params(e);
+    p.want_fe = want_fe ? 1 : 0;
+    p.iterations = iterations;
+    const bool big = m.d > mnreg::kSmallMaxD;
+    rxhip_status st;
+    if ((st = prof_begin(e, RXHIP_K_GMM_UPDATE))) return st;
+    if (m.online) {   // ONE launch for all T steps of every series
+        if (big) hipLaunchKernelGGL(k_mnreg_online<true>, dim3((unsigned)C), dim3(64), 0, e->stream, p);
+        else hipLaunchKernelGGL(k_mnreg_online<false>, dim3((unsigned)C), dim3(64), 0, e->stream, p);
+    } else {          // every run starts from the initial q(ψ); ONE launch for all iterations
+        if (big) hipLaunchKernelGGL(k_mnreg_iterate<true>, dim3((unsigned)C), dim3(64), 0, e->stream, p);
+        else hipLaunchKernelGGL(k_mnreg_iterate<false>, dim3((unsigned)C), dim3(64), 0, e->stream, p);
+    }
+    if ((st = prof_end(e))) return st;
+    if (want_fe && C > 1) hipLaunchKernelGGL(k_mnreg_fe_total, dim3((unsigned)iterations), dim3(256), 0, e->stream, p, (const double*)(m.online ? p.fe_it : p.fe));
+    HIPCHK(e, hipGetLastError());
+    finish_run(e, iterations, want_fe != 0);
+    // reference-equivalent events per problem and iteration (per step online): per row the MultinomialPolya node's message toward ψ and its ω marginals;
+    // the prior's message; the products at ψ
+    const uint64_t Cs = (uint64_t)C, N = (uint64_t)e->T, I = (uint64_t)iterations;
+    e->rule_calls = I * Cs * (m.online ? 2 * N : N + 1);
+    e->products = I * Cs * N;
+    e->marginals = I * Cs * (m.online ? 2 * N : N + 1);
+    return RXHIP_OK;
+}
+
+extern "C" {
+
+rxhip_status rxhip_mnreg_get_parameters(rxhip_engine* e, double* mean, double* cov, double* free_energy) {
+    if (!e || !is_mnreg(e)) return RXHIP_ERR_BADARG;
+    if (!e->ran) return fail(e, RXHIP_ERR_STATE, "mnreg_get_parameters: no run yet");
+    if (free_energy && !e->last_want_fe) return fail(e, RXHIP_ERR_STATE, "mnreg_get_parameters: free energy was not requested in the last run");
+    SET_DEVICE(e);
+    const size_t C = (size_t)e->n_chains, d = (size_t)e->mn.d, T = (size_t)e->T;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    const MnregParams p = mnreg_params(e);
+    if (e->mn.online) {   // the last step: mean [series][d], cov [series][d][d], F_T [series]
+        std::vector<double> last(C * (d + d * d));
+        HIPCHK(e, hipMemcpy(last.data(), p.last, sizeof(double) * last.size(), hipMemcpyDeviceToHost));
+        for (size_t s = 0; s < C; ++s) {
+            if (mean) std::memcpy(mean + s * d, &last[s * (d + d * d)], sizeof(double) * d);
+            if (cov) std::memcpy(cov + s * d * d, &last[s * (d + d * d) + d], sizeof(double) * d * d);
+        }
+        if (free_energy) HIPCHK(e, hipMemcpy(free_energy, p.fe + (T - 1) * C, sizeof(double) * C, hipMemcpyDeviceToHost));
+        return RXHIP_OK;
+    }
+    const size_t rows = (size_t)e->last_iterations * C;
+    if (mean) HIPCHK(e, hipMemcpy(mean, p.hist_m, sizeof(double) * rows * d, hipMemcpyDeviceToHost));
+    if (cov) HIPCHK(e, hipMemcpy(cov, p.hist_v, sizeof(double) * rows * d * d, hipMemcpyDeviceToHost));
+    if (free_energy) HIPCHK(e, hipMemcpy(free_energy, p.fe, sizeof(double) * rows, hipMemcpyDeviceToHost));
+    return RXHIP_OK;
+}
+
+rxhip_status rxhip_mnreg_get_history(rxhip_engine* e, double* mean, double* var, double* cov, double* free_energy) {
+    if (!e || !is_mnreg(e)) return RXHIP_ERR_BADARG;
+    if (!e->mn.online) return fail(e, RXHIP_ERR_STATE, "mnreg_get_history: the engine was not created with RXHIP_MNREG_ONLINE");
+    if (!e->ran) return fail(e, RXHIP_ERR_STATE, "mnreg_get_history: no run yet");
+    if (cov && !e->mn.keep_cov) return fail(e, RXHIP_ERR_STATE, "mnreg_get_history: the covariance history was not kept (keep_cov_history)");
+    if (free_energy && !e->last_want_fe) return fail(e, RXHIP_ERR_STATE, "mnreg_get_history: free energy was not requested in the last run");
+    SET_DEVICE(e);
+    const size_t rows = (size_t)e->T * (size_t)e->n_chains, d = (size_t)e->mn.d;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    const MnregParams p = mnreg_params(e);
+    if (mean) HIPCHK(e, hipMemcpy(mean, p.hist_m, sizeof(double) * rows * d, hipMemcpyDeviceToHost));
+    if (var) HIPCHK(e, hipMemcpy(var, p.hist_v, sizeof(double) * rows * d, hipMemcpyDeviceToHost));
+    if (cov) HIPCHK(e, hipMemcpy(cov, p.hist_cov, sizeof(double) * rows * d * d, hipMemcpyDeviceToHost));
+    if (free_energy) HIPCHK(e, hipMemcpy(free_energy, p.fe, sizeof(double) * rows, hipMemcpyDeviceToHost));
+    return RXHIP_OK;
+}
+
+rxhip_status rxhip_mnreg_get_statistics(rxhip_engine* e, double* Yout, double* Sout, double* lcout, double* nout) {
+    if (!e || !is_mnreg(e)) return RXHIP_ERR_BADARG;
+    if (e->mn.online) return fail(e, RXHIP_ERR_STATE, "mnreg_get_statistics: an online engine keeps no statistics of the whole data set");
+    SET_DEVICE(e);
+    if (rxhip_status st = mnreg_statistics(e, "mnreg_get_statistics")) return st;
+    const size_t C = (size_t)e->n_chains, K = (size_t)e->mn.K, NP = (size_t)mnreg::npart((int)K), nchunk = (size_t)e->mn.nchunk;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    std::vector<double> part(C * nchunk * NP), tot(NP), S(K), kap(K);
+    HIPCHK(e, hipMemcpy(part.data(), e->mn.d_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost));
+    for (size_t s = 0; s < C; ++s) {
+        for (size_t q = 0; q < NP; ++q) {   // ascending chunk order, as k_mnreg_iterate adds them
+            double acc = part[s * nchunk * NP + q];
+            for (size_t c = 1; c < nchunk; ++c) acc += part[(s * nchunk + c) * NP + q];
+            tot[q] = acc;
+        }
+        mnreg::suffix((int)K, tot.data(), S.data(), kap.data());
+        S[K - 1] = tot[K - 1];
+        if (Yout) std::memcpy(Yout + s * K, tot.data(), sizeof(double) * K);
+        if (Sout) std::memcpy(Sout + s * K, S.data(), sizeof(double) * K);
+        if (nout) nout[s] = tot[K];
+        if (lcout) lcout[s] = tot[K + 1];
+    }
+    return RXHIP_OK;
+}
+
+}  // extern "C"
+
 // every observation of a hidden Markov model engine is an integer code 0 … M−1 or NaN
 static rxhip_status hmm_check_data(rxhip_engine* e) {
     char msg[128];
@@ -1451,7 +1706,16 @@ const EngineFamily* rxhip::vmp_family(EngineKind kind) {
     const auto arreg_release = [](E* e) { free_buffers(e, {&e->ar.d_X, &e->ar.d_yreg, &e->ar.d_cst, &e->ar.d_part, &e->ar.d_hist, &e->ar.d_fe}); };
     static const EngineFamily arreg = {arreg_run_async, false, nullptr, arreg_set_data, arreg_host_only, nullptr, false, arreg_release};
     static const EngineFamily arreg_lagged = {arreg_run_async, false, arreg_check_data, nullptr, nullptr, nullptr, false, arreg_release};
+    // multinomial regression: two rows that share everything (the kind tells the run which resident kernel to launch)
+    const char* const mnreg_host_only = "set_data_device: the multinomial regression engine (mnreg) checks its counts on the host (rxhip_set_data)";
+    const auto mnreg_release = [](E* e) {
+        free_buffers(e, {&e->mn.d_data, &e->mn.d_cst, &e->mn.d_part, &e->mn.d_hist, &e->mn.d_fe, &e->mn.d_on, &e->mn.d_oncov, &e->mn.d_feit});
+    };
+    static const EngineFamily mnreg_row = {mnreg_run_async, false, nullptr, mnreg_set_data, mnreg_host_only, nullptr, false, mnreg_release};
+    static const EngineFamily mnreg_online = {mnreg_run_async, false, nullptr, mnreg_set_data, mnreg_host_only, nullptr, false, mnreg_release};
     switch (kind) {
+        case EngineKind::Mnreg: return &mnreg_row;
+        case EngineKind::MnregOnline: return &mnreg_online;
         case EngineKind::Arreg: return &arreg;
         case EngineKind::ArregLagged: return &arreg_lagged;
         case EngineKind::Mixture: return &mixture;

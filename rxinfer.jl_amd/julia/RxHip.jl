@@ -1045,6 +1045,97 @@ function binreg_parameters(e::Engine, iterations::Integer; free_energy::Bool = t
     return mean, cov, fe
 end
 
+# mirrors rxhip_mnreg_desc (include/rxhip.h); field order and types must match the C struct
+struct MnregDesc
+    N::Int64
+    n_problems::Int64
+    K::Int32
+    mode::Int32
+    n_trials::Int64
+    prior_xi::Ptr{Float64}
+    prior_precision::Ptr{Float64}
+    init_mean::Ptr{Float64}
+    init_cov::Ptr{Float64}
+    keep_cov_history::Int32
+    device::Int32
+    stream::Ptr{Cvoid}
+end
+const RXHIP_MNREG_BATCH = Int32(0)
+const RXHIP_MNREG_ONLINE = Int32(1)
+"""
+    MultinomialRegressionEngine(prior_xi, prior_precision; N, n_problems = 1, n_trials = 0, online = false, keep_cov_history = false,
+                                init = nothing, device = -1)
+
+`ψ ~ MvNormalWeightedMeanPrecision(prior_xi, prior_precision); y[i] ~ MultinomialPolya(N, ψ)` of test/models/regression/multinomialreg_tests.jl
+for `n_problems` independent problems of `N` count vectors with K = length(prior_xi) + 1 categories (batched stick-breaking Pólya-Gamma VMP,
+rxhip_mnreg_desc).  `online = true` streams the rows with `ξ_ψ, W_ψ = weightedmean_precision(q(ψ))` fed back.
+Then `mnreg_set_data!(e, Y)`, `run!`, `mnreg_parameters(e, iterations)` or `mnreg_history(e)`.
+"""
+function MultinomialRegressionEngine(prior_xi::AbstractVector, prior_precision::AbstractMatrix; N::Integer, n_problems::Integer = 1, n_trials::Integer = 0,
+                                     online::Bool = false, keep_cov_history::Bool = false, init = nothing, device::Integer = -1, stream = nothing)
+    d = length(prior_xi)
+    xi, w0 = rowmajor(prior_xi), rowmajor(prior_precision)
+    im = init === nothing ? Float64[] : rowmajor(init[1])
+    iv = init === nothing ? Float64[] : rowmajor(init[2])
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    st = GC.@preserve xi w0 im iv begin
+        desc = MnregDesc(N, n_problems, d + 1, online ? RXHIP_MNREG_ONLINE : RXHIP_MNREG_BATCH, n_trials, pointer(xi), pointer(w0),
+                         isempty(im) ? Ptr{Float64}(C_NULL) : pointer(im), isempty(iv) ? Ptr{Float64}(C_NULL) : pointer(iv), keep_cov_history ? 1 : 0,
+                         device, stream_handle(stream))
+        ccall((:rxhip_mnreg_create, librxhip), Int32, (Ref{MnregDesc}, Ref{Ptr{Cvoid}}), desc, h)
+    end
+    e = Engine(h[], d, 1, N, n_problems, 0)
+    if st != RXHIP_OK
+        h[] != C_NULL && (try check(e, st) finally ccall((:rxhip_destroy, librxhip), Int32, (Ptr{Cvoid},), h[]) end)
+        throw(RxHipError(st, unsafe_string(ccall((:rxhip_status_string, librxhip), Cstring, (Int32,), st))))
+    end
+    finalizer(destroy!, e)
+    return e
+end
+"""Y: one vector of count vectors per problem (or one such vector), as the reference's `data = (y = X,)`; a count vector with a `NaN` is missing."""
+function mnreg_set_data!(e::Engine, Y)
+    ys = Y[1] isa AbstractVector{<:Real} ? [Y] : Y
+    a = Float64[]
+    for prob in ys, row in prob
+        append!(a, Float64.(row))
+    end
+    check(e, ccall((:rxhip_set_data, librxhip), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Csize_t, Int32), e.handle, RXHIP_VAR_Y, a, length(a), Int32(0)))
+    return e
+end
+"""offline: q(ψ) after every one of the `iterations` of the last run: (means d × problems × iterations, covariances d × d × problems × iterations,
+free energies problems × iterations or `nothing`) — the C arrays `[iterations][problems][…]` seen column-major."""
+function mnreg_parameters(e::Engine, iterations::Integer; free_energy::Bool = true)
+    mean = Array{Float64}(undef, e.d, e.n_chains, iterations)
+    cov = Array{Float64}(undef, e.d, e.d, e.n_chains, iterations)
+    fe = free_energy ? Array{Float64}(undef, e.n_chains, iterations) : nothing
+    check(e, ccall((:rxhip_mnreg_get_parameters, librxhip), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), e.handle, mean, cov,
+                   free_energy ? fe : Ptr{Float64}(C_NULL)))
+    return mean, cov, fe
+end
+"""online: q(ψ) after every step: (means d × series × T, variances d × series × T, F_t series × T or `nothing`)."""
+function mnreg_history(e::Engine; free_energy::Bool = true)
+    mean = Array{Float64}(undef, e.d, e.n_chains, e.T)
+    var = Array{Float64}(undef, e.d, e.n_chains, e.T)
+    fe = free_energy ? Array{Float64}(undef, e.n_chains, e.T) : nothing
+    check(e, ccall((:rxhip_mnreg_get_history, librxhip), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), e.handle, mean, var,
+                   Ptr{Float64}(C_NULL), free_energy ? fe : Ptr{Float64}(C_NULL)))
+    return mean, var, fe
+end
+"""offline, the pass alone: (Y K × problems, S K × problems, lc, n per problem)."""
+function mnreg_statistics(e::Engine)
+    K = e.d + 1
+    Y, S = Array{Float64}(undef, K, e.n_chains), Array{Float64}(undef, K, e.n_chains)
+    lc, n = Vector{Float64}(undef, e.n_chains), Vector{Float64}(undef, e.n_chains)
+    check(e, ccall((:rxhip_mnreg_get_statistics, librxhip), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), e.handle, Y, S, lc, n))
+    return Y, S, lc, n
+end
+"""(rows per tile, workgroups per problem) of the statistics pass for N rows of K categories."""
+function mnreg_schedule(N::Integer, K::Integer)
+    tr, ch = Ref{Int32}(0), Ref{Int32}(0)
+    ccall((:rxhip_mnreg_schedule, librxhip), Cvoid, (Int64, Int32, Ref{Int32}, Ref{Int32}), N, K, tr, ch)
+    return Int(tr[]), Int(ch[])
+end
+
 # mirrors rxhip_arreg_desc (include/rxhip.h); field order and types must match the C struct
 struct ArregDesc
     N::Int64

@@ -139,6 +139,15 @@ class ArregDesc(ctypes.Structure):   # rxhip_arreg_desc
                 ("share_parameters", ctypes.c_int32), ("device", ctypes.c_int32), ("stream", ctypes.c_void_p)]
 
 
+MNREG_BATCH, MNREG_ONLINE = 0, 1
+
+
+class MnregDesc(ctypes.Structure):   # rxhip_mnreg_desc
+    _fields_ = [("N", ctypes.c_int64), ("n_problems", ctypes.c_int64), ("K", ctypes.c_int32), ("mode", ctypes.c_int32), ("n_trials", ctypes.c_int64)] + [
+        (n, c_double_p) for n in ("prior_xi", "prior_precision", "init_mean", "init_cov")] + [
+        ("keep_cov_history", ctypes.c_int32), ("device", ctypes.c_int32), ("stream", ctypes.c_void_p)]
+
+
 class NoisePrior(ctypes.Structure):   # rxhip_noise_prior
     _fields_ = [("nu0", ctypes.c_double), ("S0", c_double_p), ("init_nu", ctypes.c_double), ("init_V", c_double_p)]
 
@@ -253,6 +262,11 @@ SYMBOLS = [
     ("rxhip_arreg_get_parameters", ctypes.c_int32, [_H, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("rxhip_arreg_get_statistics", ctypes.c_int32, [_H, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("rxhip_arreg_schedule", None, [ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    ("rxhip_mnreg_create", ctypes.c_int32, [ctypes.POINTER(MnregDesc), ctypes.POINTER(_H)]),
+    ("rxhip_mnreg_get_parameters", ctypes.c_int32, [_H, c_double_p, c_double_p, c_double_p]),
+    ("rxhip_mnreg_get_history", ctypes.c_int32, [_H, c_double_p, c_double_p, c_double_p, c_double_p]),
+    ("rxhip_mnreg_get_statistics", ctypes.c_int32, [_H, c_double_p, c_double_p, c_double_p, c_double_p]),
+    ("rxhip_mnreg_schedule", None, [ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     ("rxhip_hgf_get_history", ctypes.c_int32, [_H, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_int32]),
     ("rxhip_set_profiling", ctypes.c_int32, [_H, ctypes.c_int32]),
     ("rxhip_get_kernel_times", ctypes.c_int32, [_H, c_double_p, c_u64_p]),

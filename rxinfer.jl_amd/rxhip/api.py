@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RxHipError
-from .engine import DriftChainEngine, GMMEngine, HGFEngine, LGSSMEngine, MvGMMEngine, ProbitEngine, HMMEngine, LAREngine, BinomialRegressionEngine, ARRegressionEngine
+from .engine import DriftChainEngine, GMMEngine, HGFEngine, LGSSMEngine, MvGMMEngine, ProbitEngine, HMMEngine, LAREngine, BinomialRegressionEngine, ARRegressionEngine, MultinomialRegressionEngine
 
 
 @dataclass
@@ -430,6 +430,77 @@ def _infer_binreg(model, data, iterations, free_energy, options, catch_exception
 
 
 @dataclass
+class MultinomialRegression:
+    """`ψ ~ MvNormalWeightedMeanPrecision(ξ0, W0); y[i] ~ MultinomialPolya(N, ψ)` with `q(ψ, ω) = q(ψ)Πq(ω_ik)`
+    (test/models/regression/multinomialreg_tests.jl)."""
+    prior_xi: np.ndarray
+    prior_precision: np.ndarray
+    n_trials: Optional[int] = None
+    init: Optional[tuple] = None
+
+
+def multinomial_regression(prior_xi, prior_precision, n_trials=None, init=None):
+    """prior_xi [K − 1], prior_precision [K − 1][K − 1]: the weighted mean ξ0 and precision W0 of ψ's prior; n_trials: the N every observed count
+    vector must sum to (None: not checked); init: (mean, covariance) of the initial q(ψ) of an offline run, None = the prior's own W0⁻¹ξ0, W0⁻¹.
+    Online (`autoupdates`), the prior is the initial q(ψ) in weighted-mean / precision form."""
+    f = lambda v: None if v is None else (np.asarray(v[0], dtype=np.float64), np.asarray(v[1], dtype=np.float64))
+    return MultinomialRegression(np.asarray(prior_xi, dtype=np.float64), np.asarray(prior_precision, dtype=np.float64),
+                                 None if n_trials is None else int(n_trials), f(init))
+
+
+def logistic_stick_breaking(m):
+    """The K probabilities of the stick-breaking map of ψ = m [K − 1]: p_k = σ(m_k)·(1 − Σ_{j<k} p_j), p_K = the remainder
+    (logistic_stic_breaking of the reference's test/utiltests.jl)."""
+    m = np.asarray(m, dtype=np.float64)
+    s = 1.0 / (1.0 + np.exp(-m))
+    rest = np.concatenate(([1.0], np.cumprod(1.0 - s)))
+    return np.concatenate((s * rest[:-1], rest[-1:]))
+
+
+def _infer_mnreg(model, data, iterations, free_energy, options, catch_exception, autoupdates, keephistory, historyvars):
+    """Y: [N][K] or [problems][N][K] counts, a row with any NaN = missing.  Offline: posteriors["ψ"]: (mean [iterations][d], cov
+    [iterations][d][d]) after every iteration (a problem axis after the iterations for a batch), free_energy [iterations] (per problem for a batch).
+    With `autoupdates` the rows are streamed (`ξ_ψ, W_ψ = weightedmean_precision(q(ψ))`), `iterations` per row: history["ψ"] = (mean [T][d], var
+    [T][d]), posteriors["ψ"] = the last step's (mean, cov), free_energy [T] = F_t; "ψ_cov" in historyvars adds history["ψ_cov"] [T][d][d]."""
+    options = _check_options(options)
+    Y = np.asarray(data["y"], dtype=np.float64)
+    single = Y.ndim == 2
+    if single:
+        Y = Y[None]
+    C, N, K = Y.shape
+    iters = 1 if iterations is None else int(iterations)
+    online = bool(autoupdates)
+    if online and keephistory not in (None, N):
+        raise ValueError(f"multinomial regression: the streamed run keeps every step, keephistory must be {N}")
+    keep_cov = online and historyvars is not None and "ψ_cov" in historyvars
+    eng = None
+    try:
+        eng = MultinomialRegressionEngine(N, K, model.prior_xi, model.prior_precision, n_trials=model.n_trials, init=None if online else model.init,
+                                          n_problems=C, online=online, keep_cov_history=keep_cov, device=int(options.get("device", -1)))
+        eng.set_data(Y)
+        eng.run(iterations=iters, free_energy=free_energy)
+        mean, cov, fe = eng.parameters()
+        if not online:
+            if single:
+                mean, cov, fe = mean[:, 0], cov[:, 0], (fe[:, 0] if fe is not None else None)
+            return InferenceResult({"ψ": (mean, cov)}, None, fe, model, None)
+        hm, hv, hc, hf = eng.history()
+        if single:
+            mean, cov, hm, hv, hc, hf = mean[0], cov[0], hm[:, 0], hv[:, 0], (hc[:, 0] if hc is not None else None), (hf[:, 0] if hf is not None else None)
+        hist = {"ψ": (hm, hv)}
+        if hc is not None:
+            hist["ψ_cov"] = hc
+        return InferenceResult({"ψ": (mean, cov)}, None, hf, model, None, history=hist, free_energy_history=hf)
+    except Exception as err:
+        if not catch_exception:
+            raise
+        return InferenceResult({}, None, None, model, err)
+    finally:
+        if eng is not None:
+            eng.close()
+
+
+@dataclass
 class GaussianRegression:
     """`γ ~ Gamma(a0, b0); θ ~ MvNormal(m0, Λ0⁻¹); y[i] ~ Normal(dot(x[i], θ), γ⁻¹)` with `q(γ, θ) = q(γ)q(θ)` (test/models/autoregressive/
     ar_tests.jl:17-46).  order is not None: the regressors are the `order` previous values of the series itself, most recent first (ar_ssm_data)."""
@@ -774,6 +845,8 @@ def infer(*, model, data, iterations=None, free_energy=False, options=None, retu
         return _infer_binreg(model, data, iterations, free_energy, options, catch_exception)
     if isinstance(model, GaussianRegression):
         return _infer_arreg(model, data, iterations, free_energy, options, catch_exception)
+    if isinstance(model, MultinomialRegression):
+        return _infer_mnreg(model, data, iterations, free_energy, options, catch_exception, autoupdates, keephistory, historyvars)
     if not isinstance(model, LinearGaussianSSM):
         raise TypeError("infer: no device schedule for this model type")
     if model.noise_precision_prior is not None:

@@ -1006,6 +1006,106 @@ class ARRegressionEngine:
         return G, h, s, n
 
 
+class MultinomialRegressionEngine:
+    """Bayesian multinomial regression `ψ ~ MvNormalWeightedMeanPrecision(ξ0, W0); y[i] ~ MultinomialPolya(N_i, ψ)`
+    (test/models/regression/multinomialreg_tests.jl) for n_problems independent problems of N count vectors with K = 2 … 65 categories, d = K − 1:
+    batched stick-breaking Pólya-Gamma VMP from the column sums (include/rxhip.h rxhip_mnreg_desc).  online=True streams the N rows of each
+    series one at a time with the posterior fed back as the next prior (`run(iterations)`: that many per step; `history()`).  n_trials: every
+    observed row must sum to it (None: not checked).  init (offline): (mean [d], covariance [d][d]) or None = the prior's W0⁻¹ξ0, W0⁻¹.
+    `set_data(Y [problems][N][K])`, a row with any NaN is missing; `parameters()`: q(ψ) after every iteration (online: after the last step);
+    `statistics()`: Y, S, lc, n per problem."""
+
+    def __init__(self, N, K, prior_xi, prior_precision, n_trials=None, init=None, n_problems=1, online=False, keep_cov_history=False, device=-1,
+                 stream=None):
+        L = _lib.lib()
+        K = int(K)
+        d = max(K - 1, 0)
+        xi, w0 = _c(prior_xi), _c(prior_precision)
+        if xi.shape != (d,) or w0.shape != (d, d):
+            raise ValueError(f"prior_xi must be [K − 1] and prior_precision [K − 1][K − 1] with K = {K}")
+        desc = _lib.MnregDesc()
+        desc.N, desc.n_problems, desc.K = int(N), int(n_problems), K
+        desc.mode = _lib.MNREG_ONLINE if online else _lib.MNREG_BATCH
+        desc.n_trials = 0 if n_trials is None else int(n_trials)
+        desc.prior_xi, desc.prior_precision = _p(xi), _p(w0)
+        if init is not None:
+            im, iv = _c(init[0]), _c(init[1])
+            if im.shape != xi.shape or iv.shape != w0.shape:
+                raise ValueError(f"init must be (mean [K − 1], covariance [K − 1][K − 1]) with K = {K}")
+            desc.init_mean, desc.init_cov = _p(im), _p(iv)
+        desc.keep_cov_history, desc.device = int(bool(keep_cov_history)), int(device)
+        desc.stream = ctypes.c_void_p(stream) if stream else None
+        self.N, self.T, self.K, self.d, self.n_problems, self.n_chains = int(N), int(N), K, d, int(n_problems), int(n_problems)
+        self.online, self.keep_cov_history = bool(online), bool(keep_cov_history)
+        self._h = ctypes.c_void_p()
+        st = L.rxhip_mnreg_create(ctypes.byref(desc), ctypes.byref(self._h))
+        if st != _lib.OK:
+            msg = L.rxhip_last_error(self._h).decode() if self._h else L.rxhip_status_string(st).decode()
+            if self._h:
+                L.rxhip_destroy(self._h)
+                self._h = None
+            raise RxHipError(st, msg or L.rxhip_status_string(st).decode())
+        self._iters = 0
+        self._fe = False
+
+    _chk = LGSSMEngine._chk
+    close = LGSSMEngine.close
+    __del__ = LGSSMEngine.__del__
+    __enter__ = LGSSMEngine.__enter__
+    __exit__ = LGSSMEngine.__exit__
+    sync = LGSSMEngine.sync
+    free_energy = LGSSMEngine.free_energy
+    free_energy_per_chain = LGSSMEngine.free_energy_per_chain
+    counters = LGSSMEngine.counters
+    stream = LGSSMEngine.stream
+    set_profiling = LGSSMEngine.set_profiling
+    kernel_times = LGSSMEngine.kernel_times
+    run = BinomialRegressionEngine.run
+    run_async = BinomialRegressionEngine.run_async
+
+    @staticmethod
+    def schedule(N, K):
+        """(rows per tile, workgroups per problem) of the statistics pass for N rows of K categories: a function of N and K only."""
+        tr, ch = ctypes.c_int32(), ctypes.c_int32()
+        _lib.lib().rxhip_mnreg_schedule(int(N), int(K), ctypes.byref(tr), ctypes.byref(ch))
+        return tr.value, ch.value
+
+    def set_data(self, Y):
+        """Y [problems][N][K] (the problem axis may be left out for one problem): counts as doubles; a row with any NaN is missing."""
+        a = _c(Y)
+        shape = (self.n_problems, self.N, self.K)
+        if a.shape != shape and not (self.n_problems == 1 and a.shape == shape[1:]):
+            raise ValueError(f"Y must be {list(shape)} (the problem axis may be left out for one problem), got {list(a.shape)}")
+        self._chk(_lib.lib().rxhip_set_data(self._h, _lib.VAR_Y, _p(a), a.size, _lib.LAYOUT_TIME_CHAIN))
+
+    def parameters(self):
+        """offline: q(ψ) after every iteration of the last run: (mean [iterations][problems][d], covariance [iterations][problems][d][d], free
+        energy [iterations][problems] or None).  online: the last step's (mean [series][d], covariance [series][d][d], F_T [series] or None)."""
+        C, d = self.n_problems, self.d
+        lead = (C,) if self.online else (max(int(self._iters), 0), C)
+        mean, cov = np.empty(lead + (d,)), np.empty(lead + (d, d))
+        fe = np.empty(lead) if self._fe else None
+        self._chk(_lib.lib().rxhip_mnreg_get_parameters(self._h, _p(mean), _p(cov), _p(fe) if self._fe else None))
+        return mean, cov, fe
+
+    def history(self):
+        """online: q(ψ) after every step: (mean [T][series][d], variances [T][series][d], covariance [T][series][d][d] or None without
+        keep_cov_history, F_t [T][series] or None when the run was without the free energy)."""
+        T, C, d = self.N, self.n_problems, self.d
+        mean, var = np.empty((T, C, d)), np.empty((T, C, d))
+        cov = np.empty((T, C, d, d)) if self.keep_cov_history else None
+        fe = np.empty((T, C)) if self._fe else None
+        self._chk(_lib.lib().rxhip_mnreg_get_history(self._h, _p(mean), _p(var), _p(cov) if cov is not None else None, _p(fe) if self._fe else None))
+        return mean, var, cov, fe
+
+    def statistics(self):
+        """offline, the pass alone: (Y [problems][K], S [problems][K], lc [problems], n [problems]) of the data in place."""
+        C, K = self.n_problems, self.K
+        Y, S, lc, n = np.empty((C, K)), np.empty((C, K)), np.empty(C), np.empty(C)
+        self._chk(_lib.lib().rxhip_mnreg_get_statistics(self._h, _p(Y), _p(S), _p(lc), _p(n)))
+        return Y, S, lc, n
+
+
 class Communicator:
     """RCCL communicator made through the C ABI (rxhip_comm_*): rank 0 calls `Communicator.unique_id()`, the 128 bytes
     travel to the other ranks by any host-side means, every rank constructs `Communicator(nranks, id, rank)`."""
