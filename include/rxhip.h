@@ -1151,6 +1151,70 @@ rxhip_status rxhip_mnreg_get_statistics(rxhip_engine* e, double* Y, double* S, d
 void rxhip_mnreg_schedule(int64_t N, int32_t K, int32_t* tile_rows, int32_t* chunks);
 
 /* ------------------------------------------------------------------------------------------
+ * Gamma mixture with a point-mass shape (reference model test/models/mixtures/gamma_mixture_tests.jl:7-40), for each of n_problems independent
+ * mixtures of N points and K = 1 … 16 components:
+ *     s ~ Dirichlet(α⁰);  a[k] ~ Gamma(shape = c⁰_k, rate = d⁰_k);  b[k] ~ Gamma(shape = e⁰_k, rate = f⁰_k)
+ *     z[i] ~ Categorical(s);  y[i] ~ GammaMixture(switch = z[i], a = a, b = b),    p(y | z = k) = Gamma(y | shape a_k, rate b_k)
+ *     q = q(s) Π q(z_i) Π q(b_k) Π δ(a_k − â_k)
+ * Every run starts from q(b_k) = Gamma(init_b_shape_k, init_b_rate_k) (NULL: 1, 1), â_k = init_a_k (NULL: 1.0, the test's starting_point) and
+ * q(s) = Dirichlet(init_s_alpha) (NULL: the prior's α⁰).
+ * One ITERATION (rxhip_run's argument) is a defined semantic of this engine (csrc/gammamix_kernels.hpp).  Write E ln b_k = ψ(e_k) − ln f_k,
+ * E b_k = e_k/f_k, E ln s_k = ψ(α_k) − ψ(Σα):
+ *   1. q(z_i) = softmax_k(E ln s_k + â_k E ln b_k − lnΓ(â_k) + (â_k − 1) ln y_i − E b_k y_i);  per component S0_k = Σ r_ik, S1_k = Σ r_ik y_i,
+ *      SL_k = Σ r_ik ln y_i, and H = −Σ r ln r;
+ *   2. α_k = α⁰_k + S0_k;
+ *   3. â_k = the unique root of g'(a) = (c⁰_k − 1)/a − d⁰_k + S0_k E ln b_k + SL_k − S0_k ψ(a), with the OLD q(b): g' falls strictly from +∞ to −∞ for
+ *      c⁰_k ≥ 1 and S0_k > 0, the exact maximiser of prior × Π GammaShapeLikelihood.  Safeguarded Newton in ln a from the previous â_k, until the
+ *      step is within 8 ulp or 40 steps.  S0_k exactly 0 (outside the contract): â_k is kept and the run ends in RXHIP_ERR_NONFINITE_FE (device
+ *      flag 0x80);
+ *   4. e_k = e⁰_k + S0_k â_k (new â), f_k = f⁰_k + S1_k;
+ *   5. F = −Σ_k[S0_k(E ln s_k + â_k E ln b_k − lnΓ(â_k)) + (â_k − 1) SL_k − E b_k S1_k] − H + KL(Dir(α)‖Dir(α⁰))
+ *          + Σ_k KL(Gamma(e_k, f_k)‖Gamma(e⁰_k, f⁰_k)) − Σ_k ln Gamma(â_k; c⁰_k, d⁰_k)     at the new q(s), â, q(b) and this iteration's q(z).
+ * Every step is an exact coordinate minimiser of this collapsed objective, so F does not rise.
+ * NOT pinned to the reference: its rule bodies (ReactiveMP) and its point-mass optimiser were not at hand, and its draws (rand(rng, MixtureModel))
+ * cannot be regenerated.  On the recorded numpy draw from the test's mixture with the test's priors (tests/golden/make_gammamix_golden.py) this
+ * definition gives F = 85.07 after the first and −131.79 after the 50th iteration, component means 0.333 / 0.346 and mixing 0.799 / 0.201, where the
+ * reference reports −146.8 ± 0.2, 0.32 / 0.33 and 0.8 / 0.2 on its own draw.  The engine is held to the definition above; the difference is an open
+ * item and nothing is tuned towards it.
+ * Data: rxhip_set_data(RXHIP_VAR_Y, y, N·n_problems, layout) with [N][problems] or [problems][N] by layout, from the host or through
+ * rxhip_set_data_device.  NaN is a missing point (weight 0, counted out); y ≤ 0 or ±Inf is refused (RXHIP_ERR_BADARG, the array counts as not set).
+ * ONE schedule, streamed, for every N and K (rxhip_gammamix_schedule): per iteration one pass over the points (grid: chunks × problems) and one update
+ * launch (a wavefront per problem), plus one launch per run for the batch's free-energy totals.  A resident schedule — every iteration of a run in one
+ * launch with the data in LDS — is not part of the library: its kernel faulted on the MI355X for a cause that was not found;
+ * `schedule = 2` is refused.  Results are bit-identical from run to run, with and without the free energy, and for a problem alone or inside a
+ * batch (no floating-point atomics, fixed summation order).  With rxhip_set_profiling the pass is counted under RXHIP_K_GMM_PASS and the update
+ * under RXHIP_K_GMM_UPDATE (the Gaussian mixture's ids: no id was added), so rxhip_get_kernel_times reports them as k_gmm_pass / k_gmm_update.
+ * Handle protocol: rxhip_set_data, rxhip_run(e, iterations, want_free_energy), rxhip_gammamix_get_history, rxhip_gammamix_get_responsibilities,
+ * rxhip_get_free_energy (per iteration, summed over the problems), rxhip_get_free_energy_per_chain (last iteration per problem), rxhip_counters,
+ * rxhip_destroy; rxhip_run_filter and RXHIP_VAR_X marginals are refused.
+ * RXHIP_ERR_BADARG with a text that names gammamix, before any device call: K outside 1 … 16, N < 1, n_problems outside 1 … 65535, a prior or
+ * initial parameter that is not positive and finite, a prior a-shape below 1, a schedule other than 0 or 1.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    int64_t N, n_problems;                            /* points per problem, problems */
+    int32_t K;                                        /* components, 1 … 16 */
+    const double *prior_a_shape, *prior_a_rate;       /* c⁰, d⁰: [n_problems][K] */
+    const double *prior_b_shape, *prior_b_rate;       /* e⁰, f⁰: [n_problems][K] */
+    const double *prior_alpha;                        /* α⁰: [n_problems][K] */
+    const double *init_a, *init_b_shape, *init_b_rate, *init_s_alpha;   /* [n_problems][K] each, or NULL = 1.0 | 1 | 1 | the prior's α⁰ */
+    int32_t schedule;                                 /* 0: by rxhip_gammamix_schedule; 1: streamed (the same today); 2 (resident): refused */
+    int32_t materialize_responsibilities;             /* keep q(z) of a run's last iteration, N·K doubles per problem */
+    int32_t device;
+    void* stream;
+} rxhip_gammamix_desc;
+rxhip_status rxhip_gammamix_create(const rxhip_gammamix_desc* desc, rxhip_engine** out);
+/* after EVERY iteration of the last run: hist [iterations][problems][4][K] = â | b shape | b rate | α, free_energy [iterations][problems]; either pointer
+ * may be NULL (free_energy: RXHIP_ERR_STATE if the run was without it) */
+rxhip_status rxhip_gammamix_get_history(rxhip_engine* e, double* hist, double* free_energy);
+/* q(z) of the last iteration of the last run, [problems][N][K] (a missing point's row is 0); RXHIP_ERR_STATE without materialize_responsibilities */
+rxhip_status rxhip_gammamix_get_responsibilities(rxhip_engine* e, double* resp);
+/* the schedule of N points and K components: 1 (streamed) for every N ≥ 1 and K = 1 … 16; 0 for arguments outside the engine's range */
+int32_t rxhip_gammamix_schedule(int64_t N, int32_t K);
+/* the pass reads ln y from memory (1, the default: stored once at ingest, 16 B/point per pass and 8 B/point of device memory) or recomputes
+ * it (0: 8 B/point and an fp64 log).  The same logarithm either way, so the results are the same bits; stored measured faster. */
+rxhip_status rxhip_gammamix_set_stored_log(rxhip_engine* e, int32_t stored);
+
+/* ------------------------------------------------------------------------------------------
  * Several GPUs (one process per GPU; chains / series / points shard).  The path's only exchange is the sum
  * over shards of the Bethe free energy (reference: the single `sumreduce` of src/model/plugins/reactivemp_free_energy.jl:99-123
  * over ALL nodes and variables of the model) and, for the mixture, of the responsibility-weighted statistics that

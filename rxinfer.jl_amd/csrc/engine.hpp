@@ -1,7 +1,7 @@
 // engine.hpp — what every translation unit behind the C ABI shares: the engine object, its family table, the error path, the device guards and the
 // helpers every creator and run uses.
 //   rxhip.hip       runtime (pools, arenas), the state-space and drift-chain engines, the entry points common to all engines, the shared helpers
-//   vmp_engines.hip the mixture, HGF, probit, HMM, latent-AR, binomial-, linear- and multinomial-regression engines and their family rows
+//   vmp_engines.hip the mixture, HGF, probit, HMM, latent-AR, binomial-, linear- and multinomial-regression and Gamma-mixture engines and their family rows
 //   graph_abi.hip   the graph entry points: host-only lowering (graph_lowering.hpp), rxhip_create, the node-array executor's rxhip_tree_* wrappers
 //   rccl_abi.hip    the RCCL exchange entry points (rxhip_comm_*, rxhip_allreduce_free_energy, rxhip_gmm_allreduce_statistics)
 //   tree_engine.hip the node-array executor itself (behind tree_engine.hpp)
@@ -92,6 +92,7 @@ enum class EngineKind : int {
     Mnreg = 11,         // multinomial regression, batched stick-breaking Pólya-Gamma VMP from the column sums (mnreg_kernels.hpp), offline: every
                         // iteration of a run in one resident launch
     MnregOnline = 12,   // … streamed one row at a time with the posterior fed back as the next prior (the same plumbing, release and getters)
+    GammaMix = 13,      // Gamma mixture with a point-mass shape, batched VMP (gammamix_kernels.hpp): a streamed pass and an update launch per iteration
 };
 struct rxhip_engine : rxhip_engine_life {
     // one device allocation holds every buffer of a state-space engine (creation / destruction cost two driver calls
@@ -171,6 +172,12 @@ struct rxhip_engine : rxhip_engine_life {
         bool have = false, stats_ready = false;
         uint64_t stats_launches = 0;
     } mn;
+    struct GammaMix {  // kind 13: priors, the state every run starts from, the current state and the pass's partials, history, free energies, q(z) on request,
+                       // the problem-major copy of a batch's data and (pass on stored logarithms) ln y
+        int K = 0, KT = 0, sched = 0, nchunk = 0, hist_cap = 0, materialize = 0, stored_log = 0;
+        double *d_prior = nullptr, *d_init = nullptr, *d_state = nullptr, *d_part = nullptr, *d_hist = nullptr, *d_fe = nullptr, *d_resp = nullptr, *d_yt = nullptr,
+               *d_ly = nullptr;
+    } gx;
     struct Gmm {
         long long N = 0;
         int K = 0, KT = 0, materialize = 0, nblocks = 0, it = 0, iterations = 0, hist_cap = 0;

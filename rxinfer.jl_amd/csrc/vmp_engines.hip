@@ -9,6 +9,7 @@
 //   arreg     regression / autoregression with unknown coefficients and noise precision, Normal-Gamma VMP from the statistics (arreg_kernels.hpp): two
 //             rows, X and y from the host or the raw series through the common ingest
 //   mnreg     multinomial regression, stick-breaking Pólya-Gamma VMP from the column sums (mnreg_kernels.hpp): two rows, offline and online
+//   gammamix  Gamma mixture with a point-mass shape (gammamix_kernels.hpp): a streamed pass and an update launch per iteration
 // The runtime they share with the state-space engines — streams, profiling events, the engine handle, the creation and run helpers — is rxhip.hip's
 // (engine.hpp).  No kernels of the state-space path live here.
 #include "../../include/rxhip.h"
@@ -33,6 +34,7 @@
 #include "binreg_kernels.hpp"
 #include "arreg_kernels.hpp"
 #include "mnreg_kernels.hpp"
+#include "gammamix_kernels.hpp"
 #include "engine.hpp"
 
 using namespace rxhip;
@@ -1666,6 +1668,211 @@ static rxhip_status hgf_run_async(rxhip_engine* e, int32_t iterations, int32_t w
     return RXHIP_OK;
 }
 
+// ---- Gamma mixture with a point-mass shape (gammamix_kernels.hpp): one row ----
+static GammaMixParams gammamix_params(const rxhip_engine* e) {
+    const auto& g = e->gx;
+    GammaMixParams p;
+    p.N = e->T; p.C = e->n_chains;
+    p.K = g.K; p.nchunk = g.nchunk; p.want_fe = 0; p.iterations = 0; p.iteration = 0; p.write_resp = 0;
+    p.y = e->n_chains > 1 ? g.d_yt : e->d_y; p.ly = g.d_ly;
+    p.prior = g.d_prior; p.init = g.d_init; p.state = g.d_state; p.part = g.d_part; p.hist = g.d_hist; p.fe = g.d_fe;
+    p.fe_total = e->d_fe_total; p.fe_chain = e->d_fe_chain; p.resp = g.d_resp; p.status = e->d_status;
+    return p;
+}
+
+// what the kernels read beside the ingested array: the problem-major copy of a batch, and ln y for the streamed pass on stored logarithms
+static rxhip_status gammamix_prepare(rxhip_engine* e) {
+    auto& g = e->gx;
+    const size_t n = (size_t)e->T * (size_t)e->n_chains;
+    const bool want_yt = e->n_chains > 1, want_ly = g.stored_log != 0;
+    if (!want_yt && !want_ly) return RXHIP_OK;
+    SET_DEVICE(e);
+    if (want_yt && !g.d_yt) HIPCHK(e, hipMalloc(&g.d_yt, sizeof(double) * n));
+    if (want_ly && !g.d_ly) HIPCHK(e, hipMalloc(&g.d_ly, sizeof(double) * n));
+    hipLaunchKernelGGL(k_gammamix_prepare, dim3((unsigned)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, e->stream, (const double*)e->d_y, (long long)e->T,
+                       (long long)e->n_chains, want_yt ? g.d_yt : nullptr, want_ly ? g.d_ly : nullptr);
+    HIPCHK(e, hipGetLastError());
+    return RXHIP_OK;
+}
+
+// the observations arrived through the common ingest (host or device): positive and finite, or NaN = missing; checked on the device copy
+static rxhip_status gammamix_check_data(rxhip_engine* e) {
+    rxhip_status st = check_observations(e, [](rxhip_engine* e, long long n, unsigned nb) {
+        hipLaunchKernelGGL(k_gammamix_check_y, dim3(nb), dim3(256), 0, e->stream, (const double*)e->d_y, n, e->d_status);
+    }, ST_GAMMAMIX_BAD_Y, "set_data: gammamix: an observation is zero, negative or infinite (positive finite values and NaN = missing are accepted)");
+    return st ? st : gammamix_prepare(e);
+}
+
+template <int KT>
+static void gammamix_launch_pass(const GammaMixParams& p, bool stored_log, hipStream_t s) {
+    const dim3 grid((unsigned)p.nchunk, (unsigned)p.C);
+    if (stored_log) hipLaunchKernelGGL((k_gammamix_pass<KT, true>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((k_gammamix_pass<KT, false>), grid, dim3(256), 0, s, p);
+}
+#define GAMMAMIX_BY_KT(KT, CALL)            \
+    switch (KT) {                           \
+        case 1: CALL(1); break;             \
+        case 2: CALL(2); break;             \
+        case 4: CALL(4); break;             \
+        case 8: CALL(8); break;             \
+        default: CALL(16);                  \
+    }
+
+static rxhip_status gammamix_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
+    if (rxhip_status st = run_preamble(e, iterations)) return st;
+    SET_DEVICE(e);
+    auto& g = e->gx;
+    const size_t C = (size_t)e->n_chains;
+    rxhip_status rs = reserve(e, &e->fe_total_cap, iterations, {{&e->d_fe_total, 1}});
+    if (!rs) rs = reserve(e, &g.hist_cap, iterations, {{&g.d_hist, C * 4 * (size_t)g.K}, {&g.d_fe, C}});
+    if (rs) return rs;
+    GammaMixParams p = gammamix_params(e);
+    p.want_fe = want_fe ? 1 : 0;
+    p.iterations = iterations;
+    rxhip_status st;
+    {   // every run starts from the initial state (the kernels of iteration 0 read d_init)
+        const bool stored = g.stored_log != 0;
+        for (int it = 0; it < iterations; ++it) {
+            p.iteration = it;
+            p.write_resp = g.materialize && it == iterations - 1;
+            if ((st = prof_begin(e, RXHIP_K_GMM_PASS))) return st;
+#define GX_CALL(KT) gammamix_launch_pass<KT>(p, stored, e->stream)
+            GAMMAMIX_BY_KT(g.KT, GX_CALL)
+#undef GX_CALL
+            if ((st = prof_end(e))) return st;
+            if ((st = prof_begin(e, RXHIP_K_GMM_UPDATE))) return st;
+            hipLaunchKernelGGL(k_gammamix_update, dim3((unsigned)C), dim3(64), 0, e->stream, p);
+            if ((st = prof_end(e))) return st;
+        }
+    }
+    if (want_fe && C > 1) hipLaunchKernelGGL(k_gammamix_fe_total, dim3((unsigned)iterations), dim3(256), 0, e->stream, p);
+    HIPCHK(e, hipGetLastError());
+    finish_run(e, iterations, want_fe != 0);
+    // reference-equivalent events per problem and iteration: per point the GammaMixture node's messages toward z, and toward a[k], b[k] per component;
+    // the Categorical's message; per component and for s the product of the N + 1 messages and the marginal; the point's q(z)
+    const uint64_t N = (uint64_t)e->T, K = (uint64_t)g.K, I = (uint64_t)iterations;
+    e->rule_calls = I * C * (N * (2 + 2 * K) + 2 * K + 1);
+    e->products = I * C * (N * (2 * K + 2));
+    e->marginals = I * C * (N + 2 * K + 1);
+    return RXHIP_OK;
+}
+
+extern "C" {
+
+int32_t rxhip_gammamix_schedule(int64_t N, int32_t K) { return gammamix::schedule(N, K); }
+
+rxhip_status rxhip_gammamix_create(const rxhip_gammamix_desc* ds, rxhip_engine** out) {
+    if (!out) return RXHIP_ERR_BADARG;
+    *out = nullptr;
+    if (!ds) return RXHIP_ERR_BADARG;
+    rxhip_engine* e = new rxhip_engine();   // from here on every refusal carries a text (rxhip_last_error; the caller destroys the handle)
+    *out = e;
+    e->kind = EngineKind::GammaMix;
+    e->device = -1;
+    constexpr int KS = gammamix::kMaxK;
+    if (ds->K < 1 || ds->K > KS) return fail(e, RXHIP_ERR_BADARG, "gammamix: K must be 1 … %d (got %d)", KS, ds->K);
+    if (ds->N < 1) return fail(e, RXHIP_ERR_BADARG, "gammamix: N must be at least 1 (got %lld)", (long long)ds->N);
+    if (ds->n_problems < 1 || ds->n_problems > 65535)
+        return fail(e, RXHIP_ERR_BADARG, "gammamix: n_problems must be 1 … 65535 (got %lld)", (long long)ds->n_problems);
+    if (ds->schedule < 0 || ds->schedule > 2) return fail(e, RXHIP_ERR_BADARG, "gammamix: schedule must be 0 (auto) or 1 (streamed) (got %d)", ds->schedule);
+    if (ds->schedule == gammamix::SCHED_RESIDENT)
+        return fail(e, RXHIP_ERR_BADARG, "gammamix: schedule 2 (resident: a run in one launch) is not part of this build; 0 and 1 run the streamed schedule");
+    if (!ds->prior_a_shape || !ds->prior_a_rate || !ds->prior_b_shape || !ds->prior_b_rate || !ds->prior_alpha)
+        return fail(e, RXHIP_ERR_BADARG, "gammamix: prior_a_shape, prior_a_rate, prior_b_shape, prior_b_rate and prior_alpha are required ([n_problems][K] each)");
+    const int K = ds->K;
+    const size_t C = (size_t)ds->n_problems, PK = C * (size_t)K;
+    auto positive = [](double v) { return v > 0.0 && std::isfinite(v); };
+    const struct { const double* p; const char* name; } arrays[] = {
+        {ds->prior_a_shape, "prior_a_shape"}, {ds->prior_a_rate, "prior_a_rate"}, {ds->prior_b_shape, "prior_b_shape"}, {ds->prior_b_rate, "prior_b_rate"},
+        {ds->prior_alpha, "prior_alpha"}, {ds->init_a, "init_a"}, {ds->init_b_shape, "init_b_shape"}, {ds->init_b_rate, "init_b_rate"}, {ds->init_s_alpha, "init_s_alpha"}};
+    for (const auto& a : arrays)
+        for (size_t q = 0; a.p && q < PK; ++q)
+            if (!positive(a.p[q])) return fail(e, RXHIP_ERR_BADARG, "gammamix: %s must be positive and finite (entry %zu is %g)", a.name, q, a.p[q]);
+    for (size_t q = 0; q < PK; ++q)
+        if (ds->prior_a_shape[q] < 1.0)
+            return fail(e, RXHIP_ERR_BADARG, "gammamix: prior_a_shape must be at least 1 (entry %zu is %g): below it the shape's objective is not concave", q, ds->prior_a_shape[q]);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(e, RXHIP_ERR_NO_DEVICE, "no HIP device visible");
+    auto& g = e->gx;
+    g.K = K; g.KT = gammamix::padded_k(K);
+    g.sched = ds->schedule ? ds->schedule : gammamix::schedule(ds->N, K);
+    g.nchunk = gammamix::chunks(ds->N);
+    g.materialize = ds->materialize_responsibilities ? 1 : 0;
+    g.stored_log = 1;   // the measured choice: the streamed pass reads ln y stored at ingest
+    e->T = ds->N;
+    e->n_chains = ds->n_problems;
+    e->d = e->dy = e->dpad = 1;
+    DevGuard guard;
+    if (rxhip_status st = open_device(e, guard, ds->device, ds->stream, ndev)) return st;
+    // the prior blocks and the state every run starts from (with the constants of its first pass), rows of kMaxK
+    std::vector<double> prior(C * gammamix::kPriorRows * KS, 1.0), init(C * gammamix::kStateRows * KS, 1.0);
+    for (size_t c = 0; c < C; ++c) {
+        double *pr = &prior[c * gammamix::kPriorRows * KS], *st = &init[c * gammamix::kStateRows * KS];
+        double asum = 0.0;
+        for (int k = 0; k < K; ++k) {
+            const size_t q = c * (size_t)K + (size_t)k;
+            pr[k] = ds->prior_a_shape[q]; pr[KS + k] = ds->prior_a_rate[q]; pr[2 * KS + k] = ds->prior_b_shape[q]; pr[3 * KS + k] = ds->prior_b_rate[q];
+            pr[4 * KS + k] = ds->prior_alpha[q];
+            st[k] = ds->init_a ? ds->init_a[q] : 1.0;
+            st[KS + k] = ds->init_b_shape ? ds->init_b_shape[q] : 1.0;
+            st[2 * KS + k] = ds->init_b_rate ? ds->init_b_rate[q] : 1.0;
+            st[3 * KS + k] = ds->init_s_alpha ? ds->init_s_alpha[q] : ds->prior_alpha[q];
+            asum += st[3 * KS + k];
+        }
+        for (int k = 0; k < KS; ++k) {
+            double c0 = -1e300, c1 = 0.0, c2 = 0.0;   // padding components never receive responsibility
+            if (k < K) gammamix::pass_constants(st[k], st[KS + k], st[2 * KS + k], digamma_dev(st[3 * KS + k]) - digamma_dev(asum), std::lgamma(st[k]), c0, c1, c2);
+            st[4 * KS + k] = c0; st[5 * KS + k] = c1; st[6 * KS + k] = c2;
+        }
+    }
+    const size_t NQ = 3 * (size_t)g.KT + 1;
+    HIPCHK(e, hipMalloc(&g.d_prior, sizeof(double) * prior.size()));
+    HIPCHK(e, hipMemcpy(g.d_prior, prior.data(), sizeof(double) * prior.size(), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMalloc(&g.d_init, sizeof(double) * init.size()));
+    HIPCHK(e, hipMemcpy(g.d_init, init.data(), sizeof(double) * init.size(), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMalloc(&g.d_state, sizeof(double) * init.size()));
+    HIPCHK(e, hipMalloc(&g.d_part, sizeof(double) * C * (size_t)g.nchunk * NQ));
+    if (g.materialize) HIPCHK(e, hipMalloc(&g.d_resp, sizeof(double) * C * (size_t)ds->N * (size_t)K));
+    HIPCHK(e, hipMalloc(&e->d_fe_chain, sizeof(double) * C));
+    HIPCHK(e, hipMemset(e->d_fe_chain, 0, sizeof(double) * C));
+    if (rxhip_status st = reserve(e, &e->fe_total_cap, 32, {{&e->d_fe_total, 1}})) return st;
+    HIPCHK(e, hipMalloc(&e->d_status, sizeof(int)));
+    HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
+    return RXHIP_OK;
+}
+
+rxhip_status rxhip_gammamix_set_stored_log(rxhip_engine* e, int32_t stored) {
+    if (!e || e->kind != EngineKind::GammaMix) return RXHIP_ERR_BADARG;
+    if (stored != 0 && stored != 1) return fail(e, RXHIP_ERR_BADARG, "gammamix_set_stored_log: 0 (recompute ln y in the pass) or 1 (read it from memory, the default)");
+    const bool fill = stored && !e->gx.stored_log && e->have_data;   // switched on with the data in place: ln y is computed now
+    e->gx.stored_log = stored;
+    return fill ? gammamix_prepare(e) : RXHIP_OK;
+}
+
+rxhip_status rxhip_gammamix_get_history(rxhip_engine* e, double* hist, double* free_energy) {
+    if (!e || e->kind != EngineKind::GammaMix) return RXHIP_ERR_BADARG;
+    if (!e->ran) return fail(e, RXHIP_ERR_STATE, "gammamix_get_history: no run yet");
+    if (free_energy && !e->last_want_fe) return fail(e, RXHIP_ERR_STATE, "gammamix_get_history: free energy was not requested in the last run");
+    SET_DEVICE(e);
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    const size_t rows = (size_t)e->last_iterations * (size_t)e->n_chains;
+    if (hist) HIPCHK(e, hipMemcpy(hist, e->gx.d_hist, sizeof(double) * rows * 4 * (size_t)e->gx.K, hipMemcpyDeviceToHost));
+    if (free_energy) HIPCHK(e, hipMemcpy(free_energy, e->gx.d_fe, sizeof(double) * rows, hipMemcpyDeviceToHost));
+    return RXHIP_OK;
+}
+
+rxhip_status rxhip_gammamix_get_responsibilities(rxhip_engine* e, double* resp) {
+    if (!e || e->kind != EngineKind::GammaMix || !resp) return RXHIP_ERR_BADARG;
+    if (!e->gx.materialize) return fail(e, RXHIP_ERR_STATE, "gammamix_get_responsibilities: the engine was created without materialize_responsibilities");
+    if (!e->ran) return fail(e, RXHIP_ERR_STATE, "gammamix_get_responsibilities: no run yet");
+    SET_DEVICE(e);
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    HIPCHK(e, hipMemcpy(resp, e->gx.d_resp, sizeof(double) * (size_t)e->n_chains * (size_t)e->T * (size_t)e->gx.K, hipMemcpyDeviceToHost));
+    return RXHIP_OK;
+}
+
+}  // extern "C"
+
 // the mixture engines' run: the split-phase entry points (several GPUs all-reduce the statistics between accumulate and update) back to back
 static rxhip_status mixture_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
     rxhip_status st = rxhip_gmm_begin_run(e, iterations);
@@ -1713,7 +1920,12 @@ const EngineFamily* rxhip::vmp_family(EngineKind kind) {
     };
     static const EngineFamily mnreg_row = {mnreg_run_async, false, nullptr, mnreg_set_data, mnreg_host_only, nullptr, false, mnreg_release};
     static const EngineFamily mnreg_online = {mnreg_run_async, false, nullptr, mnreg_set_data, mnreg_host_only, nullptr, false, mnreg_release};
+    // Gamma mixture: the common ingest (host or device) with its own check of the observations
+    static const EngineFamily gammamix_row = {gammamix_run_async, false, gammamix_check_data, nullptr, nullptr, nullptr, false, [](E* e) {
+        free_buffers(e, {&e->gx.d_prior, &e->gx.d_init, &e->gx.d_state, &e->gx.d_part, &e->gx.d_hist, &e->gx.d_fe, &e->gx.d_resp, &e->gx.d_yt, &e->gx.d_ly});
+    }};
     switch (kind) {
+        case EngineKind::GammaMix: return &gammamix_row;
         case EngineKind::Mnreg: return &mnreg_row;
         case EngineKind::MnregOnline: return &mnreg_online;
         case EngineKind::Arreg: return &arreg;

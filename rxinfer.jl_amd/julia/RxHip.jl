@@ -1136,6 +1136,81 @@ function mnreg_schedule(N::Integer, K::Integer)
     return Int(tr[]), Int(ch[])
 end
 
+# mirrors rxhip_gammamix_desc (include/rxhip.h); field order and types must match the C struct
+struct GammaMixDesc
+    N::Int64
+    n_problems::Int64
+    K::Int32
+    prior_a_shape::Ptr{Float64}
+    prior_a_rate::Ptr{Float64}
+    prior_b_shape::Ptr{Float64}
+    prior_b_rate::Ptr{Float64}
+    prior_alpha::Ptr{Float64}
+    init_a::Ptr{Float64}
+    init_b_shape::Ptr{Float64}
+    init_b_rate::Ptr{Float64}
+    init_s_alpha::Ptr{Float64}
+    schedule::Int32
+    materialize_responsibilities::Int32
+    device::Int32
+    stream::Ptr{Cvoid}
+end
+"""
+    GammaMixtureEngine(prior_a, prior_b, prior_alpha; N, n_problems = 1, init_a = nothing, init_b = nothing, init_s = nothing, schedule = 0,
+                       materialize = false, device = -1)
+
+`s ~ Dirichlet(α⁰); a[k] ~ Gamma(c⁰_k, d⁰_k); b[k] ~ Gamma(e⁰_k, f⁰_k); z[i] ~ Categorical(s); y[i] ~ GammaMixture(switch = z[i], a = a, b = b)` with a
+point-mass `q(a_k)` (test/models/mixtures/gamma_mixture_tests.jl:7-40) for `n_problems` independent mixtures (rxhip_gammamix_desc).  `prior_a`, `prior_b`,
+`init_b`: `(shapes, rates)`; every array `K × n_problems` (column-major Julia storage is the C layout [problems][K]) or a vector for one problem.
+`schedule`: 0 or 1, the streamed schedule (2, resident, is refused by the library).  Then `gammamix_set_data!`, `run!`, `gammamix_history`, `gammamix_responsibilities`.
+"""
+function GammaMixtureEngine(prior_a, prior_b, prior_alpha; N::Integer, n_problems::Integer = 1, init_a = nothing, init_b = nothing, init_s = nothing,
+                            schedule::Integer = 0, materialize::Bool = false, device::Integer = -1, stream = nothing)
+    K = size(prior_alpha, 1)
+    arr(v) = v === nothing ? Float64[] : vec(Array{Float64}(v))
+    ptr(a) = isempty(a) ? Ptr{Float64}(C_NULL) : pointer(a)
+    ca, da, eb, fb, al = arr(prior_a[1]), arr(prior_a[2]), arr(prior_b[1]), arr(prior_b[2]), arr(prior_alpha)
+    ia, ibs, ibr, is = arr(init_a), arr(init_b === nothing ? nothing : init_b[1]), arr(init_b === nothing ? nothing : init_b[2]), arr(init_s)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    st = GC.@preserve ca da eb fb al ia ibs ibr is begin
+        desc = GammaMixDesc(N, n_problems, K, ptr(ca), ptr(da), ptr(eb), ptr(fb), ptr(al), ptr(ia), ptr(ibs), ptr(ibr), ptr(is), schedule, materialize ? 1 : 0,
+                            device, stream_handle(stream))
+        ccall((:rxhip_gammamix_create, librxhip), Int32, (Ref{GammaMixDesc}, Ref{Ptr{Cvoid}}), desc, h)
+    end
+    e = Engine(h[], K, 1, N, n_problems, 0)
+    if st != RXHIP_OK
+        h[] != C_NULL && (try check(e, st) finally ccall((:rxhip_destroy, librxhip), Int32, (Ptr{Cvoid},), h[]) end)
+        throw(RxHipError(st, unsafe_string(ccall((:rxhip_status_string, librxhip), Cstring, (Int32,), st))))
+    end
+    finalizer(destroy!, e)
+    return e
+end
+"""y: `N × n_problems` (a vector for one problem); column-major Julia storage is the C layout [problems][N]; `NaN` = a missing point."""
+function gammamix_set_data!(e::Engine, y::AbstractVecOrMat)
+    a = Array{Float64}(y)
+    check(e, ccall((:rxhip_set_data, librxhip), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Csize_t, Int32), e.handle, RXHIP_VAR_Y, a, length(a),
+                   RXHIP_LAYOUT_CHAIN_TIME))
+    return e
+end
+"""after every one of the `iterations` of the last run: (history K × 4 × problems × iterations = â | b shape | b rate | α, free energies problems ×
+iterations or `nothing`) — the C arrays `[iterations][problems][4][K]` and `[iterations][problems]` seen column-major."""
+function gammamix_history(e::Engine, iterations::Integer; free_energy::Bool = true)
+    hist = Array{Float64}(undef, e.d, 4, e.n_chains, iterations)
+    fe = free_energy ? Array{Float64}(undef, e.n_chains, iterations) : nothing
+    check(e, ccall((:rxhip_gammamix_get_history, librxhip), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), e.handle, hist, free_energy ? fe : Ptr{Float64}(C_NULL)))
+    return hist, fe
+end
+"""q(z) of the last iteration, K × N × problems (an engine created with `materialize = true`)"""
+function gammamix_responsibilities(e::Engine)
+    r = Array{Float64}(undef, e.d, e.T, e.n_chains)
+    check(e, ccall((:rxhip_gammamix_get_responsibilities, librxhip), Int32, (Ptr{Cvoid}, Ptr{Float64}), e.handle, r))
+    return r
+end
+"""1: streamed, for every N and K of the engine's range; 0: outside it"""
+gammamix_schedule(N::Integer, K::Integer) = Int(ccall((:rxhip_gammamix_schedule, librxhip), Int32, (Int64, Int32), N, K))
+"""the streamed pass reads ln y from memory (true, the default) or recomputes it (false): the same bits, a measurement switch"""
+gammamix_set_stored_log!(e::Engine, stored::Bool) = (check(e, ccall((:rxhip_gammamix_set_stored_log, librxhip), Int32, (Ptr{Cvoid}, Int32), e.handle, stored ? 1 : 0)); e)
+
 # mirrors rxhip_arreg_desc (include/rxhip.h); field order and types must match the C struct
 struct ArregDesc
     N::Int64

@@ -148,6 +148,16 @@ class MnregDesc(ctypes.Structure):   # rxhip_mnreg_desc
         ("keep_cov_history", ctypes.c_int32), ("device", ctypes.c_int32), ("stream", ctypes.c_void_p)]
 
 
+GAMMAMIX_AUTO, GAMMAMIX_STREAMED, GAMMAMIX_RESIDENT = 0, 1, 2
+
+
+class GammaMixDesc(ctypes.Structure):   # rxhip_gammamix_desc
+    _fields_ = [("N", ctypes.c_int64), ("n_problems", ctypes.c_int64), ("K", ctypes.c_int32)] + [
+        (n, c_double_p) for n in ("prior_a_shape", "prior_a_rate", "prior_b_shape", "prior_b_rate", "prior_alpha", "init_a", "init_b_shape", "init_b_rate",
+                                  "init_s_alpha")] + [
+        ("schedule", ctypes.c_int32), ("materialize_responsibilities", ctypes.c_int32), ("device", ctypes.c_int32), ("stream", ctypes.c_void_p)]
+
+
 class NoisePrior(ctypes.Structure):   # rxhip_noise_prior
     _fields_ = [("nu0", ctypes.c_double), ("S0", c_double_p), ("init_nu", ctypes.c_double), ("init_V", c_double_p)]
 
@@ -267,6 +277,11 @@ SYMBOLS = [
     ("rxhip_mnreg_get_history", ctypes.c_int32, [_H, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("rxhip_mnreg_get_statistics", ctypes.c_int32, [_H, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("rxhip_mnreg_schedule", None, [ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    ("rxhip_gammamix_create", ctypes.c_int32, [ctypes.POINTER(GammaMixDesc), ctypes.POINTER(_H)]),
+    ("rxhip_gammamix_get_history", ctypes.c_int32, [_H, c_double_p, c_double_p]),
+    ("rxhip_gammamix_get_responsibilities", ctypes.c_int32, [_H, c_double_p]),
+    ("rxhip_gammamix_schedule", ctypes.c_int32, [ctypes.c_int64, ctypes.c_int32]),
+    ("rxhip_gammamix_set_stored_log", ctypes.c_int32, [_H, ctypes.c_int32]),
     ("rxhip_hgf_get_history", ctypes.c_int32, [_H, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_int32]),
     ("rxhip_set_profiling", ctypes.c_int32, [_H, ctypes.c_int32]),
     ("rxhip_get_kernel_times", ctypes.c_int32, [_H, c_double_p, c_u64_p]),

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RxHipError
-from .engine import DriftChainEngine, GMMEngine, HGFEngine, LGSSMEngine, MvGMMEngine, ProbitEngine, HMMEngine, LAREngine, BinomialRegressionEngine, ARRegressionEngine, MultinomialRegressionEngine
+from .engine import DriftChainEngine, GMMEngine, HGFEngine, LGSSMEngine, MvGMMEngine, ProbitEngine, HMMEngine, LAREngine, BinomialRegressionEngine, ARRegressionEngine, MultinomialRegressionEngine, GammaMixtureEngine
 
 
 @dataclass
@@ -572,6 +572,77 @@ def _infer_arreg(model, data, iterations, free_energy, options, catch_exception)
 
 
 @dataclass
+class GammaMixture:
+    """`s ~ Dirichlet(α⁰); a[k] ~ Gamma(c⁰_k, d⁰_k); b[k] ~ Gamma(e⁰_k, f⁰_k); z[i] ~ Categorical(s); y[i] ~ GammaMixture(switch = z[i], a = a, b = b)`
+    with `q = q(s) Π q(z_i) Π q(b_k) Π δ(a_k − â_k)` (test/models/mixtures/gamma_mixture_tests.jl:7-40).  Arrays are [K] or [problems][K]."""
+    prior_a: tuple
+    prior_b: tuple
+    prior_alpha: np.ndarray
+    init_a: Optional[np.ndarray] = None
+    init_b: Optional[tuple] = None
+    init_s: Optional[np.ndarray] = None
+
+
+def _gamma_pairs(v, name):
+    """a GammaShapeRate / GammaShapeScale, a sequence of them, or a sequence of (shape, rate) pairs -> (shape [K], rate [K])"""
+    if isinstance(v, (GammaShapeRate, GammaShapeScale)):
+        return np.atleast_1d(np.asarray(v.shape, dtype=np.float64)), np.atleast_1d(np.asarray(v.rate, dtype=np.float64))
+    items = list(v)
+    if items and all(isinstance(q, (GammaShapeRate, GammaShapeScale)) or np.ndim(q) == 1 for q in items):   # one entry per component
+        pair = lambda q: (float(q.shape), float(np.asarray(q.rate))) if isinstance(q, (GammaShapeRate, GammaShapeScale)) else (float(q[0]), float(q[1]))
+        if any(not isinstance(q, (GammaShapeRate, GammaShapeScale)) and len(q) != 2 for q in items):
+            raise ValueError(f"{name} must be a sequence of GammaShapeRate / GammaShapeScale or of (shape, rate) pairs")
+        a = np.array([pair(q) for q in items], dtype=np.float64)
+    else:
+        a = np.asarray(items, dtype=np.float64)
+    if a.ndim < 2 or a.shape[-1] != 2:
+        raise ValueError(f"{name} must be a sequence of GammaShapeRate / GammaShapeScale or of (shape, rate) pairs")
+    return np.ascontiguousarray(a[..., 0]), np.ascontiguousarray(a[..., 1])
+
+
+def gamma_mixture(prior_a, prior_b, prior_alpha, init_a=None, init_b=None, init_s=None):
+    """Gamma mixture with a point-mass shape: `data={"y": y}`, y [N] or [problems][N] (NaN = a missing point).  prior_a, prior_b (and init_b): sequences of
+    GammaShapeRate / GammaShapeScale or of (shape, rate) pairs, one per component; prior_alpha (and init_s): a Dirichlet or an array; init_a: the
+    starting shapes (default 1.0, the reference test's starting_point); init_b default GammaShapeRate(1, 1); init_s default the prior."""
+    al = lambda v: None if v is None else np.asarray(v.alpha if isinstance(v, Dirichlet) else v, dtype=np.float64)
+    return GammaMixture(_gamma_pairs(prior_a, "prior_a"), _gamma_pairs(prior_b, "prior_b"), al(prior_alpha),
+                        None if init_a is None else np.asarray(init_a, dtype=np.float64), None if init_b is None else _gamma_pairs(init_b, "init_b"), al(init_s))
+
+
+def _infer_gammamix(model, data, iterations, free_energy, options, catch_exception):
+    """posteriors["as"]: the point masses â [iterations][K]; ["bs"]: (shape, rate), each [iterations][K] (KeepEach; a problem axis after the iterations for
+    a batch); ["s"]: the last α [K]; ["z"]: the last q(z) [N][K]; free_energy: one value per iteration (summed over the problems)."""
+    options = _check_options(options)
+    dev = int(options.get("device", -1))
+    iters = 1 if iterations is None else int(iterations)
+    eng = None
+    try:
+        y = np.asarray(data["y"], dtype=np.float64)
+        single = y.ndim == 1
+        if single:
+            y = y[None]
+        C, N = y.shape
+        K = int(np.asarray(model.prior_alpha).shape[-1])
+        eng = GammaMixtureEngine(N, K, model.prior_a, model.prior_b, model.prior_alpha, model.init_a, model.init_b, model.init_s, n_problems=C,
+                                 materialize=True, device=dev)
+        eng.set_data(y, layout="chain_time")
+        eng.run(iterations=iters, free_energy=free_energy)
+        h = eng.history()
+        fe = eng.free_energy() if free_energy else None
+        a, bs, br, alpha, z = h["a"], h["b_shape"], h["b_rate"], h["alpha"][-1], eng.responsibilities()
+        if single:
+            a, bs, br, alpha, z = a[:, 0], bs[:, 0], br[:, 0], alpha[0], z[0]
+        return InferenceResult({"as": a, "bs": (bs, br), "s": alpha, "z": z}, None, fe, model, None)
+    except Exception as err:
+        if not catch_exception:
+            raise
+        return InferenceResult({}, None, None, model, err)
+    finally:
+        if eng is not None:
+            eng.close()
+
+
+@dataclass
 class InferenceResult:
     """src/inference/batch.jl:18-24"""
     posteriors: dict
@@ -847,6 +918,8 @@ def infer(*, model, data, iterations=None, free_energy=False, options=None, retu
         return _infer_arreg(model, data, iterations, free_energy, options, catch_exception)
     if isinstance(model, MultinomialRegression):
         return _infer_mnreg(model, data, iterations, free_energy, options, catch_exception, autoupdates, keephistory, historyvars)
+    if isinstance(model, GammaMixture):
+        return _infer_gammamix(model, data, iterations, free_energy, options, catch_exception)
     if not isinstance(model, LinearGaussianSSM):
         raise TypeError("infer: no device schedule for this model type")
     if model.noise_precision_prior is not None:

@@ -1106,6 +1106,103 @@ class MultinomialRegressionEngine:
         return Y, S, lc, n
 
 
+class GammaMixtureEngine:
+    """Gamma mixture with a point-mass shape, `s ~ Dirichlet(α⁰); a[k] ~ Gamma(c⁰_k, d⁰_k); b[k] ~ Gamma(e⁰_k, f⁰_k); z[i] ~ Categorical(s); y[i] ~
+    GammaMixture(switch = z[i], a = a, b = b)` with `q = q(s) Π q(z_i) Π q(b_k) Π δ(a_k − â_k)` (test/models/mixtures/gamma_mixture_tests.jl:7-40)
+    for n_problems independent mixtures of N points and K = 1 … 16 components (include/rxhip.h rxhip_gammamix_desc).  prior_a, prior_b: (shape,
+    rate), each [K] (every problem the same) or [problems][K]; prior_alpha the same; init_a (default 1.0), init_b (default (1, 1)), init_s (default
+    the prior's α⁰) alike.  schedule: 'auto' or 'streamed' (the same; 'resident' is a value of the C descriptor that the library refuses).  `set_data(y, layout)`: [N][problems] ('time_chain')
+    or [problems][N] ('chain_time'), NaN = a missing point; `run(iterations)`; `history()`: â, b shape, b rate, α after every iteration;
+    `responsibilities()`: q(z) of the last one (materialize=True)."""
+
+    SCHEDULES = {"auto": _lib.GAMMAMIX_AUTO, "streamed": _lib.GAMMAMIX_STREAMED, "resident": _lib.GAMMAMIX_RESIDENT}
+
+    def __init__(self, N, K, prior_a, prior_b, prior_alpha, init_a=None, init_b=None, init_s=None, n_problems=1, schedule="auto", materialize=False,
+                 device=-1, stream=None):
+        L = _lib.lib()
+        K, C = int(K), int(n_problems)
+        shape = (max(C, 0), max(K, 0))
+
+        def full(v, name):
+            a = _c(v)
+            if a.shape == shape[1:]:
+                a = np.ascontiguousarray(np.broadcast_to(a, shape))
+            if a.shape != shape:
+                raise ValueError(f"{name} must be [K] or [problems][K] = {list(shape)}, got {list(a.shape)}")
+            return a
+
+        keep = [full(prior_a[0], "prior_a shape"), full(prior_a[1], "prior_a rate"), full(prior_b[0], "prior_b shape"), full(prior_b[1], "prior_b rate"),
+                full(prior_alpha, "prior_alpha")]
+        desc = _lib.GammaMixDesc()
+        desc.N, desc.n_problems, desc.K = int(N), C, K
+        desc.prior_a_shape, desc.prior_a_rate, desc.prior_b_shape, desc.prior_b_rate, desc.prior_alpha = [_p(a) for a in keep]
+        if init_a is not None:
+            keep.append(full(init_a, "init_a"))
+            desc.init_a = _p(keep[-1])
+        if init_b is not None:
+            keep += [full(init_b[0], "init_b shape"), full(init_b[1], "init_b rate")]
+            desc.init_b_shape, desc.init_b_rate = _p(keep[-2]), _p(keep[-1])
+        if init_s is not None:
+            keep.append(full(init_s, "init_s"))
+            desc.init_s_alpha = _p(keep[-1])
+        desc.schedule = self.SCHEDULES[schedule] if isinstance(schedule, str) else int(schedule)
+        desc.materialize_responsibilities, desc.device = int(bool(materialize)), int(device)
+        desc.stream = ctypes.c_void_p(stream) if stream else None
+        self.N, self.T, self.K, self.n_problems, self.n_chains, self.materialize = int(N), int(N), K, C, C, bool(materialize)
+        self._h = ctypes.c_void_p()
+        st = L.rxhip_gammamix_create(ctypes.byref(desc), ctypes.byref(self._h))
+        if st != _lib.OK:
+            msg = L.rxhip_last_error(self._h).decode() if self._h else L.rxhip_status_string(st).decode()
+            if self._h:
+                L.rxhip_destroy(self._h)
+                self._h = None
+            raise RxHipError(st, msg or L.rxhip_status_string(st).decode())
+        self._iters = 0
+        self._fe = False
+        self._data_ref = None
+
+    _chk = LGSSMEngine._chk
+    close = LGSSMEngine.close
+    __del__ = LGSSMEngine.__del__
+    __enter__ = LGSSMEngine.__enter__
+    __exit__ = LGSSMEngine.__exit__
+    sync = LGSSMEngine.sync
+    set_data = HGFEngine.set_data                  # [N][problems] ('time_chain') or [problems][N] ('chain_time')
+    set_data_device = HGFEngine.set_data_device
+    free_energy = LGSSMEngine.free_energy
+    free_energy_per_chain = LGSSMEngine.free_energy_per_chain
+    counters = LGSSMEngine.counters
+    stream = LGSSMEngine.stream
+    set_profiling = LGSSMEngine.set_profiling
+    kernel_times = LGSSMEngine.kernel_times
+    run = BinomialRegressionEngine.run
+    run_async = BinomialRegressionEngine.run_async
+
+    @staticmethod
+    def schedule(N, K):
+        """1: streamed, for every N and K of the engine's range; 0: outside it."""
+        return int(_lib.lib().rxhip_gammamix_schedule(int(N), int(K)))
+
+    def set_stored_log(self, stored):
+        """the streamed pass reads ln y from memory (True, the default) or recomputes it (False): the same bits, a measurement switch."""
+        self._chk(_lib.lib().rxhip_gammamix_set_stored_log(self._h, int(bool(stored))))
+
+    def history(self):
+        """after every iteration of the last run: dict of a, b_shape, b_rate, alpha, each [iterations][problems][K], and fe [iterations][problems] (None
+        when the run was without the free energy)."""
+        n = max(int(self._iters), 0)
+        h = np.empty((n, self.n_problems, 4, self.K))
+        fe = np.empty((n, self.n_problems)) if self._fe else None
+        self._chk(_lib.lib().rxhip_gammamix_get_history(self._h, _p(h), _p(fe) if self._fe else None))
+        return dict(a=h[:, :, 0], b_shape=h[:, :, 1], b_rate=h[:, :, 2], alpha=h[:, :, 3], fe=fe)
+
+    def responsibilities(self):
+        """q(z) of the last iteration: [problems][N][K] (a missing point's row is 0)."""
+        r = np.empty((self.n_problems, self.N, self.K))
+        self._chk(_lib.lib().rxhip_gammamix_get_responsibilities(self._h, _p(r)))
+        return r
+
+
 class Communicator:
     """RCCL communicator made through the C ABI (rxhip_comm_*): rank 0 calls `Communicator.unique_id()`, the 128 bytes
     travel to the other ranks by any host-side means, every rank constructs `Communicator(nranks, id, rank)`."""
