@@ -1,5 +1,8 @@
 // engine.hpp — what every translation unit behind the C ABI shares: the engine object, its family table, the error path, the device guards and the
-// helpers every creator and run uses.
+// helpers every creator, run and result getter uses.  A new family writes its descriptor checks, its buffers, its kernels' launches and one row of the
+// family table; it gets for free the handle and its refusal path (new_handle, count_devices, open_device, finish_create), the start and the bookkeeping
+// of a run (run_preamble, reserve, finish_run), the check of ingested observations (check_observations), the preamble of its getters (results_ready,
+// open_results, sum_chunk_partials) and every entry point common to all engines.
 //   rxhip.hip       runtime (pools, arenas), the state-space and drift-chain engines, the entry points common to all engines, the shared helpers
 //   vmp_engines.hip the mixture, HGF, probit, HMM, latent-AR, binomial-, linear- and multinomial-regression and Gamma-mixture engines and their family rows
 //   graph_abi.hip   the graph entry points: host-only lowering (graph_lowering.hpp), rxhip_create, the node-array executor's rxhip_tree_* wrappers
@@ -362,10 +365,21 @@ rxhip_status prof_end(rxhip_engine* e);
 bool host_chol_inv(int n, const double* A, double* out, double* logdet);   // host Cholesky inverse + log-determinant of an SPD matrix
 
 // ---- creators -------------------------------------------------------------------------------------------------------------------
+// A handle-first creator is: new_handle, the family's own refusals (each with a text), count_devices, the description, open_device, the family's
+// buffers, finish_create.
+// The head: `out` and the descriptor are checked (a null `out`, or desc_ok false: a bare RXHIP_ERR_BADARG with *out == nullptr), then *out is a
+// fresh handle of `kind` with device = -1, so that every later refusal of the creator can leave its text in it (fail; the caller reads it with
+// rxhip_last_error and destroys the handle).
+rxhip_status new_handle(bool desc_ok, rxhip_engine** out, EngineKind kind);
+// the number of visible devices, or the refusal "no HIP device visible"
+rxhip_status count_devices(rxhip_engine* e, int* ndev);
 // The device and stream of a new engine: desc.device (≥ 0: checked against the `ndev` visible ones; else the caller's current device) becomes e->device and
 // is SELECTED through the creator's own guard — declared before the call, so that it covers the rest of the creator and hands the caller its device
 // back on every way out — then desc.stream is adopted or a pooled one acquired.
 rxhip_status open_device(rxhip_engine* e, DevGuard& guard, int device, void* stream, int ndev);
+// The tail: the common free-energy buffers — d_fe_chain [chains], zeroed, and d_fe_total with room for `fe_capacity` iterations (runs grow it
+// with reserve) — and the zeroed status word of the kernels.
+rxhip_status finish_create(rxhip_engine* e, size_t chains, int fe_capacity);
 // ---- runs -----------------------------------------------------------------------------------------------------------------------
 // "iterations must be positive", "no observations": the refusals every run starts with (need_data false: the family has a data check of its own)
 rxhip_status run_preamble(rxhip_engine* e, int32_t iterations, bool need_data = true);
@@ -383,4 +397,13 @@ inline void finish_run(rxhip_engine* e, int iterations, bool want_fe, bool filte
 // A family's check of freshly ingested observations, on the device copy, whichever way it arrived: `launch` enqueues the kernel that raises `bit` of
 // d_status over the n = T · chains values (nb blocks of 256); a refused array counts as not set.
 rxhip_status check_observations(rxhip_engine* e, void (*launch)(rxhip_engine* e, long long n, unsigned nb), int bit, const char* message);
+// The refusals of a result getter, in this order: "<name>: no run yet", then — a free-energy array was passed — "<name>: free energy was not
+// requested in the last run".  `name` is the entry point's without the rxhip_ prefix.
+rxhip_status results_ready(rxhip_engine* e, const char* name, bool wants_fe);
+// The whole preamble of a result getter: a bare RXHIP_ERR_BADARG unless kind_ok (the family's predicate; false for a null handle), results_ready, then
+// the engine's device selected through the getter's own guard (declared before the call, as for open_device) and its stream drained.  A getter with
+// refusals of its own that come before "no run yet" has tested the kind for them and passes true.
+rxhip_status open_results(rxhip_engine* e, DevGuard& guard, bool kind_ok, const char* name, bool wants_fe);
+// tot[q] = Σ_c part[c · n + q], q < n, over the nchunk partials of one chain in ascending chunk order: the order in which the iterate kernels add them
+void sum_chunk_partials(const double* part, size_t nchunk, size_t n, double* tot);
 }  // namespace rxhip

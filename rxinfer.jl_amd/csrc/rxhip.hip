@@ -138,7 +138,30 @@ hipError_t rxhip::stream_acquire(int device, hipStream_t* out) {
     }
     return hipStreamCreateWithFlags(out, hipStreamNonBlocking);
 }
-// ---- what every creator and every run shares (engine.hpp) ----
+// ---- what every creator, every run and every result getter shares (engine.hpp) ----
+rxhip_status rxhip::new_handle(bool desc_ok, rxhip_engine** out, EngineKind kind) {
+    if (!out) return RXHIP_ERR_BADARG;
+    *out = nullptr;
+    if (!desc_ok) return RXHIP_ERR_BADARG;
+    rxhip_engine* e = new rxhip_engine();   // from here on every refusal carries a text (rxhip_last_error; the caller destroys the handle)
+    *out = e;
+    e->kind = kind;
+    e->device = -1;
+    return RXHIP_OK;
+}
+rxhip_status rxhip::count_devices(rxhip_engine* e, int* ndev) {
+    *ndev = 0;
+    if (hipGetDeviceCount(ndev) != hipSuccess || *ndev <= 0) return fail(e, RXHIP_ERR_NO_DEVICE, "no HIP device visible");
+    return RXHIP_OK;
+}
+rxhip_status rxhip::finish_create(rxhip_engine* e, size_t chains, int fe_capacity) {
+    HIPCHK(e, hipMalloc(&e->d_fe_chain, sizeof(double) * chains));
+    HIPCHK(e, hipMemset(e->d_fe_chain, 0, sizeof(double) * chains));
+    if (rxhip_status st = reserve(e, &e->fe_total_cap, fe_capacity, {{&e->d_fe_total, 1}})) return st;
+    HIPCHK(e, hipMalloc(&e->d_status, sizeof(int)));
+    HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
+    return RXHIP_OK;
+}
 rxhip_status rxhip::open_device(rxhip_engine* e, DevGuard& guard, int device, void* stream, int ndev) {
     if (device >= 0) {
         if (device >= ndev) return fail(e, RXHIP_ERR_BADARG, "device %d out of range (%d visible)", device, ndev);
@@ -184,6 +207,25 @@ rxhip_status rxhip::check_observations(rxhip_engine* e, void (*launch)(rxhip_eng
         return fail(e, RXHIP_ERR_BADARG, "%s", message);
     }
     return RXHIP_OK;
+}
+rxhip_status rxhip::results_ready(rxhip_engine* e, const char* name, bool wants_fe) {
+    if (!e->ran) return fail(e, RXHIP_ERR_STATE, "%s: no run yet", name);
+    if (wants_fe && !e->last_want_fe) return fail(e, RXHIP_ERR_STATE, "%s: free energy was not requested in the last run", name);
+    return RXHIP_OK;
+}
+rxhip_status rxhip::open_results(rxhip_engine* e, DevGuard& guard, bool kind_ok, const char* name, bool wants_fe) {
+    if (!kind_ok) return RXHIP_ERR_BADARG;
+    if (rxhip_status st = results_ready(e, name, wants_fe)) return st;
+    HIPCHK(e, guard.set(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return RXHIP_OK;
+}
+void rxhip::sum_chunk_partials(const double* part, size_t nchunk, size_t n, double* tot) {
+    for (size_t q = 0; q < n; ++q) {
+        double acc = part[q];
+        for (size_t c = 1; c < nchunk; ++c) acc += part[c * n + q];
+        tot[q] = acc;
+    }
 }
 // Arenas up to 2 GB are parked the same way — hipFree of a multi-megabyte block costs ≈120–170 µs (more than a whole sweep of
 // the reference's own benchmark sizes), hipMalloc + hipFree of the 1 GB of a d = 64, T = 10⁴ engine ≈40 ms.  At most 4 blocks /

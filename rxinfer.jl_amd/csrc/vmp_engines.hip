@@ -338,9 +338,8 @@ rxhip_status rxhip_gmm_update(rxhip_engine* e, int32_t want_fe) {
 rxhip_status rxhip_gmm_get_history(rxhip_engine* e, double* hist) {
     TREE_GUARD(e);
     if (!e || e->kind != EngineKind::Mixture || !hist) return RXHIP_ERR_BADARG;
-    if (!e->ran) return fail(e, RXHIP_ERR_STATE, "get_history: no run yet");
-    SET_DEVICE(e);
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    DevGuard guard;
+    if (rxhip_status st = open_results(e, guard, true, "get_history", false)) return st;
     HIPCHK(e, hipMemcpy(hist, e->g.d_hist, sizeof(double) * (size_t)e->g.it * e->g.hist_stride, hipMemcpyDeviceToHost));
     return RXHIP_OK;
 }
@@ -439,19 +438,14 @@ rxhip_status rxhip_hgf_create(const rxhip_hgf_desc* ds, rxhip_engine** out) {
 }
 
 rxhip_status rxhip_probit_create(const rxhip_probit_desc* ds, rxhip_engine** out) {
-    if (!out) return RXHIP_ERR_BADARG;
-    *out = nullptr;
-    if (!ds || ds->T <= 0 || ds->n_series <= 0) return RXHIP_ERR_BADARG;
-    rxhip_engine* e = new rxhip_engine();   // from here on every refusal carries a text (rxhip_last_error; the caller destroys the handle)
-    *out = e;
-    e->kind = EngineKind::Probit;
-    e->device = -1;
+    if (rxhip_status st = new_handle(ds && ds->T > 0 && ds->n_series > 0, out, EngineKind::Probit)) return st;
+    rxhip_engine* e = *out;
     if (!(ds->q > 0) || !std::isfinite(ds->q)) return fail(e, RXHIP_ERR_BADARG, "probit: the transition variance q must be positive and finite (got %g)", ds->q);
     if (!(ds->v0 > 0) || !std::isfinite(ds->v0)) return fail(e, RXHIP_ERR_BADARG, "probit: the prior variance v0 must be positive and finite (got %g)", ds->v0);
     if (ds->n_gh < 1 || ds->n_gh > 32) return fail(e, RXHIP_ERR_BADARG, "probit: n_gh must be 1 … 32 Gauss-Hermite points (got %d)", ds->n_gh);
     if (!std::isfinite(ds->a) || !std::isfinite(ds->c) || !std::isfinite(ds->m0)) return fail(e, RXHIP_ERR_BADARG, "probit: a, c and m0 must be finite");
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(e, RXHIP_ERR_NO_DEVICE, "no HIP device visible");
+    if (rxhip_status st = count_devices(e, &ndev)) return st;
     e->pb.ds = *ds;
     e->T = ds->T;
     e->H = 1;   // x has T + 1 entries: the posterior arrays carry one row beyond the observations
@@ -466,11 +460,7 @@ rxhip_status rxhip_probit_create(const rxhip_probit_desc* ds, rxhip_engine** out
     HIPCHK(e, hipMalloc(&e->pb.d_block, sizeof(double) * (4 * R * C + C + chunks * C)));
     HIPCHK(e, hipMalloc(&e->d_mean, sizeof(double) * R * C));
     HIPCHK(e, hipMalloc(&e->d_cov, sizeof(double) * R * C));
-    HIPCHK(e, hipMalloc(&e->d_fe_chain, sizeof(double) * C));
-    if (rxhip_status st = reserve(e, &e->fe_total_cap, 16, {{&e->d_fe_total, 1}})) return st;
-    HIPCHK(e, hipMalloc(&e->d_status, sizeof(int)));
-    HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
-    return RXHIP_OK;
+    return finish_create(e, C, 16);
 }
 
 // the hidden Markov model's parameter block (doubles): π | prior | init | counts | log tables ×2 | Ã B̃ | KL | statistics | their sum | log Z̃
@@ -499,13 +489,8 @@ static size_t hmm_param_doubles(size_t C, size_t K, size_t M, bool shared) {
 }
 
 rxhip_status rxhip_hmm_create(const rxhip_hmm_desc* ds, rxhip_engine** out) {
-    if (!out) return RXHIP_ERR_BADARG;
-    *out = nullptr;
-    if (!ds) return RXHIP_ERR_BADARG;
-    rxhip_engine* e = new rxhip_engine();   // from here on every refusal carries a text (rxhip_last_error; the caller destroys the handle)
-    *out = e;
-    e->kind = EngineKind::Hmm;
-    e->device = -1;
+    if (rxhip_status st = new_handle(ds != nullptr, out, EngineKind::Hmm)) return st;
+    rxhip_engine* e = *out;
     if (ds->T < 1) return fail(e, RXHIP_ERR_BADARG, "hmm: T must be at least 1 (got %lld)", (long long)ds->T);
     if (ds->n_series < 1) return fail(e, RXHIP_ERR_BADARG, "hmm: n_series must be at least 1 (got %lld)", (long long)ds->n_series);
     if (ds->K < 2 || ds->K > hmm::kMaxK) return fail(e, RXHIP_ERR_BADARG, "hmm: K must be 2 … %d states (got %d)", hmm::kMaxK, ds->K);
@@ -528,7 +513,7 @@ rxhip_status rxhip_hmm_create(const rxhip_hmm_desc* ds, rxhip_engine** out) {
     if (!positive(ds->prior_s0, K) || !(std::fabs(psum - 1.0) <= 1e-12))
         return fail(e, RXHIP_ERR_BADARG, "hmm: prior_s0 must be positive probabilities summing to 1 within 1e-12 (sum − 1 = %g)", psum - 1.0);
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(e, RXHIP_ERR_NO_DEVICE, "no HIP device visible");
+    if (rxhip_status st = count_devices(e, &ndev)) return st;
     e->hm.K = ds->K; e->hm.M = ds->M; e->hm.shared = ds->share_parameters ? 1 : 0;
     e->T = ds->T;
     e->H = 1;   // s has T + 1 entries
@@ -553,21 +538,16 @@ rxhip_status rxhip_hmm_create(const rxhip_hmm_desc* ds, rxhip_engine** out) {
     HIPCHK(e, hipMemcpy(e->hm.d_par, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice));
     HIPCHK(e, hipMalloc(&e->hm.d_alpha, sizeof(double) * R * C * K));
     HIPCHK(e, hipMalloc(&e->hm.d_gamma, sizeof(double) * R * C * K));
-    HIPCHK(e, hipMalloc(&e->d_fe_chain, sizeof(double) * C));
-    if (rxhip_status st = reserve(e, &e->fe_total_cap, 32, {{&e->d_fe_total, 1}})) return st;
-    HIPCHK(e, hipMalloc(&e->d_status, sizeof(int)));
-    HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
-    return RXHIP_OK;
+    return finish_create(e, C, 32);
 }
 
 rxhip_status rxhip_hmm_get_states(rxhip_engine* e, double* probs, int32_t layout) {
     if (!e || e->kind != EngineKind::Hmm) return RXHIP_ERR_BADARG;
     if (!probs) return fail(e, RXHIP_ERR_BADARG, "hmm_get_states: no output array");
     if (layout != RXHIP_LAYOUT_TIME_CHAIN && layout != RXHIP_LAYOUT_CHAIN_TIME) return fail(e, RXHIP_ERR_BADARG, "hmm_get_states: unknown layout %d", layout);
-    if (!e->ran) return fail(e, RXHIP_ERR_STATE, "hmm_get_states: no run yet");
-    SET_DEVICE(e);
+    DevGuard guard;
+    if (rxhip_status st = open_results(e, guard, true, "hmm_get_states", false)) return st;
     const size_t C = (size_t)e->n_chains, K = (size_t)e->hm.K, R = (size_t)e->T + 1;
-    HIPCHK(e, hipStreamSynchronize(e->stream));
     if (layout == RXHIP_LAYOUT_TIME_CHAIN || C == 1) {
         HIPCHK(e, hipMemcpy(probs, e->hm.d_gamma, sizeof(double) * R * C * K, hipMemcpyDeviceToHost));
         return RXHIP_OK;
@@ -580,11 +560,9 @@ rxhip_status rxhip_hmm_get_states(rxhip_engine* e, double* probs, int32_t layout
 }
 
 rxhip_status rxhip_hmm_get_parameters(rxhip_engine* e, double* A_counts, double* B_counts) {
-    if (!e || e->kind != EngineKind::Hmm) return RXHIP_ERR_BADARG;
-    if (!e->ran) return fail(e, RXHIP_ERR_STATE, "hmm_get_parameters: no run yet");
-    SET_DEVICE(e);
+    DevGuard guard;
+    if (rxhip_status st = open_results(e, guard, e && e->kind == EngineKind::Hmm, "hmm_get_parameters", false)) return st;
     const size_t C = (size_t)e->n_chains, K = (size_t)e->hm.K, M = (size_t)e->hm.M, KM = (K + M) * K, G = e->hm.shared ? 1 : C;
-    HIPCHK(e, hipStreamSynchronize(e->stream));
     std::vector<double> tmp(G * KM);
     HIPCHK(e, hipMemcpy(tmp.data(), hmm_params(e).counts, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost));
     for (size_t g = 0; g < G; ++g) {
@@ -635,13 +613,8 @@ static bool spd_inverse(int p, const double* a, std::vector<double>& sym, std::v
 extern "C" {
 
 rxhip_status rxhip_lar_create(const rxhip_lar_desc* ds, rxhip_engine** out) {
-    if (!out) return RXHIP_ERR_BADARG;
-    *out = nullptr;
-    if (!ds) return RXHIP_ERR_BADARG;
-    rxhip_engine* e = new rxhip_engine();   // from here on every refusal carries a text (rxhip_last_error; the caller destroys the handle)
-    *out = e;
-    e->kind = EngineKind::Lar;
-    e->device = -1;
+    if (rxhip_status st = new_handle(ds != nullptr, out, EngineKind::Lar)) return st;
+    rxhip_engine* e = *out;
     if (ds->order < 1 || ds->order > lar::kMaxP) return fail(e, RXHIP_ERR_BADARG, "lar: order must be 1 … %d (got %d)", lar::kMaxP, ds->order);
     if (ds->T < 1) return fail(e, RXHIP_ERR_BADARG, "lar: T must be at least 1 (got %lld)", (long long)ds->T);
     if (ds->n_series < 1) return fail(e, RXHIP_ERR_BADARG, "lar: n_series must be at least 1 (got %lld)", (long long)ds->n_series);
@@ -673,7 +646,7 @@ rxhip_status rxhip_lar_create(const rxhip_lar_desc* ds, rxhip_engine** out) {
     } else
         vinit = vth0;   // the prior's own covariance
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(e, RXHIP_ERR_NO_DEVICE, "no HIP device visible");
+    if (rxhip_status st = count_devices(e, &ndev)) return st;
     e->la.P = P; e->la.shared = ds->share_parameters ? 1 : 0;
     e->T = ds->T;
     e->n_chains = ds->n_series;
@@ -713,20 +686,15 @@ rxhip_status rxhip_lar_create(const rxhip_lar_desc* ds, rxhip_engine** out) {
     HIPCHK(e, hipMemcpy(e->la.d_par, init.data(), sizeof(double) * init.size(), hipMemcpyHostToDevice));
     HIPCHK(e, hipMalloc(&e->la.d_rec, sizeof(double) * n * (size_t)(P + 2) * C));
     HIPCHK(e, hipMalloc(&e->la.d_out, sizeof(double) * n * (size_t)(P + 2) * C));   // m [n][series] | band [n][P + 1][series]
-    HIPCHK(e, hipMalloc(&e->d_fe_chain, sizeof(double) * C));
-    if (rxhip_status st = reserve(e, &e->fe_total_cap, 32, {{&e->d_fe_total, 1}})) return st;
-    HIPCHK(e, hipMalloc(&e->d_status, sizeof(int)));
-    HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
-    return RXHIP_OK;
+    return finish_create(e, C, 32);
 }
 
 rxhip_status rxhip_lar_get_states(rxhip_engine* e, double* mean, double* cov, int32_t layout) {
     if (!e || e->kind != EngineKind::Lar) return RXHIP_ERR_BADARG;
     if (layout != RXHIP_LAYOUT_TIME_CHAIN && layout != RXHIP_LAYOUT_CHAIN_TIME) return fail(e, RXHIP_ERR_BADARG, "lar_get_states: unknown layout %d", layout);
-    if (!e->ran) return fail(e, RXHIP_ERR_STATE, "lar_get_states: no run yet");
-    SET_DEVICE(e);
+    DevGuard guard;
+    if (rxhip_status st = open_results(e, guard, true, "lar_get_states", false)) return st;
     const size_t C = (size_t)e->n_chains, T = (size_t)e->T, P = (size_t)e->la.P, n = T + P;
-    HIPCHK(e, hipStreamSynchronize(e->stream));
     std::vector<double> tmp(n * (P + 2) * C);
     HIPCHK(e, hipMemcpy(tmp.data(), e->la.d_out, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost));
     const double *zm = tmp.data(), *band = zm + n * C;
@@ -748,11 +716,9 @@ rxhip_status rxhip_lar_get_states(rxhip_engine* e, double* mean, double* cov, in
 }
 
 rxhip_status rxhip_lar_get_parameters(rxhip_engine* e, double* theta_mean, double* theta_cov, double* gamma_shape, double* gamma_rate) {
-    if (!e || e->kind != EngineKind::Lar) return RXHIP_ERR_BADARG;
-    if (!e->ran) return fail(e, RXHIP_ERR_STATE, "lar_get_parameters: no run yet");
-    SET_DEVICE(e);
+    DevGuard guard;
+    if (rxhip_status st = open_results(e, guard, e && e->kind == EngineKind::Lar, "lar_get_parameters", false)) return st;
     const size_t C = (size_t)e->n_chains, P = (size_t)e->la.P, G = e->la.shared ? 1 : C, NQ = (size_t)lar::nq((int)P), rows = (size_t)e->last_iterations * G;
-    HIPCHK(e, hipStreamSynchronize(e->stream));
     std::vector<double> tmp(rows * NQ);
     HIPCHK(e, hipMemcpy(tmp.data(), e->la.d_hist, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost));
     for (size_t r = 0; r < rows; ++r) {
@@ -847,13 +813,8 @@ void rxhip_binreg_schedule(int64_t N, int32_t d, int32_t* tile_points, int32_t* 
 }
 
 rxhip_status rxhip_binreg_create(const rxhip_binreg_desc* ds, rxhip_engine** out) {
-    if (!out) return RXHIP_ERR_BADARG;
-    *out = nullptr;
-    if (!ds) return RXHIP_ERR_BADARG;
-    rxhip_engine* e = new rxhip_engine();   // from here on every refusal carries a text (rxhip_last_error; the caller destroys the handle)
-    *out = e;
-    e->kind = EngineKind::Binreg;
-    e->device = -1;
+    if (rxhip_status st = new_handle(ds != nullptr, out, EngineKind::Binreg)) return st;
+    rxhip_engine* e = *out;
     if (ds->d < 1 || ds->d > breg::kMaxD) return fail(e, RXHIP_ERR_BADARG, "binreg: d must be 1 … %d (got %d)", breg::kMaxD, ds->d);
     if (ds->N < 1) return fail(e, RXHIP_ERR_BADARG, "binreg: N must be at least 1 (got %lld)", (long long)ds->N);
     if (ds->n_problems < 1) return fail(e, RXHIP_ERR_BADARG, "binreg: n_problems must be at least 1 (got %lld)", (long long)ds->n_problems);
@@ -871,7 +832,7 @@ rxhip_status rxhip_binreg_create(const rxhip_binreg_desc* ds, rxhip_engine** out
     } else
         vinit = v0;   // the prior's own covariance
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(e, RXHIP_ERR_NO_DEVICE, "no HIP device visible");
+    if (rxhip_status st = count_devices(e, &ndev)) return st;
     e->br.d = d;
     e->T = ds->N;
     e->n_chains = ds->n_problems;
@@ -905,20 +866,13 @@ rxhip_status rxhip_binreg_create(const rxhip_binreg_desc* ds, rxhip_engine** out
     HIPCHK(e, hipMalloc(&e->br.d_S, sizeof(double) * C * DP * DP));
     HIPCHK(e, hipMalloc(&e->br.d_part, sizeof(double) * C * (size_t)e->br.nchunk * (size_t)breg::npart(d)));
     HIPCHK(e, hipMalloc(&e->br.d_xi_part, sizeof(double) * C * (size_t)e->br.nchunk_xi * 32));
-    HIPCHK(e, hipMalloc(&e->d_fe_chain, sizeof(double) * C));
-    if (rxhip_status st = reserve(e, &e->fe_total_cap, 32, {{&e->d_fe_total, 1}})) return st;
-    HIPCHK(e, hipMalloc(&e->d_status, sizeof(int)));
-    HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
-    return RXHIP_OK;
+    return finish_create(e, C, 32);
 }
 
 rxhip_status rxhip_binreg_get_parameters(rxhip_engine* e, double* mean, double* cov, double* free_energy) {
-    if (!e || e->kind != EngineKind::Binreg) return RXHIP_ERR_BADARG;
-    if (!e->ran) return fail(e, RXHIP_ERR_STATE, "binreg_get_parameters: no run yet");
-    if (free_energy && !e->last_want_fe) return fail(e, RXHIP_ERR_STATE, "binreg_get_parameters: free energy was not requested in the last run");
-    SET_DEVICE(e);
+    DevGuard guard;
+    if (rxhip_status st = open_results(e, guard, e && e->kind == EngineKind::Binreg, "binreg_get_parameters", free_energy != nullptr)) return st;
     const size_t C = (size_t)e->n_chains, d = (size_t)e->br.d, rows = (size_t)e->last_iterations * C;
-    HIPCHK(e, hipStreamSynchronize(e->stream));
     const BregParams p = breg_params(e);
     if (mean) HIPCHK(e, hipMemcpy(mean, p.hist_m, sizeof(double) * rows * d, hipMemcpyDeviceToHost));
     if (cov) HIPCHK(e, hipMemcpy(cov, p.hist_v, sizeof(double) * rows * d * d, hipMemcpyDeviceToHost));
@@ -1065,13 +1019,9 @@ void rxhip_arreg_schedule(int64_t n_rows, int32_t d, int32_t* tile_rows, int32_t
 }
 
 rxhip_status rxhip_arreg_create(const rxhip_arreg_desc* ds, rxhip_engine** out) {
-    if (!out) return RXHIP_ERR_BADARG;
-    *out = nullptr;
-    if (!ds) return RXHIP_ERR_BADARG;
-    rxhip_engine* e = new rxhip_engine();   // from here on every refusal carries a text (rxhip_last_error; the caller destroys the handle)
-    *out = e;
-    e->kind = ds->lagged ? EngineKind::ArregLagged : EngineKind::Arreg;
-    e->device = -1;
+    if (rxhip_status st = new_handle(ds != nullptr, out, EngineKind::Arreg)) return st;
+    rxhip_engine* e = *out;
+    if (ds->lagged) e->kind = EngineKind::ArregLagged;
     if (ds->d < 1 || ds->d > arreg::kMaxD) return fail(e, RXHIP_ERR_BADARG, "arreg: d must be 1 … %d (got %d)", arreg::kMaxD, ds->d);
     if (ds->N < 1) return fail(e, RXHIP_ERR_BADARG, "arreg: N must be at least 1 (got %lld)", (long long)ds->N);
     if (ds->n_series < 1) return fail(e, RXHIP_ERR_BADARG, "arreg: n_series must be at least 1 (got %lld)", (long long)ds->n_series);
@@ -1089,7 +1039,7 @@ rxhip_status rxhip_arreg_create(const rxhip_arreg_desc* ds, rxhip_engine** out) 
     double ld_l0 = 0.0;
     if (!spd_inverse(d, ds->prior_theta_precision, l0, v0, &ld_l0)) return fail(e, RXHIP_ERR_BADARG, "arreg: prior_theta_precision is not symmetric positive definite");
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(e, RXHIP_ERR_NO_DEVICE, "no HIP device visible");
+    if (rxhip_status st = count_devices(e, &ndev)) return st;
     auto& a = e->ar;
     a.d = d; a.lagged = ds->lagged ? 1 : 0; a.shared = ds->share_parameters ? 1 : 0;
     a.rows = a.lagged ? arreg::lag_rows(ds->N, d) : ds->N;
@@ -1121,12 +1071,7 @@ rxhip_status rxhip_arreg_create(const rxhip_arreg_desc* ds, rxhip_engine** out) 
         HIPCHK(e, hipMalloc(&a.d_yreg, sizeof(double) * C * N));
     }
     HIPCHK(e, hipMalloc(&a.d_part, sizeof(double) * C * (size_t)a.nchunk * (size_t)arreg::nstat(d)));
-    HIPCHK(e, hipMalloc(&e->d_fe_chain, sizeof(double) * C));
-    HIPCHK(e, hipMemset(e->d_fe_chain, 0, sizeof(double) * C));
-    if (rxhip_status st = reserve(e, &e->fe_total_cap, 32, {{&e->d_fe_total, 1}})) return st;
-    HIPCHK(e, hipMalloc(&e->d_status, sizeof(int)));
-    HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
-    return RXHIP_OK;
+    return finish_create(e, C, 32);
 }
 
 }  // extern "C"
@@ -1223,12 +1168,9 @@ static rxhip_status arreg_run_async(rxhip_engine* e, int32_t iterations, int32_t
 extern "C" {
 
 rxhip_status rxhip_arreg_get_parameters(rxhip_engine* e, double* theta_mean, double* theta_cov, double* gamma_shape, double* gamma_rate, double* free_energy) {
-    if (!e || !is_arreg(e)) return RXHIP_ERR_BADARG;
-    if (!e->ran) return fail(e, RXHIP_ERR_STATE, "arreg_get_parameters: no run yet");
-    if (free_energy && !e->last_want_fe) return fail(e, RXHIP_ERR_STATE, "arreg_get_parameters: free energy was not requested in the last run");
-    SET_DEVICE(e);
+    DevGuard guard;
+    if (rxhip_status st = open_results(e, guard, e && is_arreg(e), "arreg_get_parameters", free_energy != nullptr)) return st;
     const size_t C = (size_t)e->n_chains, d = (size_t)e->ar.d, G = e->ar.shared ? 1 : C, NH = (size_t)arreg::nhist((int)d), rows = (size_t)e->last_iterations * G;
-    HIPCHK(e, hipStreamSynchronize(e->stream));
     std::vector<double> tmp(rows * NH);
     HIPCHK(e, hipMemcpy(tmp.data(), e->ar.d_hist, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost));
     for (size_t r = 0; r < rows; ++r) {
@@ -1251,11 +1193,7 @@ rxhip_status rxhip_arreg_get_statistics(rxhip_engine* e, double* Gout, double* h
     std::vector<double> part(C * nchunk * NS), tot(NS);
     HIPCHK(e, hipMemcpy(part.data(), e->ar.d_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost));
     for (size_t s = 0; s < C; ++s) {
-        for (size_t q = 0; q < NS; ++q) {   // ascending chunk order, as k_arreg_iterate adds them
-            double acc = part[s * nchunk * NS + q];
-            for (size_t c = 1; c < nchunk; ++c) acc += part[(s * nchunk + c) * NS + q];
-            tot[q] = acc;
-        }
+        sum_chunk_partials(&part[s * nchunk * NS], nchunk, NS, tot.data());   // as k_arreg_iterate adds them
         for (size_t i = 0; i < d; ++i) {
             if (Gout)
                 for (size_t j = 0; j < d; ++j) {
@@ -1300,13 +1238,9 @@ void rxhip_mnreg_schedule(int64_t N, int32_t K, int32_t* tile_rows, int32_t* chu
 }
 
 rxhip_status rxhip_mnreg_create(const rxhip_mnreg_desc* ds, rxhip_engine** out) {
-    if (!out) return RXHIP_ERR_BADARG;
-    *out = nullptr;
-    if (!ds) return RXHIP_ERR_BADARG;
-    rxhip_engine* e = new rxhip_engine();   // from here on every refusal carries a text (rxhip_last_error; the caller destroys the handle)
-    *out = e;
-    e->kind = ds->mode == RXHIP_MNREG_ONLINE ? EngineKind::MnregOnline : EngineKind::Mnreg;
-    e->device = -1;
+    if (rxhip_status st = new_handle(ds != nullptr, out, EngineKind::Mnreg)) return st;
+    rxhip_engine* e = *out;
+    if (ds->mode == RXHIP_MNREG_ONLINE) e->kind = EngineKind::MnregOnline;
     if (ds->mode != RXHIP_MNREG_BATCH && ds->mode != RXHIP_MNREG_ONLINE) return fail(e, RXHIP_ERR_BADARG, "mnreg: mode must be RXHIP_MNREG_BATCH or RXHIP_MNREG_ONLINE (got %d)", ds->mode);
     if (ds->K < mnreg::kMinK || ds->K > mnreg::kMaxK) return fail(e, RXHIP_ERR_BADARG, "mnreg: K must be %d … %d (got %d)", mnreg::kMinK, mnreg::kMaxK, ds->K);
     if (ds->N < 1) return fail(e, RXHIP_ERR_BADARG, "mnreg: N must be at least 1 (got %lld)", (long long)ds->N);
@@ -1326,7 +1260,7 @@ rxhip_status rxhip_mnreg_create(const rxhip_mnreg_desc* ds, rxhip_engine** out) 
     } else
         vinit = v0;   // the prior's own covariance
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(e, RXHIP_ERR_NO_DEVICE, "no HIP device visible");
+    if (rxhip_status st = count_devices(e, &ndev)) return st;
     auto& m = e->mn;
     m.K = K; m.d = d; m.online = ds->mode == RXHIP_MNREG_ONLINE; m.keep_cov = m.online && ds->keep_cov_history ? 1 : 0; m.n_trials = ds->n_trials;
     m.nchunk = mnreg::chunks(ds->N, K);
@@ -1358,12 +1292,7 @@ rxhip_status rxhip_mnreg_create(const rxhip_mnreg_desc* ds, rxhip_engine** out) 
         if (m.keep_cov) HIPCHK(e, hipMalloc(&m.d_oncov, sizeof(double) * N * C * D * D));
     } else
         HIPCHK(e, hipMalloc(&m.d_part, sizeof(double) * C * (size_t)m.nchunk * (size_t)mnreg::npart(K)));
-    HIPCHK(e, hipMalloc(&e->d_fe_chain, sizeof(double) * C));
-    HIPCHK(e, hipMemset(e->d_fe_chain, 0, sizeof(double) * C));
-    if (rxhip_status st = reserve(e, &e->fe_total_cap, 32, {{&e->d_fe_total, 1}})) return st;
-    HIPCHK(e, hipMalloc(&e->d_status, sizeof(int)));
-    HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
-    return RXHIP_OK;
+    return finish_create(e, C, 32);
 }
 
 }  // extern "C"
@@ -1457,12 +1386,9 @@ static rxhip_status mnreg_run_async(rxhip_engine* e, int32_t iterations, int32_t
 extern "C" {
 
 rxhip_status rxhip_mnreg_get_parameters(rxhip_engine* e, double* mean, double* cov, double* free_energy) {
-    if (!e || !is_mnreg(e)) return RXHIP_ERR_BADARG;
-    if (!e->ran) return fail(e, RXHIP_ERR_STATE, "mnreg_get_parameters: no run yet");
-    if (free_energy && !e->last_want_fe) return fail(e, RXHIP_ERR_STATE, "mnreg_get_parameters: free energy was not requested in the last run");
-    SET_DEVICE(e);
+    DevGuard guard;
+    if (rxhip_status st = open_results(e, guard, e && is_mnreg(e), "mnreg_get_parameters", free_energy != nullptr)) return st;
     const size_t C = (size_t)e->n_chains, d = (size_t)e->mn.d, T = (size_t)e->T;
-    HIPCHK(e, hipStreamSynchronize(e->stream));
     const MnregParams p = mnreg_params(e);
     if (e->mn.online) {   // the last step: mean [series][d], cov [series][d][d], F_T [series]
         std::vector<double> last(C * (d + d * d));
@@ -1484,12 +1410,11 @@ rxhip_status rxhip_mnreg_get_parameters(rxhip_engine* e, double* mean, double* c
 rxhip_status rxhip_mnreg_get_history(rxhip_engine* e, double* mean, double* var, double* cov, double* free_energy) {
     if (!e || !is_mnreg(e)) return RXHIP_ERR_BADARG;
     if (!e->mn.online) return fail(e, RXHIP_ERR_STATE, "mnreg_get_history: the engine was not created with RXHIP_MNREG_ONLINE");
-    if (!e->ran) return fail(e, RXHIP_ERR_STATE, "mnreg_get_history: no run yet");
+    if (rxhip_status st = results_ready(e, "mnreg_get_history", false)) return st;
     if (cov && !e->mn.keep_cov) return fail(e, RXHIP_ERR_STATE, "mnreg_get_history: the covariance history was not kept (keep_cov_history)");
-    if (free_energy && !e->last_want_fe) return fail(e, RXHIP_ERR_STATE, "mnreg_get_history: free energy was not requested in the last run");
-    SET_DEVICE(e);
+    DevGuard guard;
+    if (rxhip_status st = open_results(e, guard, true, "mnreg_get_history", free_energy != nullptr)) return st;
     const size_t rows = (size_t)e->T * (size_t)e->n_chains, d = (size_t)e->mn.d;
-    HIPCHK(e, hipStreamSynchronize(e->stream));
     const MnregParams p = mnreg_params(e);
     if (mean) HIPCHK(e, hipMemcpy(mean, p.hist_m, sizeof(double) * rows * d, hipMemcpyDeviceToHost));
     if (var) HIPCHK(e, hipMemcpy(var, p.hist_v, sizeof(double) * rows * d, hipMemcpyDeviceToHost));
@@ -1508,11 +1433,7 @@ rxhip_status rxhip_mnreg_get_statistics(rxhip_engine* e, double* Yout, double* S
     std::vector<double> part(C * nchunk * NP), tot(NP), S(K), kap(K);
     HIPCHK(e, hipMemcpy(part.data(), e->mn.d_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost));
     for (size_t s = 0; s < C; ++s) {
-        for (size_t q = 0; q < NP; ++q) {   // ascending chunk order, as k_mnreg_iterate adds them
-            double acc = part[s * nchunk * NP + q];
-            for (size_t c = 1; c < nchunk; ++c) acc += part[(s * nchunk + c) * NP + q];
-            tot[q] = acc;
-        }
+        sum_chunk_partials(&part[s * nchunk * NP], nchunk, NP, tot.data());   // as k_mnreg_iterate adds them
         mnreg::suffix((int)K, tot.data(), S.data(), kap.data());
         S[K - 1] = tot[K - 1];
         if (Yout) std::memcpy(Yout + s * K, tot.data(), sizeof(double) * K);
@@ -1762,13 +1683,8 @@ extern "C" {
 int32_t rxhip_gammamix_schedule(int64_t N, int32_t K) { return gammamix::schedule(N, K); }
 
 rxhip_status rxhip_gammamix_create(const rxhip_gammamix_desc* ds, rxhip_engine** out) {
-    if (!out) return RXHIP_ERR_BADARG;
-    *out = nullptr;
-    if (!ds) return RXHIP_ERR_BADARG;
-    rxhip_engine* e = new rxhip_engine();   // from here on every refusal carries a text (rxhip_last_error; the caller destroys the handle)
-    *out = e;
-    e->kind = EngineKind::GammaMix;
-    e->device = -1;
+    if (rxhip_status st = new_handle(ds != nullptr, out, EngineKind::GammaMix)) return st;
+    rxhip_engine* e = *out;
     constexpr int KS = gammamix::kMaxK;
     if (ds->K < 1 || ds->K > KS) return fail(e, RXHIP_ERR_BADARG, "gammamix: K must be 1 … %d (got %d)", KS, ds->K);
     if (ds->N < 1) return fail(e, RXHIP_ERR_BADARG, "gammamix: N must be at least 1 (got %lld)", (long long)ds->N);
@@ -1792,7 +1708,7 @@ rxhip_status rxhip_gammamix_create(const rxhip_gammamix_desc* ds, rxhip_engine**
         if (ds->prior_a_shape[q] < 1.0)
             return fail(e, RXHIP_ERR_BADARG, "gammamix: prior_a_shape must be at least 1 (entry %zu is %g): below it the shape's objective is not concave", q, ds->prior_a_shape[q]);
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(e, RXHIP_ERR_NO_DEVICE, "no HIP device visible");
+    if (rxhip_status st = count_devices(e, &ndev)) return st;
     auto& g = e->gx;
     g.K = K; g.KT = gammamix::padded_k(K);
     g.sched = ds->schedule ? ds->schedule : gammamix::schedule(ds->N, K);
@@ -1833,12 +1749,7 @@ rxhip_status rxhip_gammamix_create(const rxhip_gammamix_desc* ds, rxhip_engine**
     HIPCHK(e, hipMalloc(&g.d_state, sizeof(double) * init.size()));
     HIPCHK(e, hipMalloc(&g.d_part, sizeof(double) * C * (size_t)g.nchunk * NQ));
     if (g.materialize) HIPCHK(e, hipMalloc(&g.d_resp, sizeof(double) * C * (size_t)ds->N * (size_t)K));
-    HIPCHK(e, hipMalloc(&e->d_fe_chain, sizeof(double) * C));
-    HIPCHK(e, hipMemset(e->d_fe_chain, 0, sizeof(double) * C));
-    if (rxhip_status st = reserve(e, &e->fe_total_cap, 32, {{&e->d_fe_total, 1}})) return st;
-    HIPCHK(e, hipMalloc(&e->d_status, sizeof(int)));
-    HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
-    return RXHIP_OK;
+    return finish_create(e, C, 32);
 }
 
 rxhip_status rxhip_gammamix_set_stored_log(rxhip_engine* e, int32_t stored) {
@@ -1850,11 +1761,8 @@ rxhip_status rxhip_gammamix_set_stored_log(rxhip_engine* e, int32_t stored) {
 }
 
 rxhip_status rxhip_gammamix_get_history(rxhip_engine* e, double* hist, double* free_energy) {
-    if (!e || e->kind != EngineKind::GammaMix) return RXHIP_ERR_BADARG;
-    if (!e->ran) return fail(e, RXHIP_ERR_STATE, "gammamix_get_history: no run yet");
-    if (free_energy && !e->last_want_fe) return fail(e, RXHIP_ERR_STATE, "gammamix_get_history: free energy was not requested in the last run");
-    SET_DEVICE(e);
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    DevGuard guard;
+    if (rxhip_status st = open_results(e, guard, e && e->kind == EngineKind::GammaMix, "gammamix_get_history", free_energy != nullptr)) return st;
     const size_t rows = (size_t)e->last_iterations * (size_t)e->n_chains;
     if (hist) HIPCHK(e, hipMemcpy(hist, e->gx.d_hist, sizeof(double) * rows * 4 * (size_t)e->gx.K, hipMemcpyDeviceToHost));
     if (free_energy) HIPCHK(e, hipMemcpy(free_energy, e->gx.d_fe, sizeof(double) * rows, hipMemcpyDeviceToHost));
@@ -1864,9 +1772,8 @@ rxhip_status rxhip_gammamix_get_history(rxhip_engine* e, double* hist, double* f
 rxhip_status rxhip_gammamix_get_responsibilities(rxhip_engine* e, double* resp) {
     if (!e || e->kind != EngineKind::GammaMix || !resp) return RXHIP_ERR_BADARG;
     if (!e->gx.materialize) return fail(e, RXHIP_ERR_STATE, "gammamix_get_responsibilities: the engine was created without materialize_responsibilities");
-    if (!e->ran) return fail(e, RXHIP_ERR_STATE, "gammamix_get_responsibilities: no run yet");
-    SET_DEVICE(e);
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    DevGuard guard;
+    if (rxhip_status st = open_results(e, guard, true, "gammamix_get_responsibilities", false)) return st;
     HIPCHK(e, hipMemcpy(resp, e->gx.d_resp, sizeof(double) * (size_t)e->n_chains * (size_t)e->T * (size_t)e->gx.K, hipMemcpyDeviceToHost));
     return RXHIP_OK;
 }

@@ -7,6 +7,7 @@ same C ABI; this mirror exists because no Julia toolchain is present in the buil
 parity tests are written against it in the reference tests' own shape
 (test/models/statespace/mlgssm_test.jl)."""
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Any, Optional
 
 import numpy as np
@@ -190,19 +191,44 @@ def univariate_drift_chain(prior_mean, prior_var, c, obs_var, prior_through_tran
     return UnivariateDriftChain(float(prior_mean), float(prior_var), float(c), float(obs_var), bool(prior_through_transition))
 
 
-def _infer_drift_chain(model, data, iterations, free_energy, options, catch_exception):
+def _guarded(model, kw, body):
+    """The second half of every per-family function.  `body(own)` constructs its engines as `own(Engine(...))`, which closes them on every way
+    out; what the body raises propagates, or with `catch_exception` comes back as the result's `error` (src/inference/batch.jl:440-446).  What a
+    family raises BEFORE it calls this (unknown options, shapes, a missing `initialization`) propagates always."""
+    owned = []
+
+    def own(eng):
+        owned.append(eng)
+        return eng
+
+    try:
+        return body(own)
+    except Exception as err:
+        if not kw.catch_exception:
+            raise
+        return InferenceResult({}, None, None, model, err)
+    finally:
+        for eng in owned:
+            eng.close()
+
+
+def _iterations(kw):
+    return 1 if kw.iterations is None else int(kw.iterations)
+
+
+def _infer_drift_chain(model, data, kw):
     """posteriors["x"] = NormalMeanVariance with mean / var [T] (or [chain][T]); free_energy one value per iteration."""
-    options = _check_options(options)
+    options = _check_options(kw.options)
     y = np.asarray(data["y"], dtype=np.float64)
     single = y.ndim == 1
     if single:
         y = y[None]
     C, T = y.shape
-    iters = 1 if iterations is None else int(iterations)
-    eng = None
-    try:
-        eng = DriftChainEngine(T, model.prior_mean, model.prior_var, model.c, model.obs_var, n_chains=C,
-                               prior_through_transition=model.prior_through_transition, device=int(options.get("device", -1)))
+    iters, free_energy = _iterations(kw), kw.free_energy
+
+    def body(own):
+        eng = own(DriftChainEngine(T, model.prior_mean, model.prior_var, model.c, model.obs_var, n_chains=C,
+                                   prior_through_transition=model.prior_through_transition, device=int(options.get("device", -1))))
         eng.set_data(y[..., None], layout="chain_time")
         eng.run(iterations=iters, free_energy=free_energy)
         mean, var = eng.marginals(layout="chain_time")
@@ -212,13 +238,8 @@ def _infer_drift_chain(model, data, iterations, free_energy, options, catch_exce
             mean, var = mean[0], var[0]
             fe = fe[0] if fe is not None else None
         return InferenceResult({"x": NormalMeanVariance(mean, var)}, None, fe, model, None)
-    except Exception as err:
-        if not catch_exception:
-            raise
-        return InferenceResult({}, None, None, model, err)
-    finally:
-        if eng is not None:
-            eng.close()
+
+    return _guarded(model, kw, body)
 
 
 @dataclass
@@ -237,20 +258,20 @@ def probit_ssm(a, c, q, prior_mean, prior_var, n_gh=32):
     return ProbitSSM(float(a), float(c), float(q), float(prior_mean), float(prior_var), int(n_gh))
 
 
-def _infer_probit(model, data, iterations, free_energy, options, catch_exception):
+def _infer_probit(model, data, kw):
     """y: [T] or [T][series], entries 0, 1 or NaN (missing).  posteriors["x"] = NormalMeanVariance with mean / var [T+1] (or [T+1][series]);
     free_energy: one value per parallel-EP iteration (summed over the series of a batch)."""
-    options = _check_options(options)
+    options = _check_options(kw.options)
     y = np.asarray(data["y"], dtype=np.float64)
     single = y.ndim == 1
     if single:
         y = y[:, None]
     T, C = y.shape
-    iters = 1 if iterations is None else int(iterations)
-    eng = None
-    try:
-        eng = ProbitEngine(T, model.a, model.c, model.q, model.prior_mean, model.prior_var, n_series=C, n_gh=model.n_gh,
-                           device=int(options.get("device", -1)))
+    iters, free_energy = _iterations(kw), kw.free_energy
+
+    def body(own):
+        eng = own(ProbitEngine(T, model.a, model.c, model.q, model.prior_mean, model.prior_var, n_series=C, n_gh=model.n_gh,
+                               device=int(options.get("device", -1))))
         eng.set_data(y, layout="time_chain")
         eng.run(iterations=iters, free_energy=free_energy)
         mean, var = eng.marginals(layout="time_chain")
@@ -258,13 +279,8 @@ def _infer_probit(model, data, iterations, free_energy, options, catch_exception
         if single:
             mean, var = mean[:, 0], var[:, 0]
         return InferenceResult({"x": NormalMeanVariance(mean, var)}, None, fe, model, None)
-    except Exception as err:
-        if not catch_exception:
-            raise
-        return InferenceResult({}, None, None, model, err)
-    finally:
-        if eng is not None:
-            eng.close()
+
+    return _guarded(model, kw, body)
 
 
 @dataclass
@@ -292,21 +308,21 @@ def one_hot_to_codes(vectors):
     return np.where(ok, np.argmax(v, axis=-1).astype(np.float64), np.nan)
 
 
-def _infer_hmm(model, data, iterations, free_energy, options, catch_exception):
+def _infer_hmm(model, data, kw):
     """x: integer symbol codes [T] or [T][series] (floats with NaN = missing are taken as they are).  posteriors["s"]: probabilities
     [T+1][K] (or [T+1][series][K]); posteriors["A"], ["B"]: Dirichlet counts [K][K], [M][K] (a leading series axis for an unshared batch);
     free_energy: one value per iteration (summed over the series of a batch)."""
-    options = _check_options(options)
+    options = _check_options(kw.options)
     x = np.asarray(data["x"], dtype=np.float64)
     single = x.ndim == 1
     if single:
         x = x[:, None]
     T, C = x.shape
-    iters = 1 if iterations is None else int(iterations)
-    eng = None
-    try:
-        eng = HMMEngine(T, model.prior_A, model.prior_B, model.prior_s0, model.init_A, model.init_B, n_series=C,
-                        share_parameters=model.share_parameters, device=int(options.get("device", -1)))
+    iters, free_energy = _iterations(kw), kw.free_energy
+
+    def body(own):
+        eng = own(HMMEngine(T, model.prior_A, model.prior_B, model.prior_s0, model.init_A, model.init_B, n_series=C,
+                            share_parameters=model.share_parameters, device=int(options.get("device", -1))))
         eng.set_data(x, layout="time_chain")
         eng.run(iterations=iters, free_energy=free_energy)
         s = eng.states(layout="time_chain")
@@ -317,13 +333,8 @@ def _infer_hmm(model, data, iterations, free_energy, options, catch_exception):
         if single or model.share_parameters:
             a, b = a[0], b[0]
         return InferenceResult({"s": s, "A": a, "B": b}, None, fe, model, None)
-    except Exception as err:
-        if not catch_exception:
-            raise
-        return InferenceResult({}, None, None, model, err)
-    finally:
-        if eng is not None:
-            eng.close()
+
+    return _guarded(model, kw, body)
 
 
 @dataclass
@@ -348,21 +359,21 @@ def latent_autoregressive(order, tau, prior_theta=None, prior_gamma=(1, 1), prio
     return LatentAutoregressive(int(order), float(tau), f(prior_theta), g(prior_gamma), f(prior_x0), f(init_theta), g(init_gamma), bool(share_parameters))
 
 
-def _infer_lar(model, data, iterations, free_energy, options, catch_exception):
+def _infer_lar(model, data, kw):
     """y: [T] or [T][series], NaN = missing.  posteriors["x"]: (mean [T][p], cov [T][p][p]) of the last iteration (a series axis after T for a
     batch); posteriors["theta"]: (mean [iterations][p], cov [iterations][p][p]) and posteriors["gamma"]: (shape [iterations], rate [iterations])
     per iteration (a series axis after the iterations for an unshared batch); free_energy: one value per iteration (summed over the series)."""
-    options = _check_options(options)
+    options = _check_options(kw.options)
     y = np.asarray(data["y"], dtype=np.float64)
     single = y.ndim == 1
     if single:
         y = y[:, None]
     T, C = y.shape
-    iters = 1 if iterations is None else int(iterations)
-    eng = None
-    try:
-        eng = LAREngine(T, model.order, model.tau, model.prior_theta, model.prior_gamma, model.prior_x0, model.init_theta, model.init_gamma,
-                        n_series=C, share_parameters=model.share_parameters, device=int(options.get("device", -1)))
+    iters, free_energy = _iterations(kw), kw.free_energy
+
+    def body(own):
+        eng = own(LAREngine(T, model.order, model.tau, model.prior_theta, model.prior_gamma, model.prior_x0, model.init_theta, model.init_gamma,
+                            n_series=C, share_parameters=model.share_parameters, device=int(options.get("device", -1))))
         eng.set_data(y, layout="time_chain")
         eng.run(iterations=iters, free_energy=free_energy)
         xm, xc = eng.states(layout="time_chain")
@@ -373,13 +384,8 @@ def _infer_lar(model, data, iterations, free_energy, options, catch_exception):
         if single or model.share_parameters:
             tm, tc, ga, gb = tm[:, 0], tc[:, 0], ga[:, 0], gb[:, 0]
         return InferenceResult({"x": (xm, xc), "theta": (tm, tc), "gamma": (ga, gb)}, None, fe, model, None)
-    except Exception as err:
-        if not catch_exception:
-            raise
-        return InferenceResult({}, None, None, model, err)
-    finally:
-        if eng is not None:
-            eng.close()
+
+    return _guarded(model, kw, body)
 
 
 @dataclass
@@ -398,11 +404,11 @@ def binomial_regression(prior_xi, prior_precision, init=None):
     return BinomialRegression(np.asarray(prior_xi, dtype=np.float64), np.asarray(prior_precision, dtype=np.float64), f(init))
 
 
-def _infer_binreg(model, data, iterations, free_energy, options, catch_exception):
+def _infer_binreg(model, data, kw):
     """X: [N][d] or [problems][N][d]; y, n_trials: [N] or [problems][N], a NaN y = missing.  posteriors["β"]: (mean [iterations][d], cov
     [iterations][d][d]) after every iteration (a problem axis after the iterations for a batch); free_energy: one value per iteration, per
     problem ([iterations][problems]) for a batch."""
-    options = _check_options(options)
+    options = _check_options(kw.options)
     X = np.asarray(data["X"], dtype=np.float64)
     single = X.ndim == 2
     if single:
@@ -410,23 +416,18 @@ def _infer_binreg(model, data, iterations, free_energy, options, catch_exception
     y = np.asarray(data["y"], dtype=np.float64).reshape(X.shape[:2])
     n = np.asarray(data["n_trials"], dtype=np.float64).reshape(X.shape[:2])
     C, N, d = X.shape
-    iters = 1 if iterations is None else int(iterations)
-    eng = None
-    try:
-        eng = BinomialRegressionEngine(N, d, model.prior_xi, model.prior_precision, model.init, n_problems=C, device=int(options.get("device", -1)))
+    iters = _iterations(kw)
+
+    def body(own):
+        eng = own(BinomialRegressionEngine(N, d, model.prior_xi, model.prior_precision, model.init, n_problems=C, device=int(options.get("device", -1))))
         eng.set_data(X, y, n)
-        eng.run(iterations=iters, free_energy=free_energy)
+        eng.run(iterations=iters, free_energy=kw.free_energy)
         mean, cov, fe = eng.parameters()
         if single:
             mean, cov, fe = mean[:, 0], cov[:, 0], (fe[:, 0] if fe is not None else None)
         return InferenceResult({"β": (mean, cov)}, None, fe, model, None)
-    except Exception as err:
-        if not catch_exception:
-            raise
-        return InferenceResult({}, None, None, model, err)
-    finally:
-        if eng is not None:
-            eng.close()
+
+    return _guarded(model, kw, body)
 
 
 @dataclass
@@ -457,28 +458,28 @@ def logistic_stick_breaking(m):
     return np.concatenate((s * rest[:-1], rest[-1:]))
 
 
-def _infer_mnreg(model, data, iterations, free_energy, options, catch_exception, autoupdates, keephistory, historyvars):
+def _infer_mnreg(model, data, kw):
     """Y: [N][K] or [problems][N][K] counts, a row with any NaN = missing.  Offline: posteriors["ψ"]: (mean [iterations][d], cov
     [iterations][d][d]) after every iteration (a problem axis after the iterations for a batch), free_energy [iterations] (per problem for a batch).
     With `autoupdates` the rows are streamed (`ξ_ψ, W_ψ = weightedmean_precision(q(ψ))`), `iterations` per row: history["ψ"] = (mean [T][d], var
     [T][d]), posteriors["ψ"] = the last step's (mean, cov), free_energy [T] = F_t; "ψ_cov" in historyvars adds history["ψ_cov"] [T][d][d]."""
-    options = _check_options(options)
+    options = _check_options(kw.options)
     Y = np.asarray(data["y"], dtype=np.float64)
     single = Y.ndim == 2
     if single:
         Y = Y[None]
     C, N, K = Y.shape
-    iters = 1 if iterations is None else int(iterations)
-    online = bool(autoupdates)
-    if online and keephistory not in (None, N):
+    iters = _iterations(kw)
+    online = bool(kw.autoupdates)
+    if online and kw.keephistory not in (None, N):
         raise ValueError(f"multinomial regression: the streamed run keeps every step, keephistory must be {N}")
-    keep_cov = online and historyvars is not None and "ψ_cov" in historyvars
-    eng = None
-    try:
-        eng = MultinomialRegressionEngine(N, K, model.prior_xi, model.prior_precision, n_trials=model.n_trials, init=None if online else model.init,
-                                          n_problems=C, online=online, keep_cov_history=keep_cov, device=int(options.get("device", -1)))
+    keep_cov = online and kw.historyvars is not None and "ψ_cov" in kw.historyvars
+
+    def body(own):
+        eng = own(MultinomialRegressionEngine(N, K, model.prior_xi, model.prior_precision, n_trials=model.n_trials, init=None if online else model.init,
+                                              n_problems=C, online=online, keep_cov_history=keep_cov, device=int(options.get("device", -1))))
         eng.set_data(Y)
-        eng.run(iterations=iters, free_energy=free_energy)
+        eng.run(iterations=iters, free_energy=kw.free_energy)
         mean, cov, fe = eng.parameters()
         if not online:
             if single:
@@ -491,13 +492,8 @@ def _infer_mnreg(model, data, iterations, free_energy, options, catch_exception,
         if hc is not None:
             hist["ψ_cov"] = hc
         return InferenceResult({"ψ": (mean, cov)}, None, hf, model, None, history=hist, free_energy_history=hf)
-    except Exception as err:
-        if not catch_exception:
-            raise
-        return InferenceResult({}, None, None, model, err)
-    finally:
-        if eng is not None:
-            eng.close()
+
+    return _guarded(model, kw, body)
 
 
 @dataclass
@@ -528,22 +524,22 @@ def gaussian_regression(prior_mean, prior_precision, prior_gamma=(1, 1), init_ga
                               bool(share_parameters))
 
 
-def _infer_arreg(model, data, iterations, free_energy, options, catch_exception):
+def _infer_arreg(model, data, kw):
     """posteriors["θ"]: (mean [iterations][d], cov [iterations][d][d]) and posteriors["γ"]: (shape [iterations], rate [iterations]) after every
     iteration (KeepEach; a series axis after the iterations for an unshared batch); free_energy: one value per iteration (summed over the series)."""
-    options = _check_options(options)
+    options = _check_options(kw.options)
     dev = int(options.get("device", -1))
-    iters = 1 if iterations is None else int(iterations)
-    eng = None
-    try:
+    iters = _iterations(kw)
+
+    def body(own):
         if model.order is not None:
             y = np.asarray(data["y"], dtype=np.float64)
             single = y.ndim == 1
             if single:
                 y = y[:, None]
             T, C = y.shape
-            eng = ARRegressionEngine(T, model.order, model.prior_theta, model.prior_gamma, model.init_gamma, n_series=C, lagged=True,
-                                     share_parameters=model.share_parameters, device=dev)
+            eng = own(ARRegressionEngine(T, model.order, model.prior_theta, model.prior_gamma, model.init_gamma, n_series=C, lagged=True,
+                                         share_parameters=model.share_parameters, device=dev))
             eng.set_data(y, layout="time_chain")
         else:
             X = np.asarray(data["x"], dtype=np.float64)
@@ -552,23 +548,18 @@ def _infer_arreg(model, data, iterations, free_energy, options, catch_exception)
                 X = X[None]
             C, N, d = X.shape
             y = np.asarray(data["y"], dtype=np.float64).reshape(C, N)
-            eng = ARRegressionEngine(N, d, model.prior_theta, model.prior_gamma, model.init_gamma, n_series=C, share_parameters=model.share_parameters,
-                                     device=dev)
+            eng = own(ARRegressionEngine(N, d, model.prior_theta, model.prior_gamma, model.init_gamma, n_series=C, share_parameters=model.share_parameters,
+                                         device=dev))
             eng.set_regressors(X)
             eng.set_observations(y)
-        eng.run(iterations=iters, free_energy=free_energy)
+        eng.run(iterations=iters, free_energy=kw.free_energy)
         tm, tc, ga, gb, _ = eng.parameters()
-        fe = eng.free_energy() if free_energy else None
+        fe = eng.free_energy() if kw.free_energy else None
         if single or model.share_parameters:
             tm, tc, ga, gb = tm[:, 0], tc[:, 0], ga[:, 0], gb[:, 0]
         return InferenceResult({"θ": (tm, tc), "γ": (ga, gb)}, None, fe, model, None)
-    except Exception as err:
-        if not catch_exception:
-            raise
-        return InferenceResult({}, None, None, model, err)
-    finally:
-        if eng is not None:
-            eng.close()
+
+    return _guarded(model, kw, body)
 
 
 @dataclass
@@ -609,37 +600,32 @@ def gamma_mixture(prior_a, prior_b, prior_alpha, init_a=None, init_b=None, init_
                         None if init_a is None else np.asarray(init_a, dtype=np.float64), None if init_b is None else _gamma_pairs(init_b, "init_b"), al(init_s))
 
 
-def _infer_gammamix(model, data, iterations, free_energy, options, catch_exception):
+def _infer_gammamix(model, data, kw):
     """posteriors["as"]: the point masses â [iterations][K]; ["bs"]: (shape, rate), each [iterations][K] (KeepEach; a problem axis after the iterations for
     a batch); ["s"]: the last α [K]; ["z"]: the last q(z) [N][K]; free_energy: one value per iteration (summed over the problems)."""
-    options = _check_options(options)
+    options = _check_options(kw.options)
     dev = int(options.get("device", -1))
-    iters = 1 if iterations is None else int(iterations)
-    eng = None
-    try:
+    iters = _iterations(kw)
+
+    def body(own):
         y = np.asarray(data["y"], dtype=np.float64)
         single = y.ndim == 1
         if single:
             y = y[None]
         C, N = y.shape
         K = int(np.asarray(model.prior_alpha).shape[-1])
-        eng = GammaMixtureEngine(N, K, model.prior_a, model.prior_b, model.prior_alpha, model.init_a, model.init_b, model.init_s, n_problems=C,
-                                 materialize=True, device=dev)
+        eng = own(GammaMixtureEngine(N, K, model.prior_a, model.prior_b, model.prior_alpha, model.init_a, model.init_b, model.init_s, n_problems=C,
+                                     materialize=True, device=dev))
         eng.set_data(y, layout="chain_time")
-        eng.run(iterations=iters, free_energy=free_energy)
+        eng.run(iterations=iters, free_energy=kw.free_energy)
         h = eng.history()
-        fe = eng.free_energy() if free_energy else None
+        fe = eng.free_energy() if kw.free_energy else None
         a, bs, br, alpha, z = h["a"], h["b_shape"], h["b_rate"], h["alpha"][-1], eng.responsibilities()
         if single:
             a, bs, br, alpha, z = a[:, 0], bs[:, 0], br[:, 0], alpha[0], z[0]
         return InferenceResult({"as": a, "bs": (bs, br), "s": alpha, "z": z}, None, fe, model, None)
-    except Exception as err:
-        if not catch_exception:
-            raise
-        return InferenceResult({}, None, None, model, err)
-    finally:
-        if eng is not None:
-            eng.close()
+
+    return _guarded(model, kw, body)
 
 
 @dataclass
@@ -666,130 +652,115 @@ def _check_options(options):
     return options
 
 
-def _infer_mixture(model, data, iterations, free_energy, options, initialization, catch_exception):
+def _infer_mixture(model, data, kw):
     """posteriors (KeepEach, one entry per iteration as `returnvars = KeepEach()`): m -> NormalMeanVariance [it][K],
     p -> GammaShapeRate [it][K], s -> Dirichlet [it][K]; z (last iteration) if options['materialize_z'].
     Only the fixed point is pinned to the reference: the update order inside an iteration is an assumption, so per-iteration
     entries are drop-in for RxInfer's `KeepEach` results up to that order (include/rxhip.h)."""
-    options = _check_options(options)
+    options, initialization = _check_options(kw.options), kw.initialization
     if initialization is None:
         raise ValueError("mean-field VMP needs `initialization` (q(m), q(p), q(s)); cf. test/inference/inference_tests.jl:361-363")
     y = np.asarray(data["y"], dtype=np.float64).ravel()
-    iters = 1 if iterations is None else int(iterations)
+    iters = _iterations(kw)
     K = model.prior_mean.size
     qm, qp = initialization["m"], initialization["p"]
     qs = initialization.get("s", Dirichlet(np.ones(K)))
-    eng = None
-    try:
-        eng = GMMEngine(y.size, model.prior_mean, model.prior_var, model.prior_shape, model.prior_rate, model.prior_alpha,
-                        qm.mean, qm.var, qp.shape, qp.rate, qs.alpha,
-                        materialize_responsibilities=bool(options.get("materialize_z", False)), device=int(options.get("device", -1)))
+
+    def body(own):
+        eng = own(GMMEngine(y.size, model.prior_mean, model.prior_var, model.prior_shape, model.prior_rate, model.prior_alpha,
+                            qm.mean, qm.var, qp.shape, qp.rate, qs.alpha,
+                            materialize_responsibilities=bool(options.get("materialize_z", False)), device=int(options.get("device", -1))))
         eng.set_data(y)
-        eng.run(iters, free_energy)
+        eng.run(iters, kw.free_energy)
         h = eng.history()
         post = {"m": NormalMeanVariance(h[:, 0], h[:, 1]), "p": GammaShapeRate(h[:, 2], h[:, 3]), "s": Dirichlet(h[:, 4])}
         if options.get("materialize_z", False):
             post["z"] = eng.responsibilities()
-        return InferenceResult(post, None, eng.free_energy() if free_energy else None, model, None)
-    except Exception as err:
-        if not catch_exception:
-            raise
-        return InferenceResult({}, None, None, model, err)
-    finally:
-        if eng is not None:
-            eng.close()
+        return InferenceResult(post, None, eng.free_energy() if kw.free_energy else None, model, None)
+
+    return _guarded(model, kw, body)
 
 
-def _infer_mv_mixture(model, data, iterations, free_energy, options, initialization, catch_exception):
+def _infer_mv_mixture(model, data, kw):
     """posteriors (KeepEach): m -> MvNormalMeanCovariance [it][K], w -> Wishart [it][K], s -> Dirichlet [it][K];
     z (last iteration) if options['materialize_z'].  initialization = {"m": MvNormalMeanCovariance, "w": Wishart, "s": Dirichlet}."""
-    options = _check_options(options)
+    options, initialization = _check_options(kw.options), kw.initialization
     if initialization is None or "m" not in initialization or "w" not in initialization:
         raise ValueError("mean-field VMP needs `initialization` (q(m), q(w)[, q(s)]); cf. test/models/mixtures/gmm_multivariate_tests.jl:66-70")
     y = np.asarray(data["y"], dtype=np.float64)
-    iters = 1 if iterations is None else int(iterations)
+    iters = _iterations(kw)
     K = model.prior_mean.shape[0]
     qm, qw = initialization["m"], initialization["w"]
     qs = initialization.get("s", Dirichlet(np.ones(K)))
-    eng = None
-    try:
-        eng = MvGMMEngine(y.shape[0], model.prior_mean, model.prior_cov, model.prior_nu, model.prior_scale, model.prior_alpha,
-                          qm.mean, qm.cov, np.broadcast_to(np.asarray(qw.nu, dtype=np.float64), (K,)).copy(), qw.S, qs.alpha,
-                          materialize_responsibilities=bool(options.get("materialize_z", False)), device=int(options.get("device", -1)))
+
+    def body(own):
+        eng = own(MvGMMEngine(y.shape[0], model.prior_mean, model.prior_cov, model.prior_nu, model.prior_scale, model.prior_alpha,
+                              qm.mean, qm.cov, np.broadcast_to(np.asarray(qw.nu, dtype=np.float64), (K,)).copy(), qw.S, qs.alpha,
+                              materialize_responsibilities=bool(options.get("materialize_z", False)), device=int(options.get("device", -1))))
         eng.set_data(y)
-        eng.run(iters, free_energy)
+        eng.run(iters, kw.free_energy)
         h = eng.history()
         post = {"m": MvNormalMeanCovariance(h["mean"], h["cov"]), "w": Wishart(h["nu"], h["V"]), "s": Dirichlet(h["alpha"])}
         if options.get("materialize_z", False):
             post["z"] = eng.responsibilities()
-        return InferenceResult(post, None, eng.free_energy() if free_energy else None, model, None)
-    except Exception as err:
-        if not catch_exception:
-            raise
-        return InferenceResult({}, None, None, model, err)
-    finally:
-        if eng is not None:
-            eng.close()
+        return InferenceResult(post, None, eng.free_energy() if kw.free_energy else None, model, None)
+
+    return _guarded(model, kw, body)
 
 
-def _infer_hgf(model, data, iterations, free_energy, options, initialization, catch_exception):
+def _infer_hgf(model, data, kw):
     """history[:zt], history[:xt] (KeepLast per observation) as NormalMeanVariance [T] (or [series][T]);
     free_energy = free_energy_history: mean over observations per VMP iteration (per series)."""
-    options = _check_options(options)
+    options = _check_options(kw.options)
     y = np.asarray(data["y"], dtype=np.float64)
     single = y.ndim == 1
     if single:
         y = y[None]
     S, T = y.shape
-    iters = 1 if iterations is None else int(iterations)
-    init = initialization or {}
+    iters = _iterations(kw)
+    init = kw.initialization or {}
     z0 = init.get("zt", NormalMeanVariance(0.0, 5.0))
     x0 = init.get("xt", NormalMeanVariance(0.0, 5.0))
-    eng = None
-    try:
-        eng = HGFEngine(T, S, model.kappa, model.omega, model.z_variance, model.y_variance, (float(z0.mean), float(z0.var)),
-                        (float(x0.mean), float(x0.var)), n_gh=model.n_gh, device=int(options.get("device", -1)))
+
+    def body(own):
+        eng = own(HGFEngine(T, S, model.kappa, model.omega, model.z_variance, model.y_variance, (float(z0.mean), float(z0.var)),
+                            (float(x0.mean), float(x0.var)), n_gh=model.n_gh, device=int(options.get("device", -1))))
         eng.set_data(y, layout="chain_time")
-        eng.run(iters, free_energy)
+        eng.run(iters, kw.free_energy)
         zm, zv, xm, xv = eng.history("chain_time")
         fe = None
-        if free_energy:
+        if kw.free_energy:
             fe = eng.free_energy() / S if single else None
             if not single:
                 fe = eng.free_energy_per_chain()
         if single:
             zm, zv, xm, xv = zm[0], zv[0], xm[0], xv[0]
         return InferenceResult({"zt": NormalMeanVariance(zm, zv), "xt": NormalMeanVariance(xm, xv)}, None, fe, model, None)
-    except Exception as err:
-        if not catch_exception:
-            raise
-        return InferenceResult({}, None, None, model, err)
-    finally:
-        if eng is not None:
-            eng.close()
+
+    return _guarded(model, kw, body)
 
 
-def _infer_lgssm_filtering(model, data, free_energy, options, initialization, catch_exception):
+def _infer_lgssm_filtering(model, data, kw):
     """Streaming inference with posterior -> prior feedback (`autoupdates`), the notebook's
     `rxinfer_inference_filtering` (benchmarks notebook cell 7): history["x"] = q(x_t) after every observation
     (`historyvars = (x_t = KeepLast(),)`, `keephistory = T`); free_energy_history = mean over observations of the
     per-observation free energy, one value (iterations = 1) per chain.  `initialization = {"x": MvNormalMeanCovariance}`
     overrides the model's prior as the initial q(x_t)."""
-    options = _check_options(options)
+    options, free_energy = _check_options(kw.options), kw.free_energy
     y = np.asarray(data["y"], dtype=np.float64)
     single = y.ndim == 2
     if single:
         y = y[None]
     C, T, dy = y.shape
     m0, V0 = model.prior_mean, model.prior_cov
-    if initialization and "x" in initialization:
-        m0, V0 = initialization["x"].mean, initialization["x"].cov
-    eng = None
-    try:
-        eng = LGSSMEngine(model.A, model.B, model.P, model.Q, m0, V0, T=T, n_chains=C,
-                          prior_through_transition=model.prior_through_transition,
-                          state_offset=model.state_offset, obs_offset=model.obs_offset,
-                          segments=int(options.get("segments", 0)), device=int(options.get("device", -1)))
+    if kw.initialization and "x" in kw.initialization:
+        m0, V0 = kw.initialization["x"].mean, kw.initialization["x"].cov
+
+    def body(own):
+        eng = own(LGSSMEngine(model.A, model.B, model.P, model.Q, m0, V0, T=T, n_chains=C,
+                              prior_through_transition=model.prior_through_transition,
+                              state_offset=model.state_offset, obs_offset=model.obs_offset,
+                              segments=int(options.get("segments", 0)), device=int(options.get("device", -1))))
         if single:   # one series: the whole call in one round trip
             m1, c1, f1 = eng.infer(y[0][:, None, :], free_energy=free_energy, filtering=True)
             mean, cov = np.transpose(m1, (1, 0, 2)), np.transpose(c1, (1, 0, 2, 3))
@@ -804,24 +775,16 @@ def _infer_lgssm_filtering(model, data, free_energy, options, initialization, ca
             fe = fe[0] if fe is not None else None
         return InferenceResult({}, None, None, model, None, history={"x": MvNormalMeanCovariance(mean, cov)},
                                free_energy_history=fe)
-    except Exception as err:
-        if not catch_exception:
-            raise
-        return InferenceResult({}, None, None, model, err)
-    finally:
-        if eng is not None:
-            eng.close()
+
+    return _guarded(model, kw, body)
 
 
-def _infer_lgssm_noise(model, data, iterations, free_energy, options, initialization, returnvars, catch_exception):
+def _infer_lgssm_noise(model, data, kw):
     """mean-field VMP of the chain with an unknown observation-noise precision (LGSSMNoiseEngine)"""
     from .engine import LGSSMNoiseEngine
-    options = dict(options or {})
-    unknown = set(options) - _OPTION_KEYS
-    if unknown:
-        raise ValueError(f"Unknown option keys {sorted(unknown)}; available: {sorted(_OPTION_KEYS)}")
-    eng = None
-    try:
+    options, initialization, free_energy = _check_options(kw.options), kw.initialization, kw.free_energy
+
+    def body(own):
         y = np.asarray(data["y"], dtype=np.float64)
         single = y.ndim == 2
         if single:
@@ -833,13 +796,12 @@ def _infer_lgssm_noise(model, data, iterations, free_energy, options, initializa
         init = (initialization or {}).get("W")
         if init is None:   # the reference refuses mean-field VMP without an @initialization marginal
             raise ValueError("mean-field VMP needs initialization = {\"W\": Wishart(ν, V)}")
-        iters = 1 if iterations is None else int(iterations)
-        eng = LGSSMNoiseEngine(model.A, model.B, model.P, model.prior_mean, model.prior_cov, T, float(pri.nu), np.asarray(pri.S, float).reshape(dy, dy),
-                               float(init.nu), np.asarray(init.S, float).reshape(dy, dy), n_chains=C,
-                               prior_through_transition=model.prior_through_transition, segments=int(options.get("segments", 0)),
-                               device=int(options.get("device", -1)))
+        eng = own(LGSSMNoiseEngine(model.A, model.B, model.P, model.prior_mean, model.prior_cov, T, float(pri.nu), np.asarray(pri.S, float).reshape(dy, dy),
+                                   float(init.nu), np.asarray(init.S, float).reshape(dy, dy), n_chains=C,
+                                   prior_through_transition=model.prior_through_transition, segments=int(options.get("segments", 0)),
+                                   device=int(options.get("device", -1))))
         eng.set_data(y, layout="chain_time")
-        eng.run(iterations=iters, free_energy=free_energy)
+        eng.run(iterations=_iterations(kw), free_energy=free_energy)
         mean, cov = eng.marginals(layout="chain_time")
         nu, V = eng.noise_posterior()
         fe = None
@@ -850,16 +812,11 @@ def _infer_lgssm_noise(model, data, iterations, free_energy, options, initializa
         if single:
             mean, cov, nu, V = mean[0], cov[0], nu[0], V[0]
         post = {"x": MvNormalMeanCovariance(mean, cov), "W": Wishart(nu, V)}
-        if returnvars is not None:
-            post = {k: v for k, v in post.items() if k in returnvars}
+        if kw.returnvars is not None:
+            post = {k: v for k, v in post.items() if k in kw.returnvars}
         return InferenceResult(post, None, fe, model, None)
-    except Exception as err:
-        if not catch_exception:
-            raise
-        return InferenceResult({}, None, None, model, err)
-    finally:
-        if eng is not None:
-            eng.close()
+
+    return _guarded(model, kw, body)
 
 
 def _smooth_on_executor(model, y, iters, free_energy, allow_missing, device):
@@ -885,55 +842,17 @@ def _smooth_on_executor(model, y, iters, free_energy, allow_missing, device):
     return np.stack([post[v][0] for v in xs], axis=1), np.stack([post[v][1] for v in xs], axis=1), fe
 
 
-def infer(*, model, data, iterations=None, free_energy=False, options=None, returnvars=None, predictvars=None,
-          catch_exception=False, initialization=None, autoupdates=None, keephistory=None, historyvars=None):
-    """Static (batch) inference on the device engine; with `autoupdates` (any truthy value: the state-space spec has
-    exactly one feedback, `mean_cov(q(x_t))` -> prior of the next step) the streaming / filtering twin.
-
-    data = {"y": array}: [T][dy] for one chain (as `data = (y = observations,)`), or
-    [chain][T][dy] for a batch of independent chains sharing the model.
-    Returns posteriors["x"] as MvNormalMeanCovariance with mean [T][d] / [chain][T][d].
-    `predictvars = ("y",)` (reference: `predictvars = (y = KeepLast(),)`): result.predictions["y"] holds the message toward
-    every y[t] — leave-one-out predictive for observed steps.  NaN rows of `y` are `missing` observations: a tail that no
-    chain observed is a forecast horizon (posteriors and predictions there are forward predictions, the sweep stays
-    time-parallel); `missing` values anywhere else select the masked schedule (any d, dy ≤ 64), where a missing y[t] sends no
-    message and its prediction is the smoothed predictive."""
-    if isinstance(model, UnivariateGaussianMixture):
-        return _infer_mixture(model, data, iterations, free_energy, options, initialization, catch_exception)
-    if isinstance(model, MultivariateGaussianMixture):
-        return _infer_mv_mixture(model, data, iterations, free_energy, options, initialization, catch_exception)
-    if isinstance(model, HierarchicalGaussianFilter):
-        return _infer_hgf(model, data, iterations, free_energy, options, initialization, catch_exception)
-    if isinstance(model, UnivariateDriftChain):
-        return _infer_drift_chain(model, data, iterations, free_energy, options, catch_exception)
-    if isinstance(model, ProbitSSM):
-        return _infer_probit(model, data, iterations, free_energy, options, catch_exception)
-    if isinstance(model, HiddenMarkovModel):
-        return _infer_hmm(model, data, iterations, free_energy, options, catch_exception)
-    if isinstance(model, LatentAutoregressive):
-        return _infer_lar(model, data, iterations, free_energy, options, catch_exception)
-    if isinstance(model, BinomialRegression):
-        return _infer_binreg(model, data, iterations, free_energy, options, catch_exception)
-    if isinstance(model, GaussianRegression):
-        return _infer_arreg(model, data, iterations, free_energy, options, catch_exception)
-    if isinstance(model, MultinomialRegression):
-        return _infer_mnreg(model, data, iterations, free_energy, options, catch_exception, autoupdates, keephistory, historyvars)
-    if isinstance(model, GammaMixture):
-        return _infer_gammamix(model, data, iterations, free_energy, options, catch_exception)
-    if not isinstance(model, LinearGaussianSSM):
-        raise TypeError("infer: no device schedule for this model type")
+def _infer_lgssm(model, data, kw):
+    """The state-space family: unknown observation precision, the filtering twin, else smoothing on the chain engine (see `infer`)."""
     if model.noise_precision_prior is not None:
-        if autoupdates or predictvars:
+        if kw.autoupdates or kw.predictvars:
             raise ValueError("unknown observation precision: no streaming twin and no predictions on the device")
-        return _infer_lgssm_noise(model, data, iterations, free_energy, options, initialization, returnvars, catch_exception)
-    if autoupdates:
-        if iterations not in (None, 1):
+        return _infer_lgssm_noise(model, data, kw)
+    if kw.autoupdates:
+        if kw.iterations not in (None, 1):
             raise ValueError("filtering: the one-step graph is a tree, iterations must be 1")
-        return _infer_lgssm_filtering(model, data, free_energy, options, initialization, catch_exception)
-    options = dict(options or {})
-    unknown = set(options) - _OPTION_KEYS
-    if unknown:  # closed key set, as reactivemp_inference.jl:129-143
-        raise ValueError(f"Unknown option keys {sorted(unknown)}; available: {sorted(_OPTION_KEYS)}")
+        return _infer_lgssm_filtering(model, data, kw)
+    options = _check_options(kw.options)   # closed key set, as reactivemp_inference.jl:129-143
     if "y" not in data:
         raise ValueError("data must provide `y`")
     y = np.asarray(data["y"], dtype=np.float64)
@@ -941,7 +860,7 @@ def infer(*, model, data, iterations=None, free_energy=False, options=None, retu
     if single:
         y = y[None]
     C, T, dy = y.shape
-    iters = 1 if iterations is None else int(iterations)
+    iters, free_energy, returnvars, predictvars = _iterations(kw), kw.free_energy, kw.returnvars, kw.predictvars
     horizon, allow_missing = 0, False
     nans = np.isnan(y)
     if nans.any():
@@ -956,8 +875,8 @@ def infer(*, model, data, iterations=None, free_energy=False, options=None, retu
             horizon, allow_missing = 0, True
         else:
             y, T = y[:, :T - horizon], T - horizon
-    eng = None
-    try:
+
+    def body(own):
         m0, V0, step_model = model.prior_mean, model.prior_cov, model.step_model
         if step_model is not None:
             if step_model.shape[0] != T + horizon:
@@ -965,12 +884,12 @@ def infer(*, model, data, iterations=None, free_energy=False, options=None, retu
             M = model.A.shape[0]
             m0, V0 = np.broadcast_to(m0, (M,) + m0.shape[-1:]), np.broadcast_to(V0, (M,) + V0.shape[-2:])
         try:
-            eng = LGSSMEngine(model.A, model.B, model.P, model.Q, m0, V0, T=T, n_chains=C,
-                              prior_through_transition=model.prior_through_transition, horizon=horizon,
-                              allow_missing=allow_missing, step_model=step_model,
-                              state_offset=(model.state_offset if model.input_matrix is None else np.zeros(model.A.shape[-1])),
-                              obs_offset=model.obs_offset,
-                              segments=int(options.get("segments", 0)), device=int(options.get("device", -1)))
+            eng = own(LGSSMEngine(model.A, model.B, model.P, model.Q, m0, V0, T=T, n_chains=C,
+                                  prior_through_transition=model.prior_through_transition, horizon=horizon,
+                                  allow_missing=allow_missing, step_model=step_model,
+                                  state_offset=(model.state_offset if model.input_matrix is None else np.zeros(model.A.shape[-1])),
+                                  obs_offset=model.obs_offset,
+                                  segments=int(options.get("segments", 0)), device=int(options.get("device", -1))))
         except RxHipError as err:
             # a model beyond the conditioning envelope of the information-form chain engines (include/rxhip.h rxhip_set_conditioning_guard): the same graph on the
             # node-array executor, as rxhip_create does for a host that hands over the graph — plain smoothing only (the executor has no forecast / prediction entry)
@@ -1019,10 +938,33 @@ def infer(*, model, data, iterations=None, free_energy=False, options=None, retu
         if returnvars is not None:
             post = {k: v for k, v in post.items() if k in returnvars}
         return InferenceResult(post, pred, fe, model, None)
-    except Exception as err:  # catch_exception semantics of batch.jl:440-446
-        if not catch_exception:
-            raise
-        return InferenceResult({}, None, None, model, err)
-    finally:
-        if eng is not None:
-            eng.close()
+
+    return _guarded(model, kw, body)
+
+
+# model type -> the function that runs it; every one takes (model, data, kw) with kw the keyword arguments of `infer`
+_FAMILIES = {UnivariateGaussianMixture: _infer_mixture, MultivariateGaussianMixture: _infer_mv_mixture, HierarchicalGaussianFilter: _infer_hgf,
+             UnivariateDriftChain: _infer_drift_chain, ProbitSSM: _infer_probit, HiddenMarkovModel: _infer_hmm, LatentAutoregressive: _infer_lar,
+             BinomialRegression: _infer_binreg, GaussianRegression: _infer_arreg, MultinomialRegression: _infer_mnreg, GammaMixture: _infer_gammamix,
+             LinearGaussianSSM: _infer_lgssm}
+
+
+def infer(*, model, data, iterations=None, free_energy=False, options=None, returnvars=None, predictvars=None,
+          catch_exception=False, initialization=None, autoupdates=None, keephistory=None, historyvars=None):
+    """Static (batch) inference on the device engine; with `autoupdates` (any truthy value: the state-space spec has
+    exactly one feedback, `mean_cov(q(x_t))` -> prior of the next step) the streaming / filtering twin.
+
+    data = {"y": array}: [T][dy] for one chain (as `data = (y = observations,)`), or
+    [chain][T][dy] for a batch of independent chains sharing the model.
+    Returns posteriors["x"] as MvNormalMeanCovariance with mean [T][d] / [chain][T][d].
+    `predictvars = ("y",)` (reference: `predictvars = (y = KeepLast(),)`): result.predictions["y"] holds the message toward
+    every y[t] — leave-one-out predictive for observed steps.  NaN rows of `y` are `missing` observations: a tail that no
+    chain observed is a forecast horizon (posteriors and predictions there are forward predictions, the sweep stays
+    time-parallel); `missing` values anywhere else select the masked schedule (any d, dy ≤ 64), where a missing y[t] sends no
+    message and its prediction is the smoothed predictive."""
+    family = _FAMILIES.get(type(model)) or next((f for cls, f in _FAMILIES.items() if isinstance(model, cls)), None)
+    if family is None:
+        raise TypeError("infer: no device schedule for this model type")
+    return family(model, data, SimpleNamespace(iterations=iterations, free_energy=free_energy, options=options, returnvars=returnvars,
+                                               predictvars=predictvars, catch_exception=catch_exception, initialization=initialization,
+                                               autoupdates=autoupdates, keephistory=keephistory, historyvars=historyvars))

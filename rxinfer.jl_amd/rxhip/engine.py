@@ -1,4 +1,5 @@
-"""LGSSMEngine — thin object wrapper over the rxhip C ABI (one handle = one batch of chains)."""
+"""The engine classes — thin object wrappers over the rxhip C ABI (one handle = one batch of chains / series / problems).  `_Engine` owns what is
+true of every handle; a family's class adds its descriptor and its own getters."""
 import ctypes
 
 import numpy as np
@@ -18,7 +19,150 @@ def _p(a):
     return a.ctypes.data_as(c_double_p)
 
 
-class LGSSMEngine:
+def _lay(layout):
+    return _lib.LAYOUT_TIME_CHAIN if layout == "time_chain" else _lib.LAYOUT_CHAIN_TIME
+
+
+class _Engine:
+    """One `rxhip_engine*` and what the C ABI answers for every kind of it: creation failure, lifecycle, runs, free energies, counters and
+    measurement.  A family's class fills its descriptor, calls its creator into `self._h = ctypes.c_void_p()` and hands the status to `_created`;
+    what exists only for some kinds (marginals, the filtering twin, a family's getters and `schedule`) stays on the classes that have it."""
+
+    n_chains = 1   # free_energy_per_chain: the engines without a batch axis are one chain
+
+    def _created(self, st, text=""):
+        """The end of every constructor.  A refused creation leaves no handle behind and raises with `text` (the graph entry points report
+        through rxhip_lowering_error), else the handle's own message, else the name of the status."""
+        if st != _lib.OK:
+            L = _lib.lib()
+            msg = text or (self._last_error() if self._h else "") or L.rxhip_status_string(st).decode()
+            if self._h:
+                L.rxhip_destroy(self._h)
+            self._h = None
+            raise RxHipError(st, msg)
+        self._iters, self._fe, self._data_ref = 0, False, None
+
+    def _last_error(self):
+        return _lib.lib().rxhip_last_error(self._h).decode()
+
+    def _chk(self, st):
+        if st != _lib.OK:
+            raise RxHipError(st, self._last_error())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().rxhip_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    # -- inference --------------------------------------------------------------------------
+    def run(self, iterations=1, free_energy=True):
+        self._chk(_lib.lib().rxhip_run(self._h, int(iterations), int(bool(free_energy))))
+        self._iters, self._fe = int(iterations), bool(free_energy)
+
+    def run_async(self, iterations=1, free_energy=True):
+        self._chk(_lib.lib().rxhip_run_async(self._h, int(iterations), int(bool(free_energy))))
+        self._iters, self._fe = int(iterations), bool(free_energy)
+
+    def sync(self):
+        self._chk(_lib.lib().rxhip_sync(self._h))
+
+    def free_energy(self):
+        out = np.empty(self._iters)
+        self._chk(_lib.lib().rxhip_get_free_energy(self._h, _p(out)))
+        return out
+
+    def free_energy_per_chain(self):
+        out = np.empty(self.n_chains)
+        self._chk(_lib.lib().rxhip_get_free_energy_per_chain(self._h, _p(out)))
+        return out
+
+    def free_energy_device(self):
+        p = ctypes.c_void_p()
+        self._chk(_lib.lib().rxhip_get_free_energy_device(self._h, ctypes.byref(p)))
+        return p.value
+
+    def copy_free_energy_to_device(self, dst_ptr):
+        self._chk(_lib.lib().rxhip_copy_free_energy_to_device(self._h, ctypes.c_void_p(dst_ptr)))
+
+    def allreduce_free_energy(self, comm):
+        """Sum the free energies of the last run over all ranks of the RCCL communicator `comm` (a `Communicator` or a raw
+        ncclComm_t address), in place on the device, on the engine's stream."""
+        self._chk(_lib.lib().rxhip_allreduce_free_energy(self._h, ctypes.c_void_p(int(getattr(comm, "handle", comm) or 0))))
+
+    def counters(self):
+        r, p, m = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(_lib.lib().rxhip_counters(self._h, ctypes.byref(r), ctypes.byref(p), ctypes.byref(m)))
+        return {"rule_calls": r.value, "products": p.value, "marginals": m.value}
+
+    # -- measurement ------------------------------------------------------------------------
+    def set_profiling(self, on=True):
+        self._chk(_lib.lib().rxhip_set_profiling(self._h, int(bool(on))))
+
+    def reset_kernel_times(self):
+        self._chk(_lib.lib().rxhip_reset_kernel_times(self._h))
+
+    def kernel_times(self):
+        ms = (ctypes.c_double * _lib.K_COUNT)()
+        n = (ctypes.c_uint64 * _lib.K_COUNT)()
+        self._chk(_lib.lib().rxhip_get_kernel_times(self._h, ms, n))
+        return {name: {"ms_avg": ms[i], "launches": n[i]} for i, name in enumerate(_lib.KERNEL_NAMES)}
+
+    def stream(self):
+        p = ctypes.c_void_p()
+        self._chk(_lib.lib().rxhip_get_stream(self._h, ctypes.byref(p)))
+        return p.value
+
+
+class _SeriesEngine(_Engine):
+    """The engines whose observations are one series per chain through the common ingest, from the host or from device memory."""
+
+    def set_data(self, y, layout="time_chain"):
+        """y: [T][chain] (layout='time_chain') or [chain][T] ('chain_time'), with a trailing [dy] where observations are vectors; host array."""
+        y = _c(y)
+        self._chk(_lib.lib().rxhip_set_data(self._h, _lib.VAR_Y, _p(y), y.size, _lay(layout)))
+
+    def set_data_device(self, ptr, n, layout="time_chain", keepalive=None):
+        """Observations already in device memory (e.g. a torch tensor's data_ptr())."""
+        self._data_ref = keepalive
+        self._chk(_lib.lib().rxhip_set_data_device(self._h, _lib.VAR_Y, ctypes.c_void_p(ptr), n, _lay(layout)))
+
+
+class _StateEngine(_SeriesEngine):
+    """The families with posteriors of a latent state x[t] in the common arrays (d_mean / d_cov: the rows of the family table with has_x)."""
+
+    def marginals(self, layout="time_chain", want_cov=True):
+        d, T, C = self.d, self.T + getattr(self, "horizon", 0), self.n_chains
+        shp = (T, C) if layout == "time_chain" else (C, T)
+        mean = np.empty(shp + (d,))
+        cov = np.empty(shp + (d, d)) if want_cov else None
+        self._chk(_lib.lib().rxhip_get_marginals(self._h, _lib.VAR_X, _p(mean), _p(cov) if want_cov else None, _lay(layout)))
+        return mean, cov
+
+    def marginals_of_chains(self, chains, want_cov=True):
+        """Posteriors of the selected chains only, chain-major: mean [n][T][d], cov [n][T][d][d] (strided gather on the
+        device + one copy; rxhip_get_marginals_chains)."""
+        ch = np.ascontiguousarray(chains, dtype=np.int64).ravel()
+        T = self.T + getattr(self, "horizon", 0)
+        mean = np.empty((ch.size, T, self.d))
+        cov = np.empty((ch.size, T, self.d, self.d)) if want_cov else None
+        self._chk(_lib.lib().rxhip_get_marginals_chains(self._h, _lib.VAR_X, ch.ctypes.data_as(_lib.c_int64_p), ch.size,
+                                                         _p(mean), _p(cov) if want_cov else None))
+        return mean, cov
+
+
+class LGSSMEngine(_StateEngine):
     """Batch of linear Gaussian state-space factor graphs on one MI355X.
 
     A, B, P, Q, m0, V0 may carry a leading model axis ([n_models, ...]); chain_model maps chains
@@ -71,63 +215,16 @@ class LGSSMEngine:
                 setattr(desc, name, _p(a))
         self._h = ctypes.c_void_p()
         st = self._create(L, desc)
-        if st != _lib.OK:
-            msg = L.rxhip_last_error(self._h).decode() if self._h else (L.rxhip_lowering_error().decode() if st == _lib.ERR_UNSUPPORTED else "") or L.rxhip_status_string(st).decode()
-            if self._h:
-                L.rxhip_destroy(self._h)
-                self._h = None
-            raise RxHipError(st, msg or L.rxhip_status_string(st).decode())
-        self._data_ref = None
-        self._iters = 0
+        # without a handle, an unsupported model was refused by the graph lowering, which reports through its own channel
+        self._created(st, L.rxhip_lowering_error().decode() if st == _lib.ERR_UNSUPPORTED and not self._h else "")
 
     def _create(self, L, desc):
         return L.rxhip_lgssm_create(ctypes.byref(desc), ctypes.byref(self._h))
 
-    # -- plumbing ---------------------------------------------------------------------------
-    def _chk(self, st):
-        if st != _lib.OK:
-            raise RxHipError(st, _lib.lib().rxhip_last_error(self._h).decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.lib().rxhip_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    # -- data -------------------------------------------------------------------------------
-    def set_data(self, y, layout="time_chain"):
-        """y: [T][chain][dy] (layout='time_chain') or [chain][T][dy] ('chain_time'), host array."""
-        y = _c(y)
-        lay = _lib.LAYOUT_TIME_CHAIN if layout == "time_chain" else _lib.LAYOUT_CHAIN_TIME
-        self._chk(_lib.lib().rxhip_set_data(self._h, _lib.VAR_Y, _p(y), y.size, lay))
-
     def set_inputs(self, u, layout="time_chain"):
         """Data inputs u[t] of `A * x[t-1] + B_u * u[t]` (engines built from a graph with such inputs): [T][chain][du] / [chain][T][du]."""
         u = _c(u)
-        lay = _lib.LAYOUT_TIME_CHAIN if layout == "time_chain" else _lib.LAYOUT_CHAIN_TIME
-        self._chk(_lib.lib().rxhip_set_data(self._h, _lib.VAR_U, _p(u), u.size, lay))
-
-    def set_data_device(self, ptr, n, layout="time_chain", keepalive=None):
-        """Observations already in device memory (e.g. a torch tensor's data_ptr())."""
-        lay = _lib.LAYOUT_TIME_CHAIN if layout == "time_chain" else _lib.LAYOUT_CHAIN_TIME
-        self._data_ref = keepalive
-        self._chk(_lib.lib().rxhip_set_data_device(self._h, _lib.VAR_Y, ctypes.c_void_p(ptr), n, lay))
-
-    # -- inference --------------------------------------------------------------------------
-    def run(self, iterations=1, free_energy=True):
-        self._chk(_lib.lib().rxhip_run(self._h, int(iterations), int(bool(free_energy))))
-        self._iters = int(iterations)
+        self._chk(_lib.lib().rxhip_set_data(self._h, _lib.VAR_U, _p(u), u.size, _lay(layout)))
 
     def infer(self, y, iterations=1, free_energy=True, want_cov=True, filtering=False):
         """set_data + run + marginals (+ per-chain free energy) in one round trip (rxhip_lgssm_infer); y: [T][chain][dy].
@@ -141,10 +238,6 @@ class LGSSMEngine:
                                                _p(cov) if want_cov else None, _p(fe) if free_energy else None))
         self._iters = int(iterations)
         return mean, cov, fe
-
-    def run_async(self, iterations=1, free_energy=True):
-        self._chk(_lib.lib().rxhip_run_async(self._h, int(iterations), int(bool(free_energy))))
-        self._iters = int(iterations)
 
     def run_filter(self, free_energy=True):
         """Streaming / filtering run (rxhip_run_filter): afterwards `marginals()` holds q(x_t | y_1..t) and
@@ -180,20 +273,17 @@ class LGSSMEngine:
         shp = (lambda k: (To, C, k)) if layout == "time_chain" else (lambda k: (C, To, k))
         cx = None if state_offset is None else _c(state_offset, shp(self.d))
         cy = None if obs_offset is None else _c(obs_offset, shp(self.dy))
-        lay = _lib.LAYOUT_TIME_CHAIN if layout == "time_chain" else _lib.LAYOUT_CHAIN_TIME
+        lay = _lay(layout)
         self._chk(_lib.lib().rxhip_lgssm_set_chain_offsets(self._h, _p(cx) if cx is not None else None,
                                                            _p(cy) if cy is not None else None, lay))
 
     def filter_reset(self):
         self._chk(_lib.lib().rxhip_filter_reset(self._h))
 
-    def sync(self):
-        self._chk(_lib.lib().rxhip_sync(self._h))
-
     def predictions(self, layout="time_chain", want_cov=True):
         """Messages toward y[1..T+horizon] (`predictvars`): mean [T+H][chain][dy], cov [...][dy][dy] (rxhip_get_predictions)."""
         dy, T, C = self.dy, self.T + getattr(self, "horizon", 0), self.n_chains
-        lay = _lib.LAYOUT_TIME_CHAIN if layout == "time_chain" else _lib.LAYOUT_CHAIN_TIME
+        lay = _lay(layout)
         shp = (T, C) if layout == "time_chain" else (C, T)
         mean = np.empty(shp + (dy,))
         cov = np.empty(shp + (dy, dy)) if want_cov else None
@@ -204,30 +294,10 @@ class LGSSMEngine:
         """Node-local joints q(x[t], A x[t-1]) of the transition nodes (rxhip_get_node_marginals): mean [T-1][chain][2d],
         cov [T-1][chain][2d][2d] in (out, μ) order."""
         d2, T, C = 2 * self.d, self.T - 1, self.n_chains
-        lay = _lib.LAYOUT_TIME_CHAIN if layout == "time_chain" else _lib.LAYOUT_CHAIN_TIME
+        lay = _lay(layout)
         shp = (T, C) if layout == "time_chain" else (C, T)
         mean, cov = np.empty(shp + (d2,)), np.empty(shp + (d2, d2))
         self._chk(_lib.lib().rxhip_get_node_marginals(self._h, _lib.NODE_MVNORMAL_MEAN_COV, _p(mean), _p(cov), lay))
-        return mean, cov
-
-    def marginals(self, layout="time_chain", want_cov=True):
-        d, T, C = self.d, self.T + getattr(self, "horizon", 0), self.n_chains
-        lay = _lib.LAYOUT_TIME_CHAIN if layout == "time_chain" else _lib.LAYOUT_CHAIN_TIME
-        shp = (T, C) if layout == "time_chain" else (C, T)
-        mean = np.empty(shp + (d,))
-        cov = np.empty(shp + (d, d)) if want_cov else None
-        self._chk(_lib.lib().rxhip_get_marginals(self._h, _lib.VAR_X, _p(mean), _p(cov) if want_cov else None, lay))
-        return mean, cov
-
-    def marginals_of_chains(self, chains, want_cov=True):
-        """Posteriors of the selected chains only, chain-major: mean [n][T][d], cov [n][T][d][d] (strided gather on the
-        device + one copy; rxhip_get_marginals_chains)."""
-        ch = np.ascontiguousarray(chains, dtype=np.int64).ravel()
-        T = self.T + getattr(self, "horizon", 0)
-        mean = np.empty((ch.size, T, self.d))
-        cov = np.empty((ch.size, T, self.d, self.d)) if want_cov else None
-        self._chk(_lib.lib().rxhip_get_marginals_chains(self._h, _lib.VAR_X, ch.ctypes.data_as(_lib.c_int64_p), ch.size,
-                                                         _p(mean), _p(cov) if want_cov else None))
         return mean, cov
 
     def marginals_device(self):
@@ -235,47 +305,7 @@ class LGSSMEngine:
         self._chk(_lib.lib().rxhip_get_marginals_device(self._h, _lib.VAR_X, ctypes.byref(m), ctypes.byref(c)))
         return m.value, c.value
 
-    def free_energy(self):
-        out = np.empty(self._iters)
-        self._chk(_lib.lib().rxhip_get_free_energy(self._h, _p(out)))
-        return out
-
-    def free_energy_per_chain(self):
-        out = np.empty(self.n_chains)
-        self._chk(_lib.lib().rxhip_get_free_energy_per_chain(self._h, _p(out)))
-        return out
-
-    def free_energy_device(self):
-        p = ctypes.c_void_p()
-        self._chk(_lib.lib().rxhip_get_free_energy_device(self._h, ctypes.byref(p)))
-        return p.value
-
-    def copy_free_energy_to_device(self, dst_ptr):
-        self._chk(_lib.lib().rxhip_copy_free_energy_to_device(self._h, ctypes.c_void_p(dst_ptr)))
-
-    def allreduce_free_energy(self, comm):
-        """Sum the free energies of the last run over all ranks of the RCCL communicator `comm` (a `Communicator` or a raw
-        ncclComm_t address), in place on the device, on the engine's stream."""
-        self._chk(_lib.lib().rxhip_allreduce_free_energy(self._h, ctypes.c_void_p(int(getattr(comm, "handle", comm) or 0))))
-
-    def counters(self):
-        r, p, m = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-        self._chk(_lib.lib().rxhip_counters(self._h, ctypes.byref(r), ctypes.byref(p), ctypes.byref(m)))
-        return {"rule_calls": r.value, "products": p.value, "marginals": m.value}
-
     # -- measurement ------------------------------------------------------------------------
-    def set_profiling(self, on=True):
-        self._chk(_lib.lib().rxhip_set_profiling(self._h, int(bool(on))))
-
-    def reset_kernel_times(self):
-        self._chk(_lib.lib().rxhip_reset_kernel_times(self._h))
-
-    def kernel_times(self):
-        ms = (ctypes.c_double * _lib.K_COUNT)()
-        n = (ctypes.c_uint64 * _lib.K_COUNT)()
-        self._chk(_lib.lib().rxhip_get_kernel_times(self._h, ms, n))
-        return {name: {"ms_avg": ms[i], "launches": n[i]} for i, name in enumerate(_lib.KERNEL_NAMES)}
-
     def model_tables_ms(self):
         """device time of the once-per-engine kernels (tables that depend on the model only); 0 without such tables"""
         ms = ctypes.c_double()
@@ -315,11 +345,6 @@ class LGSSMEngine:
         self._chk(_lib.lib().rxhip_get_schedule(self._h, ctypes.byref(s), ctypes.byref(l)))
         return {"segments": s.value, "segment_len": l.value}
 
-    def stream(self):
-        p = ctypes.c_void_p()
-        self._chk(_lib.lib().rxhip_get_stream(self._h, ctypes.byref(p)))
-        return p.value
-
 
 class LGSSMNoiseEngine(LGSSMEngine):
     """State-space chains with an UNKNOWN observation-noise precision, `W ~ Wishart(nu0, S0); y[t] ~ MvNormal(μ = B * x[t], Λ = W)` with
@@ -350,7 +375,7 @@ class LGSSMNoiseEngine(LGSSMEngine):
         return nu, V
 
 
-class GMMEngine:
+class GMMEngine(_Engine):
     """Mean-field VMP for the univariate Gaussian mixture on one MI355X (see include/rxhip.h rxhip_gmm_desc).
     K = 1 is the iid Gaussian with unknown mean and precision."""
 
@@ -373,29 +398,7 @@ class GMMEngine:
         desc.device = int(device)
         desc.stream = ctypes.c_void_p(stream) if stream else None
         self._h = ctypes.c_void_p()
-        st = L.rxhip_gmm_create(ctypes.byref(desc), ctypes.byref(self._h))
-        if st != _lib.OK:
-            msg = L.rxhip_last_error(self._h).decode() if self._h else L.rxhip_status_string(st).decode()
-            if self._h:
-                L.rxhip_destroy(self._h)
-                self._h = None
-            raise RxHipError(st, msg or L.rxhip_status_string(st).decode())
-        self._iters = 0
-        self._data_ref = None
-
-    _chk = LGSSMEngine._chk
-    close = LGSSMEngine.close
-    __del__ = LGSSMEngine.__del__
-    __enter__ = LGSSMEngine.__enter__
-    __exit__ = LGSSMEngine.__exit__
-    sync = LGSSMEngine.sync
-    free_energy = LGSSMEngine.free_energy
-    free_energy_device = LGSSMEngine.free_energy_device
-    counters = LGSSMEngine.counters
-    set_profiling = LGSSMEngine.set_profiling
-    reset_kernel_times = LGSSMEngine.reset_kernel_times
-    kernel_times = LGSSMEngine.kernel_times
-    stream = LGSSMEngine.stream
+        self._created(L.rxhip_gmm_create(ctypes.byref(desc), ctypes.byref(self._h)))
 
     def set_data(self, y):
         y = _c(y).ravel()
@@ -404,14 +407,6 @@ class GMMEngine:
     def set_data_device(self, ptr, n, keepalive=None):
         self._data_ref = keepalive
         self._chk(_lib.lib().rxhip_set_data_device(self._h, _lib.VAR_Y, ctypes.c_void_p(ptr), n, _lib.LAYOUT_TIME_CHAIN))
-
-    def run(self, iterations=1, free_energy=True):
-        self._chk(_lib.lib().rxhip_run(self._h, int(iterations), int(bool(free_energy))))
-        self._iters = int(iterations)
-
-    def run_async(self, iterations=1, free_energy=True):
-        self._chk(_lib.lib().rxhip_run_async(self._h, int(iterations), int(bool(free_energy))))
-        self._iters = int(iterations)
 
     # split-phase iteration (several GPUs: all-reduce the statistics between accumulate and update)
     def begin_run(self, iterations):
@@ -442,8 +437,6 @@ class GMMEngine:
     def allreduce_statistics(self, comm):
         """Sum the statistics of this iteration over all ranks of the RCCL communicator (between accumulate and update)."""
         self._chk(_lib.lib().rxhip_gmm_allreduce_statistics(self._h, ctypes.c_void_p(int(getattr(comm, "handle", comm) or 0))))
-
-    allreduce_free_energy = LGSSMEngine.allreduce_free_energy
 
     def update(self, free_energy=True):
         self._chk(_lib.lib().rxhip_gmm_update(self._h, int(bool(free_energy))))
@@ -484,15 +477,7 @@ class MvGMMEngine(GMMEngine):
         desc.device = int(device)
         desc.stream = ctypes.c_void_p(stream) if stream else None
         self._h = ctypes.c_void_p()
-        st = L.rxhip_mvgmm_create(ctypes.byref(desc), ctypes.byref(self._h))
-        if st != _lib.OK:
-            msg = L.rxhip_last_error(self._h).decode() if self._h else L.rxhip_status_string(st).decode()
-            if self._h:
-                L.rxhip_destroy(self._h)
-                self._h = None
-            raise RxHipError(st, msg or L.rxhip_status_string(st).decode())
-        self._iters = 0
-        self._data_ref = None
+        self._created(L.rxhip_mvgmm_create(ctypes.byref(desc), ctypes.byref(self._h)))
 
     def set_data(self, y):
         y = _c(y)
@@ -509,7 +494,7 @@ class MvGMMEngine(GMMEngine):
                     V=h[..., d + dd + 1:d + 2 * dd + 1].reshape(h.shape[:-1] + (d, d)), alpha=h[..., -1], raw=h)
 
 
-class HGFEngine:
+class HGFEngine(_SeriesEngine):
     """Online hierarchical Gaussian filter (GCV node) for n_series independent series (include/rxhip.h rxhip_hgf_desc)."""
 
     def __init__(self, T, n_series, kappa, omega, z_variance, y_variance, z0=(0.0, 5.0), x0=(0.0, 5.0), n_gh=31,
@@ -523,56 +508,18 @@ class HGFEngine:
         desc.stream = ctypes.c_void_p(stream) if stream else None
         self.T, self.n_series, self.n_chains = int(T), int(n_series), int(n_series)
         self._h = ctypes.c_void_p()
-        st = L.rxhip_hgf_create(ctypes.byref(desc), ctypes.byref(self._h))
-        if st != _lib.OK:
-            msg = L.rxhip_last_error(self._h).decode() if self._h else L.rxhip_status_string(st).decode()
-            if self._h:
-                L.rxhip_destroy(self._h)
-                self._h = None
-            raise RxHipError(st, msg or L.rxhip_status_string(st).decode())
-        self._iters = 0
-        self._data_ref = None
-
-    _chk = LGSSMEngine._chk
-    close = LGSSMEngine.close
-    __del__ = LGSSMEngine.__del__
-    __enter__ = LGSSMEngine.__enter__
-    __exit__ = LGSSMEngine.__exit__
-    sync = LGSSMEngine.sync
-    run = LGSSMEngine.run
-    run_async = LGSSMEngine.run_async
-    free_energy = LGSSMEngine.free_energy
-    free_energy_per_chain = LGSSMEngine.free_energy_per_chain
-    free_energy_device = LGSSMEngine.free_energy_device
-    copy_free_energy_to_device = LGSSMEngine.copy_free_energy_to_device
-    allreduce_free_energy = LGSSMEngine.allreduce_free_energy
-    counters = LGSSMEngine.counters
-    set_profiling = LGSSMEngine.set_profiling
-    reset_kernel_times = LGSSMEngine.reset_kernel_times
-    kernel_times = LGSSMEngine.kernel_times
-    stream = LGSSMEngine.stream
-
-    def set_data(self, y, layout="time_chain"):
-        """y: [T][series] ('time_chain') or [series][T] ('chain_time')."""
-        y = _c(y)
-        lay = _lib.LAYOUT_TIME_CHAIN if layout == "time_chain" else _lib.LAYOUT_CHAIN_TIME
-        self._chk(_lib.lib().rxhip_set_data(self._h, _lib.VAR_Y, _p(y), y.size, lay))
-
-    def set_data_device(self, ptr, n, layout="time_chain", keepalive=None):
-        lay = _lib.LAYOUT_TIME_CHAIN if layout == "time_chain" else _lib.LAYOUT_CHAIN_TIME
-        self._data_ref = keepalive
-        self._chk(_lib.lib().rxhip_set_data_device(self._h, _lib.VAR_Y, ctypes.c_void_p(ptr), n, lay))
+        self._created(L.rxhip_hgf_create(ctypes.byref(desc), ctypes.byref(self._h)))
 
     def history(self, layout="time_chain"):
         """(z_mean, z_var, x_mean, x_var), each [T][series] (or [series][T])."""
-        lay = _lib.LAYOUT_TIME_CHAIN if layout == "time_chain" else _lib.LAYOUT_CHAIN_TIME
+        lay = _lay(layout)
         shp = (self.T, self.n_series) if layout == "time_chain" else (self.n_series, self.T)
         outs = [np.empty(shp) for _ in range(4)]
         self._chk(_lib.lib().rxhip_hgf_get_history(self._h, *[_p(o) for o in outs], lay))
         return tuple(outs)
 
 
-class DriftChainEngine:
+class DriftChainEngine(_StateEngine):
     """Noise-free drift chain `x_prior ~ Normal(m0, v0); x[t] ~ x[t-1] + c; y[t] ~ Normal(x[t], obs_var)`
     (test/models/statespace/ulgssm_tests.jl:8-15) for n_chains independent chains (include/rxhip.h rxhip_drift_chain_desc)."""
 
@@ -586,40 +533,11 @@ class DriftChainEngine:
         desc.stream = ctypes.c_void_p(stream) if stream else None
         self.T, self.n_chains, self.d, self.dy, self.n_models = int(T), int(n_chains), 1, 1, 1
         self._h = ctypes.c_void_p()
-        st = L.rxhip_drift_chain_create(ctypes.byref(desc), ctypes.byref(self._h))
-        if st != _lib.OK:
-            msg = L.rxhip_last_error(self._h).decode() if self._h else L.rxhip_status_string(st).decode()
-            if self._h:
-                L.rxhip_destroy(self._h)
-                self._h = None
-            raise RxHipError(st, msg or L.rxhip_status_string(st).decode())
-        self._iters = 0
-        self._data_ref = None
+        self._created(L.rxhip_drift_chain_create(ctypes.byref(desc), ctypes.byref(self._h)))
         self._keep = []
 
-    _chk = LGSSMEngine._chk
-    close = LGSSMEngine.close
-    __del__ = LGSSMEngine.__del__
-    __enter__ = LGSSMEngine.__enter__
-    __exit__ = LGSSMEngine.__exit__
-    sync = LGSSMEngine.sync
-    run = LGSSMEngine.run
-    run_async = LGSSMEngine.run_async
-    set_data = LGSSMEngine.set_data
-    set_data_device = LGSSMEngine.set_data_device
-    marginals = LGSSMEngine.marginals
-    marginals_of_chains = LGSSMEngine.marginals_of_chains
-    free_energy = LGSSMEngine.free_energy
-    free_energy_per_chain = LGSSMEngine.free_energy_per_chain
-    allreduce_free_energy = LGSSMEngine.allreduce_free_energy
-    counters = LGSSMEngine.counters
-    set_profiling = LGSSMEngine.set_profiling
-    reset_kernel_times = LGSSMEngine.reset_kernel_times
-    kernel_times = LGSSMEngine.kernel_times
-    stream = LGSSMEngine.stream
 
-
-class ProbitEngine:
+class ProbitEngine(_StateEngine):
     """Scalar Gaussian chain observed through Probit, `x[1] ~ Normal(m0, v0); x[k] ~ Normal(a x[k-1] + c, q); y[k-1] ~ Probit(x[k])`
     (test/models/statespace/probit_tests.jl:11-18), for n_series independent series: batched parallel EP (include/rxhip.h rxhip_probit_desc).
     `run(iterations)`: that many parallel-EP updates from empty sites; `marginals()`: mean / variance of x[1 … T+1]."""
@@ -633,42 +551,15 @@ class ProbitEngine:
         desc.stream = ctypes.c_void_p(stream) if stream else None
         self.T, self.n_series, self.n_chains, self.d, self.dy, self.horizon = int(T), int(n_series), int(n_series), 1, 1, 1
         self._h = ctypes.c_void_p()
-        st = L.rxhip_probit_create(ctypes.byref(desc), ctypes.byref(self._h))
-        if st != _lib.OK:
-            msg = L.rxhip_last_error(self._h).decode() if self._h else L.rxhip_status_string(st).decode()
-            if self._h:
-                L.rxhip_destroy(self._h)
-                self._h = None
-            raise RxHipError(st, msg or L.rxhip_status_string(st).decode())
-        self._iters = 0
-        self._data_ref = None
-
-    _chk = LGSSMEngine._chk
-    close = LGSSMEngine.close
-    __del__ = LGSSMEngine.__del__
-    __enter__ = LGSSMEngine.__enter__
-    __exit__ = LGSSMEngine.__exit__
-    sync = LGSSMEngine.sync
-    run = LGSSMEngine.run
-    run_async = LGSSMEngine.run_async
-    set_data = HGFEngine.set_data
-    set_data_device = HGFEngine.set_data_device
-    free_energy = LGSSMEngine.free_energy
-    free_energy_per_chain = LGSSMEngine.free_energy_per_chain
-    allreduce_free_energy = LGSSMEngine.allreduce_free_energy
-    counters = LGSSMEngine.counters
-    set_profiling = LGSSMEngine.set_profiling
-    reset_kernel_times = LGSSMEngine.reset_kernel_times
-    kernel_times = LGSSMEngine.kernel_times
-    stream = LGSSMEngine.stream
+        self._created(L.rxhip_probit_create(ctypes.byref(desc), ctypes.byref(self._h)))
 
     def marginals(self, layout="time_chain"):
         """(mean, var) of x[1 … T+1]: [T+1][series] ('time_chain') or [series][T+1] ('chain_time')."""
-        mean, cov = LGSSMEngine.marginals(self, layout)
+        mean, cov = super().marginals(layout)
         return mean[..., 0], cov[..., 0, 0]
 
 
-class HMMEngine:
+class HMMEngine(_SeriesEngine):
     """Hidden Markov model with unknown transition and observation matrices (test/models/statespace/hmm_tests.jl:8-24) for n_series independent
     series: batched forward–backward VMP (include/rxhip.h rxhip_hmm_desc).  prior_A [K][K] and prior_B [M][K] are Dirichlet counts per COLUMN
     (A[i, j] = p(s_t = i | s_{t-1} = j), B[m, i] = p(x_t = m | s_t = i)), prior_s0 [K] probabilities; init_A / init_B the initial q (None: ones).
@@ -696,34 +587,11 @@ class HMMEngine:
         self.T, self.n_series, self.n_chains, self.K, self.M = int(T), int(n_series), int(n_series), desc.K, desc.M
         self.share_parameters = bool(share_parameters)
         self._h = ctypes.c_void_p()
-        st = L.rxhip_hmm_create(ctypes.byref(desc), ctypes.byref(self._h))
-        if st != _lib.OK:
-            msg = L.rxhip_last_error(self._h).decode() if self._h else L.rxhip_status_string(st).decode()
-            if self._h:
-                L.rxhip_destroy(self._h)
-                self._h = None
-            raise RxHipError(st, msg or L.rxhip_status_string(st).decode())
-        self._iters = 0
-        self._data_ref = None
-
-    _chk = LGSSMEngine._chk
-    close = LGSSMEngine.close
-    __del__ = LGSSMEngine.__del__
-    __enter__ = LGSSMEngine.__enter__
-    __exit__ = LGSSMEngine.__exit__
-    sync = LGSSMEngine.sync
-    run = LGSSMEngine.run
-    run_async = LGSSMEngine.run_async
-    set_data = HGFEngine.set_data
-    set_data_device = HGFEngine.set_data_device
-    free_energy = LGSSMEngine.free_energy
-    free_energy_per_chain = LGSSMEngine.free_energy_per_chain
-    counters = LGSSMEngine.counters
-    stream = LGSSMEngine.stream
+        self._created(L.rxhip_hmm_create(ctypes.byref(desc), ctypes.byref(self._h)))
 
     def states(self, layout="time_chain"):
         """q(s_t), t = 0 … T: [T+1][series][K] ('time_chain') or [series][T+1][K] ('chain_time')."""
-        lay = _lib.LAYOUT_TIME_CHAIN if layout == "time_chain" else _lib.LAYOUT_CHAIN_TIME
+        lay = _lay(layout)
         out = np.empty((self.T + 1, self.n_series, self.K) if layout == "time_chain" else (self.n_series, self.T + 1, self.K))
         self._chk(_lib.lib().rxhip_hmm_get_states(self._h, _p(out), lay))
         return out
@@ -736,7 +604,7 @@ class HMMEngine:
         return a, b
 
 
-class LAREngine:
+class LAREngine(_SeriesEngine):
     """Latent autoregressive model of order p = 1 … 8 with unknown coefficients θ and driving-noise precision γ
     (test/models/autoregressive/lar_tests.jl:51-76) for n_series independent series: batched banded structured VMP (include/rxhip.h
     rxhip_lar_desc).  prior_theta / prior_x0: (mean [p], precision [p][p]) or None = zero mean and identity precision; prior_gamma: (shape, rate);
@@ -775,34 +643,11 @@ class LAREngine:
         self.T, self.n_series, self.n_chains, self.order = int(T), int(n_series), int(n_series), p
         self.share_parameters = bool(share_parameters)
         self._h = ctypes.c_void_p()
-        st = L.rxhip_lar_create(ctypes.byref(desc), ctypes.byref(self._h))
-        if st != _lib.OK:
-            msg = L.rxhip_last_error(self._h).decode() if self._h else L.rxhip_status_string(st).decode()
-            if self._h:
-                L.rxhip_destroy(self._h)
-                self._h = None
-            raise RxHipError(st, msg or L.rxhip_status_string(st).decode())
-        self._iters = 0
-        self._data_ref = None
-
-    _chk = LGSSMEngine._chk
-    close = LGSSMEngine.close
-    __del__ = LGSSMEngine.__del__
-    __enter__ = LGSSMEngine.__enter__
-    __exit__ = LGSSMEngine.__exit__
-    sync = LGSSMEngine.sync
-    run = LGSSMEngine.run
-    run_async = LGSSMEngine.run_async
-    set_data = HGFEngine.set_data
-    set_data_device = HGFEngine.set_data_device
-    free_energy = LGSSMEngine.free_energy
-    free_energy_per_chain = LGSSMEngine.free_energy_per_chain
-    counters = LGSSMEngine.counters
-    stream = LGSSMEngine.stream
+        self._created(L.rxhip_lar_create(ctypes.byref(desc), ctypes.byref(self._h)))
 
     def states(self, layout="time_chain"):
         """q(x[t]), t = 1 … T, x[t] = (z_t … z_{t-p+1}): (mean [T][series][p], cov [T][series][p][p]) ('time_chain') or [series][T][…] ('chain_time')."""
-        lay = _lib.LAYOUT_TIME_CHAIN if layout == "time_chain" else _lib.LAYOUT_CHAIN_TIME
+        lay = _lay(layout)
         lead = (self.T, self.n_series) if layout == "time_chain" else (self.n_series, self.T)
         mean, cov = np.empty(lead + (self.order,)), np.empty(lead + (self.order, self.order))
         self._chk(_lib.lib().rxhip_lar_get_states(self._h, _p(mean), _p(cov), lay))
@@ -817,7 +662,7 @@ class LAREngine:
         return tm, tc, ga, gb
 
 
-class BinomialRegressionEngine:
+class BinomialRegressionEngine(_Engine):
     """Bayesian binomial (logistic) regression `β ~ MvNormalWeightedMeanPrecision(ξ0, W0); y[i] ~ BinomialPolya(X[i], n_trials[i], β)`
     (test/models/regression/binomialreg_tests.jl) for n_problems independent regressions of N points and d = 1 … 32 features: batched
     Pólya-Gamma VMP (include/rxhip.h rxhip_binreg_desc).  init: (mean [d], covariance [d][d]) or None = the prior's W0⁻¹ξ0, W0⁻¹.
@@ -841,26 +686,7 @@ class BinomialRegressionEngine:
         desc.stream = ctypes.c_void_p(stream) if stream else None
         self.N, self.d, self.n_problems, self.n_chains = int(N), d, int(n_problems), int(n_problems)
         self._h = ctypes.c_void_p()
-        st = L.rxhip_binreg_create(ctypes.byref(desc), ctypes.byref(self._h))
-        if st != _lib.OK:
-            msg = L.rxhip_last_error(self._h).decode() if self._h else L.rxhip_status_string(st).decode()
-            if self._h:
-                L.rxhip_destroy(self._h)
-                self._h = None
-            raise RxHipError(st, msg or L.rxhip_status_string(st).decode())
-        self._iters = 0
-        self._fe = False
-
-    _chk = LGSSMEngine._chk
-    close = LGSSMEngine.close
-    __del__ = LGSSMEngine.__del__
-    __enter__ = LGSSMEngine.__enter__
-    __exit__ = LGSSMEngine.__exit__
-    sync = LGSSMEngine.sync
-    free_energy = LGSSMEngine.free_energy
-    free_energy_per_chain = LGSSMEngine.free_energy_per_chain
-    counters = LGSSMEngine.counters
-    stream = LGSSMEngine.stream
+        self._created(L.rxhip_binreg_create(ctypes.byref(desc), ctypes.byref(self._h)))
 
     @staticmethod
     def schedule(N, d):
@@ -890,14 +716,6 @@ class BinomialRegressionEngine:
         self.set_trials(n_trials)
         self.set_observations(y)
 
-    def run(self, iterations=1, free_energy=True):
-        self._chk(_lib.lib().rxhip_run(self._h, int(iterations), int(bool(free_energy))))
-        self._iters, self._fe = int(iterations), bool(free_energy)
-
-    def run_async(self, iterations=1, free_energy=True):
-        self._chk(_lib.lib().rxhip_run_async(self._h, int(iterations), int(bool(free_energy))))
-        self._iters, self._fe = int(iterations), bool(free_energy)
-
     def parameters(self):
         """q(β) after every iteration of the last run: (mean [iterations][problems][d], covariance [iterations][problems][d][d], free energy
         [iterations][problems] or None when the run was without it)."""
@@ -908,7 +726,7 @@ class BinomialRegressionEngine:
         return mean, cov, fe
 
 
-class ARRegressionEngine:
+class ARRegressionEngine(_SeriesEngine):
     """Bayesian linear regression with unknown coefficients θ and noise precision γ, `γ ~ Gamma(a0, b0); θ ~ MvNormal(m0, Λ0⁻¹); y[i] ~
     Normal(dot(x[i], θ), γ⁻¹)` with `q(γ, θ) = q(γ)q(θ)` (test/models/autoregressive/ar_tests.jl:17-46) for n_series independent problems or one
     θ, γ for all of them, d = 1 … 32: batched Normal-Gamma VMP from the statistics G, h, s, n (include/rxhip.h rxhip_arreg_desc).
@@ -942,31 +760,7 @@ class ARRegressionEngine:
         self.N, self.T, self.d, self.n_series, self.n_chains = int(N), int(N), d, int(n_series), int(n_series)
         self.lagged, self.share_parameters = bool(lagged), bool(share_parameters)
         self._h = ctypes.c_void_p()
-        st = L.rxhip_arreg_create(ctypes.byref(desc), ctypes.byref(self._h))
-        if st != _lib.OK:
-            msg = L.rxhip_last_error(self._h).decode() if self._h else L.rxhip_status_string(st).decode()
-            if self._h:
-                L.rxhip_destroy(self._h)
-                self._h = None
-            raise RxHipError(st, msg or L.rxhip_status_string(st).decode())
-        self._iters = 0
-        self._fe = False
-        self._data_ref = None
-
-    _chk = LGSSMEngine._chk
-    close = LGSSMEngine.close
-    __del__ = LGSSMEngine.__del__
-    __enter__ = LGSSMEngine.__enter__
-    __exit__ = LGSSMEngine.__exit__
-    sync = LGSSMEngine.sync
-    set_data = HGFEngine.set_data                  # lagged mode: the raw series, [T][series] ('time_chain') or [series][T] ('chain_time')
-    set_data_device = HGFEngine.set_data_device
-    free_energy = LGSSMEngine.free_energy
-    free_energy_per_chain = LGSSMEngine.free_energy_per_chain
-    counters = LGSSMEngine.counters
-    stream = LGSSMEngine.stream
-    run = BinomialRegressionEngine.run
-    run_async = BinomialRegressionEngine.run_async
+        self._created(L.rxhip_arreg_create(ctypes.byref(desc), ctypes.byref(self._h)))
 
     @staticmethod
     def schedule(n_rows, d):
@@ -1006,7 +800,7 @@ class ARRegressionEngine:
         return G, h, s, n
 
 
-class MultinomialRegressionEngine:
+class MultinomialRegressionEngine(_Engine):
     """Bayesian multinomial regression `ψ ~ MvNormalWeightedMeanPrecision(ξ0, W0); y[i] ~ MultinomialPolya(N_i, ψ)`
     (test/models/regression/multinomialreg_tests.jl) for n_problems independent problems of N count vectors with K = 2 … 65 categories, d = K − 1:
     batched stick-breaking Pólya-Gamma VMP from the column sums (include/rxhip.h rxhip_mnreg_desc).  online=True streams the N rows of each
@@ -1038,30 +832,7 @@ class MultinomialRegressionEngine:
         self.N, self.T, self.K, self.d, self.n_problems, self.n_chains = int(N), int(N), K, d, int(n_problems), int(n_problems)
         self.online, self.keep_cov_history = bool(online), bool(keep_cov_history)
         self._h = ctypes.c_void_p()
-        st = L.rxhip_mnreg_create(ctypes.byref(desc), ctypes.byref(self._h))
-        if st != _lib.OK:
-            msg = L.rxhip_last_error(self._h).decode() if self._h else L.rxhip_status_string(st).decode()
-            if self._h:
-                L.rxhip_destroy(self._h)
-                self._h = None
-            raise RxHipError(st, msg or L.rxhip_status_string(st).decode())
-        self._iters = 0
-        self._fe = False
-
-    _chk = LGSSMEngine._chk
-    close = LGSSMEngine.close
-    __del__ = LGSSMEngine.__del__
-    __enter__ = LGSSMEngine.__enter__
-    __exit__ = LGSSMEngine.__exit__
-    sync = LGSSMEngine.sync
-    free_energy = LGSSMEngine.free_energy
-    free_energy_per_chain = LGSSMEngine.free_energy_per_chain
-    counters = LGSSMEngine.counters
-    stream = LGSSMEngine.stream
-    set_profiling = LGSSMEngine.set_profiling
-    kernel_times = LGSSMEngine.kernel_times
-    run = BinomialRegressionEngine.run
-    run_async = BinomialRegressionEngine.run_async
+        self._created(L.rxhip_mnreg_create(ctypes.byref(desc), ctypes.byref(self._h)))
 
     @staticmethod
     def schedule(N, K):
@@ -1106,7 +877,7 @@ class MultinomialRegressionEngine:
         return Y, S, lc, n
 
 
-class GammaMixtureEngine:
+class GammaMixtureEngine(_SeriesEngine):
     """Gamma mixture with a point-mass shape, `s ~ Dirichlet(α⁰); a[k] ~ Gamma(c⁰_k, d⁰_k); b[k] ~ Gamma(e⁰_k, f⁰_k); z[i] ~ Categorical(s); y[i] ~
     GammaMixture(switch = z[i], a = a, b = b)` with `q = q(s) Π q(z_i) Π q(b_k) Π δ(a_k − â_k)` (test/models/mixtures/gamma_mixture_tests.jl:7-40)
     for n_problems independent mixtures of N points and K = 1 … 16 components (include/rxhip.h rxhip_gammamix_desc).  prior_a, prior_b: (shape,
@@ -1150,33 +921,7 @@ class GammaMixtureEngine:
         desc.stream = ctypes.c_void_p(stream) if stream else None
         self.N, self.T, self.K, self.n_problems, self.n_chains, self.materialize = int(N), int(N), K, C, C, bool(materialize)
         self._h = ctypes.c_void_p()
-        st = L.rxhip_gammamix_create(ctypes.byref(desc), ctypes.byref(self._h))
-        if st != _lib.OK:
-            msg = L.rxhip_last_error(self._h).decode() if self._h else L.rxhip_status_string(st).decode()
-            if self._h:
-                L.rxhip_destroy(self._h)
-                self._h = None
-            raise RxHipError(st, msg or L.rxhip_status_string(st).decode())
-        self._iters = 0
-        self._fe = False
-        self._data_ref = None
-
-    _chk = LGSSMEngine._chk
-    close = LGSSMEngine.close
-    __del__ = LGSSMEngine.__del__
-    __enter__ = LGSSMEngine.__enter__
-    __exit__ = LGSSMEngine.__exit__
-    sync = LGSSMEngine.sync
-    set_data = HGFEngine.set_data                  # [N][problems] ('time_chain') or [problems][N] ('chain_time')
-    set_data_device = HGFEngine.set_data_device
-    free_energy = LGSSMEngine.free_energy
-    free_energy_per_chain = LGSSMEngine.free_energy_per_chain
-    counters = LGSSMEngine.counters
-    stream = LGSSMEngine.stream
-    set_profiling = LGSSMEngine.set_profiling
-    kernel_times = LGSSMEngine.kernel_times
-    run = BinomialRegressionEngine.run
-    run_async = BinomialRegressionEngine.run_async
+        self._created(L.rxhip_gammamix_create(ctypes.byref(desc), ctypes.byref(self._h)))
 
     @staticmethod
     def schedule(N, K):

@@ -7,14 +7,16 @@ import numpy as np
 
 from . import _lib
 from ._lib import RxHipError, c_double_p, c_int64_p
+from .engine import _Engine
 
 
 def _c(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
-class TreeEngine:
-    """One compiled graph × n_replicas independent copies (different data, same constants)."""
+class TreeEngine(_Engine):
+    """One compiled graph × n_replicas independent copies (different data, same constants).  `stream` here is the streamed run of the
+    executor (rxhip_tree_stream), not the base class's HIP-stream getter."""
 
     def __init__(self, gb, n_replicas=1, device=-1, stream=None, force_executor=True, allow_missing=False):
         """gb: GraphBuilder.  force_executor=False goes through rxhip_create (pattern matcher first; raises if a specialised engine took the graph).
@@ -27,25 +29,12 @@ class TreeEngine:
             st = L.rxhip_tree_create(ctypes.byref(g), int(device), ctypes.c_void_p(stream) if stream else None, ctypes.byref(self._h))
         else:
             st = L.rxhip_create(ctypes.byref(g), 0, int(device), ctypes.c_void_p(stream) if stream else None, ctypes.byref(self._h))
-        if st != _lib.OK:
-            msg = L.rxhip_lowering_error().decode()
-            if self._h:
-                L.rxhip_destroy(self._h)
-            self._h = None
-            raise RxHipError(st, msg or L.rxhip_status_string(st).decode())
-        self.gb, self.n_replicas = gb, int(n_replicas)
+        self._created(st, L.rxhip_lowering_error().decode())   # the graph entry points report through the lowering's channel
+        self.gb, self.n_replicas, self.n_chains = gb, int(n_replicas), int(n_replicas)
         info = _lib.TreeInfo()
         if L.rxhip_tree_get_info(self._h, ctypes.byref(info)) != _lib.OK:
-            L.rxhip_destroy(self._h)
-            self._h = None
-            raise RxHipError(_lib.ERR_BADARG, "the pattern matcher took this graph: not an engine of the node-array executor")
+            self._created(_lib.ERR_BADARG, "the pattern matcher took this graph: not an engine of the node-array executor")
         self.info = {k: int(getattr(info, k)) for k, _ in _lib.TreeInfo._fields_ if k != "last_iteration_ms"}
-        self._iters = 0
-
-    def allreduce_free_energy(self, comm):
-        """Sum the last run's per-iteration free energies over the ranks of `comm` (rxhip.Communicator), in rank order, in place on the device —
-        replicas shard over GPUs with no other exchange (include/rxhip.h rxhip_allreduce_free_energy)."""
-        self._chk(_lib.lib().rxhip_allreduce_free_energy(self._h, ctypes.c_void_p(int(getattr(comm, "handle", comm) or 0))))
 
     def last_iteration_ms(self):
         """device time of the last run ÷ its iterations"""
@@ -58,27 +47,6 @@ class TreeEngine:
         run(1) then equal one run(k) — how a driver that takes one VMP iteration per call (batch.jl:391-430) uses the engine"""
         self._chk(_lib.lib().rxhip_tree_continue(self._h, int(bool(on))))
 
-    def _chk(self, st):
-        if st != _lib.OK:
-            raise RxHipError(st, _lib.lib().rxhip_last_error(self._h).decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.lib().rxhip_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
     def set_data(self, variables, values):
         """variables: data variable ids; values: [replica][Σ rows] (the rows of the variables side by side, in list order; a data matrix — the `A` of a `*`
         node, GraphBuilder.datavar(rows, cols=…) — takes rows·cols values, row-major)"""
@@ -88,10 +56,6 @@ class TreeEngine:
         if x.shape[1] != rows:
             raise ValueError(f"values must be [replicas][{rows}]")
         self._chk(_lib.lib().rxhip_tree_set_data(self._h, v.ctypes.data_as(c_int64_p), len(v), x.ctypes.data_as(c_double_p)))
-
-    def run(self, iterations=1, free_energy=True):
-        self._chk(_lib.lib().rxhip_run(self._h, int(iterations), int(bool(free_energy))))
-        self._iters = int(iterations)
 
     def set_autoupdates(self, table):
         """The `@autoupdates` of a streamed model (rxhip_tree_set_autoupdates): [(target, source, "mean" | "var" | "precision"), …] — before every observation of
@@ -173,14 +137,7 @@ class TreeEngine:
         return fe
 
     def free_energy_per_replica(self):
-        fe = np.empty(self.n_replicas)
-        self._chk(_lib.lib().rxhip_get_free_energy_per_chain(self._h, fe.ctypes.data_as(c_double_p)))
-        return fe
-
-    def counters(self):
-        r, p, m = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-        self._chk(_lib.lib().rxhip_counters(self._h, ctypes.byref(r), ctypes.byref(p), ctypes.byref(m)))
-        return dict(rule_calls=r.value, products=p.value, marginals=m.value)
+        return self.free_energy_per_chain()
 
 
 _AU_KINDS = {"mean": _lib.AU_MEAN, "var": _lib.AU_VAR, "precision": _lib.AU_PRECISION}

@@ -43,6 +43,11 @@ def _feed_binreg(eng, y):
     eng.set_data(np.linspace(-1.0, 1.0, 8).reshape(1, 8, 1), y.reshape(1, 8), np.full((1, 8), 3.0))
 
 
+def _feed_arreg(eng, y):
+    eng.set_regressors(np.linspace(-1.0, 1.0, 8).reshape(1, 8, 1))
+    eng.set_observations(y.reshape(1, 8))
+
+
 # name -> (factory, n_chains, good observations, has RXHIP_VAR_X marginals, a value the family's check of device data refuses (or None))
 _rng = np.random.default_rng(7)
 FAMILIES = {
@@ -57,8 +62,21 @@ FAMILIES = {
             np.array([[0.0], [1.0], [1.0], [0.0]]), False, 2.0),
     "lar": (lambda rx: rx.LAREngine(4, 1, 1.0), 1, _rng.standard_normal((4, 1)), False, np.inf),
     "binreg": (_binreg, 1, np.array([0.0, 1.0, 0.0, 2.0, 1.0, 3.0, 2.0, 3.0]), False, None),
+    # one problem / series each at the smallest shapes: regression on regressors (N = 8, d = 1) and on the series' own lag (T = 8, order 1),
+    # multinomial regression offline (N = 8, K = 3) and streamed (N = 4, K = 3), Gamma mixture (N = 8, K = 2)
+    "arreg": (lambda rx: rx.ARRegressionEngine(8, 1), 1, _rng.standard_normal(8), False, None),
+    "arreg_lagged": (lambda rx: rx.ARRegressionEngine(8, 1, lagged=True), 1, _rng.standard_normal((8, 1)), False, np.inf),
+    "mnreg": (lambda rx: rx.MultinomialRegressionEngine(8, 3, np.zeros(2), np.eye(2)), 1, _rng.integers(0, 5, (1, 8, 3)).astype(np.float64), False, None),
+    "mnreg_online": (lambda rx: rx.MultinomialRegressionEngine(4, 3, np.zeros(2), np.eye(2), online=True), 1,
+                     _rng.integers(0, 5, (1, 4, 3)).astype(np.float64), False, None),
+    "gammamix": (lambda rx: rx.GammaMixtureEngine(8, 2, (np.ones(2), np.ones(2)), (np.ones(2), np.ones(2)), np.ones(2), init_a=np.array([1.0, 3.0])), 1,
+                 _rng.gamma(2.0, 1.0, (8, 1)), False, -1.0),
 }
 MIXTURES = ("gmm", "mvgmm2", "mvgmm5")
+HOST_CHECKED = ("binreg", "arreg", "mnreg", "mnreg_online")   # families whose own set_data checks the arrays on the host: no device data
+NO_DATA_MNREG = "run: no observations (the multinomial regression engine, mnreg, takes its counts through rxhip_set_data with RXHIP_VAR_Y)"
+NO_DATA_OF = {"binreg": NO_DATA_BINREG, "arreg": "run: the regression engine needs RXHIP_VAR_REGRESSORS and RXHIP_VAR_Y (missing: regressors y)",
+              "mnreg": NO_DATA_MNREG, "mnreg_online": NO_DATA_MNREG}
 NAMES = list(FAMILIES)
 
 
@@ -71,6 +89,8 @@ def _feed(name, eng, y=None):
     y = FAMILIES[name][2] if y is None else y
     if name == "binreg":
         _feed_binreg(eng, y)
+    elif name == "arreg":
+        _feed_arreg(eng, y)
     else:
         eng.set_data(y)
 
@@ -118,7 +138,7 @@ def test_run_refusals(name):
         assert L.rxhip_run(eng._h, 0, 1) == _lib.ERR_BADARG
         assert _err(eng) == "run: iterations must be positive"
         assert L.rxhip_run(eng._h, 2, 1) == _lib.ERR_STATE
-        assert _err(eng) == (NO_DATA_BINREG if name == "binreg" else NO_DATA)
+        assert _err(eng) == NO_DATA_OF.get(name, NO_DATA)
         _feed(name, eng)
         if name == "lgssm":   # the one family with a streaming twin: a filtering run
             assert L.rxhip_run_filter(eng._h, 1) == _lib.OK, _err(eng)
@@ -163,10 +183,11 @@ def test_free_energy_entry_points_and_capacity_growth(name, hip):
         # The first two entries repeat the short run bit for bit, with two exceptions that are properties of the kernels, not of the buffers.  HGF: the
         # filter carries the belief after ALL iterations of a step into the next one, so every entry depends on the run's length.  HMM: the LAST sweep
         # of a run is another instance of the kernel (it also stores the posteriors), whose statistics differ in rounding: entry 1 was computed by
-        # that instance in the short run only (8 log terms of size ≈ 1: a few ulp each, far inside 1e-13 of the sum).
+        # that instance in the short run only (8 log terms of size ≈ 1: a few ulp each, far inside 1e-13 of the sum).  The streamed multinomial
+        # regression is the HGF's case: a row's prior is the posterior after ALL iterations of the row before, and entry i sums the rows' F after i + 1.
         if name == "hmm":
             assert long[0] == short[0] and long[1] == pytest.approx(short[1], rel=1e-13, abs=0)
-        elif name != "hgf":
+        elif name not in ("hgf", "mnreg_online"):
             assert np.array_equal(long[:2], short)
         assert L.rxhip_run(eng._h, 2, 1) == _lib.OK, _err(eng)
         assert np.array_equal(_free_energy(eng, 2), short)   # … and the grown buffers serve a short run as the first ones did
@@ -202,7 +223,7 @@ def test_state_marginals_exist_or_are_refused(name):
         assert np.all(np.isfinite(mean)) and np.array_equal(one, mean.reshape(rows, n_chains)[:, 0])
 
 
-@pytest.mark.parametrize("name", [n for n in NAMES if n != "binreg"])
+@pytest.mark.parametrize("name", [n for n in NAMES if n not in HOST_CHECKED])
 def test_device_data_is_checked_and_runs_like_host_data(name, hip):
     import rxhip
     from rxhip import _lib
@@ -220,7 +241,10 @@ def test_device_data_is_checked_and_runs_like_host_data(name, hip):
             assert L.rxhip_set_data_device(eng._h, _lib.VAR_Y, pb, yb.size, _lib.LAYOUT_TIME_CHAIN) == _lib.ERR_BADARG
             assert _err(eng) == {"probit": "set_data: a Probit observation is neither 0, 1 nor NaN (missing)",
                                  "hmm": "set_data: an observation is neither an integer symbol code 0 … 1 nor NaN (missing)",
-                                 "lar": "set_data: an observation is infinite (finite values and NaN = missing are accepted)"}[name]
+                                 "lar": "set_data: an observation is infinite (finite values and NaN = missing are accepted)",
+                                 "arreg_lagged": "set_data: an observation is infinite (finite values and NaN = missing are accepted)",
+                                 "gammamix": "set_data: gammamix: an observation is zero, negative or infinite (positive finite values and NaN = missing "
+                                             "are accepted)"}[name]
             assert L.rxhip_run(eng._h, 2, 1) == _lib.ERR_STATE and _err(eng) == NO_DATA   # a refused array counts as not set
             assert hip.hipFree(pb) == 0
         pg = _to_device(hip, y)
@@ -240,6 +264,43 @@ def test_binreg_refuses_device_data(hip):
         assert hip.hipFree(p) == 0
 
 
+@pytest.mark.parametrize("name, text", [
+    ("arreg", "set_data_device: the regression engine checks X and y on the host (rxhip_set_data); the lagged mode takes device data"),
+    ("mnreg", "set_data_device: the multinomial regression engine (mnreg) checks its counts on the host (rxhip_set_data)"),
+    ("mnreg_online", "set_data_device: the multinomial regression engine (mnreg) checks its counts on the host (rxhip_set_data)")])
+def test_host_checked_families_refuse_device_data(name, text, hip):
+    import rxhip
+    from rxhip import _lib
+    factory, _, y, _, _ = FAMILIES[name]
+    with factory(rxhip) as eng:
+        p = _to_device(hip, y)
+        assert _L().rxhip_set_data_device(eng._h, _lib.VAR_Y, p, y.size, _lib.LAYOUT_TIME_CHAIN) == _lib.ERR_BADARG
+        assert _err(eng) == text
+        assert hip.hipFree(p) == 0
+
+
+@pytest.mark.parametrize("name", ["arreg", "arreg_lagged", "mnreg", "mnreg_online", "gammamix"])
+def test_result_getters_refuse_before_a_run_and_without_free_energy(name):
+    """the getters' shared preamble: "<entry point>: no run yet", then "<entry point>: free energy was not requested in the last run" """
+    import rxhip
+    from rxhip import RxHipError, _lib
+    getter = {"arreg": "arreg_get_parameters", "arreg_lagged": "arreg_get_parameters", "mnreg": "mnreg_get_parameters", "mnreg_online": "mnreg_get_parameters",
+              "gammamix": "gammamix_get_history"}[name]
+    with FAMILIES[name][0](rxhip) as eng:
+        _feed(name, eng)
+        results = eng.history if name == "gammamix" else eng.parameters
+        with pytest.raises(RxHipError) as exc:
+            results()
+        assert exc.value.status == _lib.ERR_STATE and str(exc.value).endswith(f"{getter}: no run yet")
+        eng.run(2, free_energy=False)
+        eng._fe = True   # ask for the free energies the run did not compute
+        with pytest.raises(RxHipError) as exc:
+            results()
+        assert exc.value.status == _lib.ERR_STATE and str(exc.value).endswith(f"{getter}: free energy was not requested in the last run")
+        eng._fe = False
+        assert results() is not None   # … and both refusals leave the engine usable
+
+
 def test_refused_creates_leave_a_handle_that_destroys_cleanly():
     from rxhip import _lib
     L = _L()
@@ -249,7 +310,13 @@ def test_refused_creates_leave_a_handle_that_destroys_cleanly():
     hmm = _lib.HmmDesc(T=4, n_series=1, K=1, M=2, device=-1)
     lar = _lib.LarDesc(T=4, n_series=1, order=0, tau=1.0, prior_gamma_shape=1.0, prior_gamma_rate=1.0, device=-1)
     binreg = _lib.BinregDesc(N=8, n_problems=1, d=0, device=-1)
-    for create, desc, text in ((L.rxhip_hgf_create, hgf, "hgf: kappa must be finite"),
+    arreg = _lib.ArregDesc(N=8, n_series=1, d=0, prior_gamma_shape=1.0, prior_gamma_rate=1.0, device=-1)
+    mnreg = _lib.MnregDesc(N=8, n_problems=1, K=1, mode=_lib.MNREG_BATCH, device=-1)
+    gammamix = _lib.GammaMixDesc(N=8, n_problems=1, K=0, device=-1)
+    for create, desc, text in ((L.rxhip_arreg_create, arreg, "arreg: d must be 1 … 32 (got 0)"),
+                               (L.rxhip_mnreg_create, mnreg, "mnreg: K must be 2 … 65 (got 1)"),
+                               (L.rxhip_gammamix_create, gammamix, "gammamix: K must be 1 … 16 (got 0)"),
+                               (L.rxhip_hgf_create, hgf, "hgf: kappa must be finite"),
                                (L.rxhip_probit_create, probit, "probit: the transition variance q must be positive and finite (got -1)"),
                                (L.rxhip_hmm_create, hmm, "hmm: K must be 2 … 16 states (got 1)"),
                                (L.rxhip_lar_create, lar, "lar: order must be 1 … 8 (got 0)"),
