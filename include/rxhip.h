@@ -953,6 +953,12 @@ rxhip_status rxhip_hmm_get_parameters(rxhip_engine* e, double* A_counts, double*
  * 514.653888437 (p = 5; 514.66086 ± 0.01, lar_tests.jl:202).
  * share_parameters = 1: one q(θ) and one q(γ) for all series: S is summed over the series in ascending order before steps 2 and 3,
  * a = a0 + n_series·T/2, F = Σ_series(the first four terms) + the two KL terms once.
+ * Numerical envelope, in three gauges (measured against 50 digits: tests/lar_mp.py ENVELOPE): m_i is representable to ε|m_i|, so
+ * in posterior standard deviations the error of a state mean is about ε·|m_i|/sd_i; R is formed from S and θ, so the relative error of b and
+ * the error of F are about ε·Szz/R.  The contract holds while max_i |m_i|/sd_i ≤ 1e8, R/Szz ≥ 1e-6 and cond Λ ≤ 1e8 at every iteration.  Data on a
+ * common offset that is large against the posterior width (offset·√τ above 1e8), or whose AR residual is below 1e-6 of their energy (an offset
+ * that θ can absorb, with tiny noise), are outside the contract: Λ stays SPD, so the engine still answers, with every output finite — take the
+ * offset off y first.  cond Λ alone does not secure the contract.
  * Handle protocol: rxhip_set_data(RXHIP_VAR_Y, y, T*n_series, layout) (NaN = missing; ±Inf: RXHIP_ERR_BADARG, and the engine does not run on it:
  * RXHIP_ERR_STATE), rxhip_run(e, iterations, want_free_energy), rxhip_lar_get_states, rxhip_lar_get_parameters, rxhip_get_free_energy (per
  * iteration, summed over series), rxhip_get_free_energy_per_chain (last iteration; with shared parameters the per-series parts, whose sum lacks

@@ -2,18 +2,22 @@
 through the stand-in <hip/hip_runtime.h> of tests/host_emul/ and drives the band entry, the LDLᵀ row step, the back-substitution and
 selected-inverse step, the statistics and the θ/γ update serially in the order of the device's run.  Held to the dense restatement of
 tests/lar_ref.py at the project's contract (lar_ref.hold: means 1e-6 standard deviations, parameters and (co)variances 1e-6 relative, free energy
-1e-8 relative per iteration): the check of this arithmetic that needs no GPU."""
+1e-8 relative per iteration): the check of this arithmetic that needs no GPU.  And held, at the same contract, to the 50-digit fixture
+tests/golden/lar_long.npz on every case of lar_mp.GRID with (T + p)·series ≤ 3000 and every lar_mp.SCAN case inside the envelope: every order over
+257 steps and 15 iterations, the boundary shapes at p = 5 and 8, τ and γ over twelve and nine decades, unit roots, extreme priors, offsets."""
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import lar_mp as MP
 import lar_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "rxinfer.jl_amd", "csrc")
 EMUL = os.path.join(ROOT, "tests", "host_emul")
+FIXTURE = os.path.join(ROOT, "tests", "golden", "lar_long.npz")
 
 
 @pytest.fixture(scope="module")
@@ -40,9 +44,15 @@ def parse(lines, T, C, p, iters, shared):
                 gamma_shape=gam[..., 0], gamma_rate=gam[..., 1], fe=v[5])
 
 
+def contract_specs():
+    """the cases of lar_mp that are held to the fixture here"""
+    golden = MP.load(FIXTURE)
+    return [s for s in MP.GRID if (s.T + s.p) * s.C <= 3000] + [s for s in MP.SCAN if MP.in_envelope(golden[s.name][2])], golden
+
+
 def all_cases():
     y, _ = R.reference_data()
-    return [(y[:, None], R.model(p, 5.0), 15, False) for p in (1, 5)] + [R.case(spec) for spec in R.CASES["host"]]
+    return [(y[:, None], R.model(p, 5.0), 15, False) for p in (1, 5)] + [R.case(spec) for spec in R.CASES["host"]] + [MP.case(s) for s in contract_specs()[0]]
 
 
 def test_host_build_of_the_helpers_equals_the_restatement(exe):
@@ -51,7 +61,21 @@ def test_host_build_of_the_helpers_equals_the_restatement(exe):
     lines = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.splitlines()
     assert len(lines) == 6 * len(cases)
     worst = {}
-    for n, (y, m, iters, shared) in enumerate(cases):
+    specs, golden = contract_specs()
+    assert len(specs) >= 47 + 27 and sum(s.share for s in specs) == 2 and {s.p for s in specs if s.T == 257} == set(range(1, 9))
+    first = len(cases) - len(specs)
+    fixture_worst = {}
+    for spec, (y, m, iters, shared), n in zip(specs, cases[first:], range(first, len(cases))):       # the 50-digit fixture, at the contract
+        got = parse(lines[6 * n:6 * n + 6], *y.shape, m["order"], iters, shared)
+        assert MP.checksum(y, m) == golden[spec.name][1], spec.name
+        errs = MP.errors(spec, MP.pick(spec, got), golden[spec.name][0])
+        for k, v in errs.items():
+            if v >= fixture_worst.get(k, (-1.0, None))[0]:
+                fixture_worst[k] = (v, spec.name)
+        assert all(v <= MP.CONTRACT[k] for k, v in errs.items()), (spec.name, errs)
+        assert np.all(np.diff(got["fe"]) <= 1e-9 * np.abs(got["fe"][1:])), (spec.name, got["fe"])
+    print("worst against the 50-digit fixture:", fixture_worst)
+    for n, (y, m, iters, shared) in enumerate(cases[:first]):
         ref = R.run_batch(y, **m, iterations=iters, share_parameters=shared)
         got = parse(lines[6 * n:6 * n + 6], *y.shape, m["order"], iters, shared)
         for k, v in R.hold(got, ref).items():
