@@ -71,6 +71,9 @@ extern "C" {
  *     RXHIP_Y_RING=1            reverse-filter schedule: the backward sweep (k_backward_sh_rev) with its observations one step ahead of their use instead of
  *                               the shipped ring (four steps, Y_RING_SHIPPED in csrc/lgssm_kernels.hpp); the same loop and arithmetic, the comparison arm.  Any other value is refused by
  *                               rxhip_lgssm_create (RXHIP_ERR_BADARG with a message): the depths are compiled instances, not a parameter
+ *     RXHIP_SWEEP_WAVES=1|2|4   reverse-filter schedule: wavefronts per workgroup of both sweep kernels (k_forward0_ck, k_backward_sh_rev), which share one table
+ *                               stream per workgroup; the same arithmetic per lane in every arm.  Unset: the largest shipped width whose 64·W chains divide the batch
+ *                               (rxhip_get_sweep_waves).  Any other value, and a width above 1 that does not divide the batch, is refused by rxhip_lgssm_create
  *     RXHIP_TREE_MODE=0|1|2     node-array executor: a launch per level / workgroup-resident levels / a lane (a wavefront above d = 8) per replica walks the
  *                               schedule, for both phases (default: by batch and graph shape, per phase)
  *     RXHIP_TREE_RB=n, RXHIP_TREE_WG=256|512
@@ -1277,6 +1280,9 @@ rxhip_status rxhip_get_model_tables_ms(rxhip_engine* e, double* ms);
  * computed from the model's tables; 0 when none does, when dy > d, A is singular or the schedule has no table-driven sweep.
  * RXHIP_MEAN_RECORDS / RXHIP_MEAN_CHECKPOINT (test hooks, "Environment") override the choice. */
 rxhip_status rxhip_get_mean_checkpoint_stride(rxhip_engine* e, int32_t* K);
+/* Wavefronts per workgroup of the two sweep kernels of the reverse-filter schedule: *forward for k_forward0_ck, *backward for
+ * k_backward_sh_rev — 1, 2 or 4; both 0 for an engine that does not take that schedule (rxhip_get_mean_checkpoint_stride reports 0). */
+rxhip_status rxhip_get_sweep_waves(rxhip_engine* e, int32_t* forward, int32_t* backward);
 /* Where the host time of the engine's creation went, in milliseconds: ms4[0] host arithmetic on model tables (models of state
  * dimension < 32; 0 for tables that came from the cache), ms4[1] device kernels that build tables (enqueue — or completion where
  * their status is needed before the engine exists), ms4[2] uploads (tables, constants; host → device copies + their sync),

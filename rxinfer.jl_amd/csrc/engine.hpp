@@ -206,6 +206,7 @@ struct rxhip_engine : rxhip_engine_life {
     double *d_gtab = nullptr, *d_segend = nullptr, *d_sblk = nullptr;
     // reverse-filter schedule (k_backward_sh_rev): checkpoint stride 2^ck_log2 of the z records, 0: a record per time index
     int ck_log2 = 0;
+    int sweep_waves_fwd = 1, sweep_waves_bwd = 1;   // wavefronts per workgroup of k_forward0_ck / k_backward_sh_rev (plan::sweep_waves)
     long long nck = 0;
     double *d_amp = nullptr, *d_ainv = nullptr;
     int* d_ckfail = nullptr;

@@ -45,12 +45,12 @@ struct LgssmVtbl {
     int aPI, aC, aJ, aCI, aX, aJJ;
     int scan_size, sM1, sM2, sVB, sN1, sN2, sLB;
     int f0_size, fK, fU, fSI, pos_size, pPI, pJ, pC, fs_size, fsA1, fsA2, fsW, mt_row;  // one-pass schedule (k_forward0)
-    void (*forward0)(const Params&, const double*, bool, bool, hipStream_t);
+    void (*forward0)(const Params&, const double*, bool, bool, int, hipStream_t);
     void (*time_tables)(const TimeTabParams&, hipStream_t);
     void (*fe_seg)(const Params&, hipStream_t);
     int gt_row, se_size;  // SmoothTab / SegEndTab
     void (*smooth_tables)(const SmoothTabParams&, const double*, hipStream_t);
-    void (*backward_sh)(const Params&, const double*, const double*, const double*, bool, int, bool, int, hipStream_t);
+    void (*backward_sh)(const Params&, const double*, const double*, const double*, bool, int, bool, int, int, hipStream_t);
     void (*boundary_scan_tab)(const Params&, const double*, bool, hipStream_t);
     void (*seg_aggregate)(const Params&, const double*, bool, hipStream_t);
     int ex_size;  // ElemX

@@ -212,7 +212,7 @@ struct Params {
                             // not the 160 B/U of posteriors that the next iteration overwrites unread (rxhip_get_marginals returns the LAST iteration's)
     int tinv_records;       // per-chain, time-invariant models on long segments: k_forward_tinv / k_backward_tinv (mean-only records behind the fixed point)
     int elem_full;          // test hook: k_seg_elements runs the full recursion to the end of every segment (no frozen tail)
-    // one-pass runs whose backward sweep rebuilds the filtered means by the reverse filter (k_backward_sh_rev): k_forward0<…, true>
+    // one-pass runs whose backward sweep rebuilds the filtered means by the reverse filter (k_backward_sh_rev): k_forward0_ck
     // stores z only at CHECKPOINTS — every K = 2^ck_log2 steps of a segment and at its end — in slot 1 + s·nck + j of `filt`
     // (slot 0 is the t = 0 record of the boundary scan)
     int ck_log2;
@@ -1201,9 +1201,9 @@ __device__ __forceinline__ bool load_elemx(const Params& p, long long s, long lo
 //     −2 log p(y_seg | y_before) = const_s + q0 + [m_s'A1 m_s − 2 η'A2 m_s − η'W η],   q0 = Σ_i e_i'(S⁰_i)⁻¹e_i
 // with e_i the known-start innovations (k_fe_seg evaluates the bracket, const_s is summed on the host).
 //
-// CK: the backward sweep rebuilds the filtered means by the reverse filter (k_backward_sh_rev), so z is stored only at the
-// checkpoints (Params::ck_log2); the m / η / q0 arithmetic is the same instruction sequence either way.
-template <int D, int DY, bool FE, bool CK = false>
+// This kernel stores z at every time index (the records schedule and the fallback); k_forward0_ck below is the instance of the reverse-filter
+// schedule, which stores it at the checkpoints only.  The m / η / q0 arithmetic is the same instruction sequence in both.
+template <int D, int DY, bool FE>
 __global__ void __launch_bounds__(64) k_forward0(Params p, const CstArg<CstLayout<D, DY>::SIZE> cb) {
     using CL = CstLayout<D, DY>;
     using FL = F0Layout<D, DY>;
@@ -1317,7 +1317,6 @@ __global__ void __launch_bounds__(64) k_forward0(Params p, const CstArg<CstLayou
                 }
 #pragma unroll
                 for (int a = 0; a < D; ++a) m[a] = mn[a];
-                if (CK && ((i + 1) & ((1LL << p.ck_log2) - 1)) != 0 && i + 1 != len) continue;   // not a checkpoint
                 // z_t = b_i + M_t η_i  (values, not pointers, select between LDS and memory: a pointer that may be either
                 // becomes a generic pointer, which this compiler cannot lower here)
                 double z[2 * MP2], mrow[D * D];
@@ -1337,7 +1336,7 @@ __global__ void __launch_bounds__(64) k_forward0(Params p, const CstArg<CstLayou
                     z[a] = s;
                 }
                 if (D < 2 * MP2) z[2 * MP2 - 1] = 0.0;
-                const long long slot = CK ? 1 + seg * p.nck + (i >> p.ck_log2) : t0 + i;
+                const long long slot = t0 + i;
                 double2* base = reinterpret_cast<double2*>(p.filt) + ((slot * p.nb64 + (chain >> 6)) * MP2) * 64 + (chain & 63);
 #pragma unroll
                 for (int k = 0; k < MP2; ++k) base[k * 64] = make_double2(z[2 * k], z[2 * k + 1]);
@@ -1358,6 +1357,196 @@ __global__ void __launch_bounds__(64) k_forward0(Params p, const CstArg<CstLayou
         }
         if (FE) p.fe_part[(seg + 1) * p.n_chains + chain] = -0.5 * q0;
     }
+}
+
+// What follows a stash into the table buffer the waves of a workgroup share (k_forward0_ck, k_backward_sh_rev).  W = 1: the buffer is the
+// wave's own, a wavefront fence orders the writes.  W > 1: ONE s_barrier, and the fences around it name the LDS only, so the wait in front of
+// the barrier is lgkmcnt(0) — a __syncthreads() or a fence over all address spaces would wait vmcnt(0) as well and drain the y loads and the
+// stores the wave keeps in flight across the chunk.  One barrier per chunk is enough for the double buffer: buffer b is rewritten at the end of
+// the NEXT chunk, and a wave gets there only through the barrier that every wave reached after its last read of b.
+template <int W>
+__device__ __forceinline__ void lds_publish() {
+    if constexpr (W == 1) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    } else {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+    }
+}
+
+// k_forward0 on the reverse-filter schedule: the backward sweep rebuilds the filtered means by the reverse filter (k_backward_sh_rev), so z is
+// stored only at the checkpoints (Params::ck_log2: every K steps of a segment and at its end).  That schedule needs n_chains % 64 == 0, so a wave
+// sits in ONE segment, every lane is live and the segment length is wave-uniform: the cases k_forward0 guards per lane do not exist here.  Whole
+// chunks run in a loop without per-step guards and the last len mod U steps behind it (as in k_backward_sh_rev); y and the table pieces past the
+// segment's end are loaded with the index clamped (value unused).  The M_t row is used at a checkpoint step only, so its part of the chunk is
+// fetched only for chunks that hold one.  A workgroup is W waves on W adjacent 64-chain groups of one segment (n_chains % (64·W) == 0) that
+// share ONE table stream: each 16-byte piece of a chunk is loaded by one of the 64·W lanes (lds_publish).  The step's arithmetic is k_forward0's.
+#ifndef RXHIP_F0_Y_RING
+#define RXHIP_F0_Y_RING 0   // 1: y in a per-step register ring of U slots (variant builds, as RXHIP_Y_RING_DEPTH below; measured slower, profiles/r14); 0: a whole chunk ahead, as in k_forward0
+#endif
+template <int D, int DY, bool FE, int W>
+__global__ void __launch_bounds__(64 * W) k_forward0_ck(Params p, const CstArg<CstLayout<D, DY>::SIZE> cb) {
+    using CL = CstLayout<D, DY>;
+    using FL = F0Layout<D, DY>;
+    constexpr int MT = TimeTab<D>::MT;
+    constexpr int MP2 = DimM<D>::MP2;
+    constexpr int U = 4;                    // steps per chunk
+    constexpr int NPF = U * FL::SIZE / 2;   // 16-byte pieces of the position table per chunk
+    constexpr int NPM = U * MT / 2;         // … of the time table
+    constexpr int NPC = NPF + NPM;
+    constexpr int TPB = 64 * W;             // lanes that share the table stream
+    constexpr int PPL = (NPC + TPB - 1) / TPB;
+    constexpr bool YR = RXHIP_F0_Y_RING != 0;
+    __shared__ double2 tbuf[2][NPC];
+    const int tid = threadIdx.x;
+    const int wv = W > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
+    const int lane = W > 1 ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
+    const long long g0 = ((long long)blockIdx.x * W + wv) * 64;
+    const long long seg = g0 / p.n_chains;          // (uniform across the workgroup)
+    const long long chain = g0 - seg * p.n_chains + lane;
+    const long long len = seg_len(p, seg);
+    const CPtr c{cb.v};
+    const long long t0 = seg * p.L + 1;
+    const int lg = p.ck_log2;
+    const long long kmask = (1LL << lg) - 1;
+    const long long f_last = p.L * (FL::SIZE / 2) - 1;
+    const long long m_last = p.T * (MT / 2) - 1;
+    const rx_d2v* f2 = reinterpret_cast<const rx_d2v*>(p.ftab);
+    const rx_d2v* m2 = reinterpret_cast<const rx_d2v*>(p.mtab);
+
+    double m[D], eta[D], q0 = 0.0;
+#pragma unroll
+    for (int i = 0; i < D; ++i) m[i] = eta[i] = 0.0;
+    if (len > 0) {   // (uniform across the workgroup: the barriers below are taken by all of its waves or by none)
+        rx_d2v tr[PPL];
+#pragma unroll
+        for (int k = 0; k < PPL; ++k) tr[k] = rx_d2v{0.0, 0.0};
+        // chunk i0: a step i ∈ [i0, i0 + U) with (i + 1) a multiple of K, or the segment's last step
+        auto has_ck = [&](long long i0) { return ((i0 + U) >> lg) != (i0 >> lg) || (i0 < len && len <= i0 + U); };
+        auto fetch = [&](long long i0) {
+            const bool ck = has_ck(i0);
+#pragma unroll
+            for (int k = 0; k < PPL; ++k) {
+                const int idx = k * TPB + tid < NPC ? k * TPB + tid : NPC - 1;
+                if (idx < NPF) {
+                    const long long gi = i0 * (FL::SIZE / 2) + idx;
+                    tr[k] = f2[gi < f_last ? gi : f_last];
+                } else if (ck) {
+                    const long long gi = (t0 + i0) * (MT / 2) + (idx - NPF);
+                    tr[k] = m2[gi < m_last ? gi : m_last];
+                }
+            }
+        };
+        auto stash = [&](int b) {
+#pragma unroll
+            for (int k = 0; k < PPL; ++k) {
+                const int idx = k * TPB + tid;
+                if ((k + 1) * TPB <= NPC || idx < NPC) tbuf[b][idx] = make_double2(tr[k].x, tr[k].y);
+            }
+        };
+        fetch(0);
+        stash(0);
+        lds_publish<W>();
+
+        double yb[U][DY], yn[U][DY];
+        auto y_index = [&](long long i) { return t0 + (i < len ? i : len - 1); };
+#pragma unroll
+        for (int u = 0; u < U; ++u) load_y<DY>(p.y, y_index(u), p.n_chains, chain, yn[u]);
+        auto step = [&](const int u, const long long i, const int b) __attribute__((always_inline)) {
+            const double* tb = reinterpret_cast<const double*>(&tbuf[b][0]) + u * FL::SIZE;
+            const double* mt = reinterpret_cast<const double*>(&tbuf[b][NPF]) + u * MT;
+            double e[DY];
+#pragma unroll
+            for (int a = 0; a < DY; ++a) {
+                double s = YR ? yn[u][a] : yb[u][a];
+#pragma unroll
+                for (int k = 0; k < D; ++k) s -= c[CL::HF + a * D + k] * m[k];
+                e[a] = s;
+            }
+            if constexpr (YR) {   // the slot's refill, behind the last use of its value (as in k_backward_sh_rev)
+                __builtin_amdgcn_sched_barrier(0);
+                load_y<DY>(p.y, y_index(i + U), p.n_chains, chain, yn[u]);
+            }
+            if (FE) {
+#pragma unroll
+                for (int a = 0; a < DY; ++a) {
+                    double s = 0.0;
+#pragma unroll
+                    for (int k = 0; k < DY; ++k) s += tb[FL::SI + sidx(a, k)] * e[k];
+                    q0 += s * e[a];
+                }
+            }
+            double mn[D];
+#pragma unroll
+            for (int a = 0; a < D; ++a) {
+                double s = 0.0, uu = eta[a];
+#pragma unroll
+                for (int k = 0; k < D; ++k) s += c[CL::A + a * D + k] * m[k];
+#pragma unroll
+                for (int k = 0; k < DY; ++k) {
+                    s += tb[FL::K + a * DY + k] * e[k];
+                    uu += tb[FL::U + a * DY + k] * e[k];
+                }
+                mn[a] = s;
+                eta[a] = uu;
+            }
+#pragma unroll
+            for (int a = 0; a < D; ++a) m[a] = mn[a];
+            if (((i + 1) & kmask) != 0 && i + 1 != len) return;   // not a checkpoint (uniform)
+            double z[2 * MP2];   // z_t = b_i + M_t η_i
+#pragma unroll
+            for (int a = 0; a < D; ++a) {
+                double s = m[a];
+#pragma unroll
+                for (int k = 0; k < D; ++k) s += mt[a * D + k] * eta[k];
+                z[a] = s;
+            }
+            if (D < 2 * MP2) z[2 * MP2 - 1] = 0.0;
+            const long long slot = 1 + seg * p.nck + (i >> lg);
+            double2* base = reinterpret_cast<double2*>(p.filt) + ((slot * p.nb64 + (chain >> 6)) * MP2) * 64 + (chain & 63);
+#pragma unroll
+            for (int k = 0; k < MP2; ++k) base[k * 64] = make_double2(z[2 * k], z[2 * k + 1]);
+        };
+        auto next_y = [&](long long i0) {
+            if constexpr (YR) return;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+#pragma unroll
+                for (int k = 0; k < DY; ++k) yb[u][k] = yn[u][k];
+                load_y<DY>(p.y, y_index(i0 + U + u), p.n_chains, chain, yn[u]);
+            }
+        };
+        int b = 0;
+        long long i0 = 0;
+        for (; i0 + U <= len; i0 += U, b ^= 1) {   // whole chunks
+            fetch(i0 + U);
+            next_y(i0);
+#pragma unroll
+            for (int u = 0; u < U; ++u) step(u, i0 + u, b);
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            stash(b ^ 1);
+            lds_publish<W>();   // W > 1: the chunk's one workgroup barrier
+        }
+        if constexpr (!YR) {
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int k = 0; k < DY; ++k) yb[u][k] = yn[u][k];
+        }
+#pragma unroll
+        for (int u = 0; u < U - 1; ++u)   // the last len mod U steps
+            if (i0 + u < len) step(u, i0 + u, b);
+    }
+    double* o = p.elem + (seg * 2 * D) * p.n_chains + chain;
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        o[a * p.n_chains] = m[a];
+        o[(D + a) * p.n_chains] = eta[a];
+    }
+    if (FE) p.fe_part[(seg + 1) * p.n_chains + chain] = -0.5 * q0;
 }
 
 // Data-independent per-time-index tables of the one-pass schedule, once per engine: one lane per time index.
@@ -3556,7 +3745,7 @@ __device__ __forceinline__ void boundary_in_sweep(const Params& p, const CPtr c,
     store_soa<D>(p.beta, seg + 1, p.n_chains, chain, xb, Lb);
 }
 
-// Phase 4 for shared-model batches on the reverse-filter schedule: k_forward0<…, true> left z only at checkpoints (every K steps
+// Phase 4 for shared-model batches on the reverse-filter schedule: k_forward0_ck left z only at checkpoints (every K steps
 // of a segment and at its end), and this sweep rebuilds every other filtered mean by running the filter BACKWARD in time.
 // With V_p V_f⁻¹ = I + V_p B'Q⁻¹B the Kalman update inverts exactly:
 //     m_p(t+1) = m_f(t+1) + V_p(t+1) (B'Q⁻¹B m_f(t+1) − B'Q⁻¹ y_{t+1}),      m_f(t) = A⁻¹ m_p(t+1),
@@ -3587,9 +3776,9 @@ __device__ __forceinline__ void boundary_in_sweep(const Params& p, const CPtr c,
 #define RXHIP_Y_RING_DEPTH 4
 #endif
 constexpr int Y_RING_SHIPPED = RXHIP_Y_RING_DEPTH;   // steps y runs ahead of its use; divides the chunk length, so a step's ring slot is a compile-time constant
-template <int D, int DY, int R>
-__global__ void __launch_bounds__(64) k_backward_sh_rev(Params p, const double* __restrict__ gtab, const double* __restrict__ segend,
-                                                        const CstArg<CstLayout<D, DY>::SIZE> cb, const int bnd, const int write_cov) {
+template <int D, int DY, int R, int W = 1>
+__global__ void __launch_bounds__(64 * W) k_backward_sh_rev(Params p, const double* __restrict__ gtab, const double* __restrict__ segend,
+                                                            const CstArg<CstLayout<D, DY>::SIZE> cb, const int bnd, const int write_cov) {
     using ST = SmoothTab<D>;
     using CL = CstLayout<D, DY>;
     constexpr int MP2 = DimM<D>::MP2;
@@ -3597,18 +3786,25 @@ __global__ void __launch_bounds__(64) k_backward_sh_rev(Params p, const double* 
     constexpr int U = 4;                     // steps per table chunk
     constexpr int RP = ST::SIZE / 2;         // 16-byte pieces per row
     constexpr int NPC = U * RP;
-    constexpr int PPL = (NPC + 63) / 64;
+    constexpr int TPB = 64 * W;              // lanes that share the table stream
+    constexpr int PPL = (NPC + TPB - 1) / TPB;
     constexpr int NMP = 32 * D;              // 16-byte pieces of the 64 means of a time index
     constexpr int NCP = 32 * D * D;          // … of the 64 covariances
     static_assert(U % R == 0, "ring slots must be compile-time");
     static_assert(MT <= 64, "one lane per element of an N row");
-    __shared__ double2 tbuf[2][NPC];
-    __shared__ double mtile[64 * D];
-    __shared__ double bndbuf[2][BndStage<D>::N];
+    static_assert(D * D <= 64, "one lane per element of A⁻¹");
+    __shared__ double2 tbuf[2][NPC];         // ONE per workgroup: every wave reads the rows, each piece is loaded by one lane
+    __shared__ double mtile_w[W][64 * D];    // per wave
+    __shared__ double bndbuf_w[W][2][BndStage<D>::N];
     __shared__ double ainv[D * D];           // A⁻¹, read once
-    __shared__ double nrow[MT];              // N_t of the checkpoint being restarted from
-    const int lane = threadIdx.x;
-    const long long g0 = (long long)blockIdx.x * 64;  // n_chains % 64 == 0: the wave holds 64 chains of ONE segment
+    __shared__ double nrow_w[W][MT];         // N_t of the checkpoint being restarted from
+    const int tid = threadIdx.x;             // position in the table stream's split
+    const int wv = W > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
+    const int lane = W > 1 ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
+    double (&mtile)[64 * D] = mtile_w[wv];
+    double (&bndbuf)[2][BndStage<D>::N] = bndbuf_w[wv];
+    double (&nrow)[MT] = nrow_w[wv];
+    const long long g0 = ((long long)blockIdx.x * W + wv) * 64;  // n_chains % (64·W) == 0: the workgroup holds 64·W chains of ONE segment, a wave 64 of them
     const long long seg = g0 / p.n_chains;
     const long long chain0 = g0 - seg * p.n_chains;
     const long long chain = chain0 + lane;
@@ -3694,7 +3890,7 @@ __global__ void __launch_bounds__(64) k_backward_sh_rev(Params p, const double* 
     auto fetch = [&](long long i0) {   // the rows of steps i0 … i0 + U − 1, past the segment's last step its row again (never used)
 #pragma unroll
         for (int k = 0; k < PPL; ++k) {
-            const int idx = k * 64 + lane < NPC ? k * 64 + lane : NPC - 1;
+            const int idx = k * TPB + tid < NPC ? k * TPB + tid : NPC - 1;
             const long long r = i0 + idx / RP;  // step index
             tr[k] = g2[(te - 1 - (r < len ? r : len - 1)) * RP + idx % RP];
         }
@@ -3702,15 +3898,14 @@ __global__ void __launch_bounds__(64) k_backward_sh_rev(Params p, const double* 
     auto stash = [&](int b) {
 #pragma unroll
         for (int k = 0; k < PPL; ++k) {
-            const int idx = k * 64 + lane;
-            if ((k + 1) * 64 <= NPC || idx < NPC) tbuf[b][idx] = make_double2(tr[k].x, tr[k].y);
+            const int idx = k * TPB + tid;
+            if ((k + 1) * TPB <= NPC || idx < NPC) tbuf[b][idx] = make_double2(tr[k].x, tr[k].y);
         }
     };
     fetch(0);
-    if (lane < D * D) ainv[lane] = p.ainv[lane];
+    if (tid < D * D) ainv[tid] = p.ainv[tid];
     stash(0);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    lds_publish<W>();
     // the next checkpoint below te (a multiple of K past tb; none when it would be tb itself), prefetched a whole window ahead with the one
     // element of its N row that this lane carries.  Past the last checkpoint the load goes on, to the segment's first one: same operations
     // on every path, value unused.
@@ -3804,8 +3999,7 @@ __global__ void __launch_bounds__(64) k_backward_sh_rev(Params p, const double* 
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         stash(b ^ 1);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        lds_publish<W>();   // W > 1: the chunk's one workgroup barrier, on a path every wave of the block takes (`len` is the segment's)
     }
 #pragma unroll
     for (int u = 0; u < U - 1; ++u)   // the last len mod U steps

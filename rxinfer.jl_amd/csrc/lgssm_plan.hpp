@@ -38,7 +38,8 @@ namespace plan {
     X(bool, wave8_off, false)             /* RXHIP_WAVE8=0 */                                                                           \
     X(bool, no_frozen, false)             /* RXHIP_NO_FROZEN */                                                                         \
     X(bool, cov_every_sweep, false)       /* RXHIP_COV_EVERY_SWEEP=1 */                                                                 \
-    X(int, y_ring, 0)                     /* RXHIP_Y_RING=1 (0: not set, -1: any other value; rxhip_lgssm_create refuses it) */
+    X(int, y_ring, 0)                     /* RXHIP_Y_RING=1 (0: not set, -1: any other value; rxhip_lgssm_create refuses it) */                 \
+    X(int, sweep_waves, 0)                /* RXHIP_SWEEP_WAVES=1|2|4 (0: not set, -1: any other value; rxhip_lgssm_create refuses it) */
 
 struct Text { char s[16] = {0}; };   // the first 15 characters of a hook's value
 
@@ -83,6 +84,7 @@ struct ScheduleHooks {
         h.no_frozen = set("RXHIP_NO_FROZEN");
         h.cov_every_sweep = not0("RXHIP_COV_EVERY_SWEEP");
         if (const char* v = get("RXHIP_Y_RING")) h.y_ring = !std::strcmp(v, "1") ? 1 : -1;
+        if (const char* v = get("RXHIP_SWEEP_WAVES")) h.sweep_waves = !std::strcmp(v, "1") ? 1 : !std::strcmp(v, "2") ? 2 : !std::strcmp(v, "4") ? 4 : -1;
         return h;
     }
     // the hooks' part of the engine-pool key: every field, by the list above
@@ -227,6 +229,20 @@ inline bool gtab_tables(long long n_chains, const ScheduleHooks& hooks) { return
 // the tables exist; RXHIP_MEAN_RECORDS=1 keeps a record per time index, RXHIP_MEAN_CHECKPOINT=K forces the stride K.
 inline bool rev_cand(bool fused, long long n_chains, int d, int dy, long long T, const ScheduleHooks& hooks) {
     return fused && gtab_tables(n_chains, hooks) && dy <= d && T > 1 && !hooks.mean_records;
+}
+
+// Wavefronts per workgroup of the two sweep kernels of the reverse-filter schedule (k_forward0_ck, k_backward_sh_rev): the W waves of a
+// workgroup take W adjacent 64-chain groups of one segment and share one table stream, so 64·W must divide the batch.  Each kernel ships the
+// width that won its own arm comparison in every round (profiles/r14/README.md): the backward sweep two waves (0.01–0.03 ms ahead of one; four
+// are no better than two), the forward kernel one (no width was ahead in every round).  RXHIP_SWEEP_WAVES forces one width for both (0: not
+// forced; the caller has refused a forced width that does not divide the batch).
+constexpr int SWEEP_WAVES_FORWARD = 1, SWEEP_WAVES_BACKWARD = 2;
+inline bool sweep_waves_divide(long long n_chains, int w) { return w >= 1 && n_chains % (64LL * w) == 0; }
+inline int sweep_waves(long long n_chains, int shipped, int forced) {
+    if (forced > 0) return forced;
+    for (int w = 4; w > 1; w >>= 1)
+        if (w <= shipped && sweep_waves_divide(n_chains, w)) return w;
+    return 1;
 }
 
 }  // namespace plan

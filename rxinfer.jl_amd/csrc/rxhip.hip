@@ -2253,6 +2253,14 @@ static rxhip_status create_lanes(rxhip_engine* e, const rxhip_lgssm_desc* ds) {
         return fail(e, RXHIP_ERR_BADARG, "RXHIP_MEAN_CHECKPOINT=%s: a power of two from 1 to 32", e->hooks.mean_checkpoint_text.s);
     if (e->hooks.y_ring != 0 && e->hooks.y_ring != 1)
         return fail(e, RXHIP_ERR_BADARG, "RXHIP_Y_RING: 1 (the depth-1 y ring of the reverse-filter sweep) or unset (depth %d)", Y_RING_SHIPPED);
+    const int waves_forced = e->hooks.sweep_waves;
+    if (waves_forced < 0)
+        return fail(e, RXHIP_ERR_BADARG, "RXHIP_SWEEP_WAVES: 1, 2 or 4 (wavefronts per workgroup of the reverse-filter sweep kernels) or unset");
+    if (waves_forced > 1 && !plan::sweep_waves_divide(e->n_chains, waves_forced))
+        return fail(e, RXHIP_ERR_BADARG, "RXHIP_SWEEP_WAVES=%d: a workgroup of %d waves takes %d chains of one segment, which does not divide the batch of %lld",
+                    waves_forced, waves_forced, 64 * waves_forced, (long long)e->n_chains);
+    e->sweep_waves_fwd = plan::sweep_waves(e->n_chains, plan::SWEEP_WAVES_FORWARD, waves_forced);
+    e->sweep_waves_bwd = plan::sweep_waves(e->n_chains, plan::SWEEP_WAVES_BACKWARD, waves_forced);
     const bool rev_cand = plan::rev_cand(e->fused, e->n_chains, e->d, e->dy, e->T, e->hooks);
     if (e->fused) {
         ap.upload(&e->d_ftab, ft.ftab.data(), sizeof(double) * ft.ftab.size());
@@ -2929,7 +2937,7 @@ static rxhip_status run_lanes(rxhip_engine* e, const RunPlan& pl, const Params& 
     const bool fe = pl.fe, fused = pl.family == RunFamily::OnePass, bnd_in_sweep = pl.bnd_in_sweep;
     if (fused) {  // one pass over the observations: known-start recursion + z_t records + evidence parts
         if ((st = prof_begin(e, RXHIP_K_FORWARD))) return st;
-        e->vt->forward0(p, e->h_cst0.data(), fe, e->ck_log2 > 0, e->stream);
+        e->vt->forward0(p, e->h_cst0.data(), fe, e->ck_log2 > 0, e->sweep_waves_fwd, e->stream);
         if ((st = prof_end(e))) return st;
     } else if (pl.family == RunFamily::SmallSweep) {   // a few chains, a short series: aggregate, boundary scan, forward, backward and the free energy in ONE launch
         e->vt->small_sweep(p, e->h_cst0.data(), fe, e->stream);
@@ -2958,7 +2966,7 @@ static rxhip_status run_lanes(rxhip_engine* e, const RunPlan& pl, const Params& 
             e->vt->fe_seg(p, e->stream);
         if (!pl.filter) {
             if ((st = prof_begin(e, RXHIP_K_BACKWARD))) return st;
-            if (pl.backward_sh) e->vt->backward_sh(p, e->h_cst0.data(), e->d_gtab, e->d_segend, e->ck_log2 > 0, bnd_in_sweep ? (fe ? 2 : 1) : 0, write_cov, e->hooks.y_ring == 1 ? 1 : Y_RING_SHIPPED, e->stream);
+            if (pl.backward_sh) e->vt->backward_sh(p, e->h_cst0.data(), e->d_gtab, e->d_segend, e->ck_log2 > 0, bnd_in_sweep ? (fe ? 2 : 1) : 0, write_cov, e->hooks.y_ring == 1 ? 1 : Y_RING_SHIPPED, e->sweep_waves_bwd, e->stream);
             else e->vt->backward(p, e->h_cst0.data(), e->uniform, e->stream);
             if ((st = prof_end(e))) return st;
         }
@@ -3506,6 +3514,13 @@ rxhip_status rxhip_get_mean_checkpoint_stride(rxhip_engine* e, int32_t* K) {
     TREE_GUARD(e);
     if (!e || !K) return RXHIP_ERR_BADARG;
     *K = e->ck_log2 ? (int32_t)1 << e->ck_log2 : 0;
+    return RXHIP_OK;
+}
+rxhip_status rxhip_get_sweep_waves(rxhip_engine* e, int32_t* forward, int32_t* backward) {
+    TREE_GUARD(e);
+    if (!e || !forward || !backward) return RXHIP_ERR_BADARG;
+    *forward = e->ck_log2 ? e->sweep_waves_fwd : 0;
+    *backward = e->ck_log2 ? e->sweep_waves_bwd : 0;
     return RXHIP_OK;
 }
 rxhip_status rxhip_get_model_tables_ms(rxhip_engine* e, double* ms) {

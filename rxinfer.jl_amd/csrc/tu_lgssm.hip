@@ -80,11 +80,19 @@ struct Launch {
         else if (p.tinv_records) hipLaunchKernelGGL((k_backward_tinv<D, DY>), grid, dim3(64), 0, s, p);
         else hipLaunchKernelGGL((k_backward<D, DY, false>), grid, dim3(64), 0, s, p, CstArg<1>{});
     }
-    static void forward0(const Params& p, const double* hc, bool fe, bool ck, hipStream_t s) {   // ck: z at checkpoints only
+    template <int W>
+    static void forward0_ck(const Params& p, const double* hc, bool fe, hipStream_t s) {   // n_chains % (64·W) == 0 (plan::sweep_waves)
+        const dim3 grid((unsigned)(p.n_chains / (64 * W) * p.S));
+        if (fe) hipLaunchKernelGGL((k_forward0_ck<D, DY, true, W>), grid, dim3(64 * W), 0, s, p, carg(hc));
+        else hipLaunchKernelGGL((k_forward0_ck<D, DY, false, W>), grid, dim3(64 * W), 0, s, p, carg(hc));
+    }
+    // ck: z at checkpoints only (the reverse-filter schedule), in workgroups of `waves` waves
+    static void forward0(const Params& p, const double* hc, bool fe, bool ck, int waves, hipStream_t s) {
         const long long total = p.n_chains * (long long)p.S;
         if (ck) {
-            if (fe) hipLaunchKernelGGL((k_forward0<D, DY, true, true>), dim3(nblk(total, 64)), dim3(64), 0, s, p, carg(hc));
-            else hipLaunchKernelGGL((k_forward0<D, DY, false, true>), dim3(nblk(total, 64)), dim3(64), 0, s, p, carg(hc));
+            if (waves == 4) forward0_ck<4>(p, hc, fe, s);
+            else if (waves == 2) forward0_ck<2>(p, hc, fe, s);
+            else forward0_ck<1>(p, hc, fe, s);
         } else if (fe) hipLaunchKernelGGL((k_forward0<D, DY, true>), dim3(nblk(total, 64)), dim3(64), 0, s, p, carg(hc));
         else hipLaunchKernelGGL((k_forward0<D, DY, false>), dim3(nblk(total, 64)), dim3(64), 0, s, p, carg(hc));
     }
@@ -104,10 +112,18 @@ struct Launch {
     // bnd (reverse-filter sweep only): 0 — a boundary-scan launch came before; 1 / 2 — the sweep's waves run the boundary recursion themselves (2: + free energy)
     // write_cov: false — the per-chain covariance array already holds the table broadcast, the sweep stores the means only
     // y_ring (reverse-filter sweep only): steps the observations run ahead of their use, 1 or Y_RING_SHIPPED
-    static void backward_sh(const Params& p, const double* hc, const double* gtab, const double* segend, bool rev, int bnd, bool write_cov, int y_ring, hipStream_t s) {
-        const dim3 grid((unsigned)(p.n_chains / 64 * p.S));
-        if (rev && y_ring == 1) hipLaunchKernelGGL((k_backward_sh_rev<D, DY, 1>), grid, dim3(64), 0, s, p, gtab, segend, carg(hc), bnd, write_cov ? 1 : 0);
-        else if (rev) hipLaunchKernelGGL((k_backward_sh_rev<D, DY, Y_RING_SHIPPED>), grid, dim3(64), 0, s, p, gtab, segend, carg(hc), bnd, write_cov ? 1 : 0);
+    // waves (reverse-filter sweep only): wavefronts per workgroup, 1, 2 or 4 with n_chains % (64·waves) == 0 (plan::sweep_waves)
+    template <int W>
+    static void backward_rev(const Params& p, const double* hc, const double* gtab, const double* segend, int bnd, bool write_cov, int y_ring, hipStream_t s) {
+        const dim3 grid((unsigned)(p.n_chains / (64 * W) * p.S));
+        if (y_ring == 1) hipLaunchKernelGGL((k_backward_sh_rev<D, DY, 1, W>), grid, dim3(64 * W), 0, s, p, gtab, segend, carg(hc), bnd, write_cov ? 1 : 0);
+        else hipLaunchKernelGGL((k_backward_sh_rev<D, DY, Y_RING_SHIPPED, W>), grid, dim3(64 * W), 0, s, p, gtab, segend, carg(hc), bnd, write_cov ? 1 : 0);
+    }
+    static void backward_sh(const Params& p, const double* hc, const double* gtab, const double* segend, bool rev, int bnd, bool write_cov, int y_ring, int waves,
+                            hipStream_t s) {
+        if (rev && waves == 4) backward_rev<4>(p, hc, gtab, segend, bnd, write_cov, y_ring, s);
+        else if (rev && waves == 2) backward_rev<2>(p, hc, gtab, segend, bnd, write_cov, y_ring, s);
+        else if (rev) backward_rev<1>(p, hc, gtab, segend, bnd, write_cov, y_ring, s);
         else hipLaunchKernelGGL((k_backward_sh<D>), dim3((unsigned)(p.n_chains / 64 * p.S)), dim3(64), 0, s, p, gtab, segend, write_cov ? 1 : 0);
     }
     static void forecast(const PredictParams& p, hipStream_t s) {

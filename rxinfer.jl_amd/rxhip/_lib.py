@@ -287,6 +287,7 @@ SYMBOLS = [
     ("rxhip_get_kernel_times", ctypes.c_int32, [_H, c_double_p, c_u64_p]),
     ("rxhip_get_model_tables_ms", ctypes.c_int32, [_H, c_double_p]),
     ("rxhip_get_mean_checkpoint_stride", ctypes.c_int32, [_H, c_int32_p]),
+    ("rxhip_get_sweep_waves", ctypes.c_int32, [_H, c_int32_p, c_int32_p]),
     ("rxhip_get_create_stages", ctypes.c_int32, [_H, c_double_p]),
     ("rxhip_set_covariance_mode", ctypes.c_int32, [_H, ctypes.c_int32]),
     ("rxhip_set_fixed_point_exits", ctypes.c_int32, [_H, ctypes.c_int32]),

@@ -319,6 +319,13 @@ class LGSSMEngine(_StateEngine):
         self._chk(_lib.lib().rxhip_get_mean_checkpoint_stride(self._h, ctypes.byref(k)))
         return k.value
 
+    def sweep_waves(self):
+        """(forward, backward): wavefronts per workgroup of the two sweep kernels of the reverse-filter schedule; (0, 0) for an
+        engine on another schedule (rxhip_get_sweep_waves)"""
+        f, b = ctypes.c_int32(), ctypes.c_int32()
+        self._chk(_lib.lib().rxhip_get_sweep_waves(self._h, ctypes.byref(f), ctypes.byref(b)))
+        return f.value, b.value
+
     def create_stages(self):
         """host milliseconds of the engine's creation by stage (rxhip_get_create_stages)"""
         ms = (ctypes.c_double * 4)()

@@ -55,6 +55,36 @@ __global__ void k_mix_streams(const double2* __restrict__ a, double2* __restrict
         for (int k = 0; k < 10; ++k) op[(u * 10 + k) * 64 + threadIdx.x] = acc;
     }
 }
+// The shared-model sweep's own layout: S streams (segments) `stream` pieces of 16 B apart, each walked DOWNWARDS in rows of 32 KB
+// (1024 chains × 32 B: 2048 pieces, a lane takes two adjacent ones as load_y does at dy = 4).  W = 1: sixteen independent 64-lane waves per row,
+// 2 KB each, nothing keeps them together.  W = 4: four workgroups of 256 lanes per row, 8 KB each, held in lock step by one s_barrier per four rows
+// (the chunk barrier of the W-wave sweep kernels).  WR: every row is also written to a second array of the same layout (1 r : 1 w), nontemporal.
+template <int W, bool WR>
+__global__ void __launch_bounds__(64 * W) k_sweep_rows(const d2v* __restrict__ a, d2v* __restrict__ o, size_t stream, int rows, double* out) {
+    constexpr int PER = 16 / W;   // workgroups per row
+    const size_t s = blockIdx.x / PER, part = blockIdx.x % PER;
+    const size_t off = s * stream + part * (128 * W) + 2 * threadIdx.x;
+    const d2v* ap = a + off;
+    d2v* op = o + off;
+    d2v acc = {0, 0};
+    for (int r0 = rows - 4; r0 >= 0; r0 -= 4) {   // (rows % 4 == 0)
+        d2v v[4][2];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            v[u][0] = ap[(size_t)(r0 + 3 - u) * 2048];
+            v[u][1] = ap[(size_t)(r0 + 3 - u) * 2048 + 1];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (WR) {
+                __builtin_nontemporal_store(v[u][0], op + (size_t)(r0 + 3 - u) * 2048);
+                __builtin_nontemporal_store(v[u][1], op + (size_t)(r0 + 3 - u) * 2048 + 1);
+            } else acc += v[u][0] + v[u][1];
+        }
+        if (W > 1) __builtin_amdgcn_s_barrier();
+    }
+    if (!WR && acc.x == 12345.678) *out = acc.x;
+}
 int main() {
     const size_t GB = 1ull << 30;
     size_t nbytes = 12 * GB, n = nbytes / 16;
@@ -88,6 +118,15 @@ int main() {
         size_t per = nunits / waves;
         char nm[64]; snprintf(nm, 64, "mix 7r:10w %d streams nt", waves);
         t(nm, (double)per * waves * 17 * 1024, [&] { hipLaunchKernelGGL(k_mix_streams_nt, dim3(waves), dim3(64), 0, 0, (const d2v*)a, (d2v*)b, per); });
+    }
+    {   // the sweep's layout: 128 streams of 780 rows of 32 KB (25 MB apart), read only and 1 r : 1 w, as 2-KB waves and as lock-stepped 8-KB workgroups
+        const int S = 128, rows = 780;
+        const size_t stream = (size_t)rows * 2048;   // pieces
+        const double bytes = (double)S * rows * 32768.0;
+        t("sweep rows read, 16 x 2 KB waves", bytes, [&] { hipLaunchKernelGGL((k_sweep_rows<1, false>), dim3(S * 16), dim3(64), 0, 0, (const d2v*)a, (d2v*)b, stream, rows, out); });
+        t("sweep rows read, 4 x 8 KB WGs", bytes, [&] { hipLaunchKernelGGL((k_sweep_rows<4, false>), dim3(S * 4), dim3(256), 0, 0, (const d2v*)a, (d2v*)b, stream, rows, out); });
+        t("sweep rows 1r:1w, 16 x 2 KB waves", 2 * bytes, [&] { hipLaunchKernelGGL((k_sweep_rows<1, true>), dim3(S * 16), dim3(64), 0, 0, (const d2v*)a, (d2v*)b, stream, rows, out); });
+        t("sweep rows 1r:1w, 4 x 8 KB WGs", 2 * bytes, [&] { hipLaunchKernelGGL((k_sweep_rows<4, true>), dim3(S * 4), dim3(256), 0, 0, (const d2v*)a, (d2v*)b, stream, rows, out); });
     }
     return 0;
 }
