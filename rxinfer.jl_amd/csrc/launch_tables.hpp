@@ -35,6 +35,14 @@
 namespace rxhip {
 
 // ------------------------------------------------------------------------------------------
+// which table-driven backward sweep LgssmVtbl::backward_sh launches (all but write_cov: the reverse-filter sweep only)
+struct SweepArgs {
+    bool rev;        // k_backward_sh_rev (z at checkpoints, the reverse filter) instead of k_backward_sh (a z record per time index)
+    int bnd;         // 0 — a boundary-scan launch came before; 1 / 2 — the sweep's waves run the boundary recursion themselves (2: + free energy)
+    bool write_cov;  // false — the per-chain covariance array already holds the table broadcast, the sweep stores the means only
+    int y_ring;      // steps the observations run ahead of their use, 1 or Y_RING_SHIPPED
+    int waves;       // wavefronts per workgroup, 1, 2 or 4 with n_chains % (64·waves) == 0 (plan::sweep_waves)
+};
 // per-(d, dy) dispatch table of the d, dy ≤ 4 kernels
 struct LgssmVtbl {
     int d, dy;
@@ -50,7 +58,7 @@ struct LgssmVtbl {
     void (*fe_seg)(const Params&, hipStream_t);
     int gt_row, se_size;  // SmoothTab / SegEndTab
     void (*smooth_tables)(const SmoothTabParams&, const double*, hipStream_t);
-    void (*backward_sh)(const Params&, const double*, const double*, const double*, bool, int, bool, int, int, hipStream_t);
+    void (*backward_sh)(const Params&, const double*, const double* gtab, const double* segend, const SweepArgs&, hipStream_t);
     void (*boundary_scan_tab)(const Params&, const double*, bool, hipStream_t);
     void (*seg_aggregate)(const Params&, const double*, bool, hipStream_t);
     int ex_size;  // ElemX

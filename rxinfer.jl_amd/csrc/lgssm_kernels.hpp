@@ -63,6 +63,65 @@ __device__ __forceinline__ void stream_store(double2* p, double a, double b) {
 #endif
 }
 
+// A table stream through LDS.  Rows every lane of a wave needs alike (gains of one model, table rows of a time index) are loaded
+// cooperatively — each of the NPIECES pieces of a chunk by one of the 64·W lanes that share the stream — into registers a chunk ahead,
+// stored into the buffer the waves are not reading, and read back with broadcast ds_reads.  (Scalar loads of the table stall the wave on
+// every step: SMEM returns out of order, so each s_load needs lgkmcnt(0) before first use.)  A kernel's chunk loop is
+//     ts.fetch(piece of chunk 0);  ts.stash(buf[0]);  ts.publish();
+//     for (chunk; …; b ^= 1) { ts.fetch(piece of the next chunk);  … the chunk's steps read buf[b] …;  ts.flip(buf[b ^ 1]); }
+// `piece(idx, v)` is the kernel's: it leaves the value of piece idx ∈ [0, PPL·TPB) in v, or leaves v as it is (a part of the chunk that is
+// not needed).  Past the chunk or the table it either yields zero behind a guard (the kernels with per-lane guards) or loads with the index
+// clamped, value unused (the kernels whose loops issue the same operations on every path); the stash stores the first NPIECES only.
+//   · publish, W = 1: the buffer is the wave's own, a wavefront fence orders the writes.  W > 1: ONE s_barrier, and the fences around it
+//     name the LDS only, so the wait in front of the barrier is lgkmcnt(0) — a __syncthreads() or a fence over all address spaces would wait
+//     vmcnt(0) as well and drain the y loads and the stores a wave keeps in flight across the chunk.
+//   · One barrier per chunk is enough for the double buffer: buffer b is rewritten at the end of the NEXT chunk, and a wave gets there only
+//     through the barrier that every wave reached after its last read of b.  The acquire fence of flip keeps the chunk's reads in front.
+//   · Whole groups of TPB pieces are stashed without a lane predicate: a predicate the compiler cannot fold is a branch around the store.
+//   · 16-byte pieces are rx_d2v, a first-class vector: as double2 the unconditional copy is a memcpy into a stack slot.
+__device__ __forceinline__ void lds_put(double2& dst, const rx_d2v v) { dst = make_double2(v.x, v.y); }
+template <class T>
+__device__ __forceinline__ void lds_put(T& dst, const T& v) { dst = v; }
+template <int NPIECES, int W, class T = rx_d2v>
+struct LdsStream {
+    static constexpr int TPB = 64 * W;                       // lanes that share the stream
+    static constexpr int PPL = (NPIECES + TPB - 1) / TPB;    // pieces per lane
+    const int tid;                                           // position in the split
+    T tr[PPL];
+    __device__ __forceinline__ explicit LdsStream(const int tid_) : tid(tid_) {}
+    template <class Piece>
+    __device__ __forceinline__ void fetch(Piece&& piece) {
+#pragma unroll
+        for (int k = 0; k < PPL; ++k) piece(k * TPB + tid, tr[k]);
+    }
+    template <class B>
+    __device__ __forceinline__ void stash(B* buf) const {
+#pragma unroll
+        for (int k = 0; k < PPL; ++k) {
+            const int idx = k * TPB + tid;
+            if ((k + 1) * TPB <= NPIECES || idx < NPIECES) lds_put(buf[idx], tr[k]);
+        }
+    }
+    static __device__ __forceinline__ void publish() {
+        if constexpr (W == 1) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        } else {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+        }
+    }
+    // the end of a chunk: the fetched pieces go into `buf`, the buffer of the next chunk (store == false: there is none, the barriers alone)
+    template <class B>
+    __device__ __forceinline__ void flip(B* buf, const bool store = true) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (store) stash(buf);
+        publish();
+    }
+};
+
 template <int D>
 struct Dim {
     static constexpr int NS = D * (D + 1) / 2;  // packed symmetric size
@@ -664,10 +723,9 @@ __device__ __forceinline__ void seg_aggregate_body(const Params& p, const CstArg
     constexpr int U = AggStage<D, DY>::U;
     constexpr int NPC = AggStage<D, DY>::NPC;
     constexpr int PPL = (NPC + 63) / 64;  // pieces per lane
-    // The per-offset gains are the same for every lane of the wave (one model): the wave streams
-    // them cooperatively global -> registers -> LDS one chunk ahead (double buffered) and reads
-    // them back with broadcast ds_reads.  (Scalar loads of the table stall the wave on every
-    // step: SMEM returns out of order, so each s_load needs lgkmcnt(0) before first use.)
+    // The per-offset gains are the same for every lane of the wave (one model): a table stream of one wave, LdsStream's protocol written
+    // out by hand — on the helper this body's instruction stream changes, in k_seg_aggregate and in k_small_sweep, which inlines it
+    // and is no part of the sweep (profiles/r15/README.md).
     double2 (*tbuf)[UNI ? NPC : 1] = reinterpret_cast<double2 (*)[UNI ? NPC : 1]>(tbuf_flat);   // [2][NPC], private to the wavefront
     const long long total = p.n_chains * (long long)p.S;
     const bool live = g < total;
@@ -1201,19 +1259,92 @@ __device__ __forceinline__ bool load_elemx(const Params& p, long long s, long lo
 //     −2 log p(y_seg | y_before) = const_s + q0 + [m_s'A1 m_s − 2 η'A2 m_s − η'W η],   q0 = Σ_i e_i'(S⁰_i)⁻¹e_i
 // with e_i the known-start innovations (k_fe_seg evaluates the bracket, const_s is summed on the host).
 //
-// This kernel stores z at every time index (the records schedule and the fallback); k_forward0_ck below is the instance of the reverse-filter
-// schedule, which stores it at the checkpoints only.  The m / η / q0 arithmetic is the same instruction sequence in both.
+// k_forward0 stores z at every time index (the records schedule and the fallback); k_forward0_ck below is the instance of the reverse-filter
+// schedule, which stores it at the checkpoints only.  Both run the step, the z store and the epilogue that follow.
+//
+// One step: e = y − (BA) m,  q0 += e'(S⁰_i)⁻¹e,  η += U_i e,  m = A m + K_i e   (tb: the position's F0Layout row)
 template <int D, int DY, bool FE>
-__global__ void __launch_bounds__(64) k_forward0(Params p, const CstArg<CstLayout<D, DY>::SIZE> cb) {
+__device__ __forceinline__ void f0_step(const CPtr c, const double* tb, const double (&y)[DY], double (&m)[D], double (&eta)[D], double& q0) {
     using CL = CstLayout<D, DY>;
     using FL = F0Layout<D, DY>;
-    constexpr int MT = TimeTab<D>::MT;
+    double e[DY];
+#pragma unroll
+    for (int a = 0; a < DY; ++a) {
+        double s = y[a];
+#pragma unroll
+        for (int k = 0; k < D; ++k) s -= c[CL::HF + a * D + k] * m[k];
+        e[a] = s;
+    }
+    if (FE) {
+#pragma unroll
+        for (int a = 0; a < DY; ++a) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < DY; ++k) s += tb[FL::SI + sidx(a, k)] * e[k];
+            q0 += s * e[a];
+        }
+    }
+    double mn[D];
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        double s = 0.0, uu = eta[a];
+#pragma unroll
+        for (int k = 0; k < D; ++k) s += c[CL::A + a * D + k] * m[k];
+#pragma unroll
+        for (int k = 0; k < DY; ++k) {
+            s += tb[FL::K + a * DY + k] * e[k];
+            uu += tb[FL::U + a * DY + k] * e[k];
+        }
+        mn[a] = s;
+        eta[a] = uu;
+    }
+#pragma unroll
+    for (int a = 0; a < D; ++a) m[a] = mn[a];
+}
+// z_t = b_i + M_t η_i (mrow: M_t), packed into record `slot` of `filt`
+template <int D>
+__device__ __forceinline__ void f0_store_z(const Params& p, const long long slot, const long long chain, const double (&m)[D], const double (&eta)[D],
+                                           const double* mrow) {
     constexpr int MP2 = DimM<D>::MP2;
-    constexpr int U = 4;                    // steps per chunk
-    constexpr int NPF = U * FL::SIZE / 2;   // 16-byte pieces of the position table per chunk
-    constexpr int NPM = U * MT / 2;         // … of the time table
-    constexpr int NPC = NPF + NPM;
-    constexpr int PPL = (NPC + 63) / 64;    // pieces per lane
+    double z[2 * MP2];
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        double s = m[a];
+#pragma unroll
+        for (int k = 0; k < D; ++k) s += mrow[a * D + k] * eta[k];
+        z[a] = s;
+    }
+    if (D < 2 * MP2) z[2 * MP2 - 1] = 0.0;
+    double2* base = reinterpret_cast<double2*>(p.filt) + ((slot * p.nb64 + (chain >> 6)) * MP2) * 64 + (chain & 63);
+#pragma unroll
+    for (int k = 0; k < MP2; ++k) base[k * 64] = make_double2(z[2 * k], z[2 * k + 1]);
+}
+// the segment's element (b, η) and its evidence partial
+template <int D, bool FE>
+__device__ __forceinline__ void f0_epilogue(const Params& p, const long long seg, const long long chain, const double (&m)[D], const double (&eta)[D],
+                                            const double q0) {
+    double* o = p.elem + (seg * 2 * D) * p.n_chains + chain;
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        o[a * p.n_chains] = m[a];
+        o[(D + a) * p.n_chains] = eta[a];
+    }
+    if (FE) p.fe_part[(seg + 1) * p.n_chains + chain] = -0.5 * q0;
+}
+template <int D, int DY>
+struct F0Stage {
+    static constexpr int U = 4;                                  // steps per chunk
+    static constexpr int NPF = U * F0Layout<D, DY>::SIZE / 2;    // 16-byte pieces of the position table per chunk
+    static constexpr int NPM = U * TimeTab<D>::MT / 2;           // … of the time table
+    static constexpr int NPC = NPF + NPM;
+};
+
+template <int D, int DY, bool FE>
+__global__ void __launch_bounds__(64) k_forward0(Params p, const CstArg<CstLayout<D, DY>::SIZE> cb) {
+    using FL = F0Layout<D, DY>;
+    using FS = F0Stage<D, DY>;
+    constexpr int MT = TimeTab<D>::MT;
+    constexpr int U = FS::U, NPF = FS::NPF, NPC = FS::NPC;
     __shared__ double2 tbuf[2][NPC];
     const int lane = threadIdx.x;
     const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1234,12 +1365,10 @@ __global__ void __launch_bounds__(64) k_forward0(Params p, const CstArg<CstLayou
     const double2* f2 = reinterpret_cast<const double2*>(p.ftab);
     const double2* m2 = reinterpret_cast<const double2*>(p.mtab);
 
-    double2 tr[PPL];
-    auto fetch = [&](long long i0) {
-#pragma unroll
-        for (int k = 0; k < PPL; ++k) {
-            const int idx = k * 64 + lane;
-            double2 v = make_double2(0.0, 0.0);
+    LdsStream<NPC, 1, double2> ts(lane);
+    auto chunk = [&](long long i0) {   // guarded: zero past the chunk and past either table
+        return [&, i0](const int idx, double2& v) {
+            v = make_double2(0.0, 0.0);
             if (idx < NPF) {
                 const long long gi = i0 * (FL::SIZE / 2) + idx;
                 if (gi < f_pieces) v = f2[gi];
@@ -1247,20 +1376,11 @@ __global__ void __launch_bounds__(64) k_forward0(Params p, const CstArg<CstLayou
                 const long long gi = (tw0 + i0) * (MT / 2) + (idx - NPF);
                 if (gi < m_pieces) v = m2[gi];
             }
-            tr[k] = v;
-        }
+        };
     };
-    auto stash = [&](int b) {
-#pragma unroll
-        for (int k = 0; k < PPL; ++k) {
-            const int idx = k * 64 + lane;
-            if (idx < NPC) tbuf[b][idx] = tr[k];
-        }
-    };
-    fetch(0);
-    stash(0);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    ts.fetch(chunk(0));
+    ts.stash(tbuf[0]);
+    ts.publish();
 
     double m[D], eta[D], q0 = 0.0;
 #pragma unroll
@@ -1271,7 +1391,7 @@ __global__ void __launch_bounds__(64) k_forward0(Params p, const CstArg<CstLayou
         if (u < len) load_y<DY>(p.y, t0 + u, p.n_chains, chain, yn[u]);
     int b = 0;
     for (long long i0 = 0; i0 < p.L; i0 += U, b ^= 1) {  // uniform trip count
-        if (i0 + U < p.L) fetch(i0 + U);
+        if (i0 + U < p.L) ts.fetch(chunk(i0 + U));
 #pragma unroll
         for (int u = 0; u < U; ++u) {
 #pragma unroll
@@ -1284,42 +1404,10 @@ __global__ void __launch_bounds__(64) k_forward0(Params p, const CstArg<CstLayou
             if (i < len) {
                 const double* tb = reinterpret_cast<const double*>(&tbuf[b][0]) + u * FL::SIZE;
                 const double* mt = reinterpret_cast<const double*>(&tbuf[b][NPF]) + u * MT;
-                double e[DY];
-#pragma unroll
-                for (int a = 0; a < DY; ++a) {
-                    double s = yb[u][a];
-#pragma unroll
-                    for (int k = 0; k < D; ++k) s -= c[CL::HF + a * D + k] * m[k];
-                    e[a] = s;
-                }
-                if (FE) {
-#pragma unroll
-                    for (int a = 0; a < DY; ++a) {
-                        double s = 0.0;
-#pragma unroll
-                        for (int k = 0; k < DY; ++k) s += tb[FL::SI + sidx(a, k)] * e[k];
-                        q0 += s * e[a];
-                    }
-                }
-                double mn[D];
-#pragma unroll
-                for (int a = 0; a < D; ++a) {
-                    double s = 0.0, uu = eta[a];
-#pragma unroll
-                    for (int k = 0; k < D; ++k) s += c[CL::A + a * D + k] * m[k];
-#pragma unroll
-                    for (int k = 0; k < DY; ++k) {
-                        s += tb[FL::K + a * DY + k] * e[k];
-                        uu += tb[FL::U + a * DY + k] * e[k];
-                    }
-                    mn[a] = s;
-                    eta[a] = uu;
-                }
-#pragma unroll
-                for (int a = 0; a < D; ++a) m[a] = mn[a];
-                // z_t = b_i + M_t η_i  (values, not pointers, select between LDS and memory: a pointer that may be either
-                // becomes a generic pointer, which this compiler cannot lower here)
-                double z[2 * MP2], mrow[D * D];
+                f0_step<D, DY, FE>(c, tb, yb[u], m, eta, q0);
+                // (values, not pointers, select between LDS and memory: a pointer that may be either becomes a generic pointer, which
+                // this compiler cannot lower here)
+                double mrow[D * D];
                 if (straddle) {
                     const double* gm = p.mtab + (t0 + i) * MT;
 #pragma unroll
@@ -1328,52 +1416,12 @@ __global__ void __launch_bounds__(64) k_forward0(Params p, const CstArg<CstLayou
 #pragma unroll
                     for (int k = 0; k < D * D; ++k) mrow[k] = mt[k];
                 }
-#pragma unroll
-                for (int a = 0; a < D; ++a) {
-                    double s = m[a];
-#pragma unroll
-                    for (int k = 0; k < D; ++k) s += mrow[a * D + k] * eta[k];
-                    z[a] = s;
-                }
-                if (D < 2 * MP2) z[2 * MP2 - 1] = 0.0;
-                const long long slot = t0 + i;
-                double2* base = reinterpret_cast<double2*>(p.filt) + ((slot * p.nb64 + (chain >> 6)) * MP2) * 64 + (chain & 63);
-#pragma unroll
-                for (int k = 0; k < MP2; ++k) base[k * 64] = make_double2(z[2 * k], z[2 * k + 1]);
+                f0_store_z<D>(p, t0 + i, chain, m, eta, mrow);
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (i0 + U < p.L) stash(b ^ 1);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        ts.flip(tbuf[b ^ 1], i0 + U < p.L);
     }
-    if (live) {
-        double* o = p.elem + (seg * 2 * D) * p.n_chains + chain;
-#pragma unroll
-        for (int a = 0; a < D; ++a) {
-            o[a * p.n_chains] = m[a];
-            o[(D + a) * p.n_chains] = eta[a];
-        }
-        if (FE) p.fe_part[(seg + 1) * p.n_chains + chain] = -0.5 * q0;
-    }
-}
-
-// What follows a stash into the table buffer the waves of a workgroup share (k_forward0_ck, k_backward_sh_rev).  W = 1: the buffer is the
-// wave's own, a wavefront fence orders the writes.  W > 1: ONE s_barrier, and the fences around it name the LDS only, so the wait in front of
-// the barrier is lgkmcnt(0) — a __syncthreads() or a fence over all address spaces would wait vmcnt(0) as well and drain the y loads and the
-// stores the wave keeps in flight across the chunk.  One barrier per chunk is enough for the double buffer: buffer b is rewritten at the end of
-// the NEXT chunk, and a wave gets there only through the barrier that every wave reached after its last read of b.
-template <int W>
-__device__ __forceinline__ void lds_publish() {
-    if constexpr (W == 1) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    } else {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-    }
+    if (live) f0_epilogue<D, FE>(p, seg, chain, m, eta, q0);
 }
 
 // k_forward0 on the reverse-filter schedule: the backward sweep rebuilds the filtered means by the reverse filter (k_backward_sh_rev), so z is
@@ -1382,25 +1430,14 @@ __device__ __forceinline__ void lds_publish() {
 // chunks run in a loop without per-step guards and the last len mod U steps behind it (as in k_backward_sh_rev); y and the table pieces past the
 // segment's end are loaded with the index clamped (value unused).  The M_t row is used at a checkpoint step only, so its part of the chunk is
 // fetched only for chunks that hold one.  A workgroup is W waves on W adjacent 64-chain groups of one segment (n_chains % (64·W) == 0) that
-// share ONE table stream: each 16-byte piece of a chunk is loaded by one of the 64·W lanes (lds_publish).  The step's arithmetic is k_forward0's.
-#ifndef RXHIP_F0_Y_RING
-#define RXHIP_F0_Y_RING 0   // 1: y in a per-step register ring of U slots (variant builds, as RXHIP_Y_RING_DEPTH below; measured slower, profiles/r14); 0: a whole chunk ahead, as in k_forward0
-#endif
+// share ONE table stream (LdsStream).
 template <int D, int DY, bool FE, int W>
 __global__ void __launch_bounds__(64 * W) k_forward0_ck(Params p, const CstArg<CstLayout<D, DY>::SIZE> cb) {
-    using CL = CstLayout<D, DY>;
     using FL = F0Layout<D, DY>;
+    using FS = F0Stage<D, DY>;
     constexpr int MT = TimeTab<D>::MT;
-    constexpr int MP2 = DimM<D>::MP2;
-    constexpr int U = 4;                    // steps per chunk
-    constexpr int NPF = U * FL::SIZE / 2;   // 16-byte pieces of the position table per chunk
-    constexpr int NPM = U * MT / 2;         // … of the time table
-    constexpr int NPC = NPF + NPM;
-    constexpr int TPB = 64 * W;             // lanes that share the table stream
-    constexpr int PPL = (NPC + TPB - 1) / TPB;
-    constexpr bool YR = RXHIP_F0_Y_RING != 0;
+    constexpr int U = FS::U, NPF = FS::NPF, NPC = FS::NPC;
     __shared__ double2 tbuf[2][NPC];
-    const int tid = threadIdx.x;
     const int wv = W > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
     const int lane = W > 1 ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
     const long long g0 = ((long long)blockIdx.x * W + wv) * 64;
@@ -1420,35 +1457,25 @@ __global__ void __launch_bounds__(64 * W) k_forward0_ck(Params p, const CstArg<C
 #pragma unroll
     for (int i = 0; i < D; ++i) m[i] = eta[i] = 0.0;
     if (len > 0) {   // (uniform across the workgroup: the barriers below are taken by all of its waves or by none)
-        rx_d2v tr[PPL];
-#pragma unroll
-        for (int k = 0; k < PPL; ++k) tr[k] = rx_d2v{0.0, 0.0};
+        LdsStream<NPC, W> ts(threadIdx.x);
+        ts.fetch([](const int, rx_d2v& v) { v = rx_d2v{0.0, 0.0}; });   // (the M_t pieces of a chunk without a checkpoint are never fetched)
         // chunk i0: a step i ∈ [i0, i0 + U) with (i + 1) a multiple of K, or the segment's last step
         auto has_ck = [&](long long i0) { return ((i0 + U) >> lg) != (i0 >> lg) || (i0 < len && len <= i0 + U); };
-        auto fetch = [&](long long i0) {
-            const bool ck = has_ck(i0);
-#pragma unroll
-            for (int k = 0; k < PPL; ++k) {
-                const int idx = k * TPB + tid < NPC ? k * TPB + tid : NPC - 1;
+        auto chunk = [&](long long i0) {   // clamped: past the chunk its last piece, past either table its last piece
+            return [&, i0, ck = has_ck(i0)](int idx, rx_d2v& v) {
+                idx = idx < NPC ? idx : NPC - 1;
                 if (idx < NPF) {
                     const long long gi = i0 * (FL::SIZE / 2) + idx;
-                    tr[k] = f2[gi < f_last ? gi : f_last];
+                    v = f2[gi < f_last ? gi : f_last];
                 } else if (ck) {
                     const long long gi = (t0 + i0) * (MT / 2) + (idx - NPF);
-                    tr[k] = m2[gi < m_last ? gi : m_last];
+                    v = m2[gi < m_last ? gi : m_last];
                 }
-            }
+            };
         };
-        auto stash = [&](int b) {
-#pragma unroll
-            for (int k = 0; k < PPL; ++k) {
-                const int idx = k * TPB + tid;
-                if ((k + 1) * TPB <= NPC || idx < NPC) tbuf[b][idx] = make_double2(tr[k].x, tr[k].y);
-            }
-        };
-        fetch(0);
-        stash(0);
-        lds_publish<W>();
+        ts.fetch(chunk(0));
+        ts.stash(tbuf[0]);
+        ts.publish();
 
         double yb[U][DY], yn[U][DY];
         auto y_index = [&](long long i) { return t0 + (i < len ? i : len - 1); };
@@ -1457,96 +1484,33 @@ __global__ void __launch_bounds__(64 * W) k_forward0_ck(Params p, const CstArg<C
         auto step = [&](const int u, const long long i, const int b) __attribute__((always_inline)) {
             const double* tb = reinterpret_cast<const double*>(&tbuf[b][0]) + u * FL::SIZE;
             const double* mt = reinterpret_cast<const double*>(&tbuf[b][NPF]) + u * MT;
-            double e[DY];
-#pragma unroll
-            for (int a = 0; a < DY; ++a) {
-                double s = YR ? yn[u][a] : yb[u][a];
-#pragma unroll
-                for (int k = 0; k < D; ++k) s -= c[CL::HF + a * D + k] * m[k];
-                e[a] = s;
-            }
-            if constexpr (YR) {   // the slot's refill, behind the last use of its value (as in k_backward_sh_rev)
-                __builtin_amdgcn_sched_barrier(0);
-                load_y<DY>(p.y, y_index(i + U), p.n_chains, chain, yn[u]);
-            }
-            if (FE) {
-#pragma unroll
-                for (int a = 0; a < DY; ++a) {
-                    double s = 0.0;
-#pragma unroll
-                    for (int k = 0; k < DY; ++k) s += tb[FL::SI + sidx(a, k)] * e[k];
-                    q0 += s * e[a];
-                }
-            }
-            double mn[D];
-#pragma unroll
-            for (int a = 0; a < D; ++a) {
-                double s = 0.0, uu = eta[a];
-#pragma unroll
-                for (int k = 0; k < D; ++k) s += c[CL::A + a * D + k] * m[k];
-#pragma unroll
-                for (int k = 0; k < DY; ++k) {
-                    s += tb[FL::K + a * DY + k] * e[k];
-                    uu += tb[FL::U + a * DY + k] * e[k];
-                }
-                mn[a] = s;
-                eta[a] = uu;
-            }
-#pragma unroll
-            for (int a = 0; a < D; ++a) m[a] = mn[a];
+            f0_step<D, DY, FE>(c, tb, yb[u], m, eta, q0);
             if (((i + 1) & kmask) != 0 && i + 1 != len) return;   // not a checkpoint (uniform)
-            double z[2 * MP2];   // z_t = b_i + M_t η_i
-#pragma unroll
-            for (int a = 0; a < D; ++a) {
-                double s = m[a];
-#pragma unroll
-                for (int k = 0; k < D; ++k) s += mt[a * D + k] * eta[k];
-                z[a] = s;
-            }
-            if (D < 2 * MP2) z[2 * MP2 - 1] = 0.0;
-            const long long slot = 1 + seg * p.nck + (i >> lg);
-            double2* base = reinterpret_cast<double2*>(p.filt) + ((slot * p.nb64 + (chain >> 6)) * MP2) * 64 + (chain & 63);
-#pragma unroll
-            for (int k = 0; k < MP2; ++k) base[k * 64] = make_double2(z[2 * k], z[2 * k + 1]);
+            f0_store_z<D>(p, 1 + seg * p.nck + (i >> lg), chain, m, eta, mt);
         };
-        auto next_y = [&](long long i0) {
-            if constexpr (YR) return;
+        int b = 0;
+        long long i0 = 0;
+        for (; i0 + U <= len; i0 += U, b ^= 1) {   // whole chunks
+            ts.fetch(chunk(i0 + U));
 #pragma unroll
             for (int u = 0; u < U; ++u) {
 #pragma unroll
                 for (int k = 0; k < DY; ++k) yb[u][k] = yn[u][k];
                 load_y<DY>(p.y, y_index(i0 + U + u), p.n_chains, chain, yn[u]);
             }
-        };
-        int b = 0;
-        long long i0 = 0;
-        for (; i0 + U <= len; i0 += U, b ^= 1) {   // whole chunks
-            fetch(i0 + U);
-            next_y(i0);
 #pragma unroll
             for (int u = 0; u < U; ++u) step(u, i0 + u, b);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            stash(b ^ 1);
-            lds_publish<W>();   // W > 1: the chunk's one workgroup barrier
+            ts.flip(tbuf[b ^ 1]);   // W > 1: the chunk's one workgroup barrier
         }
-        if constexpr (!YR) {
 #pragma unroll
-            for (int u = 0; u < U; ++u)
+        for (int u = 0; u < U; ++u)
 #pragma unroll
-                for (int k = 0; k < DY; ++k) yb[u][k] = yn[u][k];
-        }
+            for (int k = 0; k < DY; ++k) yb[u][k] = yn[u][k];
 #pragma unroll
         for (int u = 0; u < U - 1; ++u)   // the last len mod U steps
             if (i0 + u < len) step(u, i0 + u, b);
     }
-    double* o = p.elem + (seg * 2 * D) * p.n_chains + chain;
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-        o[a * p.n_chains] = m[a];
-        o[(D + a) * p.n_chains] = eta[a];
-    }
-    if (FE) p.fe_part[(seg + 1) * p.n_chains + chain] = -0.5 * q0;
+    f0_epilogue<D, FE>(p, seg, chain, m, eta, q0);
 }
 
 // Data-independent per-time-index tables of the one-pass schedule, once per engine: one lane per time index.
@@ -3467,6 +3431,63 @@ __global__ void __launch_bounds__(64) k_smooth_tab_apply(SmoothTabParams q) {
     }
 }
 
+// What the two table-driven sweeps (k_backward_sh, k_backward_sh_rev) share: the start of a segment's sweep and the store of a time index.
+// m_f(t) = z_t + N_t m_seg  (r: the record of z_t)
+template <int D>
+__device__ __forceinline__ void sweep_filt_mean(const double2 (&r)[DimM<D>::MP2], const double* N, const double (&mseg)[D], double (&mf)[D]) {
+    unpack_m_sh<D>(r, mf);
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        double s = mf[i];
+#pragma unroll
+        for (int k = 0; k < D; ++k) s += N[i * D + k] * mseg[k];
+        mf[i] = s;
+    }
+}
+// m_s(te) = H1 m_f(te) + H2 ξβ  (SegEndTab row of the segment)
+template <int D>
+__device__ __forceinline__ void sweep_segment_end(const double* segend, const long long seg, const double (&mf)[D], const double (&xb)[D], double (&ms)[D]) {
+    const double* se = segend + seg * SegEndTab<D>::SIZE;
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < D; ++k) s += se[SegEndTab<D>::H1 + i * D + k] * mf[k] + se[SegEndTab<D>::H2 + i * D + k] * xb[k];
+        ms[i] = s;
+    }
+}
+// One time index of output from a wave: means through its LDS tile, covariances straight from table row `vs`.  write_cov == 0: the means only —
+// the per-chain covariance array already holds this engine's table broadcast (rxhip_engine_life::cov_current), and the stores would rewrite
+// the same bits: 8·D² of the sweep's bytes per (chain, step).  (Whole groups of 64 pieces are stored without a lane predicate: a predicate the
+// compiler cannot fold is a branch around the store, and the wait pass then counts the path without it.)
+template <int D>
+__device__ __forceinline__ void sweep_write_out(const Params& p, double (&mtile)[64 * D], const int lane, const long long chain0, const double (&ms)[D],
+                                                const long long t, const double* vs, const int write_cov) {
+    constexpr int NMP = 32 * D;              // 16-byte pieces of the 64 means of a time index
+    constexpr int NCP = 32 * D * D;          // … of the 64 covariances
+#pragma unroll
+    for (int i = 0; i < D; ++i) mtile[lane * D + i] = ms[i];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    double2* om = reinterpret_cast<double2*>(p.mean + (t * p.n_chains + chain0) * D);
+    double2* oc = reinterpret_cast<double2*>(p.cov + (t * p.n_chains + chain0) * D * D);
+#pragma unroll
+    for (int k = 0; k < (NMP + 63) / 64; ++k) {
+        const int q = k * 64 + lane;
+        if ((k + 1) * 64 <= NMP || q < NMP) stream_store(om + q, mtile[2 * q], mtile[2 * q + 1]);
+    }
+    if (write_cov) {   // (a kernel argument: one scalar branch per time index)
+#pragma unroll
+        for (int k = 0; k < (NCP + 63) / 64; ++k) {
+            const int q = k * 64 + lane;
+            if ((k + 1) * 64 <= NCP || q < NCP) stream_store(oc + q, vs[(2 * q) % (D * D)], vs[(2 * q + 1) % (D * D)]);
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
 template <int D>
 __global__ void __launch_bounds__(64) k_backward_sh(Params p, const double* __restrict__ gtab, const double* __restrict__ segend, const int write_cov) {
     using ST = SmoothTab<D>;
@@ -3475,9 +3496,6 @@ __global__ void __launch_bounds__(64) k_backward_sh(Params p, const double* __re
     constexpr int U = 4;                     // steps per table chunk
     constexpr int RP = ST::SIZE / 2;         // 16-byte pieces per row
     constexpr int NPC = U * RP;
-    constexpr int PPL = (NPC + 63) / 64;
-    constexpr int NMP = 32 * D;              // 16-byte pieces of the 64 means of a time index
-    constexpr int NCP = 32 * D * D;          // … of the 64 covariances
     __shared__ double2 tbuf[2][NPC];
     __shared__ double mtile[64 * D];
     const int lane = threadIdx.x;
@@ -3490,94 +3508,46 @@ __global__ void __launch_bounds__(64) k_backward_sh(Params p, const double* __re
 
     double mseg[D], ms[D];
     {
-        const double* q = p.fstart + (seg * Dim<D>::NP) * p.n_chains + chain;
-        const double* bq = p.beta + ((seg + 1) * Dim<D>::NP) * p.n_chains + chain;
         double mf[D], xb[D];
+        {   // m_seg and ξβ as the boundary scan left them
+            const double* q = p.fstart + (seg * Dim<D>::NP) * p.n_chains + chain;
+            const double* bq = p.beta + ((seg + 1) * Dim<D>::NP) * p.n_chains + chain;
 #pragma unroll
-        for (int i = 0; i < D; ++i) {
-            mseg[i] = q[i * p.n_chains];
-            xb[i] = bq[i * p.n_chains];
+            for (int i = 0; i < D; ++i) {
+                mseg[i] = q[i * p.n_chains];
+                xb[i] = bq[i * p.n_chains];
+            }
         }
         if (len > 0) {
             double2 r[MP2];
             load_filt_m_sh<D>(p, te, chain, r);
-            unpack_m_sh<D>(r, mf);
-            const double* N = p.ntab + te * MT;
-#pragma unroll
-            for (int i = 0; i < D; ++i) {
-                double s = mf[i];
-#pragma unroll
-                for (int k = 0; k < D; ++k) s += N[i * D + k] * mseg[k];
-                mf[i] = s;
-            }
+            sweep_filt_mean<D>(r, p.ntab + te * MT, mseg, mf);
         } else {
 #pragma unroll
             for (int i = 0; i < D; ++i) mf[i] = mseg[i];
         }
-        const double* se = segend + seg * SegEndTab<D>::SIZE;
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-            double s = 0.0;
-#pragma unroll
-            for (int k = 0; k < D; ++k) s += se[SegEndTab<D>::H1 + i * D + k] * mf[k] + se[SegEndTab<D>::H2 + i * D + k] * xb[k];
-            ms[i] = s;
-        }
+        sweep_segment_end<D>(segend, seg, mf, xb, ms);
     }
-    // one time index of output: means through the LDS tile, covariances straight from table row `vs`.  write_cov == 0: the means only — the
-    // per-chain covariance array already holds this engine's table broadcast (rxhip_engine_life::cov_current), and the stores would rewrite
-    // the same bits: 8·D² of the sweep's bytes per (chain, step)
-    auto write_out = [&](long long t, const double* vs) {
-#pragma unroll
-        for (int i = 0; i < D; ++i) mtile[lane * D + i] = ms[i];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        double2* om = reinterpret_cast<double2*>(p.mean + (t * p.n_chains + chain0) * D);
-        double2* oc = reinterpret_cast<double2*>(p.cov + (t * p.n_chains + chain0) * D * D);
-#pragma unroll
-        for (int k = 0; k < (NMP + 63) / 64; ++k) {
-            const int q = k * 64 + lane;
-            if (q < NMP) stream_store(om + q, mtile[2 * q], mtile[2 * q + 1]);
-        }
-        if (write_cov) {   // (a kernel argument: one scalar branch per time index)
-#pragma unroll
-            for (int k = 0; k < (NCP + 63) / 64; ++k) {
-                const int q = k * 64 + lane;
-                if (q < NCP) stream_store(oc + q, vs[(2 * q) % (D * D)], vs[(2 * q + 1) % (D * D)]);
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    };
+    auto write_out = [&](long long t, const double* vs) { sweep_write_out<D>(p, mtile, lane, chain0, ms, t, vs, write_cov); };
     if (seg == p.S - 1) write_out(te, gtab + te * ST::SIZE + ST::VS);
 
     // table rows te−1, te−2, … stream through LDS one chunk ahead (the gains are the same for every lane of the wave)
     const double2* g2 = reinterpret_cast<const double2*>(gtab);
-    double2 tr[PPL];
-    auto fetch = [&](long long i0) {
-#pragma unroll
-        for (int k = 0; k < PPL; ++k) {
-            const int idx = k * 64 + lane;
+    LdsStream<NPC, 1, double2> ts(lane);
+    auto chunk = [&](long long i0) {   // guarded: zero past the chunk and past the segment's first row
+        return [&, i0](const int idx, double2& v) {
             const long long r = i0 + idx / RP;  // step index
-            tr[k] = (idx < NPC && r < len) ? g2[(te - 1 - r) * RP + idx % RP] : make_double2(0.0, 0.0);
-        }
+            v = (idx < NPC && r < len) ? g2[(te - 1 - r) * RP + idx % RP] : make_double2(0.0, 0.0);
+        };
     };
-    auto stash = [&](int b) {
-#pragma unroll
-        for (int k = 0; k < PPL; ++k) {
-            const int idx = k * 64 + lane;
-            if (idx < NPC) tbuf[b][idx] = tr[k];
-        }
-    };
-    fetch(0);
-    stash(0);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    ts.fetch(chunk(0));
+    ts.stash(tbuf[0]);
+    ts.publish();
     double2 rn[MP2];
     if (len > 0) load_filt_m_sh<D>(p, te - 1, chain, rn);
     int b = 0;
     for (long long i0 = 0; i0 < len; i0 += U, b ^= 1) {  // `len` is uniform across the wave
-        if (i0 + U < len) fetch(i0 + U);
+        if (i0 + U < len) ts.fetch(chunk(i0 + U));
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const long long i = i0 + u;
@@ -3607,11 +3577,7 @@ __global__ void __launch_bounds__(64) k_backward_sh(Params p, const double* __re
                 write_out(t, row + ST::VS);
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (i0 + U < len) stash(b ^ 1);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        ts.flip(tbuf[b ^ 1], i0 + U < len);
     }
 }
 
@@ -3629,7 +3595,6 @@ template <int D>
 struct BndStage {
     static constexpr int ROW = 2 * D * D;            // M1, M2 (prefix) or N1, N2 (suffix) of one segment
     static constexpr int N = BND_CHUNK * ROW;        // doubles per LDS buffer
-    static constexpr int PPL = (N + 63) / 64;        // … per lane
 };
 // `count` steps from segment `first` (upwards: prefix, downwards: suffix), all wave-uniform; v: the recursion's vector
 template <int D, bool SUF>
@@ -3654,32 +3619,22 @@ __device__ __forceinline__ void boundary_chain(const Params& p, const long long 
 #pragma unroll
         for (int i = 0; i < 2 * D; ++i) e[i] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(lane * 8u), (int)(i * rowb), 0));
     };
-    double tr[BS::PPL];
-    auto fetch = [&](int q0) {
-#pragma unroll
-        for (int k = 0; k < BS::PPL; ++k) {
-            const int idx = k * 64 + (int)lane;
+    LdsStream<BS::N, 1, double> ts((int)lane);   // pieces of one double
+    auto chunk = [&](int q0) {
+        return [&, q0](const int idx, double& v) {
             const int q = q0 + idx / BS::ROW;
-            tr[k] = (idx < BS::N && q < count) ? p.scan[(long long)seg_of(q) * SL::SIZE + OFF + idx % BS::ROW] : 0.0;
-        }
-    };
-    auto stash = [&](int b) {
-#pragma unroll
-        for (int k = 0; k < BS::PPL; ++k) {
-            const int idx = k * 64 + (int)lane;
-            if (idx < BS::N) lds[b][idx] = tr[k];
-        }
+            v = (idx < BS::N && q < count) ? p.scan[(long long)seg_of(q) * SL::SIZE + OFF + idx % BS::ROW] : 0.0;
+        };
     };
 #pragma unroll
     for (int j = 0; j < BND_RING; ++j)
         if (j < count) load_el(j, eb[j]);
-    fetch(0);
-    stash(0);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    ts.fetch(chunk(0));
+    ts.stash(lds[0]);
+    ts.publish();
     int b = 0;
     for (int q0 = 0; q0 < count; q0 += BND_CHUNK, b ^= 1) {
-        if (q0 + BND_CHUNK < count) fetch(q0 + BND_CHUNK);
+        if (q0 + BND_CHUNK < count) ts.fetch(chunk(q0 + BND_CHUNK));
 #pragma unroll
         for (int u = 0; u < BND_CHUNK; ++u) {
             const int q = q0 + u;
@@ -3697,11 +3652,7 @@ __device__ __forceinline__ void boundary_chain(const Params& p, const long long 
                 else scan_prefix_step<D>(t, t + D * D, bb, eta, v);
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (q0 + BND_CHUNK < count) stash(b ^ 1);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        ts.flip(lds[b ^ 1], q0 + BND_CHUNK < count);
     }
 }
 // What k_boundary_scan_tab leaves for segment `seg` and the wave's 64 chains, computed and stored by the wave itself: fstart[seg] and
@@ -3786,10 +3737,6 @@ __global__ void __launch_bounds__(64 * W) k_backward_sh_rev(Params p, const doub
     constexpr int U = 4;                     // steps per table chunk
     constexpr int RP = ST::SIZE / 2;         // 16-byte pieces per row
     constexpr int NPC = U * RP;
-    constexpr int TPB = 64 * W;              // lanes that share the table stream
-    constexpr int PPL = (NPC + TPB - 1) / TPB;
-    constexpr int NMP = 32 * D;              // 16-byte pieces of the 64 means of a time index
-    constexpr int NCP = 32 * D * D;          // … of the 64 covariances
     static_assert(U % R == 0, "ring slots must be compile-time");
     static_assert(MT <= 64, "one lane per element of an N row");
     static_assert(D * D <= 64, "one lane per element of A⁻¹");
@@ -3815,23 +3762,11 @@ __global__ void __launch_bounds__(64 * W) k_backward_sh_rev(Params p, const doub
     const long long K = 1LL << lg;
     // the checkpoint of time index t ∈ (tb, te]: slot 1 + seg·nck + (t − tb − 1)/K
     auto load_ck = [&](long long t, double2 (&r)[MP2]) { load_filt_m_sh<D>(p, 1 + seg * p.nck + ((t - tb - 1) >> lg), chain, r); };
-    double mseg[D];
-    auto ck_mean = [&](const double2 (&r)[MP2], const double* N, double (&mf)[D]) {   // m_f(t) = z_t + N_t m_seg
-        unpack_m_sh<D>(r, mf);
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-            double s = mf[i];
-#pragma unroll
-            for (int k = 0; k < D; ++k) s += N[i * D + k] * mseg[k];
-            mf[i] = s;
-        }
-    };
-
-    double mf[D], ms[D];
+    double mseg[D], mf[D], ms[D];
     {
         double xb[D];
         if (bnd) boundary_in_sweep<D, DY>(p, c, seg, chain, lane, bnd == 2, bndbuf, mseg, xb);
-        else {
+        else {   // as a boundary-scan launch left them (written out in both sweeps: as a shared function it costs k_backward_sh_rev six VGPRs, profiles/r15)
             const double* q = p.fstart + (seg * Dim<D>::NP) * p.n_chains + chain;
             const double* bq = p.beta + ((seg + 1) * Dim<D>::NP) * p.n_chains + chain;
 #pragma unroll
@@ -3843,69 +3778,30 @@ __global__ void __launch_bounds__(64 * W) k_backward_sh_rev(Params p, const doub
         if (len > 0) {
             double2 r[MP2];
             load_ck(te, r);
-            ck_mean(r, p.ntab + te * MT, mf);
+            sweep_filt_mean<D>(r, p.ntab + te * MT, mseg, mf);
         } else {
 #pragma unroll
             for (int i = 0; i < D; ++i) mf[i] = mseg[i];
         }
-        const double* se = segend + seg * SegEndTab<D>::SIZE;
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-            double s = 0.0;
-#pragma unroll
-            for (int k = 0; k < D; ++k) s += se[SegEndTab<D>::H1 + i * D + k] * mf[k] + se[SegEndTab<D>::H2 + i * D + k] * xb[k];
-            ms[i] = s;
-        }
+        sweep_segment_end<D>(segend, seg, mf, xb, ms);
     }
-    // (whole groups of 64 pieces are stored without a lane predicate: a predicate the compiler cannot fold is a branch around the store, and the
-    // wait pass then counts the path without it)
-    auto write_out = [&](long long t, const double* vs) {
-#pragma unroll
-        for (int i = 0; i < D; ++i) mtile[lane * D + i] = ms[i];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        double2* om = reinterpret_cast<double2*>(p.mean + (t * p.n_chains + chain0) * D);
-        double2* oc = reinterpret_cast<double2*>(p.cov + (t * p.n_chains + chain0) * D * D);
-#pragma unroll
-        for (int k = 0; k < (NMP + 63) / 64; ++k) {
-            const int q = k * 64 + lane;
-            if ((k + 1) * 64 <= NMP || q < NMP) stream_store(om + q, mtile[2 * q], mtile[2 * q + 1]);
-        }
-        if (write_cov) {   // (a kernel argument: one scalar branch per time index)
-#pragma unroll
-            for (int k = 0; k < (NCP + 63) / 64; ++k) {
-                const int q = k * 64 + lane;
-                if ((k + 1) * 64 <= NCP || q < NCP) stream_store(oc + q, vs[(2 * q) % (D * D)], vs[(2 * q + 1) % (D * D)]);
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    };
+    auto write_out = [&](long long t, const double* vs) { sweep_write_out<D>(p, mtile, lane, chain0, ms, t, vs, write_cov); };
     if (seg == p.S - 1) write_out(te, gtab + te * ST::SIZE + ST::VS);
     if (len <= 0) return;   // (uniform across the wave)
 
     const rx_d2v* g2 = reinterpret_cast<const rx_d2v*>(gtab);
-    rx_d2v tr[PPL];   // (a first-class vector: as double2 the unconditional copy is a memcpy into a stack slot)
-    auto fetch = [&](long long i0) {   // the rows of steps i0 … i0 + U − 1, past the segment's last step its row again (never used)
-#pragma unroll
-        for (int k = 0; k < PPL; ++k) {
-            const int idx = k * TPB + tid < NPC ? k * TPB + tid : NPC - 1;
+    LdsStream<NPC, W> ts(tid);
+    auto chunk = [&](long long i0) {   // the rows of steps i0 … i0 + U − 1; clamped: past the segment's last step its row again (never used)
+        return [&, i0](int idx, rx_d2v& v) {
+            idx = idx < NPC ? idx : NPC - 1;
             const long long r = i0 + idx / RP;  // step index
-            tr[k] = g2[(te - 1 - (r < len ? r : len - 1)) * RP + idx % RP];
-        }
+            v = g2[(te - 1 - (r < len ? r : len - 1)) * RP + idx % RP];
+        };
     };
-    auto stash = [&](int b) {
-#pragma unroll
-        for (int k = 0; k < PPL; ++k) {
-            const int idx = k * TPB + tid;
-            if ((k + 1) * TPB <= NPC || idx < NPC) tbuf[b][idx] = make_double2(tr[k].x, tr[k].y);
-        }
-    };
-    fetch(0);
+    ts.fetch(chunk(0));
     if (tid < D * D) ainv[tid] = p.ainv[tid];
-    stash(0);
-    lds_publish<W>();
+    ts.stash(tbuf[0]);
+    ts.publish();
     // the next checkpoint below te (a multiple of K past tb; none when it would be tb itself), prefetched a whole window ahead with the one
     // element of its N row that this lane carries.  Past the last checkpoint the load goes on, to the segment's first one: same operations
     // on every path, value unused.
@@ -3936,7 +3832,7 @@ __global__ void __launch_bounds__(64 * W) k_backward_sh_rev(Params p, const doub
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            ck_mean(rc, nrow, mfn);
+            sweep_filt_mean<D>(rc, nrow, mseg, mfn);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_sched_barrier(0);   // (as for the y slot below: the next record goes into the registers this one has left)
@@ -3993,13 +3889,10 @@ __global__ void __launch_bounds__(64 * W) k_backward_sh_rev(Params p, const doub
     int b = 0;
     long long i0 = 0;
     for (; i0 + U <= len; i0 += U, b ^= 1) {  // whole chunks (`len` is uniform across the wave)
-        fetch(i0 + U);
+        ts.fetch(chunk(i0 + U));
 #pragma unroll
         for (int u = 0; u < U; ++u) step(u, i0 + u, b);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        stash(b ^ 1);
-        lds_publish<W>();   // W > 1: the chunk's one workgroup barrier, on a path every wave of the block takes (`len` is the segment's)
+        ts.flip(tbuf[b ^ 1]);   // W > 1: the chunk's one workgroup barrier, on a path every wave of the block takes (`len` is the segment's)
     }
 #pragma unroll
     for (int u = 0; u < U - 1; ++u)   // the last len mod U steps

@@ -2966,8 +2966,15 @@ static rxhip_status run_lanes(rxhip_engine* e, const RunPlan& pl, const Params& 
             e->vt->fe_seg(p, e->stream);
         if (!pl.filter) {
             if ((st = prof_begin(e, RXHIP_K_BACKWARD))) return st;
-            if (pl.backward_sh) e->vt->backward_sh(p, e->h_cst0.data(), e->d_gtab, e->d_segend, e->ck_log2 > 0, bnd_in_sweep ? (fe ? 2 : 1) : 0, write_cov, e->hooks.y_ring == 1 ? 1 : Y_RING_SHIPPED, e->sweep_waves_bwd, e->stream);
-            else e->vt->backward(p, e->h_cst0.data(), e->uniform, e->stream);
+            if (pl.backward_sh) {
+                SweepArgs a;
+                a.rev = e->ck_log2 > 0;
+                a.bnd = bnd_in_sweep ? (fe ? 2 : 1) : 0;
+                a.write_cov = write_cov;
+                a.y_ring = e->hooks.y_ring == 1 ? 1 : Y_RING_SHIPPED;
+                a.waves = e->sweep_waves_bwd;
+                e->vt->backward_sh(p, e->h_cst0.data(), e->d_gtab, e->d_segend, a, e->stream);
+            } else e->vt->backward(p, e->h_cst0.data(), e->uniform, e->stream);
             if ((st = prof_end(e))) return st;
         }
         if (fe && bnd_in_sweep) e->vt->fe_seg(p, e->stream);

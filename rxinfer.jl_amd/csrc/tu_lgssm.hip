@@ -2,6 +2,7 @@
 // Compiled once per state dimension: -DRXHIP_TU_D=1…4; each object carries its own gfx950 code object, loaded by the HIP runtime when an
 // engine of that dimension launches its first kernel.
 #include <cstring>
+#include <type_traits>
 
 #define RXHIP_LAUNCH_LGSSM_ONLY
 #include "launch_tables.hpp"
@@ -12,6 +13,19 @@
 
 namespace rxhip {
 namespace {
+
+// a runtime bool, or a sweep width in {1, 2, 4}, as a template argument: `f` is a generic lambda that receives it as a std::integral_constant
+template <class F>
+void pick(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <class F>
+void pick_waves(int w, F&& f) {
+    if (w == 4) f(std::integral_constant<int, 4>{});
+    else if (w == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 1>{});
+}
 
 template <int D, int DY>
 struct Launch {
@@ -35,40 +49,29 @@ struct Launch {
     }
     static void boundary_scan(const Params& p, const double* hc, bool uni, bool fe, hipStream_t s) {
         dim3 grid(nblk(p.n_chains, 64), p.filter ? 1 : 2);  // a filtering run needs the prefix role only
-        if (uni) {
-            if (fe) hipLaunchKernelGGL((k_boundary_scan<D, DY, true, true>), grid, dim3(64), 0, s, p, carg(hc));
-            else hipLaunchKernelGGL((k_boundary_scan<D, DY, true, false>), grid, dim3(64), 0, s, p, carg(hc));
-        } else if (!p.masked && !p.step_model && !p.elem_full) {   // time-invariant per-chain models
-            if (fe) hipLaunchKernelGGL((k_boundary_scan<D, DY, false, true, true>), grid, dim3(64), 0, s, p, CstArg<1>{});
-            else hipLaunchKernelGGL((k_boundary_scan<D, DY, false, false, true>), grid, dim3(64), 0, s, p, CstArg<1>{});
-        } else {
-            if (fe) hipLaunchKernelGGL((k_boundary_scan<D, DY, false, true>), grid, dim3(64), 0, s, p, CstArg<1>{});
-            else hipLaunchKernelGGL((k_boundary_scan<D, DY, false, false>), grid, dim3(64), 0, s, p, CstArg<1>{});
-        }
+        pick(fe, [&](auto FE) {
+            if (uni) hipLaunchKernelGGL((k_boundary_scan<D, DY, true, FE()>), grid, dim3(64), 0, s, p, carg(hc));
+            else if (!p.masked && !p.step_model && !p.elem_full)   // time-invariant per-chain models
+                hipLaunchKernelGGL((k_boundary_scan<D, DY, false, FE(), true>), grid, dim3(64), 0, s, p, CstArg<1>{});
+            else hipLaunchKernelGGL((k_boundary_scan<D, DY, false, FE()>), grid, dim3(64), 0, s, p, CstArg<1>{});
+        });
     }
     static void boundary_scan_tab(const Params& p, const double* hc, bool fe, hipStream_t s) {
         dim3 grid(nblk(p.n_chains, 64), p.filter ? 1 : 2);
-        if (fe) hipLaunchKernelGGL((k_boundary_scan_tab<D, DY, true>), grid, dim3(64), 0, s, p, carg(hc));
-        else hipLaunchKernelGGL((k_boundary_scan_tab<D, DY, false>), grid, dim3(64), 0, s, p, carg(hc));
+        pick(fe, [&](auto FE) { hipLaunchKernelGGL((k_boundary_scan_tab<D, DY, FE()>), grid, dim3(64), 0, s, p, carg(hc)); });
     }
     template <bool FILT>
     static void forward_t(const Params& p, const double* hc, bool uni, bool fe, hipStream_t s) {
         const long long total = p.n_chains * (long long)p.S;
         dim3 grid(nblk(total, 64));
-        if (uni) {
-            if (fe) hipLaunchKernelGGL((k_forward<D, DY, true, true, FILT>), grid, dim3(64), 0, s, p, carg(hc));
-            else hipLaunchKernelGGL((k_forward<D, DY, true, false, FILT>), grid, dim3(64), 0, s, p, carg(hc));
-        } else if (!FILT && p.tinv_records) {
-            if (fe) hipLaunchKernelGGL((k_forward_tinv<D, DY, true>), grid, dim3(64), 0, s, p);
-            else hipLaunchKernelGGL((k_forward_tinv<D, DY, false>), grid, dim3(64), 0, s, p);
-        } else {
-            if (fe) hipLaunchKernelGGL((k_forward<D, DY, false, true, FILT>), grid, dim3(64), 0, s, p, CstArg<1>{});
-            else hipLaunchKernelGGL((k_forward<D, DY, false, false, FILT>), grid, dim3(64), 0, s, p, CstArg<1>{});
-        }
+        pick(fe, [&](auto FE) {
+            if (uni) hipLaunchKernelGGL((k_forward<D, DY, true, FE(), FILT>), grid, dim3(64), 0, s, p, carg(hc));
+            else if (!FILT && p.tinv_records) hipLaunchKernelGGL((k_forward_tinv<D, DY, FE()>), grid, dim3(64), 0, s, p);
+            else hipLaunchKernelGGL((k_forward<D, DY, false, FE(), FILT>), grid, dim3(64), 0, s, p, CstArg<1>{});
+        });
     }
     static void forward(const Params& p, const double* hc, bool uni, bool fe, hipStream_t s) {
-        if (p.filter) forward_t<true>(p, hc, uni, fe, s);
-        else forward_t<false>(p, hc, uni, fe, s);
+        pick(p.filter != 0, [&](auto FILT) { forward_t<FILT()>(p, hc, uni, fe, s); });
     }
     static void backward(const Params& p, const double* hc, bool uni, hipStream_t s) {
         const long long total = p.n_chains * (long long)p.S;
@@ -80,21 +83,16 @@ struct Launch {
         else if (p.tinv_records) hipLaunchKernelGGL((k_backward_tinv<D, DY>), grid, dim3(64), 0, s, p);
         else hipLaunchKernelGGL((k_backward<D, DY, false>), grid, dim3(64), 0, s, p, CstArg<1>{});
     }
-    template <int W>
-    static void forward0_ck(const Params& p, const double* hc, bool fe, hipStream_t s) {   // n_chains % (64·W) == 0 (plan::sweep_waves)
-        const dim3 grid((unsigned)(p.n_chains / (64 * W) * p.S));
-        if (fe) hipLaunchKernelGGL((k_forward0_ck<D, DY, true, W>), grid, dim3(64 * W), 0, s, p, carg(hc));
-        else hipLaunchKernelGGL((k_forward0_ck<D, DY, false, W>), grid, dim3(64 * W), 0, s, p, carg(hc));
-    }
-    // ck: z at checkpoints only (the reverse-filter schedule), in workgroups of `waves` waves
+    // ck: z at checkpoints only (the reverse-filter schedule), in workgroups of `waves` waves with n_chains % (64·waves) == 0 (plan::sweep_waves)
     static void forward0(const Params& p, const double* hc, bool fe, bool ck, int waves, hipStream_t s) {
         const long long total = p.n_chains * (long long)p.S;
-        if (ck) {
-            if (waves == 4) forward0_ck<4>(p, hc, fe, s);
-            else if (waves == 2) forward0_ck<2>(p, hc, fe, s);
-            else forward0_ck<1>(p, hc, fe, s);
-        } else if (fe) hipLaunchKernelGGL((k_forward0<D, DY, true>), dim3(nblk(total, 64)), dim3(64), 0, s, p, carg(hc));
-        else hipLaunchKernelGGL((k_forward0<D, DY, false>), dim3(nblk(total, 64)), dim3(64), 0, s, p, carg(hc));
+        pick(fe, [&](auto FE) {
+            if (ck)
+                pick_waves(waves, [&](auto W) {
+                    hipLaunchKernelGGL((k_forward0_ck<D, DY, FE(), W()>), dim3((unsigned)(p.n_chains / (64 * W()) * p.S)), dim3(64 * W()), 0, s, p, carg(hc));
+                });
+            else hipLaunchKernelGGL((k_forward0<D, DY, FE()>), dim3(nblk(total, 64)), dim3(64), 0, s, p, carg(hc));
+        });
     }
     static void time_tables(const TimeTabParams& q, hipStream_t s) {
         hipLaunchKernelGGL((k_time_tables<D>), dim3(nblk(q.T, 64)), dim3(64), 0, s, q);
@@ -109,22 +107,19 @@ struct Launch {
         hipLaunchKernelGGL((k_smooth_tab_chain<D>), dim3(nblk(q.S, 64)), dim3(64), 0, s, q);
         hipLaunchKernelGGL((k_smooth_tab_apply<D>), dim3(nblk(nblocks, 64)), dim3(64), 0, s, q);
     }
-    // bnd (reverse-filter sweep only): 0 — a boundary-scan launch came before; 1 / 2 — the sweep's waves run the boundary recursion themselves (2: + free energy)
-    // write_cov: false — the per-chain covariance array already holds the table broadcast, the sweep stores the means only
-    // y_ring (reverse-filter sweep only): steps the observations run ahead of their use, 1 or Y_RING_SHIPPED
-    // waves (reverse-filter sweep only): wavefronts per workgroup, 1, 2 or 4 with n_chains % (64·waves) == 0 (plan::sweep_waves)
-    template <int W>
-    static void backward_rev(const Params& p, const double* hc, const double* gtab, const double* segend, int bnd, bool write_cov, int y_ring, hipStream_t s) {
-        const dim3 grid((unsigned)(p.n_chains / (64 * W) * p.S));
-        if (y_ring == 1) hipLaunchKernelGGL((k_backward_sh_rev<D, DY, 1, W>), grid, dim3(64 * W), 0, s, p, gtab, segend, carg(hc), bnd, write_cov ? 1 : 0);
-        else hipLaunchKernelGGL((k_backward_sh_rev<D, DY, Y_RING_SHIPPED, W>), grid, dim3(64 * W), 0, s, p, gtab, segend, carg(hc), bnd, write_cov ? 1 : 0);
-    }
-    static void backward_sh(const Params& p, const double* hc, const double* gtab, const double* segend, bool rev, int bnd, bool write_cov, int y_ring, int waves,
-                            hipStream_t s) {
-        if (rev && waves == 4) backward_rev<4>(p, hc, gtab, segend, bnd, write_cov, y_ring, s);
-        else if (rev && waves == 2) backward_rev<2>(p, hc, gtab, segend, bnd, write_cov, y_ring, s);
-        else if (rev) backward_rev<1>(p, hc, gtab, segend, bnd, write_cov, y_ring, s);
-        else hipLaunchKernelGGL((k_backward_sh<D>), dim3((unsigned)(p.n_chains / 64 * p.S)), dim3(64), 0, s, p, gtab, segend, write_cov ? 1 : 0);
+    static void backward_sh(const Params& p, const double* hc, const double* gtab, const double* segend, const SweepArgs& a, hipStream_t s) {
+        const int write_cov = a.write_cov ? 1 : 0;
+        if (!a.rev) {
+            hipLaunchKernelGGL((k_backward_sh<D>), dim3((unsigned)(p.n_chains / 64 * p.S)), dim3(64), 0, s, p, gtab, segend, write_cov);
+            return;
+        }
+        pick_waves(a.waves, [&](auto W) {
+            pick(a.y_ring == 1, [&](auto R1) {
+                constexpr int R = R1() ? 1 : Y_RING_SHIPPED;
+                hipLaunchKernelGGL((k_backward_sh_rev<D, DY, R, W()>), dim3((unsigned)(p.n_chains / (64 * W()) * p.S)), dim3(64 * W()), 0, s, p, gtab, segend,
+                                   carg(hc), a.bnd, write_cov);
+            });
+        });
     }
     static void forecast(const PredictParams& p, hipStream_t s) {
         hipLaunchKernelGGL((k_forecast<D, DY>), dim3(nblk(p.n_chains, 64)), dim3(64), 0, s, p);
@@ -141,11 +136,11 @@ struct Launch {
     static void small_sweep(const Params& p, const double* hc, bool fe, hipStream_t s) {   // n_chains · S ≤ 256, n_chains ≤ 16, one model
         const size_t lds = sizeof(double) * (size_t)small_sweep_lds_doubles<D, DY>();
         const int par = p.S >= 24 ? 1 : 0;   // log-depth boundary recursion from 24 segments on (below, ⌈log₂ S⌉ rounds cost what S steps do)
-        if (p.filter) {
-            if (fe) hipLaunchKernelGGL((k_small_sweep<D, DY, true, true>), dim3(1), dim3(SMALL_SWEEP_THREADS), lds, s, p, carg(hc), par);
-            else hipLaunchKernelGGL((k_small_sweep<D, DY, false, true>), dim3(1), dim3(SMALL_SWEEP_THREADS), lds, s, p, carg(hc), par);
-        } else if (fe) hipLaunchKernelGGL((k_small_sweep<D, DY, true, false>), dim3(1), dim3(SMALL_SWEEP_THREADS), lds, s, p, carg(hc), par);
-        else hipLaunchKernelGGL((k_small_sweep<D, DY, false, false>), dim3(1), dim3(SMALL_SWEEP_THREADS), lds, s, p, carg(hc), par);
+        pick(fe, [&](auto FE) {
+            pick(p.filter != 0, [&](auto FILT) {
+                hipLaunchKernelGGL((k_small_sweep<D, DY, FE(), FILT()>), dim3(1), dim3(SMALL_SWEEP_THREADS), lds, s, p, carg(hc), par);
+            });
+        });
     }
     static void noise_reset(const NoiseParams& p, hipStream_t s) {
         hipLaunchKernelGGL((k_noise_reset<D, DY>), dim3(nblk(p.n_chains, 64)), dim3(64), 0, s, p);
