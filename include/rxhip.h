@@ -1224,6 +1224,101 @@ int32_t rxhip_gammamix_schedule(int64_t N, int32_t K);
 rxhip_status rxhip_gammamix_set_stored_log(rxhip_engine* e, int32_t stored);
 
 /* ------------------------------------------------------------------------------------------
+ * Expression programs: a user's function f : ℝᵈ → ℝᵈ (d = 1 … 4) as data, so that it reaches the device (csrc/expr.hpp; the Python tracer
+ * rxhip.trace builds one from a callable).  A straight-line three-address program over numbered value slots; an instruction is four int32
+ * (op, dst, a, b):
+ *     RXHIP_OP_CONST dst ← consts[a]     RXHIP_OP_VAR dst ← x[a]     ADD SUB MUL DIV dst ← slot a ∘ slot b
+ *     NEG SQRT EXP LOG SIN COS TANH dst ← op(slot a)                  RXHIP_OP_OUT f[dst] ← slot a
+ * Caps: 128 instructions, 16 live slots, 32 constants; every slot is written before it is read, the OUTs cover 0 … d−1, constants are finite.
+ * A program outside them is refused with a text (RXHIP_ERR_BADARG), never run.  One interpreter evaluates it in two modes: value plus tangents
+ * (forward-mode duals: f(x) and J = ∂f/∂x) and plain values at several points (sigma points).  The slots of a lane live in LDS.
+ * rxhip_expr_eval evaluates a program at n points on the device, one lane per point: x [n][d] → value [n][d] (plain mode), jac [n][d][d]
+ * (jac[i][k] = ∂f_i/∂x_k, dual mode).  A point outside a function's domain gives NaN at that point only.  Its refusals leave their text in
+ * rxhip_lowering_error() (there is no handle), like rxhip_rule_eval's.
+ * ------------------------------------------------------------------------------------------ */
+typedef enum {
+    RXHIP_OP_CONST = 0, RXHIP_OP_VAR = 1, RXHIP_OP_ADD = 2, RXHIP_OP_SUB = 3, RXHIP_OP_MUL = 4, RXHIP_OP_DIV = 5, RXHIP_OP_NEG = 6,
+    RXHIP_OP_SQRT = 7, RXHIP_OP_EXP = 8, RXHIP_OP_LOG = 9, RXHIP_OP_SIN = 10, RXHIP_OP_COS = 11, RXHIP_OP_TANH = 12, RXHIP_OP_OUT = 13
+} rxhip_expr_op;
+typedef struct {
+    int32_t n_code, n_consts, d, n_slots;
+    const int32_t* code;     /* [n_code][4] */
+    const double* consts;    /* [n_consts] */
+} rxhip_expr_program;
+rxhip_status rxhip_expr_eval(const rxhip_expr_program* program, const double* x, int64_t n, double* value, double* jac, int32_t device);
+
+/* ------------------------------------------------------------------------------------------
+ * Nonlinear state-space model: batched extended and unscented Kalman filtering / smoothing (the reference's delta node `state ~ f(previous)`
+ * under Linearization() or Unscented(): paper/example.jl, test/models/nonlinear, Unscented() in test/models/statespace/collision_tests.jl), for
+ * each of n_series independent series, d = 1 … 4, one program f for all series:
+ *     x[0] ~ N(m0, V0);   x[t] ~ N(f(x[t-1]), Q)   (Q symmetric PSD, may be 0: x[t] = f(x[t-1]))   t = 1 … T
+ *     known noise   (noise_shape = 0):  y[t] ~ N(H x[t], R)            d_y = 1 … d, R SPD
+ *     unknown noise (noise_shape > 0):  τ ~ Gamma(noise_shape, noise_rate);  y[t] ~ N(cᵀx[t], 1/τ), c = row 0 of H, d_y = 1,  q(x, τ) = q(x) q(τ)
+ * A step of y with a NaN in any component is missing.  per_series = 1: m0 is [n_series][d] and V0 [n_series][d][d].
+ * Delta node: a prior N(m, V) becomes a predicted mean m̃, covariance Ṽ and cross-covariance C̃; P = Ṽ + Q.
+ *     RXHIP_NLSSM_LINEARIZATION  m̃ = f(m), Ṽ = J V Jᵀ, C̃ = V Jᵀ, J = ∂f/∂x(m) by forward-mode duals;
+ *     RXHIP_NLSSM_UNSCENTED      λ = α²(d+κ) − d, L = chol((d+λ)V), points m, m ± L e_i, Wm₀ = λ/(d+λ), Wc₀ = Wm₀ + 1 − α² + β, W_i = 1/(2(d+λ));
+ *                                m̃, Ṽ, C̃ are the weighted moments.  THIS ENGINE'S defaults are α = 1e-3, β = 2, κ = 0 (ReactiveMP's, as far as the
+ *                                reference tree shows: the package is not vendored): a caller that wants them passes them (RXHIP_NLSSM_DEFAULT_*,
+ *                                the Python and ctypes layers do); α ≤ 0 is refused.  V must be SPD at every step.
+ * mode RXHIP_NLSSM_FILTER: one launch, the time loop inside each lane.  Known noise: the Kalman update of (m̃, P); rxhip_run's `iterations` is
+ * accepted and has no effect.  Unknown noise: `iterations` VMP iterations per observation with the feedback on the device (the schedule of
+ * paper/example.jl: @autoupdates, iterations = 5), a defined semantic of this engine: with q(τ) = Gamma(a, b) (shape, rate), E[τ] ← a/b, repeat:
+ *     k = P c, s = cᵀP c, g = E[τ]/(1 + E[τ] s);  m′ = m̃ + k g (y − cᵀm̃), V′ = P − g k kᵀ;  a′ = a + ½, b′ = b + ½((y − cᵀm′)² + cᵀV′c);  E[τ] ← a′/b′
+ * then (m, V, a, b) ← (m′, V′, a′, b′).  A missing y passes the prediction on and leaves q(τ) as it is.  The marginals are the FILTERED ones,
+ * rxhip_nlssm_get_noise returns q(τ) after every observation.
+ * mode RXHIP_NLSSM_SMOOTH (known noise only): the forward pass stores (m, V), (m̃, P), C̃ per step, a second launch runs the extended / unscented
+ * RTS pass G = C̃ P⁻¹, mˢ = m + G(mˢ₊₁ − m̃), Vˢ = V + G(Vˢ₊₁ − P)Gᵀ: the message into the delta node is the filtered one, so one
+ * forward–backward sweep is the whole schedule of the reference's unrolled graph.  P must be SPD: Q = 0 with a singular J is RXHIP_ERR_NOT_POSDEF.
+ * Free energy — DEFINED BY THIS ENGINE, per series, summed over the series for rxhip_get_free_energy (every per-iteration entry of a run holds
+ * the same value: the one after the last iteration):
+ *     known noise    −Σ_t ln N(y_t; H m̃_t, H P_t Hᵀ + R) over the observed steps: the Bethe free energy of the linearised graph;
+ *     unknown noise  Σ_t F_t,  F_t = KL(q(x_t)‖N(m̃, P)) + KL(Gamma(a′, b′)‖Gamma(a, b)) + ½(ln 2π − (ψ(a′) − ln b′) + (a′/b′)((y − cᵀm′)² + cᵀV′c))
+ *                    after the last iteration of step t; F_t = 0 at a missing step.
+ * A series with nothing observed has free energy exactly 0.
+ * Handle protocol: rxhip_set_data(RXHIP_VAR_Y, y, T*n_series*d_y, layout), rxhip_run(e, iterations, want_free_energy),
+ * rxhip_get_marginals(RXHIP_VAR_X): mean [T][series][d], cov [T][series][d][d] of x[1 … T] in either layout, rxhip_nlssm_get_noise,
+ * rxhip_get_free_energy, rxhip_get_free_energy_per_chain, rxhip_counters, rxhip_destroy; rxhip_run_filter is refused (mode is the descriptor's).
+ * RXHIP_ERR_BADARG / RXHIP_ERR_NOT_POSDEF / RXHIP_ERR_UNSUPPORTED with a text that names nlssm, before any device call: d outside 1 … 4, d_y outside
+ * 1 … d, V0 or R not SPD, Q not symmetric PSD, alpha ≤ 0, d + λ ≤ 0, a program outside the caps above, unknown noise with d_y ≠ 1 or a rate that
+ * is not positive, SMOOTH with unknown noise, an unknown method or mode.
+ * A value of f, of its Jacobian or of the predicted moments that is not finite (sqrt or log outside its domain …) is no device fault: rxhip_run /
+ * rxhip_sync return RXHIP_ERR_NONFINITE_FE with a text that names the first step and series (both counted from 0); no result of that run is
+ * valid and the engine stays usable.  In SMOOTH mode the backward pass of such a run (or of one whose forward pass lost positive definiteness) does
+ * nothing, and the non-finite status is the one reported even if other series raised the non-SPD one in the same run.
+ * Contract (against tests/nlssm_ref.py, itself held to 50 digits by tests/nlssm_mp.py): means within 1e-6 posterior standard deviations,
+ * covariances within 1e-6·√(V_ii V_jj), Gamma shape and rate within 1e-6 relative, free energy within 1e-8·max(1, |F|) per series.
+ * Numerical envelope.  The unscented weights at α = 1e-3 are of size 1/α² = 1e6: m̃ = Σ W_p f(X_p) carries about 1e6·ε·|f| of cancellation, so in
+ * posterior standard deviations the error of a mean is about 1e6·ε·|m|/sd ≈ 1e-10·|m|/sd.  The contract holds while |m|/sd ≤ 1e3 at every step
+ * under Unscented (Linearization: ε·|m|/sd, |m|/sd ≤ 1e8 as for the other state-space engines); the measured figures are tests/nlssm_mp.py
+ * ENVELOPE and DESIGN.md §3.5i.  A larger α widens the range by α².
+ * ------------------------------------------------------------------------------------------ */
+enum { RXHIP_NLSSM_LINEARIZATION = 0, RXHIP_NLSSM_UNSCENTED = 1 };
+enum { RXHIP_NLSSM_FILTER = 0, RXHIP_NLSSM_SMOOTH = 1 };
+#define RXHIP_NLSSM_DEFAULT_ALPHA 1e-3
+#define RXHIP_NLSSM_DEFAULT_BETA 2.0
+#define RXHIP_NLSSM_DEFAULT_KAPPA 0.0
+typedef struct {
+    int64_t T, n_series;
+    int32_t d, dy;
+    const rxhip_expr_program* f;
+    const double *m0, *V0;            /* [d], [d][d] row-major, or [n_series] sets with per_series */
+    const double* Q;                  /* [d][d] or NULL = 0 */
+    const double* H;                  /* [dy][d] */
+    const double* R;                  /* [dy][dy] (known noise; ignored with unknown noise) */
+    double noise_shape, noise_rate;   /* unknown noise: the Gamma prior of τ (shape, rate); noise_shape = 0: known noise */
+    int32_t method;                   /* RXHIP_NLSSM_LINEARIZATION | RXHIP_NLSSM_UNSCENTED */
+    double alpha, beta, kappa;        /* unscented (ignored under Linearization); alpha > 0 */
+    int32_t mode;                     /* RXHIP_NLSSM_FILTER | RXHIP_NLSSM_SMOOTH */
+    int32_t per_series;
+    int32_t device;
+    void* stream;
+} rxhip_nlssm_desc;
+rxhip_status rxhip_nlssm_create(const rxhip_nlssm_desc* desc, rxhip_engine** out);
+/* q(τ) after every observation of the last run: shape, rate [T][series]; either pointer may be NULL; known noise: RXHIP_ERR_BADARG */
+rxhip_status rxhip_nlssm_get_noise(rxhip_engine* e, double* shape, double* rate);
+
+/* ------------------------------------------------------------------------------------------
  * Several GPUs (one process per GPU; chains / series / points shard).  The path's only exchange is the sum
  * over shards of the Bethe free energy (reference: the single `sumreduce` of src/model/plugins/reactivemp_free_energy.jl:99-123
  * over ALL nodes and variables of the model) and, for the mixture, of the responsibility-weighted statistics that

@@ -96,6 +96,7 @@ enum class EngineKind : int {
                         // iteration of a run in one resident launch
     MnregOnline = 12,   // … streamed one row at a time with the posterior fed back as the next prior (the same plumbing, release and getters)
     GammaMix = 13,      // Gamma mixture with a point-mass shape, batched VMP (gammamix_kernels.hpp): a streamed pass and an update launch per iteration
+    Nlssm = 14,         // nonlinear state-space model, batched extended / unscented filtering and smoothing (nlssm_kernels.hpp, expr.hpp)
 };
 struct rxhip_engine : rxhip_engine_life {
     // one device allocation holds every buffer of a state-space engine (creation / destruction cost two driver calls
@@ -181,6 +182,12 @@ struct rxhip_engine : rxhip_engine_life {
         double *d_prior = nullptr, *d_init = nullptr, *d_state = nullptr, *d_part = nullptr, *d_hist = nullptr, *d_fe = nullptr, *d_resp = nullptr, *d_yt = nullptr,
                *d_ly = nullptr;
     } gx;
+    struct Nlssm {     // kind 14: the descriptor's scalars, the expression program, the priors, q(τ) history, the smoothing records, free energies, the first non-finite event
+        int method = 0, unknown = 0, per_series = 0, smooth = 0;
+        double Q[16] = {}, Hm[16] = {}, R[16] = {}, a0 = 1, b0 = 1, sc = 1, wm0 = 0, wc0 = 0, wi = 0;
+        size_t lds_bytes = 0;
+        double *d_prog = nullptr, *d_prior = nullptr, *d_noise = nullptr, *d_rec = nullptr, *d_fe_series = nullptr, *d_where = nullptr;
+    } nl;
     struct Gmm {
         long long N = 0;
         int K = 0, KT = 0, materialize = 0, nblocks = 0, it = 0, iterations = 0, hist_cap = 0;
@@ -355,6 +362,9 @@ namespace rxhip {
 // status bit of k_hmm_sweep (hmm_kernels.hpp; next to ST_NOT_POSDEF = 1, ST_NONFINITE = 2, ST_PROBIT_BAD_Y = 4, ST_HMM_BAD_X = 8, ST_LAR_BAD_Y = 16): a normaliser of
 // the forward–backward sweep underflowed.  rxhip_sync reports it as RXHIP_ERR_NONFINITE_FE with a text of its own.
 constexpr int ST_HMM_UNDERFLOW = 32;
+// status bit of k_nlssm_forward (nlssm_kernels.hpp): a value of f, of its Jacobian or of the predicted moments was not finite; the engine's `where`
+// word holds the first (step, series).  rxhip_sync reports it as RXHIP_ERR_NONFINITE_FE with a text of its own.
+constexpr int ST_NLSSM_NONFINITE = 64;
 const EngineFamily& family_of(const rxhip_engine* e);   // the row of the engine's kind
 const EngineFamily* vmp_family(EngineKind kind);        // … of a family of vmp_engines.hip (null: not one of them)
 inline double* fe_total_of(const rxhip_engine* e) { const auto f = family_of(e).fe_total; return f ? f(e) : e->d_fe_total; }
@@ -364,6 +374,8 @@ hipError_t stream_acquire(int device, hipStream_t* out);
 rxhip_status prof_begin(rxhip_engine* e, int k);
 rxhip_status prof_end(rxhip_engine* e);
 bool host_chol_inv(int n, const double* A, double* out, double* logdet);   // host Cholesky inverse + log-determinant of an SPD matrix
+// rxhip_expr_eval (vmp_engines.hip, next to the engine that runs programs): a refusal leaves its text in err
+rxhip_status expr_eval(const rxhip_expr_program* f, const double* x, int64_t n, double* value, double* jac, int device, std::string& err);
 
 // ---- creators -------------------------------------------------------------------------------------------------------------------
 // A handle-first creator is: new_handle, the family's own refusals (each with a text), count_devices, the description, open_device, the family's

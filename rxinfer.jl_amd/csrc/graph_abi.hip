@@ -183,6 +183,13 @@ rxhip_status rxhip_rule_eval(const rxhip_rule_call* call, int32_t device) {
     return st;
 }
 
+rxhip_status rxhip_expr_eval(const rxhip_expr_program* program, const double* x, int64_t n, double* value, double* jac, int32_t device) {
+    std::string err;
+    const rxhip_status st = rxhip::expr_eval(program, x, n, value, jac, device, err);
+    if (st) rxhip_lower::last_error() = err;   // (no handle either)
+    return st;
+}
+
 static rxhip_status create_pattern_matched(const rxhip_graph_desc* g, int32_t segments, int32_t device, void* stream, rxhip_engine** out);
 rxhip_status rxhip_create(const rxhip_graph_desc* g, int32_t segments, int32_t device, void* stream, rxhip_engine** out) {
     if (!out) return RXHIP_ERR_BADARG;

@@ -3146,6 +3146,12 @@ rxhip_status rxhip_sync(rxhip_engine* e) {
     HIPCHK(e, hipMemcpy(&st, e->d_status, sizeof(int), hipMemcpyDeviceToHost));
     if (st) {
         HIPCHK(e, hipMemset(e->d_status, 0, sizeof(int)));
+        if (st & ST_NLSSM_NONFINITE) {   // before ST_NOT_POSDEF: the lanes of other series may have raised that one in the same run, the first cause is this
+            unsigned long long w = 0;
+            HIPCHK(e, hipMemcpy(&w, e->nl.d_where, sizeof w, hipMemcpyDeviceToHost));
+            return fail(e, RXHIP_ERR_NONFINITE_FE, "nlssm: f, its Jacobian or the predicted moments are not finite at step %llu of series %llu (counted from 0; the first "
+                                                   "such event): no result of this run is valid (device flags 0x%x)", w >> 32, w & 0xffffffffull, st);
+        }
         if (st & ST_NOT_POSDEF)
             return fail(e, RXHIP_ERR_NOT_POSDEF, "a covariance / precision block lost positive definiteness on device");
         if (st & ST_HMM_UNDERFLOW)

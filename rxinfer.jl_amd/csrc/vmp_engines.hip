@@ -10,6 +10,7 @@
 //             rows, X and y from the host or the raw series through the common ingest
 //   mnreg     multinomial regression, stick-breaking Pólya-Gamma VMP from the column sums (mnreg_kernels.hpp): two rows, offline and online
 //   gammamix  Gamma mixture with a point-mass shape (gammamix_kernels.hpp): a streamed pass and an update launch per iteration
+//   nlssm     nonlinear state-space model, extended / unscented filtering and smoothing (nlssm_kernels.hpp) with f as an expression program (expr.hpp)
 // The runtime they share with the state-space engines — streams, profiling events, the engine handle, the creation and run helpers — is rxhip.hip's
 // (engine.hpp).  No kernels of the state-space path live here.
 #include "../../include/rxhip.h"
@@ -35,6 +36,7 @@
 #include "arreg_kernels.hpp"
 #include "mnreg_kernels.hpp"
 #include "gammamix_kernels.hpp"
+#include "nlssm_kernels.hpp"
 #include "engine.hpp"
 
 using namespace rxhip;
@@ -1780,6 +1782,232 @@ rxhip_status rxhip_gammamix_get_responsibilities(rxhip_engine* e, double* resp) 
 
 }  // extern "C"
 
+// ------------------------------------------------------------------------------------------
+// Nonlinear state-space engine (nlssm_kernels.hpp) and the expression programs it runs (expr.hpp)
+// the C descriptor of a program as the device's fixed-size block; 0 or a text
+static int expr_pack(const rxhip_expr_program* f, int d, expr::Program& out, char* msg, size_t n) {
+    if (!f || !f->code || (f->n_consts > 0 && !f->consts)) { snprintf(msg, n, "expr: the program or one of its arrays is null"); return 1; }
+    if (f->n_code < 1 || f->n_code > expr::EXPR_MAX_CODE) { snprintf(msg, n, "expr: a program has 1 … %d instructions (got %d)", expr::EXPR_MAX_CODE, f->n_code); return 1; }
+    if (f->n_consts < 0 || f->n_consts > expr::EXPR_MAX_CONSTS) { snprintf(msg, n, "expr: a program has at most %d constants (got %d)", expr::EXPR_MAX_CONSTS, f->n_consts); return 1; }
+    std::memset(&out, 0, sizeof out);
+    out.n_code = f->n_code; out.n_consts = f->n_consts; out.d = f->d; out.n_slots = f->n_slots;
+    std::memcpy(out.code, f->code, sizeof(int32_t) * 4 * (size_t)f->n_code);
+    if (f->n_consts > 0) std::memcpy(out.consts, f->consts, sizeof(double) * (size_t)f->n_consts);
+    return expr::expr_validate(out, d, msg, n);
+}
+// LDS of a workgroup that runs program p at dimension d with up to `comps` components per pass
+static size_t expr_lds_bytes(const expr::Program& p, int d, int comps) {
+    const int nc = std::min(comps, expr::expr_max_comps(p.n_slots, d));
+    return (size_t)expr::rows_of(p.n_slots, d) * (size_t)nc * expr::EXPR_LANES * sizeof(double);
+}
+template <int D>
+static void expr_eval_launch(const expr::Program* dp, const double* dx, double* dv, double* dj, long long n, size_t lds, hipStream_t s) {
+    hipLaunchKernelGGL((k_expr_eval<D>), dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, dp, dx, dv, dj, n);
+}
+extern "C++" rxhip_status rxhip::expr_eval(const rxhip_expr_program* f, const double* x, int64_t n, double* value, double* jac, int device, std::string& err) {
+    char msg[256];
+    if (!f || !x || !value || !jac || n < 1) { err = "expr_eval: null argument or no points"; return RXHIP_ERR_BADARG; }
+    expr::Program prog;
+    if (expr_pack(f, f->d, prog, msg, sizeof msg)) { err = msg; return RXHIP_ERR_BADARG; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { err = "expr_eval: no HIP device visible"; return RXHIP_ERR_NO_DEVICE; }
+    if (device >= ndev) { err = "expr_eval: device ordinal out of range"; return RXHIP_ERR_BADARG; }
+    DevGuard guard;
+    hipError_t he = hipSuccess;
+    if (device >= 0) he = guard.set(device);
+    const size_t d = (size_t)prog.d, N = (size_t)n;
+    DevTmp blk;
+    if (he == hipSuccess) he = hipMalloc(&blk.p, sizeof prog + sizeof(double) * N * (2 * d + d * d));
+    if (he == hipSuccess) {
+        double* dx = (double*)((char*)blk.p + sizeof prog);
+        double *dv = dx + N * d, *dj = dv + N * d;
+        he = hipMemcpy(blk.p, &prog, sizeof prog, hipMemcpyHostToDevice);
+        if (he == hipSuccess) he = hipMemcpy(dx, x, sizeof(double) * N * d, hipMemcpyHostToDevice);
+        if (he == hipSuccess) {
+            const size_t lds = expr_lds_bytes(prog, prog.d, prog.d + 1);
+            const expr::Program* dp = (const expr::Program*)blk.p;
+            switch (prog.d) {
+                case 1: expr_eval_launch<1>(dp, dx, dv, dj, n, lds, nullptr); break;
+                case 2: expr_eval_launch<2>(dp, dx, dv, dj, n, lds, nullptr); break;
+                case 3: expr_eval_launch<3>(dp, dx, dv, dj, n, lds, nullptr); break;
+                default: expr_eval_launch<4>(dp, dx, dv, dj, n, lds, nullptr); break;
+            }
+            he = hipGetLastError();
+        }
+        if (he == hipSuccess) he = hipDeviceSynchronize();
+        if (he == hipSuccess) he = hipMemcpy(value, dv, sizeof(double) * N * d, hipMemcpyDeviceToHost);
+        if (he == hipSuccess) he = hipMemcpy(jac, dj, sizeof(double) * N * d * d, hipMemcpyDeviceToHost);
+    }
+    if (he != hipSuccess) { err = std::string("expr_eval: ") + hipGetErrorString(he); return RXHIP_ERR_HIP; }
+    return RXHIP_OK;
+}
+
+// symmetric positive SEMI-definite (n ≤ 4): symmetric to 1e-12 of its scale, and a Cholesky in which a pivot below 1e-12 of the scale is a zero
+// pivot whose column must vanish with it
+static bool host_sym_psd(int n, const double* A) {
+    double scale = 0.0, L[16] = {0};
+    for (int i = 0; i < n * n; ++i) { if (!std::isfinite(A[i])) return false; scale = std::max(scale, std::fabs(A[i])); }
+    if (scale == 0.0) return true;
+    const double tol = 1e-12 * scale;
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < i; ++j)
+            if (std::fabs(A[i * n + j] - A[j * n + i]) > tol) return false;
+    for (int j = 0; j < n; ++j) {
+        double sum = A[j * n + j];
+        for (int k = 0; k < j; ++k) sum -= L[j * n + k] * L[j * n + k];
+        if (sum < -tol) return false;
+        const bool zero = sum <= tol;
+        L[j * n + j] = zero ? 0.0 : std::sqrt(sum);
+        for (int i = j + 1; i < n; ++i) {
+            double v = A[i * n + j];
+            for (int k = 0; k < j; ++k) v -= L[i * n + k] * L[j * n + k];
+            if (zero) { if (std::fabs(v) > 1e-6 * scale) return false; L[i * n + j] = 0.0; }
+            else L[i * n + j] = v / L[j * n + j];
+        }
+    }
+    return true;
+}
+static bool host_sym_spd(int n, const double* A) {
+    double tmp[16];
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < i; ++j)
+            if (std::fabs(A[i * n + j] - A[j * n + i]) > 1e-12 * (std::fabs(A[i * n + i]) + std::fabs(A[j * n + j]))) return false;
+    for (int i = 0; i < n * n; ++i) if (!std::isfinite(A[i])) return false;
+    return host_chol_inv(n, A, tmp, nullptr);
+}
+
+rxhip_status rxhip_nlssm_create(const rxhip_nlssm_desc* ds, rxhip_engine** out) {
+    if (rxhip_status st = new_handle(ds && ds->T > 0 && ds->n_series > 0, out, EngineKind::Nlssm)) return st;
+    rxhip_engine* e = *out;
+    const int d = ds->d, dy = ds->dy;
+    if (d < 1 || d > 4) return fail(e, RXHIP_ERR_UNSUPPORTED, "nlssm: the state dimension d must be 1 … 4 (got %d)", d);
+    if (dy < 1 || dy > d) return fail(e, RXHIP_ERR_BADARG, "nlssm: the observation dimension d_y must be 1 … d = %d (got %d)", d, dy);
+    if (!ds->m0 || !ds->V0 || !ds->H) return fail(e, RXHIP_ERR_BADARG, "nlssm: m0, V0 and H are required");
+    if (ds->method != RXHIP_NLSSM_LINEARIZATION && ds->method != RXHIP_NLSSM_UNSCENTED) return fail(e, RXHIP_ERR_BADARG, "nlssm: unknown method %d", ds->method);
+    if (ds->mode != RXHIP_NLSSM_FILTER && ds->mode != RXHIP_NLSSM_SMOOTH) return fail(e, RXHIP_ERR_BADARG, "nlssm: unknown mode %d", ds->mode);
+    const bool unknown = ds->noise_shape != 0.0;
+    if (unknown) {
+        if (dy != 1) return fail(e, RXHIP_ERR_UNSUPPORTED, "nlssm: unknown observation noise needs d_y = 1 (got %d)", dy);
+        if (!(ds->noise_shape > 0) || !(ds->noise_rate > 0) || !std::isfinite(ds->noise_shape) || !std::isfinite(ds->noise_rate))
+            return fail(e, RXHIP_ERR_BADARG, "nlssm: the Gamma prior of the observation precision needs a positive finite shape and rate (got %g, %g)", ds->noise_shape, ds->noise_rate);
+        if (ds->mode == RXHIP_NLSSM_SMOOTH) return fail(e, RXHIP_ERR_UNSUPPORTED, "nlssm: smoothing with unknown observation noise is not supported (filter mode runs it)");
+    } else {
+        if (!ds->R) return fail(e, RXHIP_ERR_BADARG, "nlssm: known observation noise needs R");
+        if (!host_sym_spd(dy, ds->R)) return fail(e, RXHIP_ERR_NOT_POSDEF, "nlssm: the observation covariance R is not symmetric positive definite");
+    }
+    const size_t npri = ds->per_series ? (size_t)ds->n_series : 1, dd = (size_t)d * d;
+    for (size_t s = 0; s < npri; ++s) {
+        for (int i = 0; i < d; ++i)
+            if (!std::isfinite(ds->m0[s * d + i])) return fail(e, RXHIP_ERR_BADARG, "nlssm: the prior mean m0 of series %zu is not finite", s);
+        if (!host_sym_spd(d, ds->V0 + s * dd)) return fail(e, RXHIP_ERR_NOT_POSDEF, "nlssm: the prior covariance V0 of series %zu is not symmetric positive definite", s);
+    }
+    if (ds->Q && !host_sym_psd(d, ds->Q)) return fail(e, RXHIP_ERR_NOT_POSDEF, "nlssm: the process covariance Q is not symmetric positive semi-definite");
+    for (int i = 0; i < dy * d; ++i)
+        if (!std::isfinite(ds->H[i])) return fail(e, RXHIP_ERR_BADARG, "nlssm: the observation matrix H is not finite");
+    rxhip_engine::Nlssm& nl = e->nl;
+    if (ds->method == RXHIP_NLSSM_UNSCENTED) {
+        if (!(ds->alpha > 0) || !std::isfinite(ds->alpha) || !std::isfinite(ds->beta) || !std::isfinite(ds->kappa))
+            return fail(e, RXHIP_ERR_BADARG, "nlssm: the unscented alpha must be positive and alpha, beta, kappa finite (got alpha = %g; this engine's defaults are "
+                                             "1e-3, 2, 0)", ds->alpha);
+        const double alpha = ds->alpha, beta = ds->beta, kappa = ds->kappa;
+        const double sc = alpha * alpha * (d + kappa);   // d + λ
+        if (!(sc > 0)) return fail(e, RXHIP_ERR_BADARG, "nlssm: the unscented parameters give d + lambda = %g, which must be positive", sc);
+        nl.sc = sc; nl.wm0 = (sc - d) / sc; nl.wc0 = nl.wm0 + 1.0 - alpha * alpha + beta; nl.wi = 0.5 / sc;
+    }
+    expr::Program prog;
+    char msg[256];
+    if (expr_pack(ds->f, d, prog, msg, sizeof msg)) return fail(e, RXHIP_ERR_BADARG, "nlssm: %s", msg);
+    int ndev = 0;
+    if (rxhip_status st = count_devices(e, &ndev)) return st;
+    e->T = ds->T; e->n_chains = ds->n_series; e->d = e->dpad = d; e->dy = dy;
+    nl.method = ds->method; nl.unknown = unknown ? 1 : 0; nl.per_series = ds->per_series ? 1 : 0; nl.smooth = ds->mode == RXHIP_NLSSM_SMOOTH;
+    nl.a0 = unknown ? ds->noise_shape : 1.0; nl.b0 = unknown ? ds->noise_rate : 1.0;
+    for (size_t i = 0; i < dd; ++i) nl.Q[i] = ds->Q ? ds->Q[i] : 0.0;
+    for (int i = 0; i < dy * d; ++i) nl.Hm[i] = ds->H[i];
+    for (int i = 0; i < dy * dy; ++i) nl.R[i] = unknown ? 0.0 : ds->R[i];
+    nl.lds_bytes = expr_lds_bytes(prog, d, ds->method == RXHIP_NLSSM_UNSCENTED ? 2 * d + 1 : d + 1);
+    DevGuard guard;
+    if (rxhip_status st = open_device(e, guard, ds->device, ds->stream, ndev)) return st;
+    const size_t C = (size_t)ds->n_series, T = (size_t)ds->T;
+    HIPCHK(e, hipMalloc(&nl.d_prog, sizeof prog));
+    HIPCHK(e, hipMemcpy(nl.d_prog, &prog, sizeof prog, hipMemcpyHostToDevice));
+    HIPCHK(e, hipMalloc(&nl.d_prior, sizeof(double) * npri * (d + dd)));
+    {
+        std::vector<double> pri(npri * (d + dd));
+        for (size_t s = 0; s < npri; ++s) {
+            std::memcpy(&pri[s * (d + dd)], ds->m0 + s * d, sizeof(double) * d);
+            std::memcpy(&pri[s * (d + dd) + d], ds->V0 + s * dd, sizeof(double) * dd);
+        }
+        HIPCHK(e, hipMemcpy(nl.d_prior, pri.data(), sizeof(double) * pri.size(), hipMemcpyHostToDevice));
+    }
+    if (unknown) HIPCHK(e, hipMalloc(&nl.d_noise, sizeof(double) * 2 * T * C));
+    if (nl.smooth) HIPCHK(e, hipMalloc(&nl.d_rec, sizeof(double) * T * (size_t)nlssm::n_records(d) * C));
+    HIPCHK(e, hipMalloc(&nl.d_fe_series, sizeof(double) * C));
+    HIPCHK(e, hipMalloc(&nl.d_where, sizeof(unsigned long long)));
+    HIPCHK(e, hipMalloc(&e->d_mean, sizeof(double) * T * C * d));
+    HIPCHK(e, hipMalloc(&e->d_cov, sizeof(double) * T * C * dd));
+    return finish_create(e, C, 16);
+}
+
+rxhip_status rxhip_nlssm_get_noise(rxhip_engine* e, double* shape, double* rate) {
+    if (!e || e->kind != EngineKind::Nlssm) return RXHIP_ERR_BADARG;
+    if (!e->nl.unknown) return fail(e, RXHIP_ERR_BADARG, "nlssm_get_noise: the observation noise of this engine is known");
+    DevGuard guard;
+    if (rxhip_status st = open_results(e, guard, true, "nlssm_get_noise", false)) return st;
+    const size_t n = (size_t)e->T * e->n_chains;
+    if (shape) HIPCHK(e, hipMemcpy(shape, e->nl.d_noise, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (rate) HIPCHK(e, hipMemcpy(rate, e->nl.d_noise + n, sizeof(double) * n, hipMemcpyDeviceToHost));
+    return RXHIP_OK;
+}
+
+template <int D>
+static void nlssm_launch(const NlssmParams& p, size_t lds, bool backward, hipStream_t s) {
+    const dim3 grid((unsigned)((p.n_series + 63) / 64));
+    if (backward) hipLaunchKernelGGL((k_nlssm_backward<D>), grid, dim3(64), 0, s, p);
+    else hipLaunchKernelGGL((k_nlssm_forward<D>), grid, dim3(64), lds, s, p);
+}
+static rxhip_status nlssm_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
+    if (rxhip_status st = run_preamble(e, iterations)) return st;
+    SET_DEVICE(e);
+    if (rxhip_status rs = reserve(e, &e->fe_total_cap, iterations, {{&e->d_fe_total, 1}})) return rs;
+    const rxhip_engine::Nlssm& nl = e->nl;
+    const size_t C = (size_t)e->n_chains, T = (size_t)e->T;
+    NlssmParams p{};
+    p.T = e->T; p.n_series = e->n_chains; p.dy = e->dy; p.method = nl.method; p.unknown = nl.unknown; p.per_series = nl.per_series;
+    p.iterations = iterations; p.smooth = nl.smooth;
+    p.prog = (const expr::Program*)nl.d_prog; p.y = e->d_y; p.prior = nl.d_prior;
+    std::memcpy(p.Q, nl.Q, sizeof p.Q); std::memcpy(p.H, nl.Hm, sizeof p.H); std::memcpy(p.R, nl.R, sizeof p.R);
+    p.a0 = nl.a0; p.b0 = nl.b0; p.u = {nl.sc, nl.wm0, nl.wc0, nl.wi};
+    p.mean = e->d_mean; p.cov = e->d_cov; p.shape = nl.d_noise; p.rate = nl.d_noise ? nl.d_noise + T * C : nullptr;
+    p.rec = nl.d_rec; p.fe_series = nl.d_fe_series; p.status = e->d_status; p.where = (unsigned long long*)nl.d_where;
+    HIPCHK(e, hipMemsetAsync(nl.d_where, 0xff, sizeof(unsigned long long), e->stream));
+    HIPCHK(e, hipMemsetAsync(nl.d_fe_series, 0, sizeof(double) * C, e->stream));
+    rxhip_status st;
+    for (int backward = 0; backward <= (nl.smooth ? 1 : 0); ++backward) {
+        if ((st = prof_begin(e, backward ? RXHIP_K_BACKWARD : RXHIP_K_FORWARD))) return st;
+        switch (e->d) {
+            case 1: nlssm_launch<1>(p, nl.lds_bytes, backward, e->stream); break;
+            case 2: nlssm_launch<2>(p, nl.lds_bytes, backward, e->stream); break;
+            case 3: nlssm_launch<3>(p, nl.lds_bytes, backward, e->stream); break;
+            default: nlssm_launch<4>(p, nl.lds_bytes, backward, e->stream); break;
+        }
+        if ((st = prof_end(e))) return st;
+    }
+    if (want_fe) {
+        hipLaunchKernelGGL(k_nlssm_fe, dim3(1), dim3(256), 0, e->stream, (const double*)nl.d_fe_series, e->n_chains, e->d_fe_total, (int)iterations, e->d_status);
+        HIPCHK(e, hipMemcpyAsync(e->d_fe_chain, nl.d_fe_series, sizeof(double) * C, hipMemcpyDeviceToDevice, e->stream));
+    }
+    HIPCHK(e, hipGetLastError());
+    finish_run(e, iterations, want_fe != 0, !nl.smooth);
+    // reference-equivalent events per series: a delta-node rule forward (and backward when smoothing) and an observation rule per step, the
+    // q(τ) and q(x) updates per VMP iteration with unknown noise; a product and a marginal per state
+    const uint64_t Cs = (uint64_t)C, Ts = (uint64_t)T, I = nl.unknown ? (uint64_t)iterations : 1;
+    e->rule_calls = Cs * Ts * ((nl.smooth ? 2 : 1) + (nl.unknown ? 2 * I : 1));
+    e->products = Cs * Ts * (nl.smooth ? 2 : 1) * I;
+    e->marginals = Cs * Ts * I;
+    return RXHIP_OK;
+}
+
 // the mixture engines' run: the split-phase entry points (several GPUs all-reduce the statistics between accumulate and update) back to back
 static rxhip_status mixture_run_async(rxhip_engine* e, int32_t iterations, int32_t want_fe) {
     rxhip_status st = rxhip_gmm_begin_run(e, iterations);
@@ -1831,7 +2059,12 @@ const EngineFamily* rxhip::vmp_family(EngineKind kind) {
     static const EngineFamily gammamix_row = {gammamix_run_async, false, gammamix_check_data, nullptr, nullptr, nullptr, false, [](E* e) {
         free_buffers(e, {&e->gx.d_prior, &e->gx.d_init, &e->gx.d_state, &e->gx.d_part, &e->gx.d_hist, &e->gx.d_fe, &e->gx.d_resp, &e->gx.d_yt, &e->gx.d_ly});
     }};
+    // nonlinear state-space model: the common ingest (any double is data, NaN = missing); the mode is the descriptor's, so no streaming twin
+    static const EngineFamily nlssm_row = {nlssm_run_async, false, nullptr, nullptr, nullptr, nullptr, true, [](E* e) {
+        free_buffers(e, {&e->nl.d_prog, &e->nl.d_prior, &e->nl.d_noise, &e->nl.d_rec, &e->nl.d_fe_series, &e->nl.d_where});
+    }};
     switch (kind) {
+        case EngineKind::Nlssm: return &nlssm_row;
         case EngineKind::GammaMix: return &gammamix_row;
         case EngineKind::Mnreg: return &mnreg_row;
         case EngineKind::MnregOnline: return &mnreg_online;

@@ -158,6 +158,23 @@ class GammaMixDesc(ctypes.Structure):   # rxhip_gammamix_desc
         ("schedule", ctypes.c_int32), ("materialize_responsibilities", ctypes.c_int32), ("device", ctypes.c_int32), ("stream", ctypes.c_void_p)]
 
 
+(OP_CONST, OP_VAR, OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_NEG, OP_SQRT, OP_EXP, OP_LOG, OP_SIN, OP_COS, OP_TANH, OP_OUT) = range(14)   # rxhip_expr_op
+NLSSM_LINEARIZATION, NLSSM_UNSCENTED = 0, 1
+NLSSM_FILTER, NLSSM_SMOOTH = 0, 1
+
+
+class ExprProgram(ctypes.Structure):   # rxhip_expr_program
+    _fields_ = [("n_code", ctypes.c_int32), ("n_consts", ctypes.c_int32), ("d", ctypes.c_int32), ("n_slots", ctypes.c_int32),
+                ("code", c_int32_p), ("consts", c_double_p)]
+
+
+class NlssmDesc(ctypes.Structure):   # rxhip_nlssm_desc
+    _fields_ = [("T", ctypes.c_int64), ("n_series", ctypes.c_int64), ("d", ctypes.c_int32), ("dy", ctypes.c_int32), ("f", ctypes.POINTER(ExprProgram))] + [
+        (n, c_double_p) for n in ("m0", "V0", "Q", "H", "R")] + [
+        ("noise_shape", ctypes.c_double), ("noise_rate", ctypes.c_double), ("method", ctypes.c_int32), ("alpha", ctypes.c_double), ("beta", ctypes.c_double),
+        ("kappa", ctypes.c_double), ("mode", ctypes.c_int32), ("per_series", ctypes.c_int32), ("device", ctypes.c_int32), ("stream", ctypes.c_void_p)]
+
+
 class NoisePrior(ctypes.Structure):   # rxhip_noise_prior
     _fields_ = [("nu0", ctypes.c_double), ("S0", c_double_p), ("init_nu", ctypes.c_double), ("init_V", c_double_p)]
 
@@ -282,6 +299,9 @@ SYMBOLS = [
     ("rxhip_gammamix_get_responsibilities", ctypes.c_int32, [_H, c_double_p]),
     ("rxhip_gammamix_schedule", ctypes.c_int32, [ctypes.c_int64, ctypes.c_int32]),
     ("rxhip_gammamix_set_stored_log", ctypes.c_int32, [_H, ctypes.c_int32]),
+    ("rxhip_expr_eval", ctypes.c_int32, [ctypes.POINTER(ExprProgram), c_double_p, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int32]),
+    ("rxhip_nlssm_create", ctypes.c_int32, [ctypes.POINTER(NlssmDesc), ctypes.POINTER(_H)]),
+    ("rxhip_nlssm_get_noise", ctypes.c_int32, [_H, c_double_p, c_double_p]),
     ("rxhip_hgf_get_history", ctypes.c_int32, [_H, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_int32]),
     ("rxhip_set_profiling", ctypes.c_int32, [_H, ctypes.c_int32]),
     ("rxhip_get_kernel_times", ctypes.c_int32, [_H, c_double_p, c_u64_p]),

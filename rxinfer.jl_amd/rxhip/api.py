@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RxHipError
-from .engine import DriftChainEngine, GMMEngine, HGFEngine, LGSSMEngine, MvGMMEngine, ProbitEngine, HMMEngine, LAREngine, BinomialRegressionEngine, ARRegressionEngine, MultinomialRegressionEngine, GammaMixtureEngine
+from .engine import DriftChainEngine, GMMEngine, HGFEngine, LGSSMEngine, MvGMMEngine, ProbitEngine, HMMEngine, LAREngine, BinomialRegressionEngine, ARRegressionEngine, MultinomialRegressionEngine, GammaMixtureEngine, NonlinearSSMEngine
 
 
 @dataclass
@@ -942,11 +942,106 @@ def _infer_lgssm(model, data, kw):
     return _guarded(model, kw, body)
 
 
+@dataclass
+class Linearization:
+    """The delta node's first-order approximation: m̃ = f(m), Ṽ = J V Jᵀ (ReactiveMP's Linearization())."""
+
+
+@dataclass
+class Unscented:
+    """The delta node's unscented transform (ReactiveMP's Unscented()); the defaults are this engine's (include/rxhip.h rxhip_nlssm_desc)."""
+    alpha: float = 1e-3
+    beta: float = 2.0
+    kappa: float = 0.0
+
+
+@dataclass
+class NonlinearSSM:
+    """`x[0] ~ MvNormal(prior_mean, prior_cov); x[t] ~ MvNormal(f(x[t-1]), process_cov)` (`x[t] := f(x[t-1])` without process_cov) under
+    `Linearization()` or `Unscented()`, observed as `y[t] ~ MvNormal(obs_matrix x[t], obs_cov)` or, with `obs_precision_prior`, as
+    `τ ~ Gamma; y[t] ~ Normal(obs_matrix x[t], 1/τ)` with q(x, τ) = q(x)q(τ) (the reference's paper/example.jl)."""
+    f: Any
+    d: int
+    prior_mean: Any
+    prior_cov: Any
+    process_cov: Any
+    obs_matrix: Any
+    obs_cov: Any
+    obs_precision_prior: Any
+    method: Any
+
+
+def nonlinear_ssm(f, d, prior_mean, prior_cov, process_cov=None, obs_matrix=None, obs_cov=None, obs_precision_prior=None, method=None):
+    """`f`: a callable on a list of d values (traced once by rxhip.trace) or a Program.  Exactly one of obs_cov (known noise) and
+    obs_precision_prior (GammaShapeRate / GammaShapeScale: unknown noise, scalar observations) is given."""
+    from .expr import trace
+    d = int(d)
+    if obs_matrix is None:
+        raise ValueError("nonlinear_ssm: obs_matrix is required")
+    if (obs_cov is None) == (obs_precision_prior is None):
+        raise ValueError("nonlinear_ssm: give obs_cov (known noise) or obs_precision_prior (unknown noise), not both")
+    if obs_precision_prior is not None and not isinstance(obs_precision_prior, (GammaShapeRate, GammaShapeScale)):
+        raise TypeError("nonlinear_ssm: obs_precision_prior is a GammaShapeRate or GammaShapeScale")
+    method = Linearization() if method is None else method
+    if not isinstance(method, (Linearization, Unscented)):
+        raise TypeError("nonlinear_ssm: method is rxhip.Linearization() or rxhip.Unscented(alpha, beta, kappa)")
+    if isinstance(method, Unscented) and not (method.alpha > 0 and np.isfinite([method.alpha, method.beta, method.kappa]).all()):
+        raise ValueError(f"nonlinear_ssm: Unscented needs alpha > 0 and finite alpha, beta, kappa (got alpha = {method.alpha})")
+    H = np.atleast_2d(np.asarray(obs_matrix, dtype=np.float64))
+    return NonlinearSSM(trace(f, d), d, np.asarray(prior_mean, dtype=np.float64), np.asarray(prior_cov, dtype=np.float64),
+                        None if process_cov is None else np.asarray(process_cov, dtype=np.float64).reshape(d, d), H,
+                        None if obs_cov is None else np.asarray(obs_cov, dtype=np.float64).reshape(H.shape[0], H.shape[0]), obs_precision_prior, method)
+
+
+def _infer_nlssm(model, data, kw):
+    """y: [T] / [T][dy] for one series, [series][T][dy] for a batch (NaN = missing).  Smoothing (known noise): posteriors["x"] =
+    MvNormalMeanCovariance of x[1 … T], free_energy per iteration entry.  With `autoupdates` (filtering): history["x"] the filtered marginals and,
+    with unknown noise, history["τ"] = GammaShapeRate after every observation, `iterations` VMP iterations per observation; `keephistory` must be T."""
+    options = _check_options(kw.options)
+    dy = model.obs_matrix.shape[0]
+    y = np.asarray(data["y"], dtype=np.float64)
+    if y.ndim == 1:
+        y = y[:, None]
+    single = y.ndim == 2
+    if single:
+        y = y[None]
+    if y.ndim != 3 or y.shape[2] != dy:
+        raise ValueError(f"nonlinear_ssm: y is [T][{dy}] or [series][T][{dy}]")
+    C, T = y.shape[:2]
+    filtering = bool(kw.autoupdates)
+    if filtering and kw.keephistory not in (None, T):
+        raise ValueError(f"nonlinear_ssm: the streamed run keeps every step, keephistory must be {T}")
+    iters, free_energy = _iterations(kw), kw.free_energy
+    m = model.method
+    prior = model.obs_precision_prior
+    noise = None if prior is None else (float(prior.shape), float(prior.rate))
+
+    def body(own):
+        eng = own(NonlinearSSMEngine(model.f, model.d, T, model.prior_mean, model.prior_cov, model.obs_matrix, R=model.obs_cov, Q=model.process_cov,
+                                     noise_prior=noise, method="unscented" if isinstance(m, Unscented) else "linearization",
+                                     unscented=(m.alpha, m.beta, m.kappa) if isinstance(m, Unscented) else None,
+                                     mode="filter" if filtering else "smooth", n_series=C, device=int(options.get("device", -1))))
+        eng.set_data(y, layout="chain_time")
+        eng.run(iterations=iters, free_energy=free_energy)
+        mean, cov = eng.marginals(layout="chain_time")
+        fe = eng.free_energy() if free_energy else None
+        x = MvNormalMeanCovariance(mean[0], cov[0]) if single else MvNormalMeanCovariance(mean, cov)
+        if not filtering:
+            return InferenceResult({"x": x}, None, fe, model, None)
+        hist = {"x": x}
+        if noise is not None:
+            shape, rate = eng.noise()
+            hist["τ"] = GammaShapeRate(shape[:, 0], rate[:, 0]) if single else GammaShapeRate(shape.T.copy(), rate.T.copy())
+        return InferenceResult({}, None, None, model, None, history=hist, free_energy_history=fe)
+
+    return _guarded(model, kw, body)
+
+
 # model type -> the function that runs it; every one takes (model, data, kw) with kw the keyword arguments of `infer`
 _FAMILIES = {UnivariateGaussianMixture: _infer_mixture, MultivariateGaussianMixture: _infer_mv_mixture, HierarchicalGaussianFilter: _infer_hgf,
              UnivariateDriftChain: _infer_drift_chain, ProbitSSM: _infer_probit, HiddenMarkovModel: _infer_hmm, LatentAutoregressive: _infer_lar,
              BinomialRegression: _infer_binreg, GaussianRegression: _infer_arreg, MultinomialRegression: _infer_mnreg, GammaMixture: _infer_gammamix,
-             LinearGaussianSSM: _infer_lgssm}
+             NonlinearSSM: _infer_nlssm, LinearGaussianSSM: _infer_lgssm}
 
 
 def infer(*, model, data, iterations=None, free_energy=False, options=None, returnvars=None, predictvars=None,

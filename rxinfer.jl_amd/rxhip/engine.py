@@ -987,3 +987,7 @@ class Communicator:
 
     def __exit__(self, *a):
         self.close()
+
+
+# the nonlinear state-space engine's class lives in a module of its own (next to the expression tracer it needs) and is part of this one's namespace
+from .nlssm import NonlinearSSMEngine  # noqa: E402,F401
